@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- decoded PCM Msamples/s of the MI355X Vorbis synthesis back end.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one pass of the hot path over one batch of synthetic, HBM-resident input: north_star's workload -- batched
@@ -11,8 +11,13 @@ Mdct.cs:15-19, StreamDecoder.cs:764-791, 594-638) through the fused kernel, 65 5
 every rank owns its own batch; streams are independent, so there is no collective on the data path.  One sample = one
 float32 PCM value of one channel; 8 algorithmic bytes per sample (4 read + 4 written).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
-  "roofline":     algorithmic bytes of the fused kernel / its HIP-event duration (events on the library's stream) vs 8 TB/s,
+A plain run sets up, runs 200 untimed steps (--ramp-steps) and W warm-up steps, times exactly K steps, and prints ONE JSON
+line (rank 0) with the contract fields ("ms_per_step": wall milliseconds of one timed step) plus
+  "roofline":     algorithmic bytes of the fused kernel / its HIP-event duration (events on the library's stream) vs 8 TB/s.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last one handed its caller to DIR/*.npy (NorthStarLine.dump);
+the inputs are seeded, so two builds given the same arguments can be compared output for output.
+--full: every other measurement of the record as well (--no-cpu-baseline / --no-extras leave parts of it out):
+  "cold_start":   the same W + K steps taken once more before the untimed ones, on the device as the fresh process found it,
   "cpu_baseline": the CPU oracle (restated reference, kind "port") on the same workload, timed on the host cores,
   "extra_workloads": N = 1: configs[1] (Mdct.Reverse alone, the contract line of rounds 1-4, with its own roofline), configs[2]
                   (mixed 256/2048 window switching), configs[3] (6 channels, Residue2-interleaved, coupled, Floor1 on the GPU;
@@ -642,6 +647,22 @@ class NorthStarLine:
                                self.capi.MEM_DEVICE)
         assert int(w[0]) == self.samples, (int(w[0]), self.samples)
 
+    def dump(self, dirname, edge=65536, sample=1 << 20, seed=0):
+        """What the last step handed its caller, as .npy files in `dirname`: the samples written per stream (float64) and
+        the planar float32 PCM of each channel -- its first and last `edge` samples and a fixed, seeded sample of `sample`
+        positions (float64) in between; 18 MB in all for the default batch instead of the whole 537 MB."""
+        import torch
+        os.makedirs(dirname, exist_ok=True)
+        pcm = self.out.view(CHANNELS, self.cap)[:, :self.samples]
+        edge, sample = min(edge, self.samples), min(sample, self.samples)
+        idx = np.sort(np.random.default_rng(seed).choice(self.samples, size=sample, replace=False))
+        arrays = {"samples_written": self.dec.last_written.astype(np.float64),
+                  "pcm_head": pcm[:, :edge], "pcm_tail": pcm[:, self.samples - edge:],
+                  "pcm_sample": pcm[:, torch.from_numpy(idx).to(self.out.device)], "pcm_sample_index": idx.astype(np.float64)}
+        for name, a in arrays.items():
+            a = a.cpu().numpy() if isinstance(a, torch.Tensor) else a
+            np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
     def close(self):
         self.dec.close()
         del self.residue, self.out
@@ -703,9 +724,13 @@ def slim(x, top=True):
     return x
 
 
-def emit(result, extras):
+def emit(result, extras, detail=True):
     """ONE JSON line on stdout (contract fields + roofline + cpu_baseline + the extras' figures, short enough for the driver's
     stdout tail); the same record with every note under gpurun_out/bench_detail.json and on stderr."""
+    if not detail:  # a plain run: its line is the whole record
+        print(json.dumps(result, separators=(",", ":")))
+        sys.stdout.flush()
+        return
     full = dict(result)
     if extras:
         full["extra_workloads"] = extras
@@ -788,17 +813,19 @@ def main_single_process(args):
                      "kernel_ms": round(max(kernel_ms), 4), "kernel_ms_per_device": [round(k, 4) for k in kernel_ms],
                      "algorithmic_bytes_per_launch": alg_bytes},
     }
+    if args.dump_outputs:
+        lines[0].dump(args.dump_outputs)
     for ln in lines:
         ln.close()
     for c in ctxs:
         c.close()
     torch.cuda.empty_cache()
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         thr = host_threads(whole_node=True) if HOST_THREADS_CAP else None  # (None: the dispatcher's own count)
         extras = {"configs[4] job, ONE process (vpzm_decode_library), %d device(s), f32 PCM" % n_dev: dispatcher_whole_job(torch, ids, thr),
                   "configs[4] job, ONE process, s16 PCM": dispatcher_whole_job(torch, ids, thr, s16=True)}
-    emit(result, extras)
+    emit(result, extras, detail=args.full)
 
 
 def cpu_plumbing_2test():
@@ -887,11 +914,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-extras", action="store_true", help="skip the configs[1]/[2]/[3]/[4] side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the contract line, the cold-start figure, the CPU baselines and "
+                    "the configs[0]-[4] / 4096 / 8192 side measurements (without it a run times the contract line alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/*.npy")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the configs[1]/[2]/[3]/[4] side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--frames", type=int, default=FRAMES, help="frames of the contract workload (default: BASELINE's 65536)")
-    ap.add_argument("--ramp-steps", type=int, default=200, help="untimed steps of the contract workload between its cold measurement and "
-                    "the one reported (the device's clocks ramp up over the first few milliseconds of load; 0: none)")
+    ap.add_argument("--ramp-steps", type=int, default=200, help="untimed steps of the contract workload in front of the measurement "
+                    "reported, after the cold one with --full (the device's clocks ramp up over the first few milliseconds of load; 0: none)")
     ap.add_argument("--extras-frames", type=int, default=FRAMES, help="frames of the configs[2] side measurement")
     ap.add_argument("--extras-frames6", type=int, default=16384, help="frames of the configs[3] side measurement")
     ap.add_argument("--host-threads", type=int, default=0, help="explicit cap on the host threads of a rank (default: every "
@@ -962,12 +992,16 @@ def main():
     # 8-12 % slower than the calls after them (profiles/r5_bench_cold_and_steady.txt: 0.254-0.268 ms per step over steps 6-25,
     # 0.229-0.232 over 200).  The contract line is the device's steady state -- what a decode service runs in --: the same W + K
     # measurement is taken twice, once cold (reported as `cold_start`) and once behind `ramp_steps` untimed steps of the workload.
-    cold_elapsed, cold_kernel_ms = measure()
+    # A plain run takes only the second one.
+    if args.full:
+        cold_elapsed, cold_kernel_ms = measure()
     ramp_steps = max(0, args.ramp_steps)
     for _ in range(ramp_steps):
         line.step()
     ctx.synchronize()
     elapsed, kernel_ms = measure()
+    if args.dump_outputs and rank == 0:
+        line.dump(args.dump_outputs)
 
     value = world * line.pcm_values * args.steps / elapsed / 1e6
     alg_bytes = line.alg_bytes  # 4 B x spectra values read + 4 B x PCM values written = 8 B per sample
@@ -987,11 +1021,8 @@ def main():
         "data": "synthetic",
         "config": {"workload": NS_WORKLOAD, "frames_per_gpu": args.frames, "channels": CHANNELS, "block_size": N,
                    "pcm_values_per_step_per_gpu": line.pcm_values, "sharding": "independent batch per GPU, no collective",
-                   "device_state": "steady: %d untimed steps of the workload between the cold measurement and this one" % ramp_steps},
-        "cold_start": {"ms_per_step": round(cold_elapsed / args.steps * 1e3, 4), "kernel_ms": round(cold_kernel_ms, 4),
-                       "value": round(world * line.pcm_values * args.steps / cold_elapsed / 1e6, 1),
-                       "frac": round(line.alg_bytes / (cold_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                       "note": "the same W warm-up + K timed steps taken first, on the device as the fresh process found it (idle clocks)"},
+                   "device_state": "steady: %d untimed steps of the workload %s" % (
+                       ramp_steps, "between the cold measurement and this one" if args.full else "in front of the W warm-up steps")},
         "roofline": {
             "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 4),
@@ -1000,16 +1031,23 @@ def main():
             "bytes_per_sample": round(alg_bytes / line.pcm_values, 3),
         },
     }
+    if args.full:
+        result["cold_start"] = {"ms_per_step": round(cold_elapsed / args.steps * 1e3, 4), "kernel_ms": round(cold_kernel_ms, 4),
+                                "value": round(world * line.pcm_values * args.steps / cold_elapsed / 1e6, 1),
+                                "frac": round(line.alg_bytes / (cold_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                "note": "the same W warm-up + K timed steps taken first, on the device as the fresh process found "
+                                        "it (idle clocks)"}
     line.close()
     del line
     torch.cuda.empty_cache()
 
     extras = {}
-    cpu = not args.no_cpu_baseline
+    cpu = args.full and not args.no_cpu_baseline
+    more = args.full and not args.no_extras
     if rank == 0 and world == 1:
         if cpu:
             result["cpu_baseline"] = cpu_baseline_contract()
-        if not args.no_extras:
+        if more:
             # configs[1]: Mdct.Reverse alone (the contract line of rounds 1-4), with its own roofline
             extras["configs[1] IMDCT only, N=2048, 131072 ch-blocks"] = imdct_only_extra(torch, ctx, device, 2048 + rank, 20, cpu)
             # configs[2]
@@ -1110,7 +1148,7 @@ def main():
                 "host": host_report(thr),
                 "note": "ONE vpzm_decode_library call: sub-batches of 16 streams on 4 contexts, int16 residue over the link (ABI v5); best of 3"}
             extras["configs[0] 2test.ogg, CPU only"] = cpu_plumbing_2test()
-    if not args.no_extras:
+    if more:
         # ---------------- configs[4], the whole job: 1024 stereo streams partitioned over the ranks (strong scaling).
         # Every rank decodes ONLY its contiguous shard of global stream ids (no data-path collective); what crosses
         # ranks is two int64 vectors: per-stream sample counts and PCM checksums.
@@ -1189,7 +1227,7 @@ def main():
     if distributed:
         sharding.finalize()
     if rank == 0:
-        emit(result, extras)
+        emit(result, extras, detail=args.full)
 
 
 if __name__ == "__main__":

@@ -1,24 +1,26 @@
-"""Checks the oracle's constant tables against the reference's source text.  Runs only where
-/root/reference exists (this container); reading the reference as text is study, not execution."""
+"""Checks the oracle's constant tables against the reference's source text.  tests/golden/reference_constants.npz holds
+the literals of that text as float32 (inverse_dB_table of Floor1.cs, LowerClip / UpperClip of Utils.cs), parsed out of
+it by `tools/make_golden_fixtures.py --reference`; reading the reference as text is study, not execution."""
+import ctypes as C
 import os
-import re
 
 import numpy as np
-import pytest
 
-REF = "/root/reference/NVorbis"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+REF = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_constants.npz"))
 
 
 def test_inverse_db_table_matches_reference_literals(oracle):
-    src = open(os.path.join(REF, "Floor1.cs")).read()
-    body = re.search(r"inverse_dB_table =\s*\{(.*?)\};", src, re.S).group(1)
-    vals = np.array([np.float32(t.strip().rstrip("f")) for t in body.replace("\n", " ").split(",") if t.strip()],
-                    dtype=np.float32)
-    assert vals.shape == (256,)
+    vals = REF["inverse_db_table"]
+    assert vals.dtype == np.float32 and vals.shape == (256,)
     assert np.array_equal(vals.view(np.uint32), oracle.inverse_db_table().view(np.uint32))
 
 
 def test_clip_constants_match_reference(oracle):
-    src = open(os.path.join(REF, "Utils.cs")).read()
-    assert "LowerClip = -0.99999994f" in src and "UpperClip = 0.99999994f" in src
+    lower, upper = REF["clip"]
+    assert lower == np.float32(-0.99999994) and upper == np.float32(0.99999994)
+    # ... and they are where the oracle clips
+    clipped = C.c_int(0)
+    for x, want in ((2.0, upper), (-2.0, lower), (0.5, np.float32(0.5))):
+        got = np.float32(oracle.lib().orc_clip_value(x, C.byref(clipped)))
+        assert got.view(np.uint32) == want.view(np.uint32), (x, got, want)
+    assert clipped.value == 1

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/profiles_$TAG
 rm -rf "$OUT" && mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats -d "$OUT/bench" -o b --output-format csv -- python bench.py --steps 20 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"
+rocprofv3 --kernel-trace --stats -d "$OUT/bench" -o b --output-format csv -- python bench.py --full --steps 20 --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err"
 python tools/prof_summary.py "$OUT/bench/b_kernel_stats.csv" > "$OUT/bench_kernel_stats.txt"
 for w in olalong ola floor real; do
   rocprofv3 --kernel-trace --memory-copy-trace --stats -d "$OUT/$w" -o k --output-format csv -- python tools/kbench_synth.py --steps 8 --which $w > "$OUT/$w.log" 2>&1

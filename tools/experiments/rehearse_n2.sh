@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 OUT=${1:-gpurun_out/bench_n2_rehearsal.json}
 mkdir -p $(dirname $OUT)
 VPZ_BENCH_REHEARSAL=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --steps 5 --warmup 2 > $OUT 2> ${OUT%.json}.err || { tail -20 ${OUT%.json}.err; exit 1; }
+    bench.py --full --gpus 2 --steps 5 --warmup 2 > $OUT 2> ${OUT%.json}.err || { tail -20 ${OUT%.json}.err; exit 1; }
 python - "$OUT" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

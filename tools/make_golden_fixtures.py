@@ -9,8 +9,13 @@ float64 synthesis; tests/test_golden_vectors_cpu.py fails if a later edit of the
 tests/test_golden_vectors_gpu.py holds the HIP path to them without needing any oracle code on the GPU box.
 
     python tools/make_golden_fixtures.py        # rewrites tests/golden/*.npz
+    python tools/make_golden_fixtures.py --reference NVORBIS_DIR
+                                                # writes tests/golden/reference_constants.npz alone: the constant tables
+                                                # of the reference's source text (NVORBIS_DIR: its NVorbis/ folder), which
+                                                # tests/test_oracle_tables.py holds the oracle to
 """
 import os
+import re
 import sys
 
 import numpy as np
@@ -89,5 +94,23 @@ def main():
             print("%-28s %7d bytes" % (n, os.path.getsize(os.path.join(OUT, n))))
 
 
+def reference_constants(src_dir):
+    """inverse_dB_table (Floor1.cs) and LowerClip / UpperClip (Utils.cs) as float32, read from the reference's source text."""
+    src = open(os.path.join(src_dir, "Floor1.cs")).read()
+    body = re.search(r"inverse_dB_table =\s*\{(.*?)\};", src, re.S).group(1)
+    table = np.array([np.float32(t.strip().rstrip("f")) for t in body.replace("\n", " ").split(",") if t.strip()],
+                     dtype=np.float32)
+    assert table.shape == (256,)
+    src = open(os.path.join(src_dir, "Utils.cs")).read()
+    clip = np.array([np.float32(re.search(r"%s = (\S+)f;" % k, src).group(1)) for k in ("LowerClip", "UpperClip")],
+                    dtype=np.float32)
+    path = os.path.join(OUT, "reference_constants.npz")
+    np.savez_compressed(path, inverse_db_table=table, clip=clip)
+    print("%-28s %7d bytes" % (os.path.basename(path), os.path.getsize(path)))
+
+
 if __name__ == "__main__":
-    main()
+    if "--reference" in sys.argv:
+        reference_constants(sys.argv[sys.argv.index("--reference") + 1])
+    else:
+        main()

@@ -11,8 +11,8 @@ cd "$GRAFT_REPO_ROOT"
 O=${1:-gpurun_out/r5_rehearsal}
 mkdir -p $O
 VPZ_BENCH_REHEARSAL=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 5 --master-addr 127.0.0.1 --master-port 29519 \
-    bench.py --gpus 5 --steps 5 --warmup 2 --host-threads 2 > $O/bench_n5_rehearsal_one_gpu.json 2> $O/bench_n5_rehearsal_one_gpu.err || { tail -20 $O/bench_n5_rehearsal_one_gpu.err; exit 1; }
-VPZ_BENCH_REHEARSAL=1 timeout -k 10 400 python bench.py --gpus 8 --single-process --steps 5 --warmup 2 > $O/bench_single_process_8groups_one_gpu.json 2> $O/bench_single_process_8groups_one_gpu.err || { tail -20 $O/bench_single_process_8groups_one_gpu.err; exit 1; }
+    bench.py --full --gpus 5 --steps 5 --warmup 2 --host-threads 2 > $O/bench_n5_rehearsal_one_gpu.json 2> $O/bench_n5_rehearsal_one_gpu.err || { tail -20 $O/bench_n5_rehearsal_one_gpu.err; exit 1; }
+VPZ_BENCH_REHEARSAL=1 timeout -k 10 400 python bench.py --full --gpus 8 --single-process --steps 5 --warmup 2 > $O/bench_single_process_8groups_one_gpu.json 2> $O/bench_single_process_8groups_one_gpu.err || { tail -20 $O/bench_single_process_8groups_one_gpu.err; exit 1; }
 python - "$O" <<'PY'
 import json, sys
 o = sys.argv[1]

@@ -239,9 +239,8 @@ def test_group_mode_equals_the_separate_coupling_pass(ctx, oracle, channels, ste
         with env(VPZ_NO_GROUP=None, VPZ_NO_PAIRS=None):  # ... and whatever route the decoder picks by itself
             dflt = run(ctx, pk, res, posts, counts, n_streams, channels, floors, mappings, layout=layout, splits=2)
         assert np.array_equal(dflt[1], g[1]) and np.array_equal(dflt[0].view(np.uint32), g[0].view(np.uint32)), (channels, layout)
-        # ... and the opt-in variant that leaves the interleaved packet as it is in LDS (LDS-DMA landing, the wave's own
-        # coupling step applied at pick-up; even channel counts, no channel in two steps -- otherwise the switch does nothing)
-        with env(VPZ_NO_GROUP=None, VPZ_NO_DUAL=1, VPZ_GROUP_DMA=1):
+        # ... and group mode where the stereo fast path would otherwise take the batch (two channels)
+        with env(VPZ_NO_GROUP=None, VPZ_NO_DUAL=1):
             d = run(ctx, pk, res, posts, counts, n_streams, channels, floors, mappings, layout=layout, splits=2)
         assert np.array_equal(d[1], g[1]) and np.array_equal(d[0].view(np.uint32), g[0].view(np.uint32)), (channels, layout)
         outs[layout] = g

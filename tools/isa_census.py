@@ -42,7 +42,7 @@ SOURCE_OF = {"synth_pairs.hip": ("synth_dual.hip", "synth_dual_kernel")}
 # inlining chain); kernel-body regions by a `// [census: cold]` mark on the line that opens their brace block.
 COLD_FUNCTIONS = [
     r"imdct256_wave8", r"imdct_mid_wave", r"render_floor_indices$", r"render_floor_indices<", r"unpack_segment",
-    r"div_floor_small", r"pickup_interleaved", r"stage_by_lds_dma", r"y_from_h", r"tail_at", r"clip_value", r"clip_track",
+    r"div_floor_small", r"y_from_h", r"tail_at", r"clip_value", r"clip_track",
     r"to_s16", r"pack_s16",
 ]
 COLD_MARK = "[census: cold]"  # on the line that opens a brace block the all-long steady state does not enter
@@ -151,7 +151,7 @@ def classify(op):
         return "waitcnt"
     if op == "s_barrier":
         return "barrier"
-    if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime", "s_store", "s_dcache")):
+    if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime")):
         return "SMEM"
     if op.startswith(("s_cbranch", "s_branch", "s_setpc", "s_endpgm", "s_call")):
         return "branch"

@@ -15,10 +15,7 @@ namespace vpz {
 
 class HostPool {
 public:
-    // spin_us: how long an idle worker polls before it blocks (VPZ_HOST_SPIN_US; a host that calls the decoder back to back
-    // -- a call every few hundred microseconds -- saves a futex wake-up per fork by polling through the gap, at the price of
-    // busy cores; the default only bridges the forks of ONE call)
-    explicit HostPool(int parties, int spin_us = 50) : parties_(parties < 1 ? 1 : parties), spin_us_(spin_us < 0 ? 0 : spin_us)
+    explicit HostPool(int parties) : parties_(parties < 1 ? 1 : parties)
     {
         for (int i = 1; i < parties_; ++i) workers_.emplace_back([this, i] { worker(i); });
     }
@@ -75,7 +72,7 @@ private:
             // short spin first: the second fork of a call follows the first within tens of microseconds
             const auto t0 = std::chrono::steady_clock::now();
             bool got = false;
-            while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(spin_us_)) {
+            while (std::chrono::steady_clock::now() - t0 < std::chrono::microseconds(kSpinUs)) {
                 if (generation_.load(std::memory_order_acquire) != seen) { got = true; break; }
             }
             if (!got) {
@@ -95,7 +92,9 @@ private:
     }
 
     const int parties_;
-    const int spin_us_;
+    // how long an idle worker polls before it blocks: bridges the forks of ONE call (longer spins, for hosts that call the
+    // decoder back to back, made no difference: DESIGN.md 5)
+    static constexpr int kSpinUs = 50;
     std::vector<std::thread> workers_;
     std::mutex m_;
     std::condition_variable cv_;

@@ -62,20 +62,6 @@ __device__ __forceinline__ float lane_mirror64(float v, int lane)
 {
     return __int_as_float(__builtin_amdgcn_ds_bpermute((63 - lane) << 2, __float_as_int(v)));
 }
-// Two values mirrored at once WITHOUT the LDS pipe (ds_bpermute goes through it; the stereo kernel keeps it ~70 % busy): lane bits 0..3
-// by a row-mirroring DPP move, bit 4 by two v_permlane16_swap, bit 5 by two v_permlane32_swap (each swap pair hands both registers
-// back with the rows / halves exchanged).  Pure data movement: the values of lane_mirror64.
-__device__ __forceinline__ void lane_mirror64_x2(float a, float b, float &ma, float &mb)
-{
-    unsigned ua = __builtin_amdgcn_update_dpp(0u, __float_as_uint(a), 0x140, 0xF, 0xF, false);  // row_mirror
-    unsigned ub = __builtin_amdgcn_update_dpp(0u, __float_as_uint(b), 0x140, 0xF, 0xF, false);
-    auto r = __builtin_amdgcn_permlane16_swap(ua, ub, false, false);   // (A0 B0 A2 B2) (A1 B1 A3 B3)
-    r = __builtin_amdgcn_permlane16_swap(r[1], r[0], false, false);    // (A1 A0 A3 A2) (B1 B0 B3 B2)
-    r = __builtin_amdgcn_permlane32_swap(r[0], r[1], false, false);    // (Alo Blo) (Ahi Bhi)
-    r = __builtin_amdgcn_permlane32_swap(r[1], r[0], false, false);    // (Ahi Alo) (Bhi Blo)
-    ma = __uint_as_float(r[0]);
-    mb = __uint_as_float(r[1]);
-}
 // value held by lane (lane ^ 7): mirror inside each group of 8 lanes
 __device__ __forceinline__ float lane_mirror8(float v, int lane)
 {
@@ -117,39 +103,6 @@ __device__ __forceinline__ void radix8_inverse(float2 (&vv)[8])
     vv[3] = f2(cadd_i(c2_, e7)); vv[7] = f2(csub_i(c2_, e7));
 }
 
-// Tuning builds only (-DVPZ_REG_TRANSPOSE): transpose 1 of dft512_wave without LDS -- register index bit b against lane
-// bit 3 + b, b = 0, 1, 2: lane bit 5 and 4 with one `v_permlane32_swap` / `v_permlane16_swap` per register pair, lane bit 3
-// with three row-rotating DPP moves.  Pure data movement: same bits.  Measured and not adopted, see DESIGN.md 4.7.
-#ifdef VPZ_REG_TRANSPOSE
-template <int kLaneBit>
-__device__ __forceinline__ void lane_reg_exchange(float &a, float &b)
-{
-    unsigned ua = __float_as_uint(a), ub = __float_as_uint(b);
-    if (kLaneBit == 32) {
-        const auto r = __builtin_amdgcn_permlane32_swap(ua, ub, false, false);  // a[32..63] <-> b[0..31]
-        ua = r[0]; ub = r[1];
-    } else if (kLaneBit == 16) {
-        const auto r = __builtin_amdgcn_permlane16_swap(ua, ub, false, false);  // odd rows of a <-> even rows of b
-        ua = r[0]; ub = r[1];
-    } else {
-        const unsigned t = __builtin_amdgcn_update_dpp(0u, ua, 0x128, 0xF, 0xF, false);  // row_ror:8: t[l] = a[l ^ 8]
-        ua = __builtin_amdgcn_update_dpp(ua, ub, 0x128, 0xF, 0xC, false);                // lanes 8..15 of a row: b[l ^ 8]
-        ub = __builtin_amdgcn_update_dpp(ub, t, 0xE4, 0xF, 0x3, false);                  // lanes 0..7 of a row: old a[l ^ 8]
-    }
-    a = __uint_as_float(ua); b = __uint_as_float(ub);
-}
-// (lane l0 + 8*l1, reg p) -> (lane l0 + 8*p, reg l1)
-__device__ __forceinline__ void transpose_lane_hi(float2 (&z)[8])
-{
-#pragma unroll
-    for (int p = 0; p < 8; ++p) if (!(p & 1)) { lane_reg_exchange<8>(z[p].x, z[p | 1].x); lane_reg_exchange<8>(z[p].y, z[p | 1].y); }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) if (!(p & 2)) { lane_reg_exchange<16>(z[p].x, z[p | 2].x); lane_reg_exchange<16>(z[p].y, z[p | 2].y); }
-#pragma unroll
-    for (int p = 0; p < 8; ++p) if (!(p & 4)) { lane_reg_exchange<32>(z[p].x, z[p | 4].x); lane_reg_exchange<32>(z[p].y, z[p | 4].y); }
-}
-#endif
-
 // LDS floats a wavefront needs for the transposes / the h staging area.
 constexpr int kWaveScratchFloat2 = 576;  // 72*8 (stage A->B), 66*7+64 = 526 (stage B->C), 512 (h)
 
@@ -169,14 +122,10 @@ __device__ __forceinline__ void dft512_wave(float2 (&z)[8], float2 *scratch, con
     for (int p = 1; p < 8; ++p) z[p] = cmul(z[p], s_twAB[p * 64 + lane]);
     // transpose 1: (lane l = l0 + 8*l1, reg p) -> (lane l0 + 8*p, reg l1); rows padded to 72
     const int l0 = lane & 7, pp = lane >> 3;
-#ifdef VPZ_REG_TRANSPOSE
-    transpose_lane_hi(z);
-#else
 #pragma unroll
     for (int p = 0; p < 8; ++p) scratch[72 * p + lane] = z[p];
 #pragma unroll
     for (int l1 = 0; l1 < 8; ++l1) z[l1] = scratch[72 * pp + l0 + 8 * l1];
-#endif
     // stage B: DFT over l1, output digit q1
     radix8_inverse(z);
 #pragma unroll
@@ -279,110 +228,21 @@ __device__ __forceinline__ void imdct256_wave8(const float2 (&xa)[8], float2 *sc
 // mirrors) are covered by the other's arithmetic -- the wave carries two dependency chains instead of one.  The
 // operations per transform and their order are exactly those of the single versions above: same bits.
 // -------------------------------------------------------------------------------------------
-__device__ __forceinline__ void dft512_wave_x2(float2 (&za)[8], float2 (&zb)[8], float2 *sa, float2 *sb,
-                                               const float2 *s_twAB, const float2 *s_twBC, int lane)
-{
-    radix8_inverse(za);
-    radix8_inverse(zb);
-#pragma unroll
-    for (int p = 1; p < 8; ++p) {
-        const float2 w = s_twAB[p * 64 + lane];
-        za[p] = cmul(za[p], w);
-        zb[p] = cmul(zb[p], w);
-    }
-    const int l0 = lane & 7, pp = lane >> 3;
-#ifdef VPZ_REG_TRANSPOSE
-    transpose_lane_hi(za);
-    transpose_lane_hi(zb);
-#else
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        sa[72 * p + lane] = za[p];
-        sb[72 * p + lane] = zb[p];
-    }
-#pragma unroll
-    for (int l1 = 0; l1 < 8; ++l1) {
-        za[l1] = sa[72 * pp + l0 + 8 * l1];
-        zb[l1] = sb[72 * pp + l0 + 8 * l1];
-    }
-#endif
-    radix8_inverse(za);
-    radix8_inverse(zb);
-#pragma unroll
-    for (int q = 1; q < 8; ++q) {
-        const float2 w = s_twBC[l0 * 8 + q];
-        za[q] = cmul(za[q], w);
-        zb[q] = cmul(zb[q], w);
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        sa[66 * l0 + pp + 8 * q] = za[q];
-        sb[66 * l0 + pp + 8 * q] = zb[q];
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        za[r] = sa[66 * r + lane];
-        zb[r] = sb[66 * r + lane];
-    }
-    radix8_inverse(za);
-    radix8_inverse(zb);
-}
-
-// imdct2048_wave for two spectra (xa -> scratch_a, xb -> scratch_b)
-__device__ __forceinline__ void imdct2048_wave_x2(const float2 (&xa)[8], const float2 (&xb)[8], float2 *scratch_a,
-                                                  float2 *scratch_b, const float2 *s_tw, const float2 *s_twAB,
-                                                  const float2 *s_twBC, int lane)
-{
-    float2 za[8], zb[8];
-    float2 tw[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) tw[m] = s_tw[lane + 64 * m];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const float ra = lane_mirror64(xa[7 - m].y, lane), rb = lane_mirror64(xb[7 - m].y, lane);
-        za[m] = cmul(make_float2(ra, xa[m].x), tw[m]);
-        zb[m] = cmul(make_float2(rb, xb[m].x), tw[m]);
-    }
-    dft512_wave_x2(za, zb, scratch_a, scratch_b, s_twAB, s_twBC, lane);
-    float wa[8], wb[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const float2 a = cmul(za[q], tw[q]), b = cmul(zb[q], tw[q]);
-        za[q].x = a.x;
-        wa[q] = -a.y;
-        zb[q].x = b.x;
-        wb[q] = -b.y;
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const float ha = lane_mirror64(wa[7 - q], lane), hb = lane_mirror64(wb[7 - q], lane);
-        scratch_a[lane + 64 * q] = make_float2(za[q].x, ha);
-        scratch_b[lane + 64 * q] = make_float2(zb[q].x, hb);
-    }
-}
-
-// ... with the three twiddle sets in REGISTERS (a lane reads the same 22 entries for every 2048 block: tw[m] = s_tw[lane + 64 m],
-// twAB[p] = s_twAB[64 p + lane], twBC[q] = s_twBC[8 (lane & 7) + q]; entries 0 of the last two are not used): the stereo kernel keeps
-// them across the frames of a run -- 11 KB less through the CU's LDS pipe per pass.  Operations and their order: imdct2048_wave_x2's.
-// kBCRegs false: the third set stays in LDS (s_twBC) -- for the variants that need its 14 registers for something worth more.
-template <bool kBCRegs>
+// imdct2048_wave for two spectra (xa -> scratch_a, xb -> scratch_b), the three twiddle sets in REGISTERS (a lane reads the same 22
+// entries for every 2048 block: tw[m] = s_tw[lane + 64 m], twAB[p] = s_twAB[64 p + lane], twBC[q] = s_twBC[8 (lane & 7) + q]; entries
+// 0 of the last two are not used): the stereo kernel keeps them across the frames of a run -- 11 KB less through the CU's LDS pipe
+// per pass.
 __device__ __forceinline__ void imdct2048_wave_x2_regs(const float2 (&xa)[8], const float2 (&xb)[8], float2 *scratch_a, float2 *scratch_b,
-                                                       const float2 (&tw)[8], const float2 (&twAB)[8], const float2 (&twBC)[8],
-                                                       const float2 *s_twBC, int lane)
+                                                       const float2 (&tw)[8], const float2 (&twAB)[8], const float2 (&twBC)[8], int lane)
 {
     float2 za[8], zb[8];
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
-#ifndef VPZ_DUAL_MIRROR_VALU  // (-DVPZ_DUAL_MIRROR_VALU: lane_mirror64_x2, measured equal -- profiles/r5_ab_lds_diet.txt)
         const float ra = lane_mirror64(xa[7 - m].y, lane), rb = lane_mirror64(xb[7 - m].y, lane);
-#else
-        float ra, rb;
-        lane_mirror64_x2(xa[7 - m].y, xb[7 - m].y, ra, rb);
-#endif
         za[m] = cmul(make_float2(ra, xa[m].x), tw[m]);
         zb[m] = cmul(make_float2(rb, xb[m].x), tw[m]);
     }
-    {   // dft512_wave_x2
+    {   // dft512_wave, both spectra
         float2 *sa = scratch_a, *sb = scratch_b;
         radix8_inverse(za);
         radix8_inverse(zb);
@@ -406,9 +266,8 @@ __device__ __forceinline__ void imdct2048_wave_x2_regs(const float2 (&xa)[8], co
         radix8_inverse(zb);
 #pragma unroll
         for (int q = 1; q < 8; ++q) {
-            const float2 w = kBCRegs ? twBC[q] : s_twBC[l0 * 8 + q];
-            za[q] = cmul(za[q], w);
-            zb[q] = cmul(zb[q], w);
+            za[q] = cmul(za[q], twBC[q]);
+            zb[q] = cmul(zb[q], twBC[q]);
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -434,12 +293,7 @@ __device__ __forceinline__ void imdct2048_wave_x2_regs(const float2 (&xa)[8], co
     }
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-#ifndef VPZ_DUAL_MIRROR_VALU  // (-DVPZ_DUAL_MIRROR_VALU: lane_mirror64_x2, measured equal -- profiles/r5_ab_lds_diet.txt)
         const float ha = lane_mirror64(wa[7 - q], lane), hb = lane_mirror64(wb[7 - q], lane);
-#else
-        float ha, hb;
-        lane_mirror64_x2(wa[7 - q], wb[7 - q], ha, hb);
-#endif
         scratch_a[lane + 64 * q] = make_float2(za[q].x, ha);
         scratch_b[lane + 64 * q] = make_float2(zb[q].x, hb);
     }

@@ -294,10 +294,6 @@ template <typename K>
 static int resident_groups(K kernel, int num_cu, int threads = kThreads)
 {
     int per_cu = 0;
-    if (const char *e = getenv("VPZ_IMDCT_GROUPS_PER_CU")) {  // tuning experiments only
-        per_cu = atoi(e);
-        if (per_cu > 0) return num_cu * per_cu;
-    }
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1) {
         (void)hipGetLastError();
         per_cu = 2;

@@ -32,11 +32,8 @@ constexpr int kBigRunMax = kMaxRunLengthBig;
 // 8192 decoders: seven waves of 17.4 KB beside 38 KB of tables -- the transform's 2048-entry twiddle table and the read half of its
 // level-2 table are in LDS too (read from global memory they cost the pass some twenty trips to the L2, one behind the other:
 // tools/kbench_slow_paths.py (c), 0.404 ms with eight waves and both in global memory, 0.376 with seven and the twiddles here)
-#ifndef VPZ_BIG_WAVES_8192
-#define VPZ_BIG_WAVES_8192 7
-#endif
-constexpr int kBigWaves8192 = VPZ_BIG_WAVES_8192;
-constexpr int kBigTw8192 = kBigWaves8192 <= 7 ? 2048 + 512 : 0;  // entries of the 8192 twiddle tables kept in LDS: tw, and the half of w2 that is read
+constexpr int kBigWaves8192 = 7;
+constexpr int kBigTw8192 = 2048 + 512;  // entries of the 8192 twiddle tables kept in LDS: tw, and the half of w2 that is read
 // wavefronts per workgroup: what the LDS holds -- 4 x 12.8 KB beside the tables for 4096 (two workgroups per CU), 8 x 17.4 KB for
 // 8192 (one; the tails are in global memory)
 __host__ __device__ inline int big_waves(int size1) { return size1 == 8192 ? kBigWaves8192 : 4; }
@@ -294,12 +291,8 @@ __global__ __launch_bounds__(kTailG ? 64 * kBigWaves8192 : 320, 1) void synth_bi
                 for (int m = 0; m < 8; ++m) { lo[m] = Xc[2 * m]; hi[m] = Xc[2 * m + 1]; }
                 const float2 *gt = (nblk == a.size1 ? a.tw_long : a.tw_short);
                 // (8192 is the long size, or both: the long set -- with the twiddle table behind it where that is staged)
-                const float2 *tw = (kTailG && kBigTw8192 > 0) ? tl + 1088 : gt + kFast8192TwOffset;
-#ifdef VPZ_BIG_W2_GLOBAL  // (A/B builds: the level-2 table read from global memory although its half is staged)
-                const float2 *w2 = gt + kFast8192W2Offset;
-#else
-                const float2 *w2 = (kTailG && kBigTw8192 > 0) ? tl + 1088 + 2048 : gt + kFast8192W2Offset;
-#endif
+                const float2 *tw = kTailG ? tl + 1088 : gt + kFast8192TwOffset;
+                const float2 *w2 = kTailG ? tl + 1088 + 2048 : gt + kFast8192W2Offset;
                 imdct8192_wave(lo, hi, h2, tw, w2, tl + 576, tl, tl + 512, ln);
             } else if (nblk == 4096) {
                 const float2 *tl = tables_of(4096);
@@ -350,10 +343,7 @@ __global__ __launch_bounds__(kTailG ? 64 * kBigWaves8192 : 320, 1) void synth_bi
                 // The window values (and, for 8192 decoders, the tail) come from global memory: a round that asks for its values and
                 // uses them at once waits a whole trip to the L2 -- sixteen trips in a row for an 8192 block.  Four rounds' loads are
                 // issued together, then their arithmetic and stores (lanes past the end clamp their reads and skip the store).
-#ifndef VPZ_BIG_OLA_ROUNDS
-#define VPZ_BIG_OLA_ROUNDS 4
-#endif
-                constexpr int kU = VPZ_BIG_OLA_ROUNDS;
+                constexpr int kU = 4;
                 for (int r0 = 0; r0 < nr; r0 += kU) {
                     float4 hv[kU], pv[kU], wl[kU], wr[kU];
                     bool in_[kU], live_[kU], pc_[kU];

@@ -381,13 +381,8 @@ __device__ __forceinline__ void store_pcm4(float4 *p, float4 v)
 __device__ __forceinline__ void store_pcm4_pair(float4 *p, float4 v0, float4 v1)
 {
     vpz_f4v t0 = {v0.x, v0.y, v0.z, v0.w}, t1 = {v1.x, v1.y, v1.z, v1.w};
-#ifdef VPZ_PAIR_STORES_NT
-    __builtin_nontemporal_store(t0, (VPZ_GLOBAL vpz_f4v *)reinterpret_cast<vpz_f4v *>(p));
-    __builtin_nontemporal_store(t1, (VPZ_GLOBAL vpz_f4v *)reinterpret_cast<vpz_f4v *>(p) + 1);
-#else
     *((VPZ_GLOBAL vpz_f4v *)reinterpret_cast<vpz_f4v *>(p)) = t0;
     *((VPZ_GLOBAL vpz_f4v *)reinterpret_cast<vpz_f4v *>(p) + 1) = t1;
-#endif
 }
 template <class T>
 __device__ __forceinline__ void store_pcm(T *p, T v) { *(VPZ_GLOBAL T *)p = v; }

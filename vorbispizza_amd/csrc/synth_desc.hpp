@@ -25,16 +25,6 @@ constexpr uint32_t kFrameStepsOffMask = 0xFFu;
 // bits 24..27: how many of the block's eight point groups (group m = bins [m * blocksize/16, (m + 1) * blocksize/16): the lane's
 // m-th point in every transform layout) lie wholly beyond the residue's support (ABI v4, vpz_mapping_config.residue_end) -- their
 // bins are +0.0 by the setup header's word and are neither loaded (group mode) nor de-coupled nor floor-multiplied.  0..8.
-// bit 28: the steady state of every stream -- a 2048 block after a 2048 block with long windows on both sides: PacketInfo
-// LeftStart 0, the overlap 1024 samples from position 1024 of the previous block, 1024 samples out, the size1 slope.  Settled
-// once where the descriptor is built (one lane per frame, or the host), so that the frame loop tests one bit instead of eight
-// fields (40 scalar instructions per pass, profiles/r4_isa_*.txt).
-constexpr uint32_t kFrameSteady = 1u << 28;
-__host__ __device__ inline bool frame_is_steady(uint32_t flags, int size1, int left_start, int packet_len, int prev_end, int out_count)
-{
-    return size1 == 2048 && (flags & kFrameLong) && (flags & kFrameSlope1) && !(flags & kFrameDrain) && left_start == 0 &&
-           packet_len == 1024 && prev_end == 1024 && out_count == 1024;
-}
 constexpr int kFrameSkipShift = 24;
 constexpr uint32_t kFrameSkipMask = 0xFu;
 // per-mapping word (SynthArgs.map_bits): steps count / offset as in the frame flags, the skip of a long block in bits 24..27,
@@ -59,10 +49,7 @@ static_assert(sizeof(FrameDesc) == 32, "FrameDesc is staged as two 16-byte words
 constexpr int kMaxRunLength = 32;
 constexpr int kMaxRunLengthGeneral = 16;  // the general-size kernel variant trades descriptor space for tables
 constexpr int kMaxRunLengthBig = 32;      // synth_big_kernel (4096 / 8192 blocks): a recomputed block is a whole big transform
-#ifndef VPZ_DUAL_WAVES
-#define VPZ_DUAL_WAVES 4   // wavefronts per workgroup of the stereo fast path (tuning builds: -DVPZ_DUAL_WAVES=10, one workgroup per CU)
-#endif
-constexpr int kMaxRunLengthDual = VPZ_DUAL_WAVES >= 10 ? 44 : 63;     // the stereo fast path: a run's frames (+ the recomputed one) are one lane each while
+constexpr int kMaxRunLengthDual = 63;     // the stereo fast path: a run's frames (+ the recomputed one) are one lane each while
                                           // its descriptors are built; runs cut to equal COST need the room -- a run rich in
                                           // short blocks holds many frames (capped at 32 frames, such runs were done in 3/4 of
                                           // the time of the others: the launch waited for the all-long ones)
@@ -144,17 +131,15 @@ struct FloorDev {
     uint32_t sorted[64];
 };
 
-// The tuning switches of the fused kernels (VPZ_SYNTH_ABLATE, VPZ_GROUP_DMA) exist in tuning builds only
-// (VPZ_EXTRA_HIPCC_FLAGS=-DVPZ_TUNING): in the product every test of them folds away at compile time.  They used to be
+// The tuning switch of the fused kernels (VPZ_SYNTH_ABLATE) exists in tuning builds only
+// (VPZ_EXTRA_HIPCC_FLAGS=-DVPZ_TUNING): in the product every test of it folds away at compile time.  They used to be
 // read from the kernel arguments inside the frame loop -- scalar loads whose `s_waitcnt lgkmcnt(0)` drains the wave's LDS
 // queue as well (profiles/r4_isa_*.txt).
 #ifdef VPZ_TUNING
 #define VPZ_ABLATE(a) ((a).ablate)
-#define VPZ_GROUP_DMA(a) ((a).group_dma != 0)
 #else
 __host__ __device__ constexpr int vpz_no_switches() { return 0; }  // (a call, so that `x && (0 & bit)` draws no warning)
 #define VPZ_ABLATE(a) vpz_no_switches()
-#define VPZ_GROUP_DMA(a) false
 #endif
 
 struct SynthArgs {
@@ -182,9 +167,6 @@ struct SynthArgs {
     int32_t n_step_pairs;
     int32_t max_steps;          // most coupling LEVELS any mapping has: barriers per frame in group mode
     int32_t group;              // 1: channels of a run share a workgroup (LDS staging), 0: waves are independent
-    int32_t group_dma;          // group mode: an interleaved packet lands in the group's rows AS IT IS ([bin][C], LDS-DMA) and every
-                                // wave picks its channel up with the inverse coupling applied in registers (even channel
-                                // counts, no channel in more than one step of any mapping)
     // type-0 floors in the stereo fast path (a record whose post count is kFloor0Marker): the record's curve over the bark
     // indices, curve[rec * f0_stride + k] (floor0_curve_kernel), and per (floor, block size) the bark index of every bin in the
     // order a lane holds its bins: f0_bark[(floor * 2 + long) * 1024 + lane * 16 + 2 * m + e] = barkMap[2 * (lane + 64 m) + e]
@@ -211,13 +193,12 @@ struct SynthArgs {
     int32_t clip;
     int32_t *clipped;           // [stream] sticky HasClipped
     int32_t no_batch;           // 1: one short block per pass (the host sets it when the runs were not cut by cost -- in runs of
-                                // equal LENGTH the ones rich in short blocks would be done early -- or for VPZ_NO_BATCH=1)
+                                // equal LENGTH the ones rich in short blocks would be done early -- or for VPZ_SYNTH_ABLATE bit 128)
     int32_t ablate;             // TUNING BUILDS ONLY (-DVPZ_TUNING; VPZ_SYNTH_ABLATE; wrong results, right timing): 1 no window / overlap-add / stores, 2 no
                                 // transform, 4 no input loads, 8 no curve, 16 no coupling, 32 no staging (group mode) / no stores
                                 // but the arithmetic (stereo path), 64 render every bin (group mode) / prologue only (stereo path),
                                 // 128 no batches of short blocks (also set by the host when runs were not cut by cost); stereo
-                                // path only: 256 no floor multiply, 512 no zero-tail bound, 1024 no tail save; group mode only: 2048 the interleaved
-                                // packet lands in the rows linearly by LDS-DMA (wrong results), 4096 ... as a per-channel dword gather (right results)
+                                // path only: 256 no floor multiply, 512 no zero-tail bound, 1024 no tail save
     unsigned long long *stamps; // diagnostic builds only (-DVPZ_STAMPS): [16] cycles per phase, summed over the waves
 };
 

@@ -444,75 +444,6 @@ __device__ __forceinline__ void stage_interleaved(const float2 (&x)[8], float *r
 }
 
 // ... or, for a planar packet, the wave's own channel straight into its row
-// Group mode, SynthArgs.group_dma: the packet lies in the group's rows as it came -- [bin][C], C even, i.e. C/2 float2 per bin
-// (stage_by_lds_dma below) -- and wave w takes the lane's 8 points of ITS channel out of it: the float2 that holds the channel,
-// and the one that holds the other channel of w's coupling step (`partner`, -1: none; usually the same float2), with the step
-// applied to the values in registers (Mapping.cs:166-225; a channel is in one step at most, so there is no order to keep).
-// Point kk = kk0 + kst * m is bins 2kk, 2kk + 1.  No ds_write, no coupling pass over LDS -- but 8-byte reads at a stride of C
-// dwords (2-way bank conflicts for C = 6) and every wave of a pair runs the step: measured SLOWER than the product's staging
-// (configs[3] 0.353 against 0.321 ms), hence opt-in only (VPZ_GROUP_DMA=1).
-__device__ __forceinline__ void pickup_interleaved(float2 (&x)[8], const float *rows, int C, int w, int partner, bool is_mag,
-                                                   int kk0, int kst)
-{
-    const float2 *v2 = reinterpret_cast<const float2 *>(rows);
-    const int hc = C >> 1;
-    const bool odd = w & 1, podd = partner & 1;
-    const float2 *own = v2 + (w >> 1) + 2 * kk0 * hc;
-    const float2 *oth = v2 + (partner >= 0 ? partner >> 1 : 0) + 2 * kk0 * hc;
-    const bool same = partner >= 0 && (partner >> 1) == (w >> 1);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const int o = 2 * kst * m * hc;
-        const float2 a0 = own[o], a1 = own[o + hc];
-        float s0 = odd ? a0.y : a0.x, s1 = odd ? a1.y : a1.x;
-        if (partner >= 0) {  // (wave-uniform)
-            float p0, p1;
-            if (same) {
-                p0 = odd ? a0.x : a0.y;
-                p1 = odd ? a1.x : a1.y;
-            } else {
-                const float2 b0 = oth[o], b1 = oth[o + hc];
-                p0 = podd ? b0.y : b0.x;
-                p1 = podd ? b1.y : b1.x;
-            }
-            if (is_mag) { couple(s0, p0); couple(s1, p1); }
-            else { couple(p0, s0); couple(p1, s1); }
-        }
-        x[m] = make_float2(s0, s1);
-    }
-}
-
-// ... landed there by LDS-DMA (`global_load_lds_dwordx4`: 16 bytes per lane straight from memory into LDS, a wave-load's 64
-// pieces back to back; no registers, no ds_write), wave w of the C taking pieces 64 w + lane + 64 C j.  The rows must have
-// been given up by the previous frame (they are one landing area: a piece lands in whichever row it falls into); the wave
-// waits for its pieces here -- nothing is in flight a frame ahead.  Also the timing experiment of VPZ_SYNTH_ABLATE bit 2048
-// (product pick-up on the landed vector: wrong results).
-__device__ __forceinline__ void stage_by_lds_dma(const float *src, float *rows, int C, int half, int w, int lane)
-{
-    const int total4 = (C * half) >> 2;  // 16-byte pieces of the packet
-    typedef __attribute__((address_space(1))) const void gvoid;
-    typedef __attribute__((address_space(3))) void lvoid;
-    asm volatile("" : "+v"(lane));
-    for (int g = 64 * w; g < total4; g += 64 * C)
-        __builtin_amdgcn_global_load_lds((gvoid *)(reinterpret_cast<const float4 *>(src) + g + lane), (lvoid *)(rows + 4 * g), 16, 0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// ... and as a GATHER (bit 4096; results are right): wave w asks for ITS channel's bins one dword per lane -- lane i of piece m
-// reads element (64 m + i) * C + w -- and LDS-DMA lands a wave-load's 64 dwords back to back: the row comes out de-interleaved,
-// no register, no ds_write, no strided LDS read.
-__device__ __forceinline__ void stage_by_lds_dma_gather(const float *src, float *row, int C, int half, int w, int lane)
-{
-    typedef __attribute__((address_space(1))) const void gvoid;
-    typedef __attribute__((address_space(3))) void lvoid;
-    asm volatile("" : "+v"(lane));
-    const float *p = src + (size_t)lane * C + w;
-    for (int b = 0; b < half; b += 64) {
-        if (b + lane < half) __builtin_amdgcn_global_load_lds((gvoid *)(p + (size_t)b * C), (lvoid *)(row + b), 4, 0, 0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 __device__ __forceinline__ void stage_planar(const float2 (&x)[8], float *row, int half, int lane, bool upper = true)
 {
     asm volatile("" : "+v"(lane));
@@ -585,15 +516,11 @@ __device__ __forceinline__ void emit_interleaved_rows(const float *rows, void *o
 // Floor: the wave renders its channel's curve (Floor1.cs:236-262, 372-397) from the record's active posts into its
 //       LDS row as one table index per bin, right before the row is needed for anything else.
 // kS16: PCM leaves as 16-bit samples (to_s16) instead of float32; offsets and strides count samples either way.
-// The steady state of a stream (2048 after 2048, long windows): tested field by field here.  The descriptor carries it as ONE
-// bit too (kFrameSteady, which the stereo fast path tests) -- measured in this kernel, the bit test is SLOWER: configs[3] 0.265 ms
-// with the eight field tests, 0.274 with the bit (three alternating rounds on one box, profiles/r4_ab_steady_bit.txt): the
-// compiler folds the geometry it has just compared into the branch's address arithmetic.  -DVPZ_GROUP_STEADY_BIT: the bit.
-#ifdef VPZ_GROUP_STEADY_BIT
-#define VPZ_STEADY(fd) ((fd).flags & kFrameSteady)
-#else
+// The steady state of a stream (2048 after 2048, long windows): tested field by field.  A one-bit flag settled where the
+// descriptor is built was measured SLOWER: configs[3] 0.265 ms with the eight field tests, 0.274 with the bit (three alternating
+// rounds on one box, profiles/r4_ab_steady_bit.txt): the compiler folds the geometry it has just compared into the branch's
+// address arithmetic.
 #define VPZ_STEADY(fd) (is_long && ((fd).flags & kFrameSlope1) && (fd).left_start == 0 && plen == 1024 && (fd).prev_end == 1024 && (fd).out_count == 1024 && k_size1 == 2048)
-#endif
 template <bool kHasFloor, int kOut, bool kGeneral, bool kGroup, bool kS16>
 __global__ __launch_bounds__(kSynthThreads, 4) void synth_kernel(SynthArgs a)
 {
@@ -774,9 +701,8 @@ __global__ __launch_bounds__(kSynthThreads, 4) void synth_kernel(SynthArgs a)
             const int hh = (size_of(fd.flags) >> 1) * (kBatchShort ? (int)((fd.flags >> kFrameBatchShift) & 7u) + 1 : 1);
             const bool shared_input = fd.flags & kFrameInterleaved;
             const VPZ_GLOBAL float *src = k_spec + fd.spec_off + (shared_input ? 0 : (int64_t)ch * hh);
-            const bool regs = valid && !(shared_input && (VPZ_GROUP_DMA(a) || (VPZ_ABLATE(a) & (2048 | 4096))));  // (the packet comes by LDS-DMA)
-            load_group_share(x, regs ? src : k_inv_db, shared_input ? 64 * ch : 0, shared_input ? 64 * C : 64,
-                             regs ? support_pieces(fd.flags, shared_input ? C : 1, hh) : 1, lane);
+            load_group_share(x, valid ? src : k_inv_db, shared_input ? 64 * ch : 0, shared_input ? 64 * C : 64,
+                             valid ? support_pieces(fd.flags, shared_input ? C : 1, hh) : 1, lane);
         } else {
             load_spectrum(x, ex ? spectrum_of(fd) : k_inv_db, ex ? lpb_of(fd.flags) : 1, lane);
         }
@@ -865,7 +791,6 @@ __global__ __launch_bounds__(kSynthThreads, 4) void synth_kernel(SynthArgs a)
             const int plen_d = (has_prev && !(cf & kCfSkip)) ? prev_stop - prev_end : 0, pend_d = (has_prev && !(cf & kCfSkip)) ? prev_end : 0;
             hi.y = (uint32_t)left_start | ((uint32_t)plen_d << 16);
             hi.z = (uint32_t)pend_d | ((uint32_t)out_count << 16);
-            if (frame_is_steady(fl, a.size1, left_start, plen_d, pend_d, out_count)) fl |= kFrameSteady;
             hi.w = fl;
             s_desc[wave][2 * lane] = lo;
             s_desc[wave][2 * lane + 1] = hi;
@@ -1012,11 +937,7 @@ __global__ __launch_bounds__(kSynthThreads, 4) void synth_kernel(SynthArgs a)
             __syncthreads();  // every wave of the group is done with its row (previous block emitted)
             VPZ_STAMP(1);  // first barrier
             if (stage && !(VPZ_ABLATE(a) & 32)) {
-                if ((fd.flags & kFrameInterleaved) && (VPZ_ABLATE(a) & 4096)) {
-                    stage_by_lds_dma_gather((const float *)(k_spec + fd.spec_off), hcur, C, nstage >> 1, ch, lane);
-                } else if ((fd.flags & kFrameInterleaved) && (VPZ_GROUP_DMA(a) || (VPZ_ABLATE(a) & 2048))) {
-                    stage_by_lds_dma((const float *)(k_spec + fd.spec_off), s_work[gw0], C, nstage >> 1, ch, lane);
-                } else if (fd.flags & kFrameInterleaved) {
+                if (fd.flags & kFrameInterleaved) {
                     if (!kKeepStagePositions) {
                         int lo = lane;
                         asm volatile("" : "+v"(lo));  // (per frame here: an opaque lane id keeps the compiler from hoisting them after all)
@@ -1039,26 +960,9 @@ __global__ __launch_bounds__(kSynthThreads, 4) void synth_kernel(SynthArgs a)
                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)stwcur.x);
             // byte k of the mapping's steps: out of the prefetched word while the mapping has at most four
             auto step_byte = [&](int k) -> uint32_t { return n_steps <= 4 ? (uint32_t)(stw >> (8 * k)) & 0xFFu : (uint32_t)st[k]; };
-            // (group_dma) the packet lies in the rows as it came: every wave takes its channel out of it, its own coupling step
-            // applied on the way; the barrier(s) below then stand between the last pick-up and the first transform
-            const bool in_place = stage && VPZ_GROUP_DMA(a) && (fd.flags & kFrameInterleaved);
-            if (in_place && (exec || batch)) {  // [census: cold]
-                int partner = -1;
-                bool is_mag = false;
-                for (int k = 0; k < n_steps; ++k) {
-                    const int sm = (int)(step_byte(2 * k) & 0x7F), sa = (int)step_byte(2 * k + 1);
-                    if (sm == ch) { partner = sa; is_mag = true; }
-                    else if (sa == ch) { partner = sm; }
-                }
-                if (VPZ_ABLATE(a) & 16) partner = -1;
-                int lb = lane;
-                asm volatile("" : "+v"(lb));  // (frame-invariant LDS addresses: keep them inside the iteration)
-                const int lpb = batch ? 8 : lpb_of(fd.flags);
-                pickup_interleaved(xcur, s_work[gw0], C, ch, partner, is_mag, batch ? (lb >> 3) * 64 + (lb & 7) : (lb & (lpb - 1)), lpb);
-            }
-            const int n_levels = VPZ_GROUP_DMA(a) ? max(k_max_steps, 1) : k_max_steps;
+            const int n_levels = k_max_steps;
             for (int lvl = 0; lvl < n_levels; ++lvl) {
-                if (stage && !in_place && !(VPZ_ABLATE(a) & 16)) {
+                if (stage && !(VPZ_ABLATE(a) & 16)) {
                     bool first = true;
                     while (sidx >= 0 && (first || !(step_byte(2 * sidx) & 0x80))) {
                         float4 *pm = reinterpret_cast<float4 *>(s_work[gw0 + (step_byte(2 * sidx) & 0x7F)]);
@@ -1079,9 +983,7 @@ __global__ __launch_bounds__(kSynthThreads, 4) void synth_kernel(SynthArgs a)
                 __syncthreads();
             }
             VPZ_STAMP(3);  // coupling levels + barriers
-            if (in_place) {
-                // (already in xcur)
-            } else if (batch) {  // lane group g takes block g of the batch: points l + 8 m of its 64  [census: cold]
+            if (batch) {  // lane group g takes block g of the batch: points l + 8 m of its 64  [census: cold]
                 const float2 *row2 = reinterpret_cast<const float2 *>(hcur);
                 int lb = lane;
                 asm volatile("" : "+v"(lb));
@@ -1714,13 +1616,12 @@ hipError_t launch_synth(const SynthArgs &args, bool has_floor, hipStream_t strea
                            : (int)((items + kSynthWaves - 1) / kSynthWaves);
     // the interleaved store patterns cost registers the planar steady state needs: one instantiation each
     const int out_kind = !args.interleaved ? 0 : (args.channels == 2 ? 2 : 1);
-    static const int extra_lds = getenv("VPZ_SYNTH_EXTRA_LDS") ? atoi(getenv("VPZ_SYNTH_EXTRA_LDS")) : 0;  // occupancy experiments
 #define VPZ_LAUNCH_SYNTH(F, O, G, R)                                                                                  \
     do {                                                                                                              \
         if (args.s16)                                                                                                 \
-            hipLaunchKernelGGL((synth_kernel<F, O, G, R, true>), dim3(grid), dim3(kSynthThreads), extra_lds, stream, args);  \
+            hipLaunchKernelGGL((synth_kernel<F, O, G, R, true>), dim3(grid), dim3(kSynthThreads), 0, stream, args);  \
         else                                                                                                          \
-            hipLaunchKernelGGL((synth_kernel<F, O, G, R, false>), dim3(grid), dim3(kSynthThreads), extra_lds, stream, args); \
+            hipLaunchKernelGGL((synth_kernel<F, O, G, R, false>), dim3(grid), dim3(kSynthThreads), 0, stream, args); \
     } while (0)
 #define VPZ_LAUNCH_SYNTH_OUT(F, G, R)                      \
     do {                                                   \

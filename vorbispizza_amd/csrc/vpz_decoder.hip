@@ -99,6 +99,11 @@ struct PinnedArena {
     DevBuf dev;  // device mirror, same layout: one hipMemcpyAsync per call
 };
 
+// arenas up to this size are read in place by the kernels (half a million packets, 1.5 MB: 2.42 -> 2.35 ms against the copy)
+constexpr size_t kZeroCopyMax = 8u << 20;
+// cut_runs, THE SKEW: how much heavier (per mille) the runs of the first half of a batch's work are cut
+constexpr int kCutSkewPermille = 25;
+
 // Mode.cs:30-66
 struct PacketInfo {
     int length, left_use_size1, left_start, left_end, right_start, right_end;
@@ -169,14 +174,11 @@ struct Decoder {
     std::vector<CutSeg> cut_segs;            // the streams of a call, long ones of a batch of few streams in pieces (cut_runs)
     std::vector<int64_t> s_units;            // cost of each segment's packets in this call (cut_runs), then
     std::vector<int64_t> cut_prefix;         // ... the cost of all segments in front of each one
-    size_t zero_copy_max = 8u << 20;         // arenas up to this size are read in place by the kernels (VPZ_ZERO_COPY_MAX;
-                                             // half a million packets, 1.5 MB: 2.42 -> 2.35 ms against the copy)
     std::vector<int32_t> mapping_steps_off;  // per mapping: offset into d_steps (pairs*2), -1 none
     std::vector<uint8_t> mapping_skip[2];    // per mapping and block size: point groups (of 8) beyond the residue's support (ABI v4)
     DevBuf b_curve, b_temp, b_cposts, b_ccount;
     // group mode of synth_kernel (channels of a packet share a workgroup; de-interleave + coupling in LDS)
     bool group_ok = false;       // channel count, step tables and floor types allow it
-    bool group_dma = false;      // ... and interleaved packets may land in LDS as they are (SynthArgs.group_dma)
     // stereo fast path (synth_dual.hip: one wavefront per stream synthesises both channels, coupling in registers)
     bool dual_ok = false;        // two channels, 256 / 2048 blocks, type-1 floors only (VPZ_NO_DUAL=1: off, for A/B tests)
     // ... and its kernel for channel PAIRS (synth_pairs.hip): 4, 6, 8, ... channels that the coupling steps of all mappings join two
@@ -214,10 +216,8 @@ struct Decoder {
     const float *f0_amp = nullptr, *f0_coeff = nullptr;
     int32_t f0_stride = 0;
     PacketInfo packet_info[8];  // Mode.GetPacketInfo by (block | prev << 1 | next << 2) == vpz_packet.flags & 7
-    int run_length_override = 0;
     int dual_run = 8;  // preferred run length of the stereo fast path's chained runs (VPZ_DUAL_RUN)
     bool no_direct_i16 = false;
-    bool no_run_inline = false;
     bool no_chain = false;  // VPZ_NO_CHAIN=1 (A/B tests): no run of the stereo fast path takes its predecessor's tail over in LDS
     int ablate = 0;  // VPZ_SYNTH_ABLATE, tuning experiments only
     bool no_early_upload = false;  // VPZ_NO_EARLY_UPLOAD=1 (A/B tests): a host-memory call's H2D copies stay behind its host pass
@@ -238,11 +238,9 @@ static int arena_begin(Context *ctx, PinnedArena &A, size_t need)
     }
     // (the event says "the arena's last readers are done", nothing about memory: without the system-scope fence a default event
     // carries -- a write-back and invalidation of the device's caches behind every call -- the next call's kernels follow this
-    // call's without that pause; VPZ_ARENA_EVENT_FENCE=1 restores the default event for A/B runs)
-    if (!A.uploaded) {
-        static const bool fence = getenv("VPZ_ARENA_EVENT_FENCE") && atoi(getenv("VPZ_ARENA_EVENT_FENCE"));
-        VPZ_HIP_TRY(ctx, hipEventCreateWithFlags(&A.uploaded, hipEventDisableTiming | (fence ? 0u : (unsigned)hipEventDisableSystemFence)));
-    }
+    // call's without that pause)
+    if (!A.uploaded)
+        VPZ_HIP_TRY(ctx, hipEventCreateWithFlags(&A.uploaded, hipEventDisableTiming | hipEventDisableSystemFence));
     if (A.cap < need) {
         if (A.base) VPZ_HIP_TRY(ctx, hipHostFree(A.base));
         A.base = nullptr;
@@ -384,15 +382,10 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
     D.mappings.assign(cfg->mappings, cfg->mappings + cfg->mapping_count);
     static_assert(VPZ_PKT_BLOCK_FLAG == 1 && VPZ_PKT_PREV_FLAG == 2 && VPZ_PKT_NEXT_FLAG == 4, "packet_info index");
     for (int f = 0; f < 8; ++f) D.packet_info[f] = get_packet_info(D.size0, D.size1, f & 1, f & 2, f & 4);
-    if (const char *e = getenv("VPZ_RUN_LENGTH")) D.run_length_override = atoi(e);
     if (const char *e = getenv("VPZ_NO_DIRECT_I16")) D.no_direct_i16 = atoi(e) != 0;  // A/B and bit-equality tests: always widen int16 residue first
-    if (const char *e = getenv("VPZ_NO_RUN_INLINE")) D.no_run_inline = atoi(e) != 0;  // A/B tests: flag bytes from cflags / cmap only
     if (const char *e = getenv("VPZ_NO_CHAIN")) D.no_chain = atoi(e) != 0;  // A/B tests: every run recomputes its predecessor block
     if (const char *e = getenv("VPZ_DUAL_RUN")) D.dual_run = std::max(4, atoi(e));
     if (const char *e = getenv("VPZ_SYNTH_ABLATE")) D.ablate = atoi(e);
-    if (const char *e = getenv("VPZ_NO_BATCH")) {  // A/B tests: one short block per pass, runs of equal length
-        if (atoi(e)) D.ablate |= 128;
-    }
     if (const char *e = getenv("VPZ_HOST_THREADS")) D.host_threads = atoi(e);
     if (const char *e = getenv("VPZ_NO_EARLY_UPLOAD")) D.no_early_upload = atoi(e) != 0;
     if (const char *e = getenv("VPZ_PAR_MIN_PACKETS")) D.par_min_packets = atoll(e);
@@ -482,25 +475,9 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
         D.dual_ok = synth_dual_supported(D.channels, D.size0, D.size1) && !D.generic && (!has_floor0 || D.f0_fused) && D.max_steps <= 255 &&
                     D.n_step_pairs <= kGroupMaxStepPairs && !(no_dual && atoi(no_dual));
         D.f0_fused = D.f0_fused && D.dual_ok;
-        // every channel in at most one step of its mapping (then a mapping has one level, and a wave can apply its own step
-        // to the pair of values it reads): the packet may stay interleaved in LDS
-        bool single_step = true;
-        for (size_t m = 0; m < D.mappings.size() && rc == VPZ_OK; ++m) {  // (the step tables are complete only then)
-            uint32_t seen[8] = {};
-            const int n = D.mappings[m].coupling_steps, off = D.mapping_steps_off[m];
-            for (int i = 0; i < n; ++i)
-                for (int k = 0; k < 2; ++k) {
-                    const uint8_t c = steps[off + 2 * i + k];
-                    if (seen[c >> 5] >> (c & 31) & 1) single_step = false;
-                    seen[c >> 5] |= 1u << (c & 31);
-                }
-        }
-        const char *want_dma = getenv("VPZ_GROUP_DMA");  // measured slower than staging through registers: opt-in
-        D.group_dma = D.group_ok && single_step && (D.channels & 1) == 0 && D.max_steps <= 4 && want_dma && atoi(want_dma);
         D.max_steps = max_levels;  // from here on: the barriers a frame's coupling needs in group mode
         const char *nc = getenv("VPZ_NO_COMPACT");
         D.no_compact = nc && atoi(nc);
-        if (const char *z = getenv("VPZ_ZERO_COPY_MAX")) D.zero_copy_max = (size_t)atoll(z);
     }
     if (rc != VPZ_OK) {  // (before anything below indexes the floor / step tables with values that failed validation)
         delete d;
@@ -867,8 +844,8 @@ struct SynthCall {
         bool has_floor0_type = false;
         for (uint8_t t : D.floor_types) has_floor0_type |= (t == 0);
         const size_t np = (size_t)n_packets;
-        // (runs hold >= 3 frames unless VPZ_RUN_LENGTH says otherwise: see cut_runs)
-        size_t need = (sizeof(FrameDesc) + (D.run_length_override > 0 ? sizeof(RunDesc) + 32 : sizeof(RunDesc) / 2 + 16) + 2 +
+        // (runs hold >= 3 frames: see cut_runs)
+        size_t need = (sizeof(FrameDesc) + sizeof(RunDesc) / 2 + 16 + 2 +
                        coupling_packet_size()) * np +
                       sizeof(RunDesc) * ((size_t)D.n_streams + 1 + 4 * 64) + (have_posts ? (size_t)n_rec : 0) +  // (+ the pieces of long streams)
                       sizeof(int64_t) * (size_t)D.n_streams + 4096;
@@ -922,8 +899,7 @@ struct SynthCall {
         if (parties < 2) return 0;
         if (!ctx->host_pool || static_cast<HostPool *>(ctx->host_pool)->parties() != parties) {
             if (ctx->host_pool) ctx->host_pool_free(ctx->host_pool);
-            static const int spin_us = getenv("VPZ_HOST_SPIN_US") ? atoi(getenv("VPZ_HOST_SPIN_US")) : 50;
-            ctx->host_pool = new HostPool(parties, spin_us);
+            ctx->host_pool = new HostPool(parties);
             ctx->host_pool_free = [](void *p) { delete static_cast<HostPool *>(p); };
         }
         HostPool &pool = *static_cast<HostPool *>(ctx->host_pool);
@@ -1141,7 +1117,6 @@ struct SynthCall {
                         fd.spec_off = pk.residue_offset;
                     }
                     fd.out_off = run;
-                    if (frame_is_steady(fd.flags, D.size1, fd.left_start, fd.packet_len, fd.prev_end, fd.out_count)) fd.flags |= kFrameSteady;
                     frames[p] = fd;
                 }
                 run += psamples[p];
@@ -1220,7 +1195,6 @@ struct SynthCall {
                     if (!compact) {
                         frames[L].out_count = (uint16_t)cnt;
                         frames[L].left_start = (uint16_t)start;
-                        frames[L].flags &= ~kFrameSteady;  // (an EOS trim changed the geometry)
                     }
                 }
                 if (pk.granule != -1 && !has_pos) {  // :459-463 at the last packet itself
@@ -1376,7 +1350,6 @@ struct SynthCall {
             else planar_seen = true;
             if (pk.residue_offset & 3) group_align_ok = false;  // group mode reads every packet in 16-byte pieces
             if (pk.residue_offset & 1) align2_ok = false;
-            if (frame_is_steady(fd.flags, D.size1, fd.left_start, fd.packet_len, fd.prev_end, fd.out_count)) fd.flags |= kFrameSteady;
             frames[s_base[pk.stream] + s_cnt[pk.stream]++] = fd;
         }
         for (int s = 0; s < D.n_streams; ++s)
@@ -1446,14 +1419,11 @@ struct SynthCall {
             return ok && prev_in_run_ok && !(pp.flags & VPZ_PKT_BLOCK_FLAG) && pk.mapping == pp.mapping &&
                    ((pk.flags ^ pp.flags) & VPZ_PKT_NO_FLOOR) == 0;
         };
-        // cost of a pass in eighths of a long block's (group mode, tools/kbench_short_long.py: a short block alone 0.74, eight
-        // in one batch 3.2 together; the stereo fast path, fitted to the waves' durations on real streams -- tools/wave_times.sh,
-        // wave_times_fit.py: a short block alone or at the head of a batch costs a whole pass, 8.6 / 7.7 eighths, every block
+        // cost of a pass in eighths of a long block's (group mode, measured: a short block alone 0.74, eight
+        // in one batch 3.2 together; the stereo fast path, fitted to the waves' durations on real streams -- -DVPZ_WAVE_TIMES,
+        // HISTORY.md: a short block alone or at the head of a batch costs a whole pass, 8.6 / 7.7 eighths, every block
         // riding along 2.0)
-        int w_short = use_dual ? 8 : 6, w_member = use_dual ? 2 : 3;
-        if (const char *w = getenv("VPZ_CUT_WEIGHTS")) (void)sscanf(w, "%d,%d", &w_short, &w_member);  // tuning
-        w_short = std::min(std::max(w_short, 1), 8);  // (a frame costs at most a whole pass: see the runs' capacity below)
-        w_member = std::min(std::max(w_member, 1), 8);
+        const int w_short = use_dual ? 8 : 6, w_member = use_dual ? 2 : 3;
         auto unit_cost = [&](int64_t p, bool ok, int pos) -> int {
             if (ok && (pos & 7) != 0) return w_member;
             return (batches && !(packets[p].flags & VPZ_PKT_BLOCK_FLAG)) ? w_short : 8;
@@ -1466,7 +1436,7 @@ struct SynthCall {
         // packets are walked ONCE (codes and cut together, one fork-join), and only if the runs do not fit the rounds
         // after all is the whole procedure gone through
         const bool reuse = batches && parties > 1 && D.cut_hint_frames == total_frames && D.cut_hint_streams == D.n_streams &&
-                           D.cut_hint_R > 0 && D.run_length_override <= 0;
+                           D.cut_hint_R > 0;
         auto packet_code = [&](int64_t p, bool ok) -> uint8_t {
             return (uint8_t)(((packets[p].flags & VPZ_PKT_BLOCK_FLAG) ? 0 : 1) | (ok ? 2 : 0) |
                              ((ok && p > 0 && packets[p].mapping == packets[p - 1].mapping &&
@@ -1501,7 +1471,7 @@ struct SynthCall {
             total_units = 0;
             for (int64_t v : part) total_units += v;
         }
-        int R = reuse ? D.cut_hint_R : std::min(D.run_length_override, r_max);
+        int R = reuse ? D.cut_hint_R : 0;
         int64_t run_slots = reuse ? D.cut_hint_slots : 0;  // runs that fit the rounds R was chosen for
         bool single_round = false;  // every run has a resident wave slot of its own from the start of the launch
         if (R <= 0) {
@@ -1546,8 +1516,7 @@ struct SynthCall {
         if (runs_arena_mark == (size_t)-1) runs_arena_mark = A->used;
         A->used = runs_arena_mark;
         // (... and the lighter half of a skewed cut holds that much less: see THE SKEW below)
-        static const int skew_cap_permille = [] { const char *e = getenv("VPZ_CUT_SKEW"); return e ? std::max(0, atoi(e)) : 25; }();
-        const int min_run_frames = std::max(1, R - 1 - ((skew_cap_permille > 0 && R >= 16) ? R * skew_cap_permille / 1000 + 2 : 0));
+        const int min_run_frames = std::max(1, R - 1 - (R >= 16 ? R * kCutSkewPermille / 1000 + 2 : 0));
         // (every segment -- a stream, or a piece of a long one -- ends with a partial run)
         runs_cap = (size_t)(total_frames / min_run_frames) + (size_t)std::max(n_segs, D.n_streams) + 1;
         runs = arena_alloc<RunDesc>(*A, runs_cap);  // (throws ArenaOverflow -> VPZ_E_NOMEM: open_arena's budget is R >= 4 runs)
@@ -1576,15 +1545,14 @@ struct SynthCall {
         if (reuse) target_units = D.cut_hint_target;
         // THE SKEW.  With one round of runs, the first half of the grid's workgroups are the first to arrive on their CUs and
         // the second half join them as each CU's second workgroup -- and the waves of the second arrivals run slower for the
-        // whole launch (measured per wave, tools/wave_times.sh: identical runs take 600 k cycles in wave slot 0 of their SIMD,
+        // whole launch (measured per wave, -DVPZ_WAVE_TIMES: identical runs take 600 k cycles in wave slot 0 of their SIMD,
         // 647 k in slot 1; priorities set with s_setprio do not change it), so with equal work the early half idles at the end
         // while the late half finishes at half occupancy.  Runs that start in the first half of the batch's WORK -- they are
-        // the first half of the grid -- are therefore cut 2 % heavier, the others as much lighter (tools/try_cut_skew.sh:
+        // the first half of the grid -- are therefore cut 2 % heavier, the others as much lighter (HISTORY.md:
         // configs[4] 0.283 -> 0.278 ms at 20 per mille, worse again from 40 on).
-        static const int skew_permille = [] { const char *e = getenv("VPZ_CUT_SKEW"); return e ? std::max(0, atoi(e)) : 25; }();
         int64_t heavy_work = reuse ? D.cut_hint_heavy : -1;
-        if (batches && !reuse && single_round && use_dual && skew_permille > 0 && R >= 16) {  // (short runs: nothing to skew by)
-            heavy_work = total_units * (1000 + skew_permille) / 2000;
+        if (batches && !reuse && single_round && use_dual && R >= 16) {  // (short runs: nothing to skew by)
+            heavy_work = total_units * (1000 + kCutSkewPermille) / 2000;
             D.cut_prefix.resize((size_t)n_segs);
             int64_t acc = 0;
             for (int st_i = 0; st_i < n_segs; ++st_i) {
@@ -1595,13 +1563,12 @@ struct SynthCall {
         if (heavy_work >= 0 && D.cut_prefix.size() != (size_t)n_segs) heavy_work = -1;
         // (all-long batches only: with short blocks in runs of equal length a frame more is not 3 % more -- configs[2] lost 2 %)
         // (group mode -- 6 channels, two workgroups of 8 waves per CU -- does not respond to it: configs[3] 0.323 either way)
-        const bool skew_frames = !batches && !any_short && single_round && use_dual && skew_permille > 0 && R >= 24 &&
-                                 R + 1 <= r_max && D.run_length_override <= 0;
+        const bool skew_frames = !batches && !any_short && single_round && use_dual && R >= 24 && R + 1 <= r_max;
         const int64_t heavy_frames = total_frames * (R + 1) / (2 * (int64_t)R);  // the first half of the frames' work at R + 1 each
         // the target of the run of stream `st_i` that starts `before` cost units into its stream
         auto target_at = [&](int st_i, int64_t before, int64_t target) -> int64_t {
             if (heavy_work < 0) return target;
-            const int64_t sk = target * skew_permille / 1000;
+            const int64_t sk = target * kCutSkewPermille / 1000;
             return D.cut_prefix[(size_t)st_i] + before < heavy_work ? target + sk : target - sk;
         };
         if (batches && run_slots > 0 && !reuse) {
@@ -1871,7 +1838,7 @@ struct SynthCall {
         }
         if (!need_coupling || use_group || use_dual) return;
         // the separate pass hands planar, de-coupled spectra over: the frames lose their group-mode bits
-        for (size_t fi = 0; fi < n_frames; ++fi) frames[fi].flags &= 0xFu | (kFrameSkipMask << kFrameSkipShift) | kFrameSteady;
+        for (size_t fi = 0; fi < n_frames; ++fi) frames[fi].flags &= 0xFu | (kFrameSkipMask << kFrameSkipShift);
         const size_t cps = coupling_packet_size();
         cpk = arena_alloc<uint8_t>(*A, cps * n_frames);
         for (size_t fi = 0; fi < n_frames; ++fi) {
@@ -2124,7 +2091,7 @@ struct SynthCall {
         // pinned host memory (each wave fetches its 64-byte run record and two bytes per frame once, at its start).
         // That takes a DMA command and its two command-processor gaps (~25 us) off every call; the arena stays
         // untouched until the kernels are done (`uploaded` is recorded after the launches in that case).
-        zero_copy = A->mapped != nullptr && A->used <= D.zero_copy_max && !D.generic;
+        zero_copy = A->mapped != nullptr && A->used <= kZeroCopyMax && !D.generic;
         if (!zero_copy) {
             VPZ_HIP_TRY(ctx, hipMemcpyAsync(A->dev.p, A->base, A->used, hipMemcpyHostToDevice, ctx->stream));
             VPZ_HIP_TRY(ctx, hipEventRecord(A->uploaded, ctx->stream));
@@ -2216,7 +2183,7 @@ struct SynthCall {
         a.frames = static_cast<const FrameDesc *>(dev(frames));
         a.cflags = static_cast<const uint8_t *>(dev(cflags));
         a.cmap = static_cast<const uint8_t *>(dev(cmap));
-        a.run_inline = (use_dual && !D.no_run_inline) ? static_cast<const uint8_t *>(dev(run_inline)) : nullptr;
+        a.run_inline = use_dual ? static_cast<const uint8_t *>(dev(run_inline)) : nullptr;
         a.map_bits = D.d_map_bits;
         a.pair_ch = D.d_pair_ch;
         a.n_pairs = C / 2;
@@ -2243,7 +2210,6 @@ struct SynthCall {
             a.n_step_pairs = D.n_pair_step_pairs;
         }
         a.group = use_group ? 1 : 0;
-        a.group_dma = (use_group && D.group_dma) ? 1 : 0;
         a.inv_db = ctx->d_inv_db;
         a.f0_curve = static_cast<const float *>(D.b_f0curve.p);
         a.f0_bark = D.d_f0_bark;
@@ -2426,14 +2392,8 @@ static int synth_impl(vpz_decoder *d, int64_t n_packets, const vpz_packet *packe
     if ((rc = call.stage_inputs()) != VPZ_OK) return rc;
     if ((rc = call.launch()) != VPZ_OK) return rc;
     if (call.zero_copy) {  // the kernels read the arena itself: it is free again when they are done
-#ifdef VPZ_TUNING  // (timing experiments only, WRONG in general: no event behind the call -- what does the queue's barrier packet cost?)
-        static const bool no_event = getenv("VPZ_UNSAFE_NO_ARENA_EVENT") != nullptr;
-        if (!no_event)
-#endif
-        {
-            VPZ_HIP_TRY(ctx, hipEventRecord(call.A->uploaded, ctx->stream));
-            call.A->pending = true;
-        }
+        VPZ_HIP_TRY(ctx, hipEventRecord(call.A->uploaded, ctx->stream));
+        call.A->pending = true;
     }
     if ((rc = call.copy_back()) != VPZ_OK) return rc;
     early_guard.completed = mem_space == VPZ_MEM_HOST;  // (copy_back has waited for the stream)

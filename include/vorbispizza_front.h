@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "vorbispizza_synth.h"
+#include "vorbispizza_entropy.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -132,6 +133,25 @@ int vpzh_decode_many_progress(int32_t n, int32_t channels, const uint8_t *const 
  * rest of the range decodes normally and the call returns VPZH_OK.  Returns the number of such packets;
  * *first_failed_packet = index of the first one relative to `first` (-1 if none); vpzh_last_error has its text. */
 int64_t vpzh_decode_failures(vpzh_stream *s, int64_t *first_failed_packet);
+
+/* ---- the entropy decode on the GPU (vorbispizza_entropy.h) ----
+ * vpzh_gpu_decode_supported: 1 when vpz_entropy_decode can decode this stream's packets -- every floor is type 1, every
+ * residue's value books tile its partitions, every Floor1 master / subclass book and every residue class book is usable --,
+ * else 0 with the reason in vpzh_last_error.  For such a setup no packet's decode can fail except by an unused mode number,
+ * which the plan already sees: the device decode never changes a packet's flags.
+ * vpzh_get_entropy_setup: writes the setup image (vorbispizza_entropy.h) to buf[capacity]; *size receives its size
+ * (buf may be NULL to ask for it; VPZH_E_ARG when capacity is too small, nothing written).  VPZH_E_UNSUPPORTED for a stream
+ * that is not supported.  Streams with equal setup headers give byte-identical images.
+ * vpzh_plan_range: the packet records vpzh_decode_range_ex writes for [first, first + count) -- flags, granule, mapping,
+ * residue offsets -- from the packet-type bit, the mode number and the window flags alone, and each packet's bytes copied to
+ * payload with spans[k] = {offset, size} relative to `payload`, followed by at least 8 zero bytes.  *payload_used: bytes of
+ * payload used (padding included), *residue_used: residue values of the range.  payload NULL (capacity 0): only the sizes.
+ * VPZH_E_ARG when payload_capacity is too small (nothing written). */
+int vpzh_gpu_decode_supported(vpzh_stream *s);
+int vpzh_get_entropy_setup(vpzh_stream *s, void *buf, uint64_t capacity, uint64_t *size);
+int vpzh_plan_range(vpzh_stream *s, int64_t first, int64_t count, int32_t stream_id, int64_t residue_base,
+                    vpz_packet *packets, vpz_entropy_span *spans, uint8_t *payload, int64_t payload_capacity,
+                    int64_t *payload_used, int64_t *residue_used);
 
 #ifdef __cplusplus
 }

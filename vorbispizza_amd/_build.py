@@ -25,6 +25,7 @@ SOURCES = {
     "floor0.hip": ["-ffp-contract=off"],
     "vpz_context.hip": ["-ffp-contract=off"],
     "vpz_decoder.hip": ["-ffp-contract=off"],
+    "entropy.hip": ["-ffp-contract=off"],  # the residue sums: plain adds in the CPU front end's order
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-constant-logical-operand", "-fno-strict-aliasing"]
@@ -45,6 +46,7 @@ def _deps(src):
         if name.endswith(".hpp"):
             deps.append(os.path.join(CSRC, name))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_synth.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_entropy.h"))
     return deps
 
 
@@ -60,7 +62,8 @@ def build_host(force=False, verbose=False):
             os.path.join(HOST_DIR, "vorbis_multi.cpp")]
     inc = os.path.join(_HERE, "..", "include")
     deps = srcs + [os.path.join(inc, "vorbispizza_front.h"), os.path.join(inc, "vorbispizza_reader.h"),
-                   os.path.join(inc, "vorbispizza_multi.h"), os.path.join(inc, "vorbispizza_synth.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi.h"), os.path.join(inc, "vorbispizza_synth.h"),
+                   os.path.join(inc, "vorbispizza_entropy.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

@@ -79,6 +79,14 @@ def lib():
         L.vpzh_default_threads.restype = C.c_int
         L.vpzh_decode_failures.argtypes = [vp, C.POINTER(C.c_int64)]
         L.vpzh_decode_failures.restype = C.c_int64
+        # the entropy decode on the GPU (vorbispizza_entropy.h): eligibility, setup image, plan
+        L.vpzh_gpu_decode_supported.argtypes = [vp]
+        L.vpzh_gpu_decode_supported.restype = C.c_int
+        L.vpzh_get_entropy_setup.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.vpzh_get_entropy_setup.restype = C.c_int
+        L.vpzh_plan_range.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, C.c_int64, vp, vp, vp, C.c_int64,
+                                      C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.vpzh_plan_range.restype = C.c_int
         # VorbisReader mirror (include/vorbispizza_reader.h)
         L.vpzr_open_memory.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp)]
         L.vpzr_open_memory.restype = C.c_int
@@ -225,6 +233,42 @@ class OggVorbisFile:
         if rc != 0:
             raise FrontError(lib().vpzh_last_error(self._h).decode())
         return packets, residue[: self.info.residue_floats], posts, counts
+
+    @property
+    def gpu_decode_supported(self):
+        """vpzh_gpu_decode_supported: vpz_entropy_decode can decode this stream's packets (every floor type 1, tiling
+        residues); when not, last_error() says why"""
+        return bool(lib().vpzh_gpu_decode_supported(self._h))
+
+    def entropy_setup(self):
+        """The setup image (vorbispizza_entropy.h) as bytes; FrontError for a stream the device cannot decode."""
+        size = C.c_uint64(0)
+        rc = lib().vpzh_get_entropy_setup(self._h, None, 0, C.byref(size))
+        if rc != 0:
+            raise FrontError("%s (status %d)" % (self.last_error(), rc))
+        buf = np.zeros(size.value, dtype=np.uint8)
+        rc = lib().vpzh_get_entropy_setup(self._h, buf.ctypes.data, buf.size, C.byref(size))
+        if rc != 0:
+            raise FrontError("%s (status %d)" % (self.last_error(), rc))
+        return buf.tobytes()
+
+    def plan_packets(self, first=0, count=None, stream_id=0, residue_base=0):
+        """vpzh_plan_range over packets [first, first + count): (packets, spans, payload, residue_values) -- the records
+        vpzh_decode_range_ex writes, spans as an int64 array [count, 2] of (offset, size) into `payload` (uint8, zero padded)
+        and the residue values of the range."""
+        count = self.audio_packets - first if count is None else count
+        need, used = C.c_int64(0), C.c_int64(0)
+        rc = lib().vpzh_plan_range(self._h, first, count, stream_id, residue_base, None, None, None, 0, C.byref(need), None)
+        if rc != 0:
+            raise FrontError("vpzh_plan_range failed (status %d)" % rc)
+        packets = capi.make_packets(count)
+        spans = np.zeros((count, 2), dtype=np.int64)
+        payload = np.zeros(need.value, dtype=np.uint8)
+        rc = lib().vpzh_plan_range(self._h, first, count, stream_id, residue_base, packets.ctypes.data, spans.ctypes.data,
+                                   payload.ctypes.data, payload.size, C.byref(need), C.byref(used))
+        if rc != 0:
+            raise FrontError("vpzh_plan_range failed (status %d)" % rc)
+        return packets, spans, payload, used.value
 
     def decode_into(self, packets, residue, posts, counts, stream_id=0, residue_base=0):
         """decode_packets into caller-owned arrays (typically slices of one batch buffer shared by many

@@ -1687,6 +1687,269 @@ int64_t vpzh_decode_failures(vpzh_stream *s, int64_t *first_failed_packet)
     return s->decode_failures;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The entropy decode on the GPU (vorbispizza_entropy.h): eligibility, the setup image, the plan.
+//
+// Why the device decode never changes a packet's flags.  decode_packet can end a packet's decode early in two ways:
+// a miss or a short read, which it handles inside (posts / residue as far as decoded, flags untouched), and a throw,
+// which decode_range_impl turns into "not decoded, without EOS".  The throws it can reach are:
+//   (1) "Unused mode index."                            -- read from the mode bits: vpzh_plan_range sees it
+//   (2) "floor1 master book out of range" (Floor1::unpack) -- excluded below: every master book is checked
+//   (3) "residue class book without dimensions" (Residue::decode) -- excluded below: every class book has dimensions >= 1
+//   (4) "residue vector overruns the block" (Residue::write_vectors) -- excluded below: with value books that tile their
+//       partitions (residue_tiles_its_partitions) every vector ends inside [begin, end) <= blocksize/2 <= the channel
+//   (5) Floor0::unpack -- excluded below: every floor is type 1
+// and std::bad_alloc, which is no property of the setup.  BitReader and Codebook::decode_scalar never throw; Floor1
+// subclass books, residue value books and class books were range-checked when the setup header was read.  So for a
+// supported setup the plan alone -- type bit, mode number, window flags -- gives every packet's final record, and the host
+// state machine of vpz_decoder_synth can run from it before the device has decoded anything.
+// ---------------------------------------------------------------------------------------------
+static const char *gpu_unsupported_reason(const SetupBlob &su)
+{
+    for (uint8_t t : su.floor_types)
+        if (t != 1) return "a floor of type 0";
+    for (const Floor1 &f : su.floors)
+        for (size_t c = 0; c < f.class_subclasses.size(); ++c)
+            if (f.class_subclasses[c] > 0 && f.class_masterbooks[c] >= su.books.size()) return "a floor1 master book out of range";
+    for (const Residue &r : su.residues) {
+        if (!residue_tiles_its_partitions(su, r)) return "a residue whose value books do not tile its partitions";
+        if (r.class_book >= (int)su.books.size() || su.books[r.class_book].dimensions < 1) return "a residue class book without dimensions";
+    }
+    return nullptr;
+}
+
+}  // extern "C"
+
+namespace {
+struct ImageWriter {
+    std::vector<uint8_t> out;
+    uint32_t put(const void *p, size_t n)  // appended 4-byte aligned, zero padded
+    {
+        while (out.size() & 3) out.push_back(0);
+        const uint32_t at = (uint32_t)out.size();
+        out.insert(out.end(), (const uint8_t *)p, (const uint8_t *)p + n);
+        while (out.size() & 3) out.push_back(0);
+        return at;
+    }
+    uint32_t reserve(size_t n)
+    {
+        while (out.size() & 3) out.push_back(0);
+        const uint32_t at = (uint32_t)out.size();
+        out.resize(out.size() + n, 0);
+        return at;
+    }
+    template <class T> void set(uint32_t at, const T &v) { memcpy(out.data() + at, &v, sizeof v); }
+};
+}  // namespace
+
+extern "C" {
+
+static std::vector<uint8_t> entropy_image(const vpzh_stream &s)
+{
+    const SetupBlob &su = *s.su;
+    ImageWriter w;
+    vpz_entropy_image_header h;
+    memset(&h, 0, sizeof h);
+    const uint32_t at_h = w.reserve(sizeof h);
+    h.magic = VPZ_ENTROPY_IMAGE_MAGIC;
+    h.version = VPZ_ENTROPY_IMAGE_VERSION;
+    h.channels = s.channels;
+    h.block_size0 = s.size0;
+    h.block_size1 = s.size1;
+    h.mode_field_bits = su.mode_field_bits;
+    h.residue_integral = residue_integral(su) ? 1 : 0;
+    h.book_count = (int32_t)su.books.size();
+    h.floor_count = (int32_t)su.floors.size();
+    h.residue_count = (int32_t)su.residues.size();
+    h.mapping_count = (int32_t)su.mappings.size();
+    h.mode_count = (int32_t)su.modes.size();
+
+    std::vector<vpz_entropy_book> books(su.books.size());
+    memset(books.data(), 0, sizeof(vpz_entropy_book) * books.size());
+    h.books = w.reserve(sizeof(vpz_entropy_book) * books.size());
+    for (size_t i = 0; i < su.books.size(); ++i) {
+        const Codebook &cb = su.books[i];
+        vpz_entropy_book &b = books[i];
+        b.dimensions = cb.dimensions;
+        b.entries = cb.entries;
+        b.max_bits = cb.max_bits;
+        b.prefix_bits = cb.prefix.empty() ? 0 : cb.prefix_bits;
+        b.prefix_count = (int32_t)cb.prefix.size();
+        if (!cb.prefix.empty()) b.prefix = w.put(cb.prefix.data(), sizeof(uint32_t) * cb.prefix.size());
+        std::vector<vpz_entropy_code> codes(cb.overflow.size());
+        for (size_t k = 0; k < codes.size(); ++k)
+            codes[k] = {(uint32_t)cb.overflow[k].value, (uint32_t)cb.overflow[k].length, (uint32_t)cb.overflow[k].bits,
+                        (uint32_t)cb.overflow[k].mask};
+        b.overflow_count = (int32_t)codes.size();
+        if (!codes.empty()) b.overflow = w.put(codes.data(), sizeof(vpz_entropy_code) * codes.size());
+        b.lookup_count = (int32_t)cb.lookup.size();
+        if (!cb.lookup.empty()) b.lookup_f32 = w.put(cb.lookup.data(), sizeof(float) * cb.lookup.size());
+        b.lookup_i16_count = (int32_t)cb.lookup_i16.size();
+        if (!cb.lookup_i16.empty()) b.lookup_i16 = w.put(cb.lookup_i16.data(), sizeof(int16_t) * cb.lookup_i16.size());
+    }
+    for (size_t i = 0; i < books.size(); ++i) w.set(h.books + (uint32_t)(i * sizeof(vpz_entropy_book)), books[i]);
+
+    h.floors = w.reserve(sizeof(vpz_entropy_floor1) * su.floors.size());
+    for (size_t i = 0; i < su.floors.size(); ++i) {
+        const Floor1 &f = su.floors[i];
+        vpz_entropy_floor1 e;
+        memset(&e, 0, sizeof e);
+        if (su.floor_types[i] == 1) {
+            e.partition_count = (int32_t)f.partition_class.size();
+            e.y_bits = f.y_bits;
+            for (size_t k = 0; k < f.partition_class.size(); ++k) e.partition_class[k] = f.partition_class[k];
+            for (size_t c = 0; c < f.class_dimensions.size(); ++c) {
+                e.class_dimensions[c] = f.class_dimensions[c];
+                e.class_subclasses[c] = f.class_subclasses[c];
+                e.class_masterbooks[c] = f.class_masterbooks[c];
+                for (int k = 0; k < 8; ++k)
+                    e.subclass_books[c * 8 + k] = (int16_t)(k < (int)f.subclass_books[c].size() ? f.subclass_books[c][k] : -1);
+            }
+        }
+        w.set(h.floors + (uint32_t)(i * sizeof e), e);
+    }
+
+    std::vector<vpz_entropy_residue> res(su.residues.size());
+    memset(res.data(), 0, sizeof(vpz_entropy_residue) * res.size());
+    h.residues = w.reserve(sizeof(vpz_entropy_residue) * res.size());
+    for (size_t i = 0; i < su.residues.size(); ++i) {
+        const Residue &r = su.residues[i];
+        vpz_entropy_residue &e = res[i];
+        e.type = r.type;
+        e.begin = r.begin;
+        e.end = r.end;
+        e.partition_size = r.partition_size;
+        e.classifications = r.classifications;
+        e.class_book = r.class_book;
+        e.max_stages = r.max_stages;
+        e.class_dim = r.class_dim;
+        e.stage_book = w.put(r.stage_book.data(), sizeof(int16_t) * r.stage_book.size());
+        std::vector<uint8_t> dm(r.decode_map.begin(), r.decode_map.end());  // (classes < 64)
+        e.decode_map_count = (int32_t)dm.size();
+        if (!dm.empty()) e.decode_map = w.put(dm.data(), dm.size());
+        e.word_stage_mask_count = (int32_t)r.word_stage_mask.size();
+        if (!r.word_stage_mask.empty()) e.word_stage_mask = w.put(r.word_stage_mask.data(), sizeof(uint32_t) * r.word_stage_mask.size());
+    }
+    for (size_t i = 0; i < res.size(); ++i) w.set(h.residues + (uint32_t)(i * sizeof(vpz_entropy_residue)), res[i]);
+
+    h.mappings = w.reserve(sizeof(vpz_entropy_mapping) * su.mappings.size());
+    for (size_t i = 0; i < su.mappings.size(); ++i) {
+        const Mapping &m = su.mappings[i];
+        vpz_entropy_mapping e;
+        memset(&e, 0, sizeof e);
+        e.submaps = (int32_t)m.submap_residue.size();
+        e.coupling_steps = (int32_t)m.coupling_angle.size();
+        for (size_t k = 0; k < m.submap_residue.size(); ++k) {
+            e.submap_floor[k] = m.submap_floor[k];
+            e.submap_residue[k] = m.submap_residue[k];
+        }
+        for (size_t c = 0; c < m.mux.size(); ++c) e.mux[c] = m.mux[c];
+        for (size_t k = 0; k < m.coupling_angle.size(); ++k) {
+            e.coupling_magnitude[k] = m.coupling_magnitude[k];
+            e.coupling_angle[k] = m.coupling_angle[k];
+        }
+        w.set(h.mappings + (uint32_t)(i * sizeof e), e);
+    }
+    h.modes = w.reserve(sizeof(vpz_entropy_mode) * su.modes.size());
+    for (size_t i = 0; i < su.modes.size(); ++i) {
+        const vpz_entropy_mode e = {su.modes[i].block_flag ? 1 : 0, su.modes[i].mapping};
+        w.set(h.modes + (uint32_t)(i * sizeof e), e);
+    }
+    while (w.out.size() & 3) w.out.push_back(0);
+    h.total_bytes = (uint32_t)w.out.size();
+    w.set(at_h, h);
+    return w.out;
+}
+
+int vpzh_gpu_decode_supported(vpzh_stream *s)
+{
+    if (!s || !s->su) return 0;
+    if (const char *why = gpu_unsupported_reason(*s->su)) {
+        s->error = std::string("not decodable on the GPU: ") + why;
+        return 0;
+    }
+    return 1;
+}
+
+int vpzh_get_entropy_setup(vpzh_stream *s, void *buf, uint64_t capacity, uint64_t *size)
+{
+    if (!s || !s->su || !size) return VPZH_E_ARG;
+    if (!vpzh_gpu_decode_supported(s)) return VPZH_E_UNSUPPORTED;
+    std::vector<uint8_t> img;
+    try {
+        img = entropy_image(*s);
+    } catch (const std::exception &e) {
+        s->error = e.what();
+        return VPZH_E_INVALID_DATA;
+    }
+    *size = img.size();
+    if (!buf) return VPZH_OK;
+    if (capacity < img.size()) return VPZH_E_ARG;
+    memcpy(buf, img.data(), img.size());
+    return VPZH_OK;
+}
+
+// The records decode_range_impl writes, from the header bits of each packet: decode_packet up to `out->granule = pk.granule`
+// (and its catch for "Unused mode index."), plus VPZ_PKT_INTERLEAVED, which only the mapping decides -- the shortcut of
+// decode_packet is taken for every packet of a mapping with one Residue2 submap over more than one channel, silent or not.
+int vpzh_plan_range(vpzh_stream *s, int64_t first, int64_t count, int32_t stream_id, int64_t residue_base,
+                    vpz_packet *packets, vpz_entropy_span *spans, uint8_t *payload, int64_t payload_capacity,
+                    int64_t *payload_used, int64_t *residue_used)
+{
+    if (!s || !s->su || first < 0 || count < 0 || first + count > (int64_t)s->audio.size() || payload_capacity < 0) return VPZH_E_ARG;
+    const SetupBlob &su = *s->su;
+    int64_t need = 8;
+    for (int64_t k = 0; k < count; ++k) need += (int64_t)s->audio[(size_t)(first + k)].size;
+    if (payload_used) *payload_used = need;
+    if (payload && payload_capacity < need) return VPZH_E_ARG;
+    int64_t off = 0, at = 0;
+    for (int64_t k = 0; k < count; ++k) {
+        const OggPacket &pk = s->audio[(size_t)(first + k)];
+        if (packets) {
+            vpz_packet *out = &packets[k];
+            memset(out, 0, sizeof *out);
+            out->stream = stream_id;
+            out->granule = -1;
+            out->residue_offset = residue_base + off;
+            if (pk.resync) out->flags |= VPZ_PKT_RESYNC;
+            BitReader p;
+            p.init(pk.data, pk.size);
+            if (p.read_bits(1) != 0) {
+                out->flags |= VPZ_PKT_NOT_DECODED;
+                if (pk.eos) out->flags |= VPZ_PKT_EOS;
+            } else {
+                const int mode_idx = (int)p.read_bits(su.mode_field_bits);
+                if ((unsigned)mode_idx >= su.modes.size()) {
+                    out->flags |= VPZ_PKT_NOT_DECODED;  // the exception's record: no EOS
+                } else if (p.is_short) {
+                    out->flags |= VPZ_PKT_NOT_DECODED;
+                    if (pk.eos) out->flags |= VPZ_PKT_EOS;
+                } else {
+                    const Mode &mode = su.modes[mode_idx];
+                    if (pk.eos) out->flags |= VPZ_PKT_EOS;
+                    if (mode.block_flag) {
+                        out->flags |= VPZ_PKT_BLOCK_FLAG;
+                        if (p.read_bit()) out->flags |= VPZ_PKT_PREV_FLAG;
+                        if (p.read_bit()) out->flags |= VPZ_PKT_NEXT_FLAG;
+                    }
+                    out->mapping = (uint8_t)mode.mapping;
+                    out->granule = pk.granule;
+                    const Mapping &map = su.mappings[mode.mapping];
+                    if (map.submap_residue.size() == 1 && s->channels > 1 && su.residues[map.submap_residue[0]].type == 2)
+                        out->flags |= VPZ_PKT_INTERLEAVED;
+                }
+            }
+        }
+        if (spans) spans[k] = {at, (int64_t)pk.size};
+        if (payload && pk.size) memcpy(payload + at, pk.data, pk.size);
+        at += (int64_t)pk.size;
+        off += s->packet_floats(pk);
+    }
+    if (payload) memset(payload + at, 0, 8);
+    if (residue_used) *residue_used = off;
+    return VPZH_OK;
+}
+
 int64_t vpzh_total_samples(vpzh_stream *s)
 {
     // PacketProvider.GetGranuleCount (:35-49): the counted length, capped by the last page's granule position

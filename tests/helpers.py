@@ -232,3 +232,114 @@ def floor0_safe_amp(coeff, bark_map_size, amp_ofs):
         p *= p * (2.0 - w)
         q *= q * (2.0 + w)
     return float(amp_ofs * np.sqrt(np.maximum(p + q, 1e-30)).min())
+
+
+# ---- all-long stereo streams through the chained by-length route (test_full_size_gpu.py, test_chained_route_gpu.py)
+
+ALL_LONG = PKT_BLOCK_FLAG | PKT_PREV_FLAG | PKT_NEXT_FLAG
+
+_CUT_LINE = (r"\[vpz host\] cut: [^,]+, by (?P<by>cost|length), R (?P<R>\d+), .*?, (?P<runs>\d+) runs for -?\d+ slots, .*?"
+             r"chained (?P<chained>\d+), runs filled by (?P<fill>the pool|the calling thread) on (?P<fill_threads>\d+) threads, "
+             r"chain sweep on (?P<chain_threads>\d+) threads")
+_CALL_LINE = r"\[vpz host\] packets (?P<packets>\d+): route (?P<route>\w+), .*? pass1 [\d.]+ us \((?P<pass1>parallel|serial)\)"
+
+
+def host_profile(err):
+    """The route of ONE synth call as VPZ_HOST_PROFILE=1 prints it on stderr: a dict of the cut line's and the call line's fields
+    (R, runs, chained, fill_threads, chain_threads as ints), or an AssertionError naming what was printed."""
+    import re
+    cut, call = re.findall(_CUT_LINE, err), re.findall(_CALL_LINE, err)
+    assert len(cut) == 1 and len(call) == 1, "expected one cut line and one call line, got:\n" + err[-2000:]
+    m = re.search(_CUT_LINE, err).groupdict()
+    m.update(re.search(_CALL_LINE, err).groupdict())
+    for k in ("R", "runs", "chained", "fill_threads", "chain_threads", "packets"):
+        m[k] = int(m[k])
+    return m
+
+
+def resolved_host_threads():
+    """What a decoder left at host_threads = 0 resolves to: VPZ_HOST_THREADS if set, else the CPUs this process may run on
+    divided by LOCAL_WORLD_SIZE, 1 ... 16 (vpz_decoder_set_host_threads)."""
+    import os
+    if int(os.environ.get("VPZ_HOST_THREADS", "0") or 0) > 0:
+        return int(os.environ["VPZ_HOST_THREADS"])
+    n = len(os.sched_getaffinity(0)) // max(1, int(os.environ.get("LOCAL_WORLD_SIZE", "1") or 1))
+    return max(1, min(n, 16))
+
+
+def by_length_runs(frames_per_stream, R):
+    """The runs of a cut by length without skew: per stream in this call, runs of R frames and a partial one.  Returns
+    [(stream, index within the stream's runs, frames in the run)] in launch order."""
+    runs = []
+    for s, n in enumerate(frames_per_stream):
+        for j, f0 in enumerate(range(0, n, R)):
+            runs.append((s, j, min(R, n - f0)))
+    return runs
+
+
+def expected_chained(frames_per_stream, R, trimmed=(), waves=4):
+    """chain_runs on an all-long batch cut by length: run i is chained unless it heads its workgroup (i % waves == 0), is its
+    stream's first run in the call, or is the one-frame last run of a stream whose last packet the EOS trim cut (`trimmed`)."""
+    runs = by_length_runs(frames_per_stream, R)
+    n = 0
+    for i, (s, j, count) in enumerate(runs):
+        last = i + 1 == len(runs) or runs[i + 1][0] != s
+        if i % waves == 0 or j == 0 or (last and count == 1 and s in trimmed):
+            continue
+        n += 1
+    return n
+
+
+def all_long_packets(frames_per_stream, first_offset=0):
+    """Stream-major all-long stereo packets (VPZ_PKT_NO_FLOOR), 2048 residue floats each, back to back from first_offset."""
+    from vorbispizza_amd import make_packets
+    counts = np.asarray(frames_per_stream, dtype=np.int64)
+    pk = make_packets(int(counts.sum()))
+    pk["stream"] = np.repeat(np.arange(len(counts)), counts)
+    pk["flags"] = ALL_LONG | PKT_NO_FLOOR
+    pk["granule"] = -1
+    pk["residue_offset"] = first_offset + np.arange(len(pk), dtype=np.int64) * 2048
+    return pk
+
+
+def compare_all_long_with_oracle(orc, flags, granule, residue, pcm, chunk=2048, threads=4):
+    """ONE all-long stereo stream against the oracle, every sample: flags / granule (numpy, per packet, stream order: the first
+    packet primes the overlap), residue its spectra (a torch tensor, 2048 floats per packet, back to back) and pcm [2, samples]
+    (torch) what the decoder wrote.  Chunk [a - 1, b) of the packets gives pcm[:, (a - 1) * 1024:(b - 1) * 1024] (a granule counts
+    from the chunk's first output sample); the device data comes to the host one chunk at a time.  Returns (max |error|, RMS
+    error, peak |oracle|, samples compared) and asserts that the sample counts agree."""
+    import concurrent.futures as cf
+    from vorbispizza_amd import make_packets
+    n = len(flags)
+    samples = int(pcm.shape[1])
+    if n < 2:
+        assert samples == 0
+        return 0.0, 0.0, 0.0, 0
+    edges = list(range(1, n, chunk)) + [n]
+
+    def one(k):
+        c0, b = edges[k] - 1, edges[k + 1]
+        m = b - c0
+        pk = make_packets(m)
+        pk["flags"] = flags[c0:b]
+        g = np.asarray(granule[c0:b], dtype=np.int64)
+        pk["granule"] = np.where(g >= 0, g - c0 * 1024, -1)
+        pk["residue_offset"] = np.arange(m, dtype=np.int64) * 2048
+        fs = orc.FlooredStream(2, 256, 2048, pk, residue[c0 * 2048:b * 2048].cpu().numpy(), None, None)
+        got = int(fs.run())
+        if b < n:
+            assert got == (m - 1) * 1024, (k, got)
+        ref = fs.pcm[:, :got].astype(np.float64)
+        gpu = pcm[:, c0 * 1024:c0 * 1024 + got].cpu().numpy().astype(np.float64)
+        assert gpu.shape == ref.shape, (k, gpu.shape, ref.shape)
+        d = np.abs(gpu - ref)
+        return got, float(d.max(initial=0.0)), float((d * d).sum()), float(np.abs(ref).max(initial=0.0)), bool(np.isfinite(gpu).all())
+
+    with cf.ThreadPoolExecutor(max_workers=threads) as ex:
+        parts = list(ex.map(one, range(len(edges) - 1)))
+    total = sum(p[0] for p in parts)
+    assert total == samples, ("oracle samples", total, "decoder samples", samples)
+    assert all(p[4] for p in parts), "NaN or Inf in the decoder's PCM"
+    max_err = max(p[1] for p in parts)
+    rms = (sum(p[2] for p in parts) / max(1, 2 * total)) ** 0.5
+    return max_err, rms, max(p[3] for p in parts), total

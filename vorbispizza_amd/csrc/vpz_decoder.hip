@@ -836,6 +836,31 @@ struct SynthCall {
     bool zero_copy = false;
     bool host_failed = false;  // a share of a fork-join threw (allocation): the call returns VPZ_E_NOMEM
 
+    // The host threads this decoder's calls may use (vpz_decoder_set_host_threads / VPZ_HOST_THREADS; 0: the CPUs the process
+    // may run on, divided by LOCAL_WORLD_SIZE, at most 16)
+    int resolved_parties = 0;
+    int host_parties()
+    {
+        if (resolved_parties > 0) return resolved_parties;
+        int parties = D.host_threads;
+        if (parties <= 0) {
+            cpu_set_t set;
+            parties = sched_getaffinity(0, sizeof set, &set) == 0 ? CPU_COUNT(&set) : (int)std::thread::hardware_concurrency();
+            // (one process per GPU: the node's cores are shared with the other ranks torchrun started here)
+            if (const char *lw = getenv("LOCAL_WORLD_SIZE")) parties /= std::max(1, atoi(lw));
+            parties = std::max(1, std::min(parties, 16));
+        }
+        return resolved_parties = parties;
+    }
+    // ... and the context's pool, if it is this decoder's: the pool another decoder of the context left behind (another party
+    // count, or any count for a decoder held to one thread) is not used -- the run cut then happens on the calling thread
+    HostPool *own_pool()
+    {
+        HostPool *pool = static_cast<HostPool *>(ctx->host_pool);
+        const int parties = host_parties();
+        return pool && parties >= 2 && pool->parties() == parties ? pool : nullptr;
+    }
+
     // Every per-call table (frame / run descriptors, coupling packets, per-record floor info, output
     // offsets, ...) is carved out of ONE pinned arena that goes to its device mirror in a single copy;
     // two arenas alternate so the host can prepare call k+1 while call k's upload is still queued.
@@ -888,14 +913,7 @@ struct SynthCall {
     int run_state_machine_parallel(int64_t *samples_written)
     {
         if (n_packets < D.par_min_packets) return 0;
-        int parties = D.host_threads;
-        if (parties <= 0) {
-            cpu_set_t set;
-            parties = sched_getaffinity(0, sizeof set, &set) == 0 ? CPU_COUNT(&set) : (int)std::thread::hardware_concurrency();
-            // (one process per GPU: the node's cores are shared with the other ranks torchrun started here)
-            if (const char *lw = getenv("LOCAL_WORLD_SIZE")) parties /= std::max(1, atoi(lw));
-            parties = std::max(1, std::min(parties, 16));
-        }
+        const int parties = host_parties();
         if (parties < 2) return 0;
         if (!ctx->host_pool || static_cast<HostPool *>(ctx->host_pool)->parties() != parties) {
             if (ctx->host_pool) ctx->host_pool_free(ctx->host_pool);
@@ -1380,7 +1398,7 @@ struct SynthCall {
         // (cutting by cost walks every packet a few times: with enough streams it is split over the host pool, streams
         // being independent; a small batch is walked on this thread; a large batch of few streams keeps runs of equal
         // length -- the kernel still batches what it finds in them -- rather than spend a millisecond of host time)
-        HostPool *pool = static_cast<HostPool *>(ctx->host_pool);
+        HostPool *pool = own_pool();
         const bool wide = pool && D.n_streams >= 2 * pool->parties();
         // (... or, with short blocks to batch, is walked in pieces: 65 536 frames of ONE stream cut by cost are a millisecond on one
         // thread and 40 us on sixteen once the cut hint applies -- and worth 12 % of the kernel's time, configs[2])
@@ -1682,6 +1700,7 @@ struct SynthCall {
             if (host_failed) { n_runs = 0; return; }
             n_runs = (size_t)total_runs;
         }
+        fill_threads = by_length_wide ? pool->parties() : parties;
         std::vector<std::vector<RunDesc>> cut(by_length_wide ? 0 : parties);
         auto cut_streams = [&](int c) {
           int s_lo, s_hi;
@@ -1745,9 +1764,11 @@ struct SynthCall {
         chain_runs();
         if (getenv("VPZ_HOST_PROFILE"))
             fprintf(stderr, "[vpz host] cut: %s, by %s, R %d, target %lld eighths, %zu runs for %lld slots, %d segments on %d threads, heavy below %lld, "
-                            "hint (frames %lld, runs %lld), chained %lld\n", reuse ? "hint reused" : "fitted", batches ? "cost" : "length", R,
+                            "hint (frames %lld, runs %lld), chained %lld, runs filled by %s on %d threads, chain sweep on %d threads\n",
+                    reuse ? "hint reused" : "fitted", batches ? "cost" : "length", R,
                     (long long)target_units, n_runs, (long long)run_slots, n_segs, parties, (long long)heavy_work,
-                    (long long)D.cut_hint_frames, (long long)D.cut_hint_runs, (long long)n_chained);
+                    (long long)D.cut_hint_frames, (long long)D.cut_hint_runs, (long long)n_chained,
+                    fill_threads > 1 ? "the pool" : "the calling thread", fill_threads, chain_threads);
     }
 
     // The stereo fast path: runs r - 1 and r of one stream that land in ONE workgroup (the kernel takes run i in wave i mod
@@ -1758,6 +1779,7 @@ struct SynthCall {
     // sweep a quarter or an eighth of the batch at a time instead of all of it).
     int64_t n_chained = 0;
     int cut_R = 0;  // the run length (or cost target, in passes) cut_runs settled on
+    int fill_threads = 1, chain_threads = 1;  // threads that wrote the run records / swept them for chaining (VPZ_HOST_PROFILE)
     void chain_runs()
     {
         n_chained = 0;
@@ -1808,9 +1830,10 @@ struct SynthCall {
             }
         };
         // (one sweep does both: a run's bytes depend on its own record only, its chaining on its predecessor's place and length)
-        HostPool *pool = static_cast<HostPool *>(ctx->host_pool);
+        HostPool *pool = own_pool();
+        chain_threads = 1;
         if (pool && pool->parties() > 1 && n_runs >= 1024) {  // (the pool's workers are still spinning from the cut's fork-join)
-            const int P = pool->parties();
+            const int P = chain_threads = pool->parties();
             std::vector<int64_t> part((size_t)P, 0);
             host_failed |= !pool->run([&](int c) {
                 const size_t lo = n_runs * (size_t)c / P, hi = n_runs * (size_t)(c + 1) / P;

@@ -1,4 +1,4 @@
-"""The edges of the stereo fast path's chained by-length route (vpz_decoder.hip cut_runs / chain_runs, synth_dual.hip's deferred pass
+"""The edges of the stereo fast path's chained by-length route (synth_plan.hip plan_runs / chain_runs, synth_dual.hip's deferred pass
 for chained runs): all-long stereo streams just below, at and above the run count from which the host pool fills the run records
 (frames / R >= 1024), an end-of-stream trim that leaves a last run of one frame, several streams -- one without packets, one of a
 single packet -- whose pool shares start in the middle of a stream, and a second call that continues some of them.  Every stream

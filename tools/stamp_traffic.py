@@ -25,7 +25,7 @@ STAMP = os.path.join(ROOT, "profiles", "traffic_stamp.json")
 FUSED_SOURCES = ["vorbispizza_amd/csrc/synth_dual.hip", "vorbispizza_amd/csrc/synth_common.hpp",
                  "vorbispizza_amd/csrc/imdct_core.hpp", "vorbispizza_amd/csrc/synth_desc.hpp",
                  # (the run cutting decides how many blocks a launch recomputes: a change there changes the bytes moved)
-                 "vorbispizza_amd/csrc/vpz_decoder.hip"]
+                 "vorbispizza_amd/csrc/synth_plan.hip"]
 WORKLOADS = {
     # key: (command after the interpreter, kernel-name substrings, sources, algorithmic bytes or None = parse the log)
     "headline": (["tools/kbench.py", "--reps", "5"], ["imdct2048_kernel"],

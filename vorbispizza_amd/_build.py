@@ -25,6 +25,7 @@ SOURCES = {
     "floor0.hip": ["-ffp-contract=off"],
     "vpz_context.hip": ["-ffp-contract=off"],
     "vpz_decoder.hip": ["-ffp-contract=off"],
+    "synth_plan.hip": ["-ffp-contract=off"],   # the host plan of a synth call: pass 1 and the run cutting, integers only
     "entropy.hip": ["-ffp-contract=off"],  # the residue sums: plain adds in the CPU front end's order
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",

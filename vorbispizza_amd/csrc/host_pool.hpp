@@ -1,5 +1,5 @@
 // A small fork-join pool for the host half of vpz_decoder_synth: the per-packet state machine of a large batch is
-// split over the host cores (vpz_decoder.hip, run_state_machine_parallel).  Workers spin for a few microseconds
+// split over the host cores (synth_plan.hip, run_state_machine_parallel).  Workers spin for a few microseconds
 // before they block, so that the two fork-joins of one call do not each pay a futex wake-up.
 #pragma once
 

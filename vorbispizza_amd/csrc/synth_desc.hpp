@@ -1,5 +1,5 @@
 // Device-visible descriptors of one vpz_decoder_synth batch.  The host-side state machine
-// (vpz_decoder.hip: ReadNextPacket / GetPacketInfo, integers only) resolves every packet into a
+// (synth_plan.hip: ReadNextPacket / GetPacketInfo, integers only) resolves every packet into a
 // FrameDesc; the kernels never see stream state other than these and the saved h tails.
 #pragma once
 

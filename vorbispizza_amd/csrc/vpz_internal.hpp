@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vorbispizza_synth.h"
+#include "synth_desc.hpp"
 
 namespace vpz {
 
@@ -84,6 +85,54 @@ hipError_t launch_imdct_exact(int n, int ld, const float *spectra, float *out, i
                               const float *A, const float *B, const float *C,
                               const uint16_t *bitrev, int num_cu, hipStream_t stream,
                               const int64_t *src_off = nullptr, const int64_t *dst_off = nullptr);
+
+// ---- launchers and host-side helpers of the fused kernels' units (synth_kernels.hip / synth_dual.hip / synth_big.hip / floor0.hip),
+// declared here for the units that define them too: a changed signature is a compile error
+hipError_t launch_floor1_unwrap(int n_rec, const int16_t *posts, const uint8_t *post_counts, const uint8_t *rec_info,
+                                const FloorDev *floors, int n_floors, int32_t *cposts, uint8_t *ccount, int16_t *dbg_y,
+                                uint8_t *dbg_f, hipStream_t stream, int f0_fused = 0);
+hipError_t launch_floor0_curves(int n_rec, const uint8_t *rec_info, const void *floors, const float *amp, const float *coeff,
+                                int coeff_stride, int k_stride, const float *wtab, float *curve, const uint8_t *post_counts,
+                                uint8_t *ccount, int32_t *cposts, hipStream_t stream);
+hipError_t launch_floor0_wtab(const void *floors, int n_floors, int k_stride, float *wtab, hipStream_t stream);
+hipError_t launch_floor1_render(int n_rec, const int32_t *cposts, const uint8_t *ccount, const uint8_t *rec_info,
+                                int half0, int half1, uint8_t *curve_y, hipStream_t stream);
+hipError_t launch_coupling(const void *pkts, int n_pkts, const uint8_t *steps, int channels,
+                           const float *residue, float *temp, int max_half, hipStream_t stream);
+hipError_t launch_synth(const SynthArgs &args, bool has_floor, hipStream_t stream);
+bool synth_supports_sizes(int size0, int size1);
+bool synth_needs_general(int size0, int size1);
+int synth_resident_waves(bool has_floor, int num_cu, int channels, bool group);
+bool synth_group_supported(int channels);
+bool synth_dual_supported(int channels, int size0, int size1);
+hipError_t launch_synth_dual(const SynthArgs &args, bool has_floor, bool interleaved_in, hipStream_t stream);
+int synth_dual_resident_slots(bool has_floor, int num_cu);
+int synth_dual_waves();
+bool synth_pairs_supported(int channels, int size0, int size1);
+hipError_t launch_synth_pairs(const SynthArgs &args, bool has_floor, bool interleaved_in, hipStream_t stream);
+bool synth_big_supported(int size0, int size1);
+hipError_t launch_synth_big(const SynthArgs &args, bool has_floor, hipStream_t stream);
+int synth_big_resident_waves(bool has_floor, int num_cu, int size0, int size1);
+int64_t synth_big_tail_floats(int size1, int64_t n_items);
+hipError_t launch_generic_floor(const GenericFrame *frames, int n_frames, int channels, int half1, float *spec,
+                                const uint8_t *post_counts, const uint8_t *curve_y, const float *inv_db,
+                                hipStream_t stream);
+hipError_t launch_generic_ola(const GenericFrame *frames, int n_frames, int channels, int size0, int size1,
+                              const float *ybuf, float *state_y, const float *slope0, const float *slope1, float *out,
+                              const int64_t *stream_out_off, int64_t channel_stride, int interleaved, int clip,
+                              int32_t *clipped, int s16, hipStream_t stream);
+hipError_t launch_generic_save_state(const GenericFrame *frames, const int32_t *save_list, int n_save, int channels,
+                                     int size1, const float *ybuf, float *state_y, hipStream_t stream);
+hipError_t launch_floor0_apply(const void *recs, int n_recs, const void *floors, const int32_t *bark_maps,
+                               const float *amp, const float *coeff, int coeff_stride, float *spec,
+                               hipStream_t stream);
+size_t floor0_dev_size();
+size_t floor0_rec_size();
+void fill_floor0_dev(void *dst, int order, int bark_map_size, int amp_ofs, int64_t off_short, int64_t off_long);
+void fill_floor0_rec(void *dst, int64_t spec_off, int rec, int floor, int half, int is_long);
+size_t coupling_packet_size();
+void fill_coupling_packet(void *dst, int64_t src_off, int64_t dst_off, int32_t half, int32_t steps_off,
+                          int32_t steps, int32_t interleaved);
 
 // offsets (in float2 units) inside BlockTables::d_fast
 constexpr int kFastTwOffset = 0;       // tw[k] = exp(+2*pi*i*(k + 1/8)/n), k < n/4   (<= 512 entries)

@@ -25,7 +25,10 @@ namespace NVorbis.Native
             public int ClipSamples;         // StreamDecoder.ClipSamples
             public int SlotsPerDevice;      // sub-batches in flight per device (0: 4 * contexts + 4)
             public int FloatResidue;        // 0: integral residues cross the link as int16 (same values, half the bytes); non-zero: always float32
-            public fixed int Reserved[2];
+            public int GpuEntropy;          // 0: every stream is entropy-decoded on host threads; non-zero: streams whose setup the device can decode
+                                            // (vpzh_gpu_decode_supported) are planned on the host and entropy-decoded on their device, the others on
+                                            // the host in the same call -- the same PCM bit for bit; with StreamsPerCall 0 such a call holds up to 64 streams
+            public int Reserved;
         }
 
         [StructLayout(LayoutKind.Sequential)]
@@ -45,6 +48,9 @@ namespace NVorbis.Native
             public fixed long DeviceStreams[16];
             public fixed long DeviceSamples[16];
             public int ThreadsPerDevice, PinnedMib;
+            // written only by a dispatcher created with GpuEntropy != 0 (a caller built against the shorter struct is never written past):
+            public fixed long DeviceGpuEntropyStreams[16];  // the group's streams entropy-decoded on the device
+            public fixed long DevicePayloadBytes[16];       // ... and the packet bytes uploaded for them
         }
 
         public sealed class DispatcherHandle : SafeHandle

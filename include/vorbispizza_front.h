@@ -126,7 +126,7 @@ int vpzh_decode_many_progress(int32_t n, int32_t channels, const uint8_t *const 
                               const int64_t *residue_room, int64_t residue_origin, vpz_packet *packets, float *residue,
                               int16_t *posts, uint8_t *post_counts, int64_t *failed_packets, int32_t *done);
 
-/* Packets of the LAST vpzh_decode_range* / vpzh_decode_all call whose entropy decode failed the way the reference's
+/* Packets of the LAST vpzh_decode_range* / vpzh_decode_all / vpzh_plan_range (with packets) call whose entropy decode failed the way the reference's
  * DecodeNextPacket throws (InvalidDataException "Unused mode index.", a residue vector overrunning its block, ...).
  * Such a packet costs only itself, like the reference's exception: it is handed over with VPZ_PKT_NOT_DECODED and
  * WITHOUT its EOS flag (the reference has not executed `_eosFound |= isEndOfStream` when the exception leaves), the

@@ -12,6 +12,9 @@
  * model), sub-batches of streams go to the GPU as one host-memory vpz_decoder_synth call each, issued while the following
  * sub-batches are still being decoded, by `contexts_per_device` issuing threads in turn so that the upload of one call
  * overlaps the download of the previous one.
+ * With vpzm_options.gpu_entropy the entropy decode of eligible streams moves to the device as well: the host threads only plan
+ * the packets, and a sub-batch is upload of the packet bytes, vpz_entropy_decode, vpz_decoder_synth on device-resident arrays,
+ * download of the PCM.
  *
  * Everything a C# host would P/Invoke is cdecl / POD / int status, like vorbispizza_synth.h.
  */
@@ -46,7 +49,12 @@ typedef struct vpzm_options {
     int32_t clip_samples;         /* StreamDecoder.ClipSamples (VorbisReader sets it to true, VorbisReader.cs:71) */
     int32_t slots_per_device;     /* sub-batches in flight per device: decoded or being decoded ahead of their synth call (0: 4 * contexts + 4; about 70 MB of page-locked memory each for stereo streams of a few seconds -- with fewer the entropy decode waits for synth calls) */
     int32_t float_residue;        /* 0 (default): the residue of streams whose setup header guarantees 16-bit integers (vpzh_residue_is_integral: every libvorbis stream) crosses the host link as int16 -- the same values at half the bytes; non-zero: always float32 */
-    int32_t reserved[2];
+    int32_t gpu_entropy;          /* 0 (default): every stream is entropy-decoded on host threads.  Non-zero: streams whose setup vpzh_gpu_decode_supported
+                                     accepts are planned on the host threads (vpzh_plan_range) and entropy-decoded on their device (vpz_entropy_decode):
+                                     their packet bytes cross the host link instead of their residue; every other stream (Floor0, residue books that do
+                                     not tile their partitions) takes the host path in the same call.  The PCM and the results are the same bit for bit.
+                                     With streams_per_call 0 a device-decoded call holds up to 64 streams (one lane per packet: small launches waste the device) */
+    int32_t reserved;
 } vpzm_options;
 
 /* One context group per entry of device_ids (an id may appear more than once: several groups on one GPU, which is how a
@@ -69,13 +77,17 @@ typedef struct vpzm_stream_result {
 typedef struct vpzm_stats {
     double wall_s;                /* the whole call */
     double device_wall_s[16];     /* per device group (the first 16): its thread's wall time */
-    double device_decode_s[16];   /* ... until its last stream was entropy-decoded */
-    double device_synth_s[16];    /* ... summed time inside vpz_decoder_synth (over its issuing threads) */
+    double device_decode_s[16];   /* ... until its last stream was entropy-decoded (gpu_entropy: planned) on the host threads */
+    double device_synth_s[16];    /* ... summed time inside vpz_decoder_synth (over its issuing threads); a device-decoded sub-batch counts from its upload to the end of its download */
     int64_t device_streams[16];
     int64_t device_samples[16];   /* samples x channels produced */
     int32_t threads_per_device;
     int32_t pinned_mib;           /* page-locked host memory the dispatcher's slots hold after this call, all groups, in MiB: it grows to
                                      slots_per_device sub-batches of the largest size seen per group and is kept until vpzm_destroy */
+    /* The two arrays below were appended for vpzm_options.gpu_entropy and are written ONLY by a dispatcher created with gpu_entropy != 0:
+     * a caller built against the shorter struct passes zero there (the field was reserved, zero), so its struct is never written past. */
+    int64_t device_gpu_entropy_streams[16];  /* the group's streams that were entropy-decoded on the device */
+    int64_t device_payload_bytes[16];        /* ... and the packet bytes uploaded for them */
 } vpzm_stats;
 
 /* Decodes containers 0..n-1 (first logical stream of each) to interleaved PCM in host memory: stream k's sample s of

@@ -28,6 +28,7 @@ struct PacketDesc {
 };
 
 constexpr int kBlock = 256;
+constexpr int64_t kSmallLaunch = 65536;  // packets below which entropy_decode_kernel is launched with one wave per workgroup
 
 // 256 one-bit flags in registers (a runtime-indexed array would live in scratch memory): channels of a packet
 struct Mask256 {
@@ -333,7 +334,7 @@ __global__ void __launch_bounds__(kBlock) entropy_decode_kernel(const uint8_t *_
                                                                 int16_t *posts, uint8_t *post_counts, int32_t *cache, int cache_words,
                                                                 T *dbuf)
 {
-    const int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (the workgroup's size is the launch's choice, kBlock at most)
     if (k < n_packets) decode_one_packet<T>(img, pk, k, payload, residue, posts, post_counts, cache, cache_words, dbuf);
 }
 
@@ -654,21 +655,26 @@ int vpz_entropy_decode(vpz_entropy_setup *S, int64_t n_packets, const vpz_packet
     }
     VPZ_HIP_TRY(ctx, hipMemsetAsync(d_posts, 0, recs * 64 * sizeof(int16_t), st));
     const unsigned zero_grid = (unsigned)std::min<int64_t>(n_packets, 8192);
-    const unsigned grid = (unsigned)((n_packets + vpz::kBlock - 1) / vpz::kBlock);
+    // One lane per packet, and a launch's time is the latency of its slowest lane's chain: a small launch gains from spreading its
+    // waves over the CUs (a wave per workgroup: 39 000 packets are 600 workgroups on 256 CUs instead of 150 that hold four waves
+    // each).  Launches of 2 900 to 39 000 packets: 2.62 / 2.73 / 2.99 ms at 64 lanes against 3.08 / 3.11 / 3.25 ms at 256
+    // (tools/kbench_entropy.py, 16 / 64 / 128 streams); nothing larger was measured, so larger launches keep kBlock.
+    const unsigned block = n_packets < vpz::kSmallLaunch ? 64u : (unsigned)vpz::kBlock;
+    const unsigned grid = (unsigned)((n_packets + block - 1) / block);
     const uint32_t *words = reinterpret_cast<const uint32_t *>(d_payload);
     int32_t *cache = static_cast<int32_t *>(S->d_cache);
     if (residue_format == VPZ_RESIDUE_I16) {
         if (any_decoded)
             hipLaunchKernelGGL(vpz::entropy_zero_kernel<int16_t>, dim3(zero_grid), dim3(vpz::kBlock), 0, st, S->d_desc, n_packets, C,
                                h.block_size0 / 2, h.block_size1 / 2, static_cast<int16_t *>(d_residue));
-        hipLaunchKernelGGL(vpz::entropy_decode_kernel<int16_t>, dim3(grid), dim3(vpz::kBlock), 0, st, S->d_image, S->d_desc, n_packets,
+        hipLaunchKernelGGL(vpz::entropy_decode_kernel<int16_t>, dim3(grid), dim3(block), 0, st, S->d_image, S->d_desc, n_packets,
                            words, static_cast<int16_t *>(d_residue), d_posts, d_counts, cache, S->cache_words,
                            static_cast<int16_t *>(S->d_dbuf));
     } else {
         if (any_decoded)
             hipLaunchKernelGGL(vpz::entropy_zero_kernel<float>, dim3(zero_grid), dim3(vpz::kBlock), 0, st, S->d_desc, n_packets, C,
                                h.block_size0 / 2, h.block_size1 / 2, static_cast<float *>(d_residue));
-        hipLaunchKernelGGL(vpz::entropy_decode_kernel<float>, dim3(grid), dim3(vpz::kBlock), 0, st, S->d_image, S->d_desc, n_packets,
+        hipLaunchKernelGGL(vpz::entropy_decode_kernel<float>, dim3(grid), dim3(block), 0, st, S->d_image, S->d_desc, n_packets,
                            words, static_cast<float *>(d_residue), d_posts, d_counts, cache, S->cache_words,
                            static_cast<float *>(S->d_dbuf));
     }

@@ -878,6 +878,9 @@ struct SetupBlob {
     std::vector<Mapping> mappings;
     std::vector<Mode> modes;
     int mode_field_bits = 0;
+    // the entropy setup image (vpzh_get_entropy_setup), built by the first stream that asks: the streams that share the blob share it
+    mutable std::once_flag image_once;
+    mutable std::vector<uint8_t> image;
 };
 struct SetupCache {
     static constexpr size_t kEntries = 16;
@@ -1875,13 +1878,13 @@ int vpzh_get_entropy_setup(vpzh_stream *s, void *buf, uint64_t capacity, uint64_
 {
     if (!s || !s->su || !size) return VPZH_E_ARG;
     if (!vpzh_gpu_decode_supported(s)) return VPZH_E_UNSUPPORTED;
-    std::vector<uint8_t> img;
     try {
-        img = entropy_image(*s);
+        std::call_once(s->su->image_once, [s] { s->su->image = entropy_image(*s); });
     } catch (const std::exception &e) {
         s->error = e.what();
         return VPZH_E_INVALID_DATA;
     }
+    const std::vector<uint8_t> &img = s->su->image;
     *size = img.size();
     if (!buf) return VPZH_OK;
     if (capacity < img.size()) return VPZH_E_ARG;
@@ -1903,6 +1906,10 @@ int vpzh_plan_range(vpzh_stream *s, int64_t first, int64_t count, int32_t stream
     if (payload_used) *payload_used = need;
     if (payload && payload_capacity < need) return VPZH_E_ARG;
     int64_t off = 0, at = 0;
+    if (packets) {  // (what vpzh_decode_failures reports: the one failure a supported setup has, counted as decode_range_impl counts it)
+        s->decode_failures = 0;
+        s->first_failed_packet = -1;
+    }
     for (int64_t k = 0; k < count; ++k) {
         const OggPacket &pk = s->audio[(size_t)(first + k)];
         if (packets) {
@@ -1921,6 +1928,10 @@ int vpzh_plan_range(vpzh_stream *s, int64_t first, int64_t count, int32_t stream
                 const int mode_idx = (int)p.read_bits(su.mode_field_bits);
                 if ((unsigned)mode_idx >= su.modes.size()) {
                     out->flags |= VPZ_PKT_NOT_DECODED;  // the exception's record: no EOS
+                    if (s->decode_failures++ == 0) {
+                        s->first_failed_packet = k;
+                        s->error = "Unused mode index.";
+                    }
                 } else if (p.is_short) {
                     out->flags |= VPZ_PKT_NOT_DECODED;
                     if (pk.eos) out->flags |= VPZ_PKT_EOS;

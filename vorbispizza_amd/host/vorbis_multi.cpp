@@ -11,10 +11,16 @@
 // with sub-batches of `streams_per_call` streams of one setup header per synth call, `slots_per_device` sub-batches in
 // flight.  Nothing is shared between groups but the caller's arrays; the C ABI below them is used exactly as any other host
 // would use it (one thread at a time per context / decoder).
+//
+// With vpzm_options.gpu_entropy a sub-batch of a setup the device can decode (vpzh_gpu_decode_supported) takes the same stages
+// with other contents: the workers PLAN its streams (vpzh_plan_range: packet records, spans, the packets' bytes) into the slot,
+// and its issuing thread uploads the bytes, entropy-decodes them on the lane's stream (vpz_entropy_decode) into arrays that
+// never leave the device, synthesises from those and downloads every member's PCM.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,8 +48,9 @@ struct Setup {
     std::vector<vpz_mapping_config> mappings;
     int f0_stride = 0;
     bool integral = false;  // every residue value is an integer of 16 bits: the residue travels as int16 (half the link bytes)
+    std::vector<uint8_t> image;  // gpu_entropy, a setup the device can decode: its entropy setup image (else empty)
 
-    bool load(vpzh_stream *h)
+    bool load(vpzh_stream *h, bool gpu_entropy)
     {
         if (vpzh_get_info(h, &info) != VPZH_OK) return false;
         floors.assign((size_t)info.floor_count, vpz_floor1_config{});
@@ -59,14 +66,22 @@ struct Setup {
             if (vpzh_get_mapping(h, i, &mappings[i]) != VPZH_OK) return false;
         f0_stride = vpzh_max_floor0_order(h);
         integral = vpzh_residue_is_integral(h) != 0;
+        uint64_t bytes = 0;
+        if (gpu_entropy && vpzh_gpu_decode_supported(h) && vpzh_get_entropy_setup(h, nullptr, 0, &bytes) == VPZH_OK) {
+            image.resize((size_t)bytes);
+            if (vpzh_get_entropy_setup(h, image.data(), bytes, &bytes) != VPZH_OK) image.clear();
+        }
         return true;
     }
+    bool on_device() const { return !image.empty(); }
     // the same decoder serves two streams iff everything it was created from is the same
     bool same(const Setup &o) const
     {
         if (info.channels != o.info.channels || info.block_size0 != o.info.block_size0 || info.block_size1 != o.info.block_size1 ||
             floors.size() != o.floors.size() || mappings.size() != o.mappings.size() || floor_types != o.floor_types || integral != o.integral)
             return false;
+        // (the synthesis does not know the codebooks, the device's entropy decode does: equal setup headers give equal images)
+        if (image != o.image) return false;
         for (size_t i = 0; i < floors.size(); ++i) {
             if (floor_types[i] == 0) {
                 if (memcmp(&floors0[i], &o.floors0[i], sizeof floors0[i]) != 0) return false;
@@ -86,6 +101,11 @@ struct Setup {
 struct Lane {  // one context (HIP stream) of a device group and the decoders that live on it
     vpz_context *ctx = nullptr;
     std::vector<std::pair<std::shared_ptr<Setup>, vpz_decoder *>> decs;
+    // gpu_entropy: the entropy setups next to the decoders (a setup belongs to a context and serves one call at a time), and
+    // what a device-decoded sub-batch keeps on the device: packet bytes in, residue / posts / counts between the two calls, PCM out
+    std::vector<std::pair<std::shared_ptr<Setup>, vpz_entropy_setup *>> esetups;
+    uint8_t *d_payload = nullptr, *d_residue = nullptr, *d_posts = nullptr, *d_counts = nullptr, *d_pcm = nullptr;
+    size_t cap_payload = 0, cap_residue = 0, cap_posts = 0, cap_counts = 0, cap_pcm = 0;  // (bytes)
 };
 
 struct Slot {  // page-locked batch arrays of one sub-batch in flight
@@ -94,7 +114,14 @@ struct Slot {  // page-locked batch arrays of one sub-batch in flight
     int16_t *posts = nullptr;
     uint8_t *counts = nullptr;
     float *f0_amp = nullptr, *f0_coeff = nullptr;
-    size_t cap_packets = 0, cap_residue = 0, cap_posts = 0, cap_counts = 0, cap_f0 = 0, cap_f0c = 0;
+    vpz_entropy_span *spans = nullptr;   // a device-decoded sub-batch holds packets, spans and payload only
+    uint8_t *payload = nullptr;
+    size_t cap_packets = 0, cap_residue = 0, cap_posts = 0, cap_counts = 0, cap_f0 = 0, cap_f0c = 0, cap_spans = 0, cap_payload = 0;
+    size_t bytes() const
+    {
+        return cap_packets * sizeof(vpz_packet) + cap_residue * sizeof(float) + cap_posts * sizeof(int16_t) + cap_counts +
+               (cap_f0 + cap_f0c) * sizeof(float) + cap_spans * sizeof(vpz_entropy_span) + cap_payload;
+    }
 };
 
 struct Group {
@@ -118,11 +145,28 @@ bool grow(vpz_context *ctx, T *&p, size_t &cap, size_t need)
     return true;
 }
 
+// the same for a lane's device buffers (bytes); the lane's stream is idle between its sub-batches, so the old one may go
+bool grow_device(vpz_context *ctx, uint8_t *&p, size_t &cap, size_t need)
+{
+    if (need <= cap) return true;
+    if (p) vpz_device_free(ctx, p);
+    p = nullptr;
+    cap = 0;
+    void *q = nullptr;
+    const size_t want = need + need / 4 + 64;
+    if (vpz_device_alloc(ctx, (uint64_t)want, &q) != VPZ_OK) return false;
+    p = static_cast<uint8_t *>(q);
+    cap = want;
+    return true;
+}
+
 }  // namespace
 
 struct vpzm_dispatcher {
     std::vector<Group> groups;
     vpzm_options opt{};
+    int device_streams_per_call = 0;  // gpu_entropy: streams of a device-decoded call (opt.streams_per_call: of a host-decoded one)
+    int call_streams() const { return std::max(opt.streams_per_call, device_streams_per_call); }  // what a decoder is created for
     std::string error;
     std::mutex err_mu;
     std::mutex call_mu;  // vpzm_decode_library holds it: calls from several host threads take the dispatcher in turn
@@ -144,6 +188,7 @@ struct Job {  // one stream of the library inside its group
     std::shared_ptr<Setup> own;  // its setup-header products, loaded when it is opened
     int setup = -1;
     int64_t packets = 0, residue_floats = 0, total_samples = 0;
+    int64_t payload_bytes = 0, plan_failures = 0;  // gpu_entropy: what its plan needs in the payload area; packets its plan gave up
     int32_t status = VPZM_OK;
     bool finished = false;  // its PCM has been written (or it has its own failure status): what an aborted run leaves alone
 };
@@ -153,7 +198,9 @@ struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
     std::shared_ptr<Setup> st;           // (its own reference: `setups` grows under the group's mutex while sub-batches are worked on outside it)
     std::vector<int> members;            // indices into jobs
     std::vector<int64_t> pbase, rbase;   // where each member's packets / residue start in the slot's arrays
-    int64_t n_packets = 0, res_floats = 0;
+    std::vector<int64_t> ybase;          // ... and its packet bytes in the slot's payload area (a device-decoded sub-batch)
+    int64_t n_packets = 0, res_floats = 0, payload_bytes = 0;
+    bool on_device = false;              // planned on the host, entropy-decoded on the device
     int decoded = 0;                     // members whose entropy decode is complete (under the group's mutex)
     bool prepped = false, prepping = false, synth_done = false;
 };
@@ -183,6 +230,7 @@ struct GroupRun {
     vpzm_stream_result *results;
     int threads;
     double t_wall = 0, t_decode = 0, t_synth = 0;
+    int64_t device_streams = 0, device_payload = 0;  // streams entropy-decoded on the device, their packet bytes
     Clock::time_point t_begin = Clock::now();
     int64_t samples_total = 0;
     const bool profile = getenv("VPZM_PROFILE") != nullptr;
@@ -205,7 +253,7 @@ struct GroupRun {
         lane_host_threads = std::max(1, std::min(8, thr / std::max(1, (int)G.lanes.size())));
     }
 
-    int wave_size() const { return 4 * m->opt.streams_per_call; }
+    int wave_size() const { return std::max(4 * m->opt.streams_per_call, 2 * m->device_streams_per_call); }
     bool all_planned() const { return waves_planned == (int)wave_left.size(); }
 
     // ---- open: the container walked (pages, CRC, lacing), the three headers parsed, the setup products read out
@@ -234,7 +282,11 @@ struct GroupRun {
             if (J.total_samples > pcm_capacity[J.k]) { J.status = VPZM_E_CAPACITY; return; }
             if (J.packets > 0) {
                 J.own = std::make_shared<Setup>();
-                if (!J.own->load(J.h)) J.status = VPZM_E_SETUP;
+                if (!J.own->load(J.h, m->opt.gpu_entropy != 0)) J.status = VPZM_E_SETUP;
+                // (the plan's sizes first, without a payload: members' payload bases are known when the sub-batch is cut)
+                if (J.status == VPZM_OK && J.own->on_device() &&
+                    vpzh_plan_range(J.h, 0, J.packets, 0, 0, nullptr, nullptr, nullptr, 0, &J.payload_bytes, nullptr) != VPZH_OK)
+                    J.own->image.clear();
             }
         } catch (...) {
             J.status = VPZM_E_OPEN;
@@ -278,18 +330,23 @@ struct GroupRun {
                 if (!sb.members.empty()) fresh.push_back(std::move(sb));
                 sb = Sub();
             };
+            // (device-resident inputs are not bound by a page-locked slot's size, and one lane per packet wants many packets)
+            const int limit = setups[q]->on_device() ? m->device_streams_per_call : S;
             for (size_t j = 0; j < v.size(); ++j) {
                 const Job &J = jobs[(size_t)v[j]];
-                if (!sb.members.empty() && ((int)sb.members.size() >= S || sb.res_floats + J.residue_floats > budget)) flush();
+                if (!sb.members.empty() && ((int)sb.members.size() >= limit || sb.res_floats + J.residue_floats > budget)) flush();
                 if (sb.members.empty()) {
                     sb.setup = (int)q;
                     sb.st = setups[q];
+                    sb.on_device = setups[q]->on_device();
                 }
                 sb.members.push_back(v[j]);
                 sb.pbase.push_back(sb.n_packets);
                 sb.rbase.push_back(sb.res_floats);
+                sb.ybase.push_back(sb.payload_bytes);
                 sb.n_packets += J.packets;
                 sb.res_floats += J.residue_floats;
+                sb.payload_bytes += (J.payload_bytes + 7) & ~(int64_t)7;
             }
             flush();
         }
@@ -313,6 +370,9 @@ struct GroupRun {
         const Setup &st = *sb.st;
         const size_t C = (size_t)st.info.channels, rec = (size_t)sb.n_packets * C;
         vpz_context *ctx = G.lanes[0].ctx;
+        if (sb.on_device)  // (no residue, posts or counts on the host: those arrays are born on the device)
+            return grow(ctx, sl.packets, sl.cap_packets, (size_t)sb.n_packets) && grow(ctx, sl.spans, sl.cap_spans, (size_t)sb.n_packets) &&
+                   grow(ctx, sl.payload, sl.cap_payload, (size_t)sb.payload_bytes);
         // (the slot's residue array is float-typed: int16 values take half the elements)
         const size_t res_elems = use_i16(st) ? ((size_t)sb.res_floats + 1) / 2 : (size_t)sb.res_floats;
         bool ok = grow(ctx, sl.packets, sl.cap_packets, (size_t)sb.n_packets) && grow(ctx, sl.residue, sl.cap_residue, res_elems) &&
@@ -322,8 +382,31 @@ struct GroupRun {
         return ok;
     }
 
+    // the plan of one member of a device-decoded sub-batch: packet records, spans and the packets' bytes into the slot.  The container
+    // stays open until the sub-batch has been issued (should the device refuse it, its members are decoded here after all)
+    void plan_member(size_t b, Sub &sb, int j)
+    {
+        Job &J = jobs[(size_t)sb.members[(size_t)j]];
+        if (J.status != VPZM_OK) return;
+        Slot &sl = G.slots[b % G.slots.size()];
+        const int64_t pb = sb.pbase[(size_t)j], yb = sb.ybase[(size_t)j];
+        int rc = VPZH_E_ARG;
+        try {
+            rc = vpzh_plan_range(J.h, 0, J.packets, j, sb.rbase[(size_t)j], sl.packets + pb, sl.spans + pb, sl.payload + yb, J.payload_bytes,
+                                 nullptr, nullptr);
+            if (rc == VPZH_OK) {
+                for (int64_t p = 0; p < J.packets; ++p) sl.spans[pb + p].offset += yb;  // (spans count from the sub-batch's payload)
+                J.plan_failures = vpzh_decode_failures(J.h, nullptr);
+            }
+        } catch (...) {
+            rc = VPZH_E_INVALID_DATA;
+        }
+        if (rc != VPZH_OK) J.status = VPZM_E_OPEN;
+    }
+
     void decode_member(size_t b, Sub &sb, int j)
     {
+        if (sb.on_device) return plan_member(b, sb, j);
         Job &J = jobs[(size_t)sb.members[(size_t)j]];
         if (J.status == VPZM_OK) {
             Slot &sl = G.slots[b % G.slots.size()];
@@ -367,7 +450,11 @@ struct GroupRun {
                     lk.unlock();
                     decode_member(b, sb, j);
                     lk.lock();
-                    if (++sb.decoded == (int)sb.members.size()) cv.notify_all();
+                    if (++sb.decoded == (int)sb.members.size()) {
+                        if (profile && sb.on_device)
+                            fprintf(stderr, "[vpzm] group %d: sub-batch %zu planned at %.2f ms\n", slot_index, b, seconds_since(t_begin) * 1e3);
+                        cv.notify_all();
+                    }
                     continue;
                 }
                 if (!sb.prepping && (b < B || subs[b - B].synth_done)) {  // its slot is free: get the arrays ready
@@ -453,7 +540,7 @@ struct GroupRun {
         cfg.floor_types = st->floor_types.data();
         cfg.floors0 = st->floors0.data();
         vpz_decoder *dec = nullptr;
-        if (vpz_decoder_create(L.ctx, &cfg, m->opt.streams_per_call, &dec) != VPZ_OK) {
+        if (vpz_decoder_create(L.ctx, &cfg, m->call_streams(), &dec) != VPZ_OK) {
             m->fail(std::string("vpz_decoder_create: ") + vpz_context_last_error(L.ctx));
             return nullptr;
         }
@@ -493,37 +580,87 @@ struct GroupRun {
         }
     }
 
+    vpz_entropy_setup *entropy_setup_for(Lane &L, const std::shared_ptr<Setup> &st)
+    {
+        for (auto &p : L.esetups)
+            if (p.first->same(*st)) return p.second;
+        vpz_entropy_setup *es = nullptr;
+        if (vpz_entropy_setup_create(L.ctx, st->image.data(), (uint64_t)st->image.size(), &es) != VPZ_OK) return nullptr;  // (refused: the host path)
+        constexpr size_t kSetupsPerContext = 8;  // (as many as decoders)
+        if (L.esetups.size() >= kSetupsPerContext) {
+            vpz_entropy_setup_destroy(L.esetups.front().second);
+            L.esetups.erase(L.esetups.begin());
+        }
+        L.esetups.emplace_back(st, es);
+        return es;
+    }
+
+    // ---- a device-decoded sub-batch's first two steps on the lane's stream: the packet bytes go up, vpz_entropy_decode writes residue,
+    // posts and counts into the lane's device arrays (asynchronous: the synth call that follows on the same stream consumes them without
+    // a synchronise).  false: the device path is not to be had for this sub-batch (no memory, an image the library refuses, a failed
+    // call) -- nothing of the job has changed, the sub-batch takes the host path
+    bool entropy_on_device(Lane &L, const Sub &sb, Slot &sl, int64_t n_pk, size_t pcm_bytes, double &t_upload, double &t_entropy)
+    {
+        if (const char *e = getenv("VPZM_FAIL_GPU_ENTROPY"))  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
+            if (atoi(e) != 0) return false;
+        const Setup &st = *sb.st;
+        const size_t rec = (size_t)n_pk * (size_t)st.info.channels, esize = use_i16(st) ? sizeof(int16_t) : sizeof(float);
+        if (!grow_device(L.ctx, L.d_payload, L.cap_payload, (size_t)sb.payload_bytes) ||
+            !grow_device(L.ctx, L.d_residue, L.cap_residue, (size_t)sb.res_floats * esize) ||
+            !grow_device(L.ctx, L.d_posts, L.cap_posts, rec * 64 * sizeof(int16_t)) || !grow_device(L.ctx, L.d_counts, L.cap_counts, rec) ||
+            !grow_device(L.ctx, L.d_pcm, L.cap_pcm, pcm_bytes))
+            return false;
+        vpz_entropy_setup *es = entropy_setup_for(L, sb.st);
+        if (!es) return false;
+        const auto t0 = Clock::now();
+        if (vpz_memcpy_h2d(L.ctx, L.d_payload, sl.payload, (uint64_t)sb.payload_bytes) != VPZ_OK) return false;
+        t_upload = seconds_since(t0);
+        const auto t1 = Clock::now();
+        if (vpz_entropy_decode(es, n_pk, sl.packets, sl.spans, L.d_payload, sb.payload_bytes, use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32,
+                               L.d_residue, sb.res_floats, reinterpret_cast<int16_t *>(L.d_posts), L.d_counts, (int64_t)rec,
+                               VPZ_MEM_DEVICE) != VPZ_OK)
+            return false;
+        if (profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the stage's own time; otherwise nothing waits here)
+        t_entropy = seconds_since(t1);
+        return true;
+    }
+
+    // the host path after all, for a sub-batch the device did not take: its slot gets the host arrays and the issuing thread decodes
+    // the members (their containers are still open)
+    void decode_on_host_after_all(size_t b, Sub &sb)
+    {
+        sb.on_device = false;
+        if (!prep_slot(b, sb)) {
+            for (int mi : sb.members)
+                if (jobs[(size_t)mi].status == VPZM_OK) jobs[(size_t)mi].status = VPZM_E_SYNTH;
+            m->fail("vpzm_decode_library: page-locked batch arrays could not be allocated");
+            return;
+        }
+        for (size_t j = 0; j < sb.members.size(); ++j) decode_member(b, sb, (int)j);
+    }
+
     void synth_sub(Lane &L, size_t b, Sub &sb)
     {
-        const int S = m->opt.streams_per_call;
+        const int S = m->call_streams();
         std::vector<int64_t> offs((size_t)S), written((size_t)S), caps((size_t)S, 0);
         std::vector<int32_t> status;
         Slot &sl = G.slots[b % G.slots.size()];
         const Setup &st = *sb.st;
         const int C = st.info.channels;
-        bool any = false, all_ok = true;
-        int64_t cap = 0, base = INT64_MAX;
-        // (the call sees the sub-batch's part of the caller's PCM array: a host-memory call mirrors its output extent on the
-        // device, so the offsets handed over start at the sub-batch's lowest one)
-        for (size_t j = 0; j < sb.members.size(); ++j) base = std::min(base, pcm_offset[jobs[(size_t)sb.members[j]].k]);
-        for (size_t j = 0; j < sb.members.size(); ++j) {
-            const Job &J = jobs[(size_t)sb.members[j]];
-            offs[j] = pcm_offset[J.k] - base;
-            if (J.status == VPZM_OK) {
-                any = true;
-                // (every stream has its own area: files of one encoder setting share a setup header and differ in length)
-                caps[j] = pcm_capacity[J.k];
-                cap = std::max(cap, caps[j]);
-            } else {
-                all_ok = false;
-            }
-        }
         const size_t elem = out_layout == VPZ_OUT_INTERLEAVED_S16 ? sizeof(int16_t) : sizeof(float);
-        void *out_at = static_cast<char *>(pcm_out) + elem * (size_t)base;
-        int64_t n_pk = sb.n_packets;
-        if (any && !all_ok) {
-            // a member whose container did not decode leaves its packets out (rare): the arrays are re-packed stream by stream,
-            // stream ids kept, so that vpz_decoder_synth sees only decoded packets; their residue stays where it is
+        bool any = false, all_ok = true;
+        int64_t cap = 0, base = INT64_MAX, n_pk = 0;
+        // a member whose container did not decode leaves its packets out (rare): the arrays are re-packed stream by stream,
+        // stream ids kept, so that vpz_decoder_synth sees only decoded packets; their residue stays where it is
+        auto repack = [&] {
+            any = false;
+            all_ok = true;
+            for (int mi : sb.members) {
+                if (jobs[(size_t)mi].status == VPZM_OK) any = true;
+                else all_ok = false;
+            }
+            n_pk = sb.n_packets;
+            if (!any || all_ok) return;
             int64_t w = 0;
             for (size_t j = 0; j < sb.members.size(); ++j) {
                 const Job &J = jobs[(size_t)sb.members[j]];
@@ -531,27 +668,77 @@ struct GroupRun {
                 const int64_t pb = sb.pbase[j];
                 if (w != pb) {
                     memmove(sl.packets + w, sl.packets + pb, sizeof(vpz_packet) * (size_t)J.packets);
-                    memmove(sl.posts + (size_t)w * 64 * C, sl.posts + (size_t)pb * 64 * C, sizeof(int16_t) * 64 * (size_t)C * (size_t)J.packets);
-                    memmove(sl.counts + (size_t)w * C, sl.counts + (size_t)pb * C, (size_t)C * (size_t)J.packets);
-                    if (st.f0_stride) {
-                        memmove(sl.f0_amp + (size_t)w * C, sl.f0_amp + (size_t)pb * C, sizeof(float) * (size_t)C * (size_t)J.packets);
-                        memmove(sl.f0_coeff + (size_t)w * C * st.f0_stride, sl.f0_coeff + (size_t)pb * C * st.f0_stride,
-                                sizeof(float) * (size_t)C * st.f0_stride * (size_t)J.packets);
+                    if (sb.on_device) {  // (the device arrays are written for the packets as they lie now)
+                        memmove(sl.spans + w, sl.spans + pb, sizeof(vpz_entropy_span) * (size_t)J.packets);
+                    } else {
+                        memmove(sl.posts + (size_t)w * 64 * C, sl.posts + (size_t)pb * 64 * C, sizeof(int16_t) * 64 * (size_t)C * (size_t)J.packets);
+                        memmove(sl.counts + (size_t)w * C, sl.counts + (size_t)pb * C, (size_t)C * (size_t)J.packets);
+                        if (st.f0_stride) {
+                            memmove(sl.f0_amp + (size_t)w * C, sl.f0_amp + (size_t)pb * C, sizeof(float) * (size_t)C * (size_t)J.packets);
+                            memmove(sl.f0_coeff + (size_t)w * C * st.f0_stride, sl.f0_coeff + (size_t)pb * C * st.f0_stride,
+                                    sizeof(float) * (size_t)C * st.f0_stride * (size_t)J.packets);
+                        }
                     }
                 }
                 w += J.packets;
             }
             n_pk = w;
+        };
+        repack();
+        const auto t0 = Clock::now();
+        double t_upload = 0, t_entropy = 0, t_download = 0;
+        int64_t on_device_streams = 0, on_device_payload = 0;
+        if (sb.on_device && any && n_pk > 0) {
+            // the members' areas of the lane's device PCM array, back to back: a stream produces at most block_size1 / 2 samples per
+            // packet, so an area need not be larger than that whatever the caller's is (one block of slack each)
+            size_t pcm_elems = 0;
+            for (size_t j = 0; j < sb.members.size(); ++j) {
+                const Job &J = jobs[(size_t)sb.members[j]];
+                if (J.status == VPZM_OK) pcm_elems += (size_t)(std::min(pcm_capacity[J.k], J.packets * (st.info.block_size1 / 2)) + st.info.block_size1) * (size_t)C;
+            }
+            if (entropy_on_device(L, sb, sl, n_pk, pcm_elems * elem, t_upload, t_entropy)) {
+                for (size_t j = 0; j < sb.members.size(); ++j) {
+                    const Job &J = jobs[(size_t)sb.members[j]];
+                    if (J.status != VPZM_OK) continue;
+                    ++on_device_streams;
+                    on_device_payload += J.payload_bytes;
+                    results[J.k].skipped_packets += J.plan_failures;  // (an unused mode number: the plan's "not decoded", counted as the host decode counts it)
+                }
+            } else {
+                decode_on_host_after_all(b, sb);
+                repack();
+            }
         }
+        const bool dev = sb.on_device;
+        // (a host-memory call sees the sub-batch's part of the caller's PCM array: it mirrors its output extent on the
+        // device, so the offsets handed over start at the sub-batch's lowest one)
+        for (size_t j = 0; j < sb.members.size(); ++j) base = std::min(base, pcm_offset[jobs[(size_t)sb.members[j]].k]);
+        int64_t dev_at = 0;
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            const Job &J = jobs[(size_t)sb.members[j]];
+            offs[j] = dev ? dev_at : pcm_offset[J.k] - base;
+            if (J.status == VPZM_OK) {
+                // (every stream has its own area: files of one encoder setting share a setup header and differ in length)
+                caps[j] = pcm_capacity[J.k];
+                if (dev) {
+                    caps[j] = std::min(caps[j], J.packets * (st.info.block_size1 / 2));
+                    dev_at += (caps[j] + st.info.block_size1) * C;
+                }
+                cap = std::max(cap, caps[j]);
+            }
+        }
+        void *out_at = dev ? static_cast<void *>(L.d_pcm) : static_cast<char *>(pcm_out) + elem * (size_t)base;
+        const float *residue = dev ? reinterpret_cast<const float *>(L.d_residue) : sl.residue;
+        const int16_t *posts = dev ? reinterpret_cast<const int16_t *>(L.d_posts) : sl.posts;
+        const uint8_t *counts = dev ? L.d_counts : sl.counts;
         int rc = VPZ_OK;
         std::vector<int> member_rc(sb.members.size(), VPZ_OK);  // (a sub-batch is one synth call; after a failed one, a call per member)
-        const auto t0 = Clock::now();
         static const bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;  // (diagnosis: the decode side of the pipeline alone)
         if (any && n_pk > 0 && !no_synth) {
             vpz_decoder *dec = decoder_for(L, sb.st);
             std::vector<int64_t> wr((size_t)S);
             // one synth call over the slot's packets [p0, p0 + n): the records, the Floor0 data and the statuses move with p0, the
-            // residue offsets are the slot's
+            // residue offsets are the slot's.  A device-decoded sub-batch's call reads the lane's device arrays, laid out the same way
             auto call = [&](int64_t p0, int64_t n) -> int {
                 int r = dec ? VPZ_OK : VPZ_E_NOMEM;
                 // the decoder is re-used for new streams: back to what a StreamDecoder is after ProcessHeaderPackets
@@ -564,8 +751,8 @@ struct GroupRun {
                 if (r == VPZ_OK) r = vpz_decoder_set_residue_format(dec, use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32);
                 if (r == VPZ_OK) r = vpz_decoder_set_stream_capacities(dec, caps.data(), S);
                 if (r == VPZ_OK)
-                    r = vpz_decoder_synth(dec, n, sl.packets + p0, sl.residue, sb.res_floats, sl.posts + (size_t)p0 * 64 * C,
-                                          sl.counts + (size_t)p0 * C, n * C, VPZ_MEM_HOST, out_at, offs.data(), cap, out_layout, 0, wr.data());
+                    r = vpz_decoder_synth(dec, n, sl.packets + p0, residue, sb.res_floats, posts + (size_t)p0 * 64 * C, counts + (size_t)p0 * C,
+                                          n * C, dev ? VPZ_MEM_DEVICE : VPZ_MEM_HOST, out_at, offs.data(), cap, out_layout, 0, wr.data());
                 if (r != VPZ_OK) m->fail(std::string("vpz_decoder_synth: ") + (dec ? vpz_context_last_error(L.ctx) : "no decoder"));
                 int64_t not_ok = 0;
                 if (r == VPZ_OK && vpz_decoder_last_packet_status(dec, nullptr, 0, &not_ok) == VPZ_OK && not_ok > 0) {
@@ -590,7 +777,7 @@ struct GroupRun {
                 std::fill(member_rc.begin(), member_rc.end(), kNoDecoder);
             } else {
                 // "a stream that fails costs only itself": whatever one member's packets did to the call, the others get a call
-                // of their own (the packets lie member by member)
+                // of their own (the packets lie member by member; a device-decoded sub-batch's arrays are not decoded again)
                 for (int64_t p = 0; p < n_pk;) {
                     const int32_t sid = sl.packets[p].stream;
                     int64_t q = p;
@@ -603,12 +790,60 @@ struct GroupRun {
                 }
             }
         }
+        double t_call = seconds_since(t0) - t_upload - t_entropy;
+        if (dev && any && n_pk > 0) {
+            if (profile) {
+                (void)vpz_context_synchronize(L.ctx);
+                t_call = seconds_since(t0) - t_upload - t_entropy;
+            }
+            // every member's PCM to the caller's area, what samples_written says and no more; neighbours whose areas touch on both sides
+            // (capacities that are the streams' lengths, offsets packed) go as one copy
+            const auto t1 = Clock::now();
+            for (size_t j = 0; j < sb.members.size();) {
+                const Job &J = jobs[(size_t)sb.members[j]];
+                if (J.status != VPZM_OK || member_rc[j] != VPZ_OK || written[j] <= 0) {
+                    ++j;
+                    continue;
+                }
+                const int64_t src = offs[j], dst = pcm_offset[J.k];
+                int64_t n = written[j] * C;
+                size_t q = j + 1;
+                for (; q < sb.members.size(); ++q) {
+                    const Job &N = jobs[(size_t)sb.members[q]];
+                    if (N.status != VPZM_OK || member_rc[q] != VPZ_OK || written[q] <= 0 || offs[q] != src + n || pcm_offset[N.k] != dst + n) break;
+                    n += written[q] * C;
+                }
+                if (vpz_memcpy_d2h(L.ctx, static_cast<char *>(pcm_out) + elem * (size_t)dst, L.d_pcm + elem * (size_t)src, (uint64_t)n * elem) != VPZ_OK) {
+                    m->fail(std::string("vpz_memcpy_d2h: ") + vpz_context_last_error(L.ctx));
+                    for (size_t r = j; r < q; ++r) member_rc[r] = VPZ_E_HIP;
+                }
+                j = q;
+            }
+            // (the slot's packet records and the lane's arrays are free again once the stream has drained)
+            if (vpz_context_synchronize(L.ctx) != VPZ_OK)
+                for (size_t j = 0; j < sb.members.size(); ++j)
+                    if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
+            t_download = seconds_since(t1);
+        }
+        for (int mi : sb.members) {  // (a device-decoded sub-batch's containers were kept open for the host path after all)
+            Job &J = jobs[(size_t)mi];
+            if (J.h) vpzh_close(J.h);
+            J.h = nullptr;
+        }
         const double dt = seconds_since(t0);
-        if (profile)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets)\n", slot_index, b,
-                    seconds_since(t_begin) * 1e3, dt * 1e3, (long long)n_pk);
+        if (profile) {
+            if (dev)
+                fprintf(stderr, "[vpzm] group %d: sub-batch %zu on the device done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, download %.2f ms; %lld packets, %lld payload bytes)\n",
+                        slot_index, b, seconds_since(t_begin) * 1e3, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, t_download * 1e3,
+                        (long long)n_pk, (long long)sb.payload_bytes);
+            else
+                fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets)\n", slot_index, b,
+                        seconds_since(t_begin) * 1e3, dt * 1e3, (long long)n_pk);
+        }
         std::lock_guard<std::mutex> lk(mu);
         t_synth += dt;
+        device_streams += on_device_streams;
+        device_payload += on_device_payload;
         for (size_t j = 0; j < sb.members.size(); ++j) {
             Job &J = jobs[(size_t)sb.members[j]];
             if (J.status != VPZM_OK) continue;
@@ -709,6 +944,10 @@ int vpzm_create(const int32_t *device_ids, int32_t n_devices, const vpzm_options
     if (opt) m->opt = *opt;
     const bool threads_by_default = m->opt.host_threads <= 0;
     if (threads_by_default) m->opt.host_threads = vpzh_default_threads();
+    // (gpu_entropy: one lane per packet, and a launch's time at small sizes is the latency of one packet's chain -- sixteen streams are
+    // too few packets for the device.  Device-resident inputs are not bound by a page-locked slot's size, so a device-decoded call
+    // takes more streams by default; a value the caller gives holds for both kinds of call)
+    if (m->opt.gpu_entropy) m->device_streams_per_call = m->opt.streams_per_call > 0 ? m->opt.streams_per_call : 64;
     if (m->opt.streams_per_call <= 0) m->opt.streams_per_call = 16;
     // (one GPU, 16 CPUs, 1 024 streams, 16-bit PCM, slots = 4 * contexts + 4: 2 contexts 90 ms, 3: 84 ms, 4: 78 ms -- a host-memory
     // synth call is upload, kernels, download in a row, and only other contexts' calls fill the link's other direction and the
@@ -756,9 +995,14 @@ void vpzm_destroy(vpzm_dispatcher *m)
             vpz_host_free(ctx0, s.counts);
             vpz_host_free(ctx0, s.f0_amp);
             vpz_host_free(ctx0, s.f0_coeff);
+            vpz_host_free(ctx0, s.spans);
+            vpz_host_free(ctx0, s.payload);
         }
         for (Lane &L : G.lanes) {
             for (auto &p : L.decs) vpz_decoder_destroy(p.second);
+            for (auto &p : L.esetups) vpz_entropy_setup_destroy(p.second);
+            for (uint8_t *d : {L.d_payload, L.d_residue, L.d_posts, L.d_counts, L.d_pcm})
+                if (d && L.ctx) vpz_device_free(L.ctx, d);
             if (L.ctx) vpz_context_destroy(L.ctx);
         }
     }
@@ -776,7 +1020,8 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
     if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_INTERLEAVED_S16) return VPZM_E_ARG;
     for (int32_t k = 0; k < n; ++k)
         if (!data[k] || pcm_offset[k] < 0 || pcm_capacity[k] < 0) return VPZM_E_ARG;
-    if (stats) *stats = vpzm_stats{};
+    // (the fields appended for gpu_entropy exist for a caller that sets the option; an older caller's struct ends before them)
+    if (stats) memset(stats, 0, m->opt.gpu_entropy ? sizeof *stats : offsetof(vpzm_stats, device_gpu_entropy_streams));
     // (slots, contexts and decoder caches belong to one call at a time: a second caller waits here, it is not refused)
     std::lock_guard<std::mutex> one_call(m->call_mu);
     m->error.clear();
@@ -808,9 +1053,7 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
         stats->threads_per_device = per_device;
         size_t pinned = 0;
         for (const Group &G : m->groups)
-            for (const Slot &sl : G.slots)
-                pinned += sl.cap_packets * sizeof(vpz_packet) + sl.cap_residue * sizeof(float) + sl.cap_posts * sizeof(int16_t) + sl.cap_counts +
-                          (sl.cap_f0 + sl.cap_f0c) * sizeof(float);
+            for (const Slot &sl : G.slots) pinned += sl.bytes();
         stats->pinned_mib = (int32_t)std::min<size_t>(pinned >> 20, 0x7fffffff);
         for (int d = 0; d < D && d < 16; ++d) {
             stats->device_wall_s[d] = runs[(size_t)d]->t_wall;
@@ -818,6 +1061,10 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
             stats->device_synth_s[d] = runs[(size_t)d]->t_synth;
             stats->device_streams[d] = runs[(size_t)d]->hi - runs[(size_t)d]->lo;
             stats->device_samples[d] = runs[(size_t)d]->samples_total;
+            if (m->opt.gpu_entropy) {
+                stats->device_gpu_entropy_streams[d] = runs[(size_t)d]->device_streams;
+                stats->device_payload_bytes[d] = runs[(size_t)d]->device_payload;
+            }
         }
     }
     return VPZM_OK;

@@ -14,7 +14,7 @@ E_OPEN, E_CAPACITY, E_SYNTH, E_SETUP = -10, -11, -12, -13
 class Options(C.Structure):
     _fields_ = [("host_threads", C.c_int32), ("streams_per_call", C.c_int32), ("contexts_per_device", C.c_int32),
                 ("clip_samples", C.c_int32), ("slots_per_device", C.c_int32), ("float_residue", C.c_int32),
-                ("reserved", C.c_int32 * 2)]
+                ("gpu_entropy", C.c_int32), ("reserved", C.c_int32)]
 
 
 class StreamResult(C.Structure):
@@ -25,7 +25,9 @@ class StreamResult(C.Structure):
 class Stats(C.Structure):
     _fields_ = [("wall_s", C.c_double), ("device_wall_s", C.c_double * 16), ("device_decode_s", C.c_double * 16),
                 ("device_synth_s", C.c_double * 16), ("device_streams", C.c_int64 * 16), ("device_samples", C.c_int64 * 16),
-                ("threads_per_device", C.c_int32), ("pinned_mib", C.c_int32)]
+                ("threads_per_device", C.c_int32), ("pinned_mib", C.c_int32),
+                # (written only by a dispatcher created with gpu_entropy: a caller with the shorter struct is never written past)
+                ("device_gpu_entropy_streams", C.c_int64 * 16), ("device_payload_bytes", C.c_int64 * 16)]
 
 
 RESULT_DTYPE = np.dtype([("status", "<i4"), ("device_slot", "<i4"), ("channels", "<i4"), ("sample_rate", "<i4"),
@@ -60,13 +62,15 @@ class MultiError(RuntimeError):
 
 
 class Dispatcher:
-    """vpzm_dispatcher: one context group per entry of `device_ids` (an id may repeat: several groups on one GPU)."""
+    """vpzm_dispatcher: one context group per entry of `device_ids` (an id may repeat: several groups on one GPU).
+    gpu_entropy: streams whose setup the device can decode (vpzh_gpu_decode_supported) are entropy-decoded there, the others on
+    the host threads in the same call; the PCM is the same bit for bit."""
 
     def __init__(self, device_ids, host_threads=0, streams_per_call=0, contexts_per_device=0, clip_samples=False,
-                 slots_per_device=0, float_residue=False):
+                 slots_per_device=0, float_residue=False, gpu_entropy=False):
         ids = (C.c_int32 * len(device_ids))(*[int(d) for d in device_ids])
         opt = Options(host_threads, streams_per_call, contexts_per_device, 1 if clip_samples else 0, slots_per_device,
-                      1 if float_residue else 0)
+                      1 if float_residue else 0, 1 if gpu_entropy else 0)
         self._h = C.c_void_p()
         rc = lib().vpzm_create(ids, len(device_ids), C.byref(opt), C.byref(self._h))
         if rc != OK:

@@ -40,12 +40,42 @@ def ogg_packets(raw):
     return out
 
 
+# The smallest packets at which the parse of a packet's first bits can go wrong, in place of audio packets 3 ... 9 of ten long
+# blocks: nothing to read, each kind of record (type bit set, unused mode number), a header that ends inside the packet, and
+# EOS on a degenerate packet.  What the front end wrote for them before the parse became one function (flags per packet,
+# vpzh_decode_failures): BLOCK 1, PREV 2, NEXT 4, EOS 8, NOT_DECODED 16, INTERLEAVED 32.
+HEADER_EDGE = {
+    "stereo_coupled_res2": ([39, 39, 39, 32, 16, 16, 39, 39, 39, 40], (0, -1)),
+    "mono_floor1_res1": ([7, 7, 7, 0, 16, 16, 7, 7, 7, 8], (1, 5)),  # (three modes: mode number 3 is unused)
+    "three_channels_two_submaps": ([7, 7, 7, 0, 16, 16, 7, 7, 7, 8], (0, -1)),
+}
+
+
+def header_edge_stream(name):
+    import synthetic_streams as ss
+    import vorbis_writer as vw
+    stream, rng = getattr(ss, name)()
+    long_mode = next(i for i, (blockflag, _) in enumerate(stream.modes) if blockflag)
+    audio = [stream.audio_packet(rng, long_mode, 1, 1)[0] for _ in range(10)]
+    mode_bits = vw.ilog(len(stream.modes) - 1)
+    unused = (1 << mode_bits) - 1
+    audio[3] = b""
+    audio[4] = b"\x01"
+    audio[5] = bytes([unused << 1]) if unused >= len(stream.modes) else b"\x01\x02"
+    audio[6] = audio[6][:1]
+    audio[7] = audio[7][:3]
+    audio[9] = b""
+    granules = [0, 0, 0] + [stream.bs1 // 2 * i for i in range(10)]
+    return bytes(vw.ogg_mux(stream.headers() + audio, granules, packets_per_page=2))
+
+
 def streams():
     """(name, container bytes) of every stream the tests below look at"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import hostile_setups as hs
     import synthetic_streams as ss
     out = [(n, open(os.path.join(GOLDEN, n), "rb").read()) for n in FIXTURES]
+    out += [("header edges:" + name, header_edge_stream(name)) for name in sorted(HEADER_EDGE)]
     for name, make in sorted(ss.ALL.items()):
         st, rng = make()
         ogg, _ = st.build(rng, 24)
@@ -127,6 +157,20 @@ def test_plan_records_equal_the_cpu_decode(front, cut):
         assert packets.tobytes() == ref.tobytes(), (name, cut)
         assert used == ref_used.value, (name, cut)
         f.close()
+
+
+@pytest.mark.parametrize("name", sorted(HEADER_EDGE))
+def test_header_edge_packets_give_the_written_down_records(front, name):
+    flags, failures = HEADER_EDGE[name]
+    f = front.OggVorbisFile(header_edge_stream(name))
+    assert f.audio_packets == 10 and f.gpu_decode_supported
+    planned = f.plan_packets()[0]
+    assert list(planned["flags"]) == flags
+    assert f.decode_failures() == failures  # (as the plan counts them ...
+    decoded = f.decode_packets()[0]
+    assert decoded.tobytes() == planned.tobytes() and list(decoded["flags"]) == flags
+    assert f.decode_failures() == failures  # ... and as the decode does)
+    f.close()
 
 
 def test_payload_spans_reproduce_the_packets(front):

@@ -3,7 +3,9 @@ own fixtures (tests/golden/*.ogg are copies of /root/reference/TestFiles/*.ogg -
 Known answers: channels, rates, block sizes, packet counts, floor / residue /
 coupling layout, and the decoded sample count, which must equal the stream's granule span."""
 import hashlib
+import json
 import os
+import sys
 import time
 
 import numpy as np
@@ -71,6 +73,18 @@ def test_decoded_sample_count_equals_granule_span(front, oracle, name):
     # decoded audio is smooth: a wrong codeword anywhere shows up as broadband noise
     d = np.diff(pcm, axis=1)
     assert np.sqrt((d ** 2).mean()) < 0.6 * np.sqrt((pcm ** 2).mean()) + 1e-3
+
+
+@pytest.mark.parametrize("name", sorted(FACTS))
+def test_fixture_records_equal_the_recorded_ones(front, name):
+    """Every byte the front end writes for a real file -- packet records, posts, post counts, the residue as float and as
+    int16, of the whole file and of a range, from the decode and from the plan -- against tests/golden/front_records.json
+    (tools/make_golden_fixtures.py --front-records; the file names the commit whose build wrote it)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(GOLDEN), os.pardir, "tools"))
+    from make_golden_fixtures import front_records
+    recorded = json.load(open(os.path.join(GOLDEN, "front_records.json")))["fixtures"][name]
+    assert "residue_i16" in recorded and recorded["range_5_40_plan_packets"] == recorded["range_5_40_decode_packets"]
+    assert front_records(front, os.path.join(GOLDEN, name)) == recorded
 
 
 def test_truncated_and_corrupt_input(front):

@@ -9,11 +9,16 @@ float64 synthesis; tests/test_golden_vectors_cpu.py fails if a later edit of the
 tests/test_golden_vectors_gpu.py holds the HIP path to them without needing any oracle code on the GPU box.
 
     python tools/make_golden_fixtures.py        # rewrites tests/golden/*.npz
+    python tools/make_golden_fixtures.py --front-records COMMIT
+                                                # writes tests/golden/front_records.json alone: what the C++ front end, built
+                                                # from COMMIT, writes for the four .ogg fixtures (tests/test_front_cpu.py)
     python tools/make_golden_fixtures.py --reference NVORBIS_DIR
                                                 # writes tests/golden/reference_constants.npz alone: the constant tables
                                                 # of the reference's source text (NVORBIS_DIR: its NVorbis/ folder), which
                                                 # tests/test_oracle_tables.py holds the oracle to
 """
+import hashlib
+import json
 import os
 import re
 import sys
@@ -24,6 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 OUT = os.path.join(ROOT, "tests", "golden")
+FIXTURES = ("1test.ogg", "2test.ogg", "3test.ogg", "issue6test.ogg")
 
 
 def main():
@@ -75,7 +81,7 @@ def main():
 
     # ---- the first 4096 PCM samples per channel of every reference fixture, and the decoded lengths
     pcm_head = {}
-    for name in ("1test.ogg", "2test.ogg", "3test.ogg", "issue6test.ogg"):
+    for name in FIXTURES:
         f = OggVorbisFile(os.path.join(OUT, name))
         pk, res, posts, counts = f.decode_packets()
         ref, pos, clipped = helpers.oracle_decode(oracle, f.channels, f.block_size0, f.block_size1,
@@ -92,6 +98,48 @@ def main():
     for n in sorted(os.listdir(OUT)):
         if n.endswith(".npz"):
             print("%-28s %7d bytes" % (n, os.path.getsize(os.path.join(OUT, n))))
+
+
+def front_records(front, path):
+    """Digests of everything the front end writes for one fixture: a whole-file decode (stream_id 0, residue_base 0) as
+    float and, where the residue is integral, as int16; and the packet records of the range first=5, count=40 (cut to the
+    file's length: 1test.ogg has 25 packets) from vpzh_decode_range_ex and from vpzh_plan_range."""
+    import ctypes as C
+
+    def sha(a):
+        return hashlib.sha256(a.tobytes()).hexdigest()
+
+    f = front.OggVorbisFile(path)
+    pk, res, posts, counts = f.decode_packets()
+    out = {"packets": sha(pk), "posts": sha(posts), "post_counts": sha(counts), "residue_f32": sha(res),
+           "residue_floats": int(f.info.residue_floats), "total_samples": int(f.total_samples),
+           "decode_failures": list(f.decode_failures())}
+    if f.residue_is_integral:
+        pk16, res16, posts16, counts16 = f.decode_packets(int16=True)
+        assert (sha(pk16), sha(posts16), sha(counts16)) == (out["packets"], out["posts"], out["post_counts"])
+        out["residue_i16"] = sha(res16)
+    first = 5
+    count = min(40, f.audio_packets - first)
+    pk_r = front.capi.make_packets(count)
+    res_r = np.zeros(count * f.channels * f.block_size1 // 2, dtype=np.float32)
+    posts_r = np.zeros((count * f.channels, 64), dtype=np.int16)
+    counts_r = np.zeros(count * f.channels, dtype=np.uint8)
+    assert front.lib().vpzh_decode_range_ex(f._h, first, count, 0, 0, pk_r.ctypes.data, res_r.ctypes.data, posts_r.ctypes.data,
+                                            counts_r.ctypes.data, None, None, None, 0) == 0
+    out["range_5_40_decode_packets"] = sha(pk_r)
+    out["range_5_40_plan_packets"] = sha(f.plan_packets(first, count)[0])
+    f.close()
+    return out
+
+
+def write_front_records(commit):
+    from vorbispizza_amd import front
+    rec = {"generated_at_commit": commit, "fixtures": {n: front_records(front, os.path.join(OUT, n)) for n in FIXTURES}}
+    path = os.path.join(OUT, "front_records.json")
+    with open(path, "w") as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("%-28s %7d bytes" % (os.path.basename(path), os.path.getsize(path)))
 
 
 def reference_constants(src_dir):
@@ -112,5 +160,7 @@ def reference_constants(src_dir):
 if __name__ == "__main__":
     if "--reference" in sys.argv:
         reference_constants(sys.argv[sys.argv.index("--reference") + 1])
+    elif "--front-records" in sys.argv:
+        write_front_records(sys.argv[sys.argv.index("--front-records") + 1])
     else:
         main()

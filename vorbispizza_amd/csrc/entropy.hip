@@ -255,6 +255,8 @@ __host__ __device__ void decode_one_packet(const uint8_t *img, const PacketDesc 
     p.words = payload;
     p.base = (uint64_t)d.payload_bit;
     p.total = d.size * 8u;
+    // the floors begin after the header bits, or where the packet ends: the CPU front end's decode_packet starts at the same
+    // bit (PacketHead::header_bits of host/vorbis_front.cpp, the same sum)
     const uint32_t header_bits = 1u + (uint32_t)h->mode_field_bits + (bf ? 2u : 0u);  // type bit, mode, window flags
     p.pos = header_bits < p.total ? header_bits : p.total;
 

@@ -57,14 +57,13 @@ float vorbis_float32(uint32_t bits)  // Utils.cs:92-105
 
 // ---------------------------------------------------------------------------------------------
 // VorbisPacket bit reader (VorbisPacket.cs:157-292): LSB-first; reads past the end return the
-// truncated value; only SkipBits past the end raises IsShort.
+// truncated value.  IsShort, which only SkipBits past the end raises, has no reader here (parse_head says why).
 // ---------------------------------------------------------------------------------------------
 struct BitReader {
     const uint8_t *data = nullptr;
     int64_t total_bits = 0, pos = 0;
-    bool is_short = false;
 
-    void init(const uint8_t *d, size_t bytes) { data = d; total_bits = (int64_t)bytes * 8; pos = 0; is_short = false; }
+    void init(const uint8_t *d, size_t bytes) { data = d; total_bits = (int64_t)bytes * 8; pos = 0; }
     int64_t remaining() const { return total_bits - pos; }
 
     uint64_t try_peek(int count, int *bits_read) const
@@ -95,7 +94,6 @@ struct BitReader {
         int64_t rem = remaining();
         if (rem >= count) { pos += count; return count; }
         pos = total_bits;
-        is_short = true;
         return (int)rem;
     }
     uint64_t read_bits(int count)
@@ -771,6 +769,10 @@ struct Residue {
 
 struct Mapping {  // Mapping.cs:19-95
     std::vector<uint8_t> coupling_angle, coupling_magnitude, mux, submap_floor, submap_residue;
+    // One submap, more than one channel, Residue2: every packet of the mapping hands its residue over as the interleaved
+    // vector (VPZ_PKT_INTERLEAVED; vpzh_stream::decode_packet).  Set by load_headers, which knows the residues.  With one
+    // submap `read` leaves every mux at 0, so that submap holds all the channels.
+    bool interleaved = false;
     void read(BitReader &p, int channels, int n_floors, int n_residues)
     {
         int submaps = 1;
@@ -816,12 +818,25 @@ struct Mode {  // Mode.cs:12-28
 // (the payload lies in the stream's one `payload` buffer: a vector per packet was ~700 heap blocks per stream, allocated by the thread
 // that opens the container and -- in the multi-device dispatcher -- freed by the one that decodes it, i.e. through the allocator's
 // cross-thread path, 16 threads at a time)
+// What the first bits of an audio packet say (parse_head, once per packet when the stream is opened): everything the
+// packet's record, its place in the batch and the sample position need.
+enum class PacketKind : uint8_t { Audio, NotAudio, Failed };  // Failed: the decode throws -- at the parse, an unused mode number
+struct PacketHead {
+    PacketKind kind = PacketKind::NotAudio;
+    uint8_t flags = 0;           // the record's flags byte, final: no decode changes it (a throw takes failed_head's instead)
+    uint8_t mapping = 0;
+    uint8_t header_bits = 0;     // type bit, mode number, window flags: where the floors begin
+    int32_t residue_values = 0;  // what the packet takes in the batch's residue vector
+    int32_t samples = 0;         // what it adds to the sample position
+};
+
 struct OggPacket {
     const uint8_t *data = nullptr;
     size_t size = 0;
     int64_t granule = -1;
     bool eos = false;
     bool resync = false;   // VorbisPacket.IsResync: the page that completes the packet was found after lost sync
+    PacketHead head;       // (audio packets only)
 };
 
 // Ogg CRC (polynomial 0x04c11db7, no reflection), Ogg/Crc.cs.  Eight tables (slicing by 8): the byte-at-a-time form is a
@@ -858,8 +873,6 @@ uint32_t crc_update(uint32_t crc, const uint8_t *d, size_t n)
     for (; i < n; ++i) crc = (crc << 8) ^ T.t[0][((crc >> 24) & 0xff) ^ d[i]];
     return crc;
 }
-
-}  // namespace
 
 // What the setup header of a stream unpacks into (StreamDecoder.cs:262-321): codebooks with their decode tables, floors,
 // residues, mappings, modes.  Files that come out of one encoder at one setting carry byte-identical setup headers, and a host
@@ -918,11 +931,290 @@ struct SetupCache {
         return b;
     }
 };
-static SetupCache &setup_cache()
+SetupCache &setup_cache()
 {
     static SetupCache c;  // (thread-safe initialisation)
     return c;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The packet layer: one parse of a packet's first bits, one rule for its record.
+// ---------------------------------------------------------------------------------------------
+// The record of an exception out of DecodeNextPacket (StreamDecoder.cs:696-762: "Unused mode index.", a residue vector
+// overrun, ...).  It costs the reference exactly that packet: it is consumed, no decoder state has changed yet -- not even
+// `_eosFound |= isEndOfStream` (:647) -- and the next Read goes on with the following packet.  So the packet is handed
+// over as "not decoded" WITHOUT its EOS flag, and only IsResync stays.
+const char kUnusedMode[] = "Unused mode index.";  // the one such exception the first bits decide: PacketKind::Failed at the parse
+PacketHead failed_head(const OggPacket &pk)
+{
+    PacketHead h;
+    h.kind = PacketKind::Failed;
+    h.flags = (uint8_t)(VPZ_PKT_NOT_DECODED | (pk.resync ? VPZ_PKT_RESYNC : 0));
+    return h;
+}
+
+// The only code that reads the type bit, the mode number (StreamDecoder.cs:728-735) and the window flags (Mode.cs:30-66).
+// Bits past the packet's end read as 0: an empty packet is a block of mode 0.  Mode.cs:32-36 gives a packet up when it
+// IsShort before the window flags, but only SkipBits raises that (VorbisPacket.cs:269,281) and nothing of a fresh packet
+// has been skipped: the test cannot fire and has no counterpart here.
+PacketHead parse_head(const OggPacket &pk, const SetupBlob &su, int channels, int size0, int size1)
+{
+    BitReader p;
+    p.init(pk.data, pk.size);
+    PacketHead h;
+    h.flags = (uint8_t)((pk.eos ? VPZ_PKT_EOS : 0) | (pk.resync ? VPZ_PKT_RESYNC : 0));
+    if (p.read_bit()) {  // not an audio packet: DecodeNextPacket returns null
+        h.flags |= VPZ_PKT_NOT_DECODED;
+        return h;
+    }
+    const size_t mode_idx = (size_t)p.read_bits(su.mode_field_bits);
+    if (mode_idx >= su.modes.size()) return failed_head(pk);  // kUnusedMode
+    const Mode &mode = su.modes[mode_idx];
+    const int size = mode.block_flag ? size1 : size0;
+    bool prev = true, next = true;
+    h.kind = PacketKind::Audio;
+    if (mode.block_flag) {
+        prev = p.read_bit();
+        next = p.read_bit();
+        h.flags |= VPZ_PKT_BLOCK_FLAG | (prev ? VPZ_PKT_PREV_FLAG : 0) | (next ? VPZ_PKT_NEXT_FLAG : 0);
+    }
+    if (su.mappings[mode.mapping].interleaved) h.flags |= VPZ_PKT_INTERLEAVED;
+    h.mapping = (uint8_t)mode.mapping;
+    h.header_bits = (uint8_t)(1 + su.mode_field_bits + (mode.block_flag ? 2 : 0));
+    h.residue_values = channels * (size / 2);
+    // PacketInfo.SampleCount = RightStart - LeftStart (Mode.cs:30-66), what IPacketGranuleCountProvider.GetPacketGranuleCount
+    // (StreamDecoder.cs:884-913) adds to the sample position
+    const int left_start = prev ? 0 : (size - size0) / 4;
+    const int right_start = next ? size / 2 : (size * 3 - size0) / 4;
+    h.samples = right_start - left_start;
+    return h;
+}
+
+// A packet's record, the same bytes whoever writes it: the CPU decode (decode_packet; decode_range with failed_head for a
+// packet that threw) and the plan of the device decode (vpzh_plan_range).
+void write_record(const PacketHead &h, const OggPacket &pk, int32_t stream_id, int64_t residue_off, vpz_packet *out)
+{
+    memset(out, 0, sizeof *out);
+    out->stream = stream_id;
+    out->flags = h.flags;
+    out->mapping = h.mapping;
+    out->granule = h.kind == PacketKind::Audio ? pk.granule : -1;
+    out->residue_offset = residue_off;
+}
+
+// Is every residue value of this stream an integer that fits 16 bits?  A residue is a sum, per bin, of at most one codebook value per
+// cascade stage (Residue0.cs:144-205); libvorbis' residue books are integer lattices, so for its streams the answer is yes and
+// the vector can travel as int16 -- exactly: sums of integers below 2^24 are the same in float32 -- at half the bytes.  Decided
+// from the setup header alone, conservatively: every value book any residue names must hold integers only, and the worst case --
+// the largest magnitude of any of a residue's books, times its stages -- must stay below 2^15.
+// A residue whose value books do not tile its partitions -- a book of more dimensions than a partition has bins, or of a
+// dimension that does not divide the partition size: the reference decodes such setups (Residue0.cs:171-203 steps by the book's
+// dimensions whatever the partition size) -- lets one vector cover several of the following partitions and overhang the
+// residue's `end`: neither the "two vectors per bin and stage" bound of residue_integral nor "nothing beyond [begin, end)" of
+// vpzh_get_mapping holds for it.  libvorbis never writes one.
+bool residue_tiles_its_partitions(const SetupBlob &su, const Residue &r)
+{
+    for (size_t cl = 0; cl < r.books.size(); ++cl)
+        for (size_t st = 0; st < r.books[cl].size(); ++st) {
+            if (!(r.cascade[cl] & (1u << st))) continue;
+            const size_t b = r.books[cl][st];
+            if (b >= su.books.size()) return false;
+            const int dim = su.books[b].dimensions;
+            if (dim <= 0 || dim > r.partition_size || r.partition_size % dim != 0) return false;
+        }
+    return true;
+}
+
+bool residue_integral(const SetupBlob &su)
+{
+    for (const Residue &r : su.residues) {
+        if (!residue_tiles_its_partitions(su, r)) return false;
+        double worst = 0.0;
+        for (size_t cl = 0; cl < r.books.size(); ++cl)
+            for (size_t st = 0; st < r.books[cl].size(); ++st) {
+                if (!(r.cascade[cl] & (1u << st))) continue;  // (no book at this stage of the class)
+                const size_t b = r.books[cl][st];
+                if (b >= su.books.size()) return false;
+                const Codebook &cb = su.books[b];
+                if (cb.lookup_i16.empty()) return false;  // (a fraction, a -0.0 or a value beyond 16 bits in the table)
+                worst = std::max(worst, cb.entry_l1);
+            }
+        // per stage a bin takes one vector's value -- two where a partition's last vector overhangs into the next partition
+        // (Residue1.cs:12-34), the sum of an entry's dimensions for residue type 0 (Residue0.cs:208-231): entry_l1 covers all three
+        if (worst * 2.0 * std::max(1, r.max_stages) >= 32768.0) return false;
+    }
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The entropy decode on the GPU (vorbispizza_entropy.h): eligibility, the setup image, the plan.
+//
+// Why the device decode never changes a packet's record.  The plan writes the records with write_record from the heads
+// parse_head left at open -- the very function and heads of the CPU decode, so there is nothing to keep in step -- and the
+// host state machine of vpz_decoder_synth runs from them before the device has decoded anything.  What is left to show is
+// that the body of a packet's decode does not change its record.  It can end early in two ways: a miss or a short read,
+// handled inside (posts / residue as far as decoded, record untouched), and a throw, which takes failed_head's record.
+// The throws are
+//   (1) "Unused mode index."                            -- no throw of the body: a kind of head, known at the parse
+//   (2) "floor1 master book out of range" (Floor1::unpack) -- excluded below: every master book is checked
+//   (3) "residue class book without dimensions" (Residue::decode) -- excluded below: every class book has dimensions >= 1
+//   (4) "residue vector overruns the block" (Residue::write_vectors) -- excluded below: with value books that tile their
+//       partitions (residue_tiles_its_partitions) every vector ends inside [begin, end) <= blocksize/2 <= the channel
+//   (5) Floor0::unpack -- excluded below: every floor is type 1
+// and std::bad_alloc, which is no property of the setup.  (2)-(5) are the body's.  BitReader and Codebook::decode_scalar never throw; Floor1
+// subclass books, residue value books and class books were range-checked when the setup header was read.
+// ---------------------------------------------------------------------------------------------
+const char *gpu_unsupported_reason(const SetupBlob &su)
+{
+    for (uint8_t t : su.floor_types)
+        if (t != 1) return "a floor of type 0";
+    for (const Floor1 &f : su.floors)
+        for (size_t c = 0; c < f.class_subclasses.size(); ++c)
+            if (f.class_subclasses[c] > 0 && f.class_masterbooks[c] >= su.books.size()) return "a floor1 master book out of range";
+    for (const Residue &r : su.residues) {
+        if (!residue_tiles_its_partitions(su, r)) return "a residue whose value books do not tile its partitions";
+        if (r.class_book >= (int)su.books.size() || su.books[r.class_book].dimensions < 1) return "a residue class book without dimensions";
+    }
+    return nullptr;
+}
+
+struct ImageWriter {
+    std::vector<uint8_t> out;
+    uint32_t put(const void *p, size_t n)  // appended 4-byte aligned, zero padded
+    {
+        while (out.size() & 3) out.push_back(0);
+        const uint32_t at = (uint32_t)out.size();
+        out.insert(out.end(), (const uint8_t *)p, (const uint8_t *)p + n);
+        while (out.size() & 3) out.push_back(0);
+        return at;
+    }
+    uint32_t reserve(size_t n)
+    {
+        while (out.size() & 3) out.push_back(0);
+        const uint32_t at = (uint32_t)out.size();
+        out.resize(out.size() + n, 0);
+        return at;
+    }
+    template <class T> void set(uint32_t at, const T &v) { memcpy(out.data() + at, &v, sizeof v); }
+};
+
+std::vector<uint8_t> entropy_image(const SetupBlob &su, int channels, int size0, int size1)
+{
+    ImageWriter w;
+    vpz_entropy_image_header h;
+    memset(&h, 0, sizeof h);
+    const uint32_t at_h = w.reserve(sizeof h);
+    h.magic = VPZ_ENTROPY_IMAGE_MAGIC;
+    h.version = VPZ_ENTROPY_IMAGE_VERSION;
+    h.channels = channels;
+    h.block_size0 = size0;
+    h.block_size1 = size1;
+    h.mode_field_bits = su.mode_field_bits;
+    h.residue_integral = residue_integral(su) ? 1 : 0;
+    h.book_count = (int32_t)su.books.size();
+    h.floor_count = (int32_t)su.floors.size();
+    h.residue_count = (int32_t)su.residues.size();
+    h.mapping_count = (int32_t)su.mappings.size();
+    h.mode_count = (int32_t)su.modes.size();
+
+    std::vector<vpz_entropy_book> books(su.books.size());
+    memset(books.data(), 0, sizeof(vpz_entropy_book) * books.size());
+    h.books = w.reserve(sizeof(vpz_entropy_book) * books.size());
+    for (size_t i = 0; i < su.books.size(); ++i) {
+        const Codebook &cb = su.books[i];
+        vpz_entropy_book &b = books[i];
+        b.dimensions = cb.dimensions;
+        b.entries = cb.entries;
+        b.max_bits = cb.max_bits;
+        b.prefix_bits = cb.prefix.empty() ? 0 : cb.prefix_bits;
+        b.prefix_count = (int32_t)cb.prefix.size();
+        if (!cb.prefix.empty()) b.prefix = w.put(cb.prefix.data(), sizeof(uint32_t) * cb.prefix.size());
+        std::vector<vpz_entropy_code> codes(cb.overflow.size());
+        for (size_t k = 0; k < codes.size(); ++k)
+            codes[k] = {(uint32_t)cb.overflow[k].value, (uint32_t)cb.overflow[k].length, (uint32_t)cb.overflow[k].bits,
+                        (uint32_t)cb.overflow[k].mask};
+        b.overflow_count = (int32_t)codes.size();
+        if (!codes.empty()) b.overflow = w.put(codes.data(), sizeof(vpz_entropy_code) * codes.size());
+        b.lookup_count = (int32_t)cb.lookup.size();
+        if (!cb.lookup.empty()) b.lookup_f32 = w.put(cb.lookup.data(), sizeof(float) * cb.lookup.size());
+        b.lookup_i16_count = (int32_t)cb.lookup_i16.size();
+        if (!cb.lookup_i16.empty()) b.lookup_i16 = w.put(cb.lookup_i16.data(), sizeof(int16_t) * cb.lookup_i16.size());
+    }
+    for (size_t i = 0; i < books.size(); ++i) w.set(h.books + (uint32_t)(i * sizeof(vpz_entropy_book)), books[i]);
+
+    h.floors = w.reserve(sizeof(vpz_entropy_floor1) * su.floors.size());
+    for (size_t i = 0; i < su.floors.size(); ++i) {
+        const Floor1 &f = su.floors[i];
+        vpz_entropy_floor1 e;
+        memset(&e, 0, sizeof e);
+        if (su.floor_types[i] == 1) {
+            e.partition_count = (int32_t)f.partition_class.size();
+            e.y_bits = f.y_bits;
+            for (size_t k = 0; k < f.partition_class.size(); ++k) e.partition_class[k] = f.partition_class[k];
+            for (size_t c = 0; c < f.class_dimensions.size(); ++c) {
+                e.class_dimensions[c] = f.class_dimensions[c];
+                e.class_subclasses[c] = f.class_subclasses[c];
+                e.class_masterbooks[c] = f.class_masterbooks[c];
+                for (int k = 0; k < 8; ++k)
+                    e.subclass_books[c * 8 + k] = (int16_t)(k < (int)f.subclass_books[c].size() ? f.subclass_books[c][k] : -1);
+            }
+        }
+        w.set(h.floors + (uint32_t)(i * sizeof e), e);
+    }
+
+    std::vector<vpz_entropy_residue> res(su.residues.size());
+    memset(res.data(), 0, sizeof(vpz_entropy_residue) * res.size());
+    h.residues = w.reserve(sizeof(vpz_entropy_residue) * res.size());
+    for (size_t i = 0; i < su.residues.size(); ++i) {
+        const Residue &r = su.residues[i];
+        vpz_entropy_residue &e = res[i];
+        e.type = r.type;
+        e.begin = r.begin;
+        e.end = r.end;
+        e.partition_size = r.partition_size;
+        e.classifications = r.classifications;
+        e.class_book = r.class_book;
+        e.max_stages = r.max_stages;
+        e.class_dim = r.class_dim;
+        e.stage_book = w.put(r.stage_book.data(), sizeof(int16_t) * r.stage_book.size());
+        std::vector<uint8_t> dm(r.decode_map.begin(), r.decode_map.end());  // (classes < 64)
+        e.decode_map_count = (int32_t)dm.size();
+        if (!dm.empty()) e.decode_map = w.put(dm.data(), dm.size());
+        e.word_stage_mask_count = (int32_t)r.word_stage_mask.size();
+        if (!r.word_stage_mask.empty()) e.word_stage_mask = w.put(r.word_stage_mask.data(), sizeof(uint32_t) * r.word_stage_mask.size());
+    }
+    for (size_t i = 0; i < res.size(); ++i) w.set(h.residues + (uint32_t)(i * sizeof(vpz_entropy_residue)), res[i]);
+
+    h.mappings = w.reserve(sizeof(vpz_entropy_mapping) * su.mappings.size());
+    for (size_t i = 0; i < su.mappings.size(); ++i) {
+        const Mapping &m = su.mappings[i];
+        vpz_entropy_mapping e;
+        memset(&e, 0, sizeof e);
+        e.submaps = (int32_t)m.submap_residue.size();
+        e.coupling_steps = (int32_t)m.coupling_angle.size();
+        for (size_t k = 0; k < m.submap_residue.size(); ++k) {
+            e.submap_floor[k] = m.submap_floor[k];
+            e.submap_residue[k] = m.submap_residue[k];
+        }
+        for (size_t c = 0; c < m.mux.size(); ++c) e.mux[c] = m.mux[c];
+        for (size_t k = 0; k < m.coupling_angle.size(); ++k) {
+            e.coupling_magnitude[k] = m.coupling_magnitude[k];
+            e.coupling_angle[k] = m.coupling_angle[k];
+        }
+        w.set(h.mappings + (uint32_t)(i * sizeof e), e);
+    }
+    h.modes = w.reserve(sizeof(vpz_entropy_mode) * su.modes.size());
+    for (size_t i = 0; i < su.modes.size(); ++i) {
+        const vpz_entropy_mode e = {su.modes[i].block_flag ? 1 : 0, su.modes[i].mapping};
+        w.set(h.modes + (uint32_t)(i * sizeof e), e);
+    }
+    while (w.out.size() & 3) w.out.push_back(0);
+    h.total_bytes = (uint32_t)w.out.size();
+    w.set(at_h, h);
+    return w.out;
+}
+
+}  // namespace
 
 struct vpzh_stream {
     std::string error;
@@ -1140,6 +1432,7 @@ struct vpzh_stream {
         for (auto &m : mappings) {
             if (p.read_bits(16) != 0) throw InvalidData("Invalid mapping type!");
             m.read(p, channels, n_floors, n_res);
+            m.interleaved = m.submap_residue.size() == 1 && channels > 1 && residues[m.submap_residue[0]].type == 2;
         }
         int n_modes = (int)p.read_bits(6) + 1;
         modes.resize(n_modes);
@@ -1160,38 +1453,6 @@ struct vpzh_stream {
         }
     }
 
-    // residue floats one packet contributes to the batch
-    int64_t packet_floats(const OggPacket &pk) const
-    {
-        BitReader p;
-        p.init(pk.data, pk.size);
-        if (p.read_bits(1) != 0) return 0;
-        int mode_idx = (int)p.read_bits(su->mode_field_bits);
-        if (mode_idx >= (int)su->modes.size()) return 0;
-        return (int64_t)channels * ((su->modes[mode_idx].block_flag ? size1 : size0) / 2);
-    }
-
-    // IPacketGranuleCountProvider.GetPacketGranuleCount (StreamDecoder.cs:884-913): what a packet adds to the
-    // sample position, from its mode bits alone -- PacketInfo.SampleCount = RightStart - LeftStart (Mode.cs:30-66)
-    int packet_sample_count(const OggPacket &pk) const
-    {
-        BitReader p;
-        p.init(pk.data, pk.size);
-        if (p.read_bits(1) != 0) return 0;
-        const int mode_idx = (int)p.read_bits(su->mode_field_bits);
-        if (mode_idx >= (int)su->modes.size()) return 0;
-        const bool bf = su->modes[mode_idx].block_flag;
-        bool prev = true, next = true;
-        if (bf) {
-            prev = p.read_bit();
-            next = p.read_bit();
-        }
-        if (p.is_short) return 0;
-        const int size = bf ? size1 : size0;
-        const int left_start = prev ? 0 : (size - size0) / 4;
-        const int right_start = next ? size / 2 : (size * 3 - size0) / 4;
-        return right_start - left_start;
-    }
     // PacketProvider._pageEndGranules, kept per packet: position after packet i when counting starts at the
     // second audio packet (the first one only primes the overlap; PacketProvider.cs:283-287)
     std::vector<int64_t> cum_samples;
@@ -1202,38 +1463,29 @@ struct vpzh_stream {
     std::vector<int16_t> &scratch_of(int16_t *) { return scratch_decode16; }
     std::vector<uint8_t> one_flag;
 
-    // StreamDecoder.DecodeNextPacket :696-762 -> Mode.Decode -> Mapping.DecodePacket :98-163
+    // StreamDecoder.DecodeNextPacket :696-762 -> Mode.Decode -> Mapping.DecodePacket :98-163, from the floors on: the first
+    // bits were read at open (pk.head, parse_head).  Throws where the reference does; decode_range writes that record.
     // (T: the residue's element type -- float, or int16_t for a stream whose residue is integral, ABI v5)
     template <class T>
     void decode_packet(const OggPacket &pk, int32_t stream_id, int64_t residue_off, vpz_packet *out, T *residue,
                        int16_t *posts, uint8_t *post_counts, float *f0_amp = nullptr, float *f0_coeff = nullptr,
                        int f0_stride = 0)
     {
-        memset(out, 0, sizeof *out);
-        out->stream = stream_id;
-        out->granule = -1;
-        out->residue_offset = residue_off;
-        if (pk.eos) out->flags |= VPZ_PKT_EOS;
-        if (pk.resync) out->flags |= VPZ_PKT_RESYNC;
+        const PacketHead &head = pk.head;
+        write_record(head, pk, stream_id, residue_off, out);
         for (int c = 0; c < channels; ++c) post_counts[c] = 0;
         memset(posts, 0, sizeof(int16_t) * 64 * (size_t)channels);
+        if (head.kind == PacketKind::NotAudio) return;
+        if (head.kind == PacketKind::Failed) throw InvalidData(kUnusedMode);
+        const bool long_block = head.flags & VPZ_PKT_BLOCK_FLAG;
+        const int block_size = long_block ? size1 : size0;
+        const int half = block_size / 2;
+        const Mapping &map = su->mappings[head.mapping];
+        // the floors begin after the header bits, or where the packet ends (entropy.hip's decode_one_packet starts at the
+        // same bit, computed the same way from the record and the image)
         BitReader p;
         p.init(pk.data, pk.size);
-        if (p.read_bits(1) != 0) { out->flags |= VPZ_PKT_NOT_DECODED; return; }
-        int mode_idx = (int)p.read_bits(su->mode_field_bits);
-        if ((unsigned)mode_idx >= su->modes.size()) throw InvalidData("Unused mode index.");
-        const Mode &mode = su->modes[mode_idx];
-        if (p.is_short) { out->flags |= VPZ_PKT_NOT_DECODED; return; }  // Mode.cs:32-36
-        const int block_size = mode.block_flag ? size1 : size0;
-        const int half = block_size / 2;
-        if (mode.block_flag) {
-            out->flags |= VPZ_PKT_BLOCK_FLAG;
-            if (p.read_bit()) out->flags |= VPZ_PKT_PREV_FLAG;
-            if (p.read_bit()) out->flags |= VPZ_PKT_NEXT_FLAG;
-        }
-        out->mapping = (uint8_t)mode.mapping;
-        out->granule = pk.granule;
-        const Mapping &map = su->mappings[mode.mapping];
+        p.pos = std::min<int64_t>(head.header_bits, p.total_bits);
 
         // floors, Mapping.cs:109-118
         std::vector<uint8_t> no_execute(channels);
@@ -1271,25 +1523,20 @@ struct vpzh_stream {
         T *dst = residue;  // planar [ch][half] unless the interleaved shortcut below is taken
         memset(dst, 0, sizeof(T) * (size_t)channels * half);
         const int submaps = (int)map.submap_residue.size();
-        if (submaps == 1 && channels > 1 && su->residues[map.submap_residue[0]].type == 2) {
-            // The common stereo / multichannel case, one Residue2 submap over every channel: decode the
-            // interleaved vector straight into the output and let the GPU de-interleave (Residue2.cs:42-51) --
-            // same values as the general path below, without its scratch buffers.
-            bool all_mux0 = true, any = false;
-            for (int j = 0; j < channels; ++j) {
-                all_mux0 &= map.mux[j] == 0;
-                any |= !no_execute[j];
+        if (map.interleaved) {
+            // The common stereo / multichannel case, one Residue2 submap over every channel (Mapping::interleaved; with one
+            // submap Mapping::read leaves every mux at 0): decode the interleaved vector straight into the output and let the
+            // GPU de-interleave (Residue2.cs:42-51) -- same values as the general path below, without its scratch buffers.
+            bool any = false;
+            for (int j = 0; j < channels; ++j) any |= !no_execute[j];
+            if (any) {
+                one_flag.assign(1, 0);
+                su->residues[map.submap_residue[0]].decode(p, one_flag, block_size * channels, dst, half * channels, su->books, residue_scratch);
             }
-            if (all_mux0) {
-                if (any) {
-                    one_flag.assign(1, 0);
-                    su->residues[map.submap_residue[0]].decode(p, one_flag, block_size * channels, dst, half * channels, su->books, residue_scratch);
-                }
-                // (a packet whose channels are all silent is zeros in either layout: it keeps the stream's layout, so that
-                // a batch has ONE input layout and the back end's fast paths -- whose loads are unconditional -- take it)
-                out->flags |= VPZ_PKT_INTERLEAVED;
-                return;
-            }
+            // (a packet whose channels are all silent is zeros in either layout: it keeps the stream's layout -- its record
+            // says VPZ_PKT_INTERLEAVED like every record of the mapping -- so that a batch has ONE input layout and the back
+            // end's fast paths, whose loads are unconditional, take it)
+            return;
         }
         std::vector<T> &decode_buffer = scratch_of(residue);
         decode_buffer.assign((size_t)channels * block_size, (T)0);
@@ -1309,12 +1556,6 @@ struct vpzh_stream {
                     std::vector<T> tmp((size_t)half * count, (T)0);
                     std::vector<uint8_t> one(1, 0);
                     res.decode(p, one, block_size * count, tmp.data(), half * count, su->books, residue_scratch);
-                    if (submaps == 1 && count == channels && channels > 1) {
-                        // hand the Residue2 vector over as it is: the GPU de-interleaves (Residue2.cs:42-51)
-                        memcpy(dst, tmp.data(), sizeof(T) * (size_t)half * channels);
-                        out->flags |= VPZ_PKT_INTERLEAVED;
-                        return;
-                    }
                     if (count == 1) {
                         memcpy(&decode_buffer[0], tmp.data(), sizeof(T) * half);
                     } else {
@@ -1328,6 +1569,45 @@ struct vpzh_stream {
             for (int k = 0; k < count; ++k)
                 memcpy(dst + (size_t)members[k] * half, &decode_buffer[(size_t)k * block_size], sizeof(T) * half);
         }
+    }
+
+    void note_failure(int64_t k, const char *what)  // what vpzh_decode_failures and vpzh_last_error report
+    {
+        if (decode_failures++ == 0) {
+            first_failed_packet = k;
+            error = what;
+        }
+    }
+
+    // vpzh_decode_range_ex (T = float) and vpzh_decode_range_i16 (T = int16_t)
+    template <class T>
+    int decode_range(int64_t first, int64_t count, int32_t stream_id, int64_t residue_base, vpz_packet *packets, T *residue,
+                     int16_t *posts, uint8_t *post_counts, int64_t *residue_values_used, float *f0_amp, float *f0_coeff,
+                     int32_t f0_stride)
+    {
+        if (!packets || !residue || !posts || !post_counts || first < 0 || count < 0 || first + count > (int64_t)audio.size())
+            return VPZH_E_ARG;
+        if (f0_amp && (!f0_coeff || f0_stride < su->max_floor0_order)) return VPZH_E_ARG;
+        decode_failures = 0;
+        first_failed_packet = -1;
+        int64_t off = 0;
+        const size_t C = (size_t)channels;
+        for (int64_t k = 0; k < count; ++k) {
+            const OggPacket &pk = audio[(size_t)(first + k)];
+            try {
+                decode_packet(pk, stream_id, residue_base + off, &packets[k], residue + off, posts + (size_t)k * 64 * C,
+                              post_counts + (size_t)k * C, f0_amp ? f0_amp + (size_t)k * C : nullptr,
+                              f0_coeff ? f0_coeff + (size_t)k * C * (size_t)f0_stride : nullptr, f0_stride);
+            } catch (const std::exception &e) {
+                // the batch goes on (failed_head); whatever the packet had written to its posts and residue stays
+                note_failure(k, e.what());
+                write_record(failed_head(pk), pk, stream_id, residue_base + off, &packets[k]);
+                for (size_t c = 0; c < C; ++c) post_counts[(size_t)k * C + c] = 0;
+            }
+            off += pk.head.residue_values;
+        }
+        if (residue_values_used) *residue_values_used = off;
+        return VPZH_OK;
     }
 };
 
@@ -1353,10 +1633,12 @@ int vpzh_open_memory_stream(const uint8_t *data, uint64_t size, int32_t stream_i
         s->load_headers(packets);
         s->audio.assign(std::make_move_iterator(packets.begin() + 3), std::make_move_iterator(packets.end()));
         s->residue_floats = 0;
-        for (const OggPacket &pk : s->audio) s->residue_floats += s->packet_floats(pk);
         s->cum_samples.assign(s->audio.size(), 0);
-        for (size_t i = 1; i < s->audio.size(); ++i)
-            s->cum_samples[i] = s->cum_samples[i - 1] + s->packet_sample_count(s->audio[i]);
+        for (size_t i = 0; i < s->audio.size(); ++i) {
+            const PacketHead &head = s->audio[i].head = parse_head(s->audio[i], *s->su, s->channels, s->size0, s->size1);
+            s->residue_floats += head.residue_values;
+            if (i) s->cum_samples[i] = s->cum_samples[i - 1] + head.samples;
+        }
     } catch (const Unsupported &e) {
         s->error = e.what();
         rc = VPZH_E_UNSUPPORTED;
@@ -1426,8 +1708,6 @@ int vpzh_get_floor1(vpzh_stream *s, int index, vpz_floor1_config *out)
     return VPZH_OK;
 }
 
-static bool residue_tiles_its_partitions(const SetupBlob &su, const Residue &r);
-
 int vpzh_get_mapping(vpzh_stream *s, int index, vpz_mapping_config *out)
 {
     if (!s || !out || index < 0 || index >= (int)s->su->mappings.size()) return VPZH_E_ARG;
@@ -1474,118 +1754,26 @@ int vpzh_get_residue_type(vpzh_stream *s, int index)
     return s->su->residues[index].type;
 }
 
-// Is every residue value of this stream an integer that fits 16 bits?  A residue is a sum, per bin, of at most one codebook value per
-// cascade stage (Residue0.cs:144-205); libvorbis' residue books are integer lattices, so for its streams the answer is yes and
-// the vector can travel as int16 -- exactly: sums of integers below 2^24 are the same in float32 -- at half the bytes.  Decided
-// from the setup header alone, conservatively: every value book any residue names must hold integers only, and the worst case --
-// the largest magnitude of any of a residue's books, times its stages -- must stay below 2^15.
-// A residue whose value books do not tile its partitions -- a book of more dimensions than a partition has bins, or of a
-// dimension that does not divide the partition size: the reference decodes such setups (Residue0.cs:171-203 steps by the book's
-// dimensions whatever the partition size) -- lets one vector cover several of the following partitions and overhang the
-// residue's `end`: neither the "two vectors per bin and stage" bound of residue_integral nor "nothing beyond [begin, end)" of
-// vpzh_get_mapping holds for it.  libvorbis never writes one.
-static bool residue_tiles_its_partitions(const SetupBlob &su, const Residue &r)
-{
-    for (size_t cl = 0; cl < r.books.size(); ++cl)
-        for (size_t st = 0; st < r.books[cl].size(); ++st) {
-            if (!(r.cascade[cl] & (1u << st))) continue;
-            const size_t b = r.books[cl][st];
-            if (b >= su.books.size()) return false;
-            const int dim = su.books[b].dimensions;
-            if (dim <= 0 || dim > r.partition_size || r.partition_size % dim != 0) return false;
-        }
-    return true;
-}
-
-static bool residue_integral(const SetupBlob &su)
-{
-    for (const Residue &r : su.residues) {
-        if (!residue_tiles_its_partitions(su, r)) return false;
-        double worst = 0.0;
-        for (size_t cl = 0; cl < r.books.size(); ++cl)
-            for (size_t st = 0; st < r.books[cl].size(); ++st) {
-                if (!(r.cascade[cl] & (1u << st))) continue;  // (no book at this stage of the class)
-                const size_t b = r.books[cl][st];
-                if (b >= su.books.size()) return false;
-                const Codebook &cb = su.books[b];
-                if (cb.lookup_i16.empty()) return false;  // (a fraction, a -0.0 or a value beyond 16 bits in the table)
-                worst = std::max(worst, cb.entry_l1);
-            }
-        // per stage a bin takes one vector's value -- two where a partition's last vector overhangs into the next partition
-        // (Residue1.cs:12-34), the sum of an entry's dimensions for residue type 0 (Residue0.cs:208-231): entry_l1 covers all three
-        if (worst * 2.0 * std::max(1, r.max_stages) >= 32768.0) return false;
-    }
-    return true;
-}
-
 int vpzh_residue_is_integral(vpzh_stream *s) { return s && s->su && residue_integral(*s->su) ? 1 : 0; }
-
-// (residue16 != nullptr: the int16 form -- the same decode with the codebooks' integer tables, summed as integers straight into the
-// caller's vector; vpzh_residue_is_integral() == 1 is what makes those sums the float ones)
-static int decode_range_impl(vpzh_stream *s, int64_t first, int64_t count, int32_t stream_id, int64_t residue_base,
-                             vpz_packet *packets, float *residue, int16_t *residue16, int16_t *posts, uint8_t *post_counts,
-                             int64_t *residue_floats_used, float *f0_amp, float *f0_coeff, int32_t f0_stride)
-{
-    if (!s || !packets || (!residue && !residue16) || !posts || !post_counts || first < 0 || count < 0 ||
-        first + count > (int64_t)s->audio.size())
-        return VPZH_E_ARG;
-    if (f0_amp && (!f0_coeff || f0_stride < s->su->max_floor0_order)) return VPZH_E_ARG;
-    s->decode_failures = 0;
-    s->first_failed_packet = -1;
-    int64_t off = 0;
-    const size_t C = (size_t)s->channels;
-    for (int64_t k = 0; k < count; ++k) {
-        const OggPacket &pk = s->audio[(size_t)(first + k)];
-        const int64_t n = s->packet_floats(pk);
-        try {
-            float *amp_k = f0_amp ? f0_amp + (size_t)k * C : nullptr;
-            float *coeff_k = f0_coeff ? f0_coeff + (size_t)k * C * (size_t)f0_stride : nullptr;
-            if (residue16)
-                s->decode_packet(pk, stream_id, residue_base + off, &packets[k], residue16 + off, posts + (size_t)k * 64 * C,
-                                 post_counts + (size_t)k * C, amp_k, coeff_k, f0_stride);
-            else
-                s->decode_packet(pk, stream_id, residue_base + off, &packets[k], residue + off, posts + (size_t)k * 64 * C,
-                                 post_counts + (size_t)k * C, amp_k, coeff_k, f0_stride);
-        } catch (const std::exception &e) {
-            // An exception out of DecodeNextPacket (StreamDecoder.cs:696-762: "Unused mode index.", a residue vector
-            // overrun, ...) costs the reference exactly that packet: it is consumed, no decoder state has changed
-            // yet -- not even `_eosFound |= isEndOfStream` (:647) -- and the next Read goes on with the following
-            // packet.  Same here: the packet is handed over as "not decoded" without its EOS flag, the batch goes on,
-            // and vpzh_decode_failures reports where it happened.
-            if (s->decode_failures++ == 0) {
-                s->first_failed_packet = k;
-                s->error = e.what();
-            }
-            const uint8_t resync = packets[k].flags & VPZ_PKT_RESYNC;
-            memset(&packets[k], 0, sizeof packets[k]);
-            packets[k].stream = stream_id;
-            packets[k].granule = -1;
-            packets[k].residue_offset = residue_base + off;
-            packets[k].flags = (uint8_t)(VPZ_PKT_NOT_DECODED | resync);
-            for (size_t c = 0; c < C; ++c) post_counts[(size_t)k * C + c] = 0;
-        }
-        off += n;
-    }
-    if (residue_floats_used) *residue_floats_used = off;
-    return VPZH_OK;
-}
 
 int vpzh_decode_range_ex(vpzh_stream *s, int64_t first, int64_t count, int32_t stream_id, int64_t residue_base,
                          vpz_packet *packets, float *residue, int16_t *posts, uint8_t *post_counts,
                          int64_t *residue_floats_used, float *f0_amp, float *f0_coeff, int32_t f0_stride)
 {
-    if (!residue) return VPZH_E_ARG;
-    return decode_range_impl(s, first, count, stream_id, residue_base, packets, residue, nullptr, posts, post_counts, residue_floats_used,
-                             f0_amp, f0_coeff, f0_stride);
+    if (!s) return VPZH_E_ARG;
+    return s->decode_range(first, count, stream_id, residue_base, packets, residue, posts, post_counts, residue_floats_used, f0_amp,
+                           f0_coeff, f0_stride);
 }
 
+// (the int16 form: the same decode with the codebooks' integer tables, summed as integers straight into the caller's vector;
+// vpzh_residue_is_integral() == 1 is what makes those sums the float ones)
 int vpzh_decode_range_i16(vpzh_stream *s, int64_t first, int64_t count, int32_t stream_id, int64_t residue_base,
                           vpz_packet *packets, int16_t *residue, int16_t *posts, uint8_t *post_counts,
                           int64_t *residue_values_used, float *f0_amp, float *f0_coeff, int32_t f0_stride)
 {
-    if (!residue || !s || !vpzh_residue_is_integral(s)) return VPZH_E_ARG;
-    return decode_range_impl(s, first, count, stream_id, residue_base, packets, nullptr, residue, posts, post_counts, residue_values_used,
-                             f0_amp, f0_coeff, f0_stride);
+    if (!s || !vpzh_residue_is_integral(s)) return VPZH_E_ARG;
+    return s->decode_range(first, count, stream_id, residue_base, packets, residue, posts, post_counts, residue_values_used, f0_amp,
+                           f0_coeff, f0_stride);
 }
 
 // Threads a call uses when the caller does not say: the cores this process may run on (its affinity mask, not the machine's
@@ -1690,180 +1878,6 @@ int64_t vpzh_decode_failures(vpzh_stream *s, int64_t *first_failed_packet)
     return s->decode_failures;
 }
 
-// ---------------------------------------------------------------------------------------------
-// The entropy decode on the GPU (vorbispizza_entropy.h): eligibility, the setup image, the plan.
-//
-// Why the device decode never changes a packet's flags.  decode_packet can end a packet's decode early in two ways:
-// a miss or a short read, which it handles inside (posts / residue as far as decoded, flags untouched), and a throw,
-// which decode_range_impl turns into "not decoded, without EOS".  The throws it can reach are:
-//   (1) "Unused mode index."                            -- read from the mode bits: vpzh_plan_range sees it
-//   (2) "floor1 master book out of range" (Floor1::unpack) -- excluded below: every master book is checked
-//   (3) "residue class book without dimensions" (Residue::decode) -- excluded below: every class book has dimensions >= 1
-//   (4) "residue vector overruns the block" (Residue::write_vectors) -- excluded below: with value books that tile their
-//       partitions (residue_tiles_its_partitions) every vector ends inside [begin, end) <= blocksize/2 <= the channel
-//   (5) Floor0::unpack -- excluded below: every floor is type 1
-// and std::bad_alloc, which is no property of the setup.  BitReader and Codebook::decode_scalar never throw; Floor1
-// subclass books, residue value books and class books were range-checked when the setup header was read.  So for a
-// supported setup the plan alone -- type bit, mode number, window flags -- gives every packet's final record, and the host
-// state machine of vpz_decoder_synth can run from it before the device has decoded anything.
-// ---------------------------------------------------------------------------------------------
-static const char *gpu_unsupported_reason(const SetupBlob &su)
-{
-    for (uint8_t t : su.floor_types)
-        if (t != 1) return "a floor of type 0";
-    for (const Floor1 &f : su.floors)
-        for (size_t c = 0; c < f.class_subclasses.size(); ++c)
-            if (f.class_subclasses[c] > 0 && f.class_masterbooks[c] >= su.books.size()) return "a floor1 master book out of range";
-    for (const Residue &r : su.residues) {
-        if (!residue_tiles_its_partitions(su, r)) return "a residue whose value books do not tile its partitions";
-        if (r.class_book >= (int)su.books.size() || su.books[r.class_book].dimensions < 1) return "a residue class book without dimensions";
-    }
-    return nullptr;
-}
-
-}  // extern "C"
-
-namespace {
-struct ImageWriter {
-    std::vector<uint8_t> out;
-    uint32_t put(const void *p, size_t n)  // appended 4-byte aligned, zero padded
-    {
-        while (out.size() & 3) out.push_back(0);
-        const uint32_t at = (uint32_t)out.size();
-        out.insert(out.end(), (const uint8_t *)p, (const uint8_t *)p + n);
-        while (out.size() & 3) out.push_back(0);
-        return at;
-    }
-    uint32_t reserve(size_t n)
-    {
-        while (out.size() & 3) out.push_back(0);
-        const uint32_t at = (uint32_t)out.size();
-        out.resize(out.size() + n, 0);
-        return at;
-    }
-    template <class T> void set(uint32_t at, const T &v) { memcpy(out.data() + at, &v, sizeof v); }
-};
-}  // namespace
-
-extern "C" {
-
-static std::vector<uint8_t> entropy_image(const vpzh_stream &s)
-{
-    const SetupBlob &su = *s.su;
-    ImageWriter w;
-    vpz_entropy_image_header h;
-    memset(&h, 0, sizeof h);
-    const uint32_t at_h = w.reserve(sizeof h);
-    h.magic = VPZ_ENTROPY_IMAGE_MAGIC;
-    h.version = VPZ_ENTROPY_IMAGE_VERSION;
-    h.channels = s.channels;
-    h.block_size0 = s.size0;
-    h.block_size1 = s.size1;
-    h.mode_field_bits = su.mode_field_bits;
-    h.residue_integral = residue_integral(su) ? 1 : 0;
-    h.book_count = (int32_t)su.books.size();
-    h.floor_count = (int32_t)su.floors.size();
-    h.residue_count = (int32_t)su.residues.size();
-    h.mapping_count = (int32_t)su.mappings.size();
-    h.mode_count = (int32_t)su.modes.size();
-
-    std::vector<vpz_entropy_book> books(su.books.size());
-    memset(books.data(), 0, sizeof(vpz_entropy_book) * books.size());
-    h.books = w.reserve(sizeof(vpz_entropy_book) * books.size());
-    for (size_t i = 0; i < su.books.size(); ++i) {
-        const Codebook &cb = su.books[i];
-        vpz_entropy_book &b = books[i];
-        b.dimensions = cb.dimensions;
-        b.entries = cb.entries;
-        b.max_bits = cb.max_bits;
-        b.prefix_bits = cb.prefix.empty() ? 0 : cb.prefix_bits;
-        b.prefix_count = (int32_t)cb.prefix.size();
-        if (!cb.prefix.empty()) b.prefix = w.put(cb.prefix.data(), sizeof(uint32_t) * cb.prefix.size());
-        std::vector<vpz_entropy_code> codes(cb.overflow.size());
-        for (size_t k = 0; k < codes.size(); ++k)
-            codes[k] = {(uint32_t)cb.overflow[k].value, (uint32_t)cb.overflow[k].length, (uint32_t)cb.overflow[k].bits,
-                        (uint32_t)cb.overflow[k].mask};
-        b.overflow_count = (int32_t)codes.size();
-        if (!codes.empty()) b.overflow = w.put(codes.data(), sizeof(vpz_entropy_code) * codes.size());
-        b.lookup_count = (int32_t)cb.lookup.size();
-        if (!cb.lookup.empty()) b.lookup_f32 = w.put(cb.lookup.data(), sizeof(float) * cb.lookup.size());
-        b.lookup_i16_count = (int32_t)cb.lookup_i16.size();
-        if (!cb.lookup_i16.empty()) b.lookup_i16 = w.put(cb.lookup_i16.data(), sizeof(int16_t) * cb.lookup_i16.size());
-    }
-    for (size_t i = 0; i < books.size(); ++i) w.set(h.books + (uint32_t)(i * sizeof(vpz_entropy_book)), books[i]);
-
-    h.floors = w.reserve(sizeof(vpz_entropy_floor1) * su.floors.size());
-    for (size_t i = 0; i < su.floors.size(); ++i) {
-        const Floor1 &f = su.floors[i];
-        vpz_entropy_floor1 e;
-        memset(&e, 0, sizeof e);
-        if (su.floor_types[i] == 1) {
-            e.partition_count = (int32_t)f.partition_class.size();
-            e.y_bits = f.y_bits;
-            for (size_t k = 0; k < f.partition_class.size(); ++k) e.partition_class[k] = f.partition_class[k];
-            for (size_t c = 0; c < f.class_dimensions.size(); ++c) {
-                e.class_dimensions[c] = f.class_dimensions[c];
-                e.class_subclasses[c] = f.class_subclasses[c];
-                e.class_masterbooks[c] = f.class_masterbooks[c];
-                for (int k = 0; k < 8; ++k)
-                    e.subclass_books[c * 8 + k] = (int16_t)(k < (int)f.subclass_books[c].size() ? f.subclass_books[c][k] : -1);
-            }
-        }
-        w.set(h.floors + (uint32_t)(i * sizeof e), e);
-    }
-
-    std::vector<vpz_entropy_residue> res(su.residues.size());
-    memset(res.data(), 0, sizeof(vpz_entropy_residue) * res.size());
-    h.residues = w.reserve(sizeof(vpz_entropy_residue) * res.size());
-    for (size_t i = 0; i < su.residues.size(); ++i) {
-        const Residue &r = su.residues[i];
-        vpz_entropy_residue &e = res[i];
-        e.type = r.type;
-        e.begin = r.begin;
-        e.end = r.end;
-        e.partition_size = r.partition_size;
-        e.classifications = r.classifications;
-        e.class_book = r.class_book;
-        e.max_stages = r.max_stages;
-        e.class_dim = r.class_dim;
-        e.stage_book = w.put(r.stage_book.data(), sizeof(int16_t) * r.stage_book.size());
-        std::vector<uint8_t> dm(r.decode_map.begin(), r.decode_map.end());  // (classes < 64)
-        e.decode_map_count = (int32_t)dm.size();
-        if (!dm.empty()) e.decode_map = w.put(dm.data(), dm.size());
-        e.word_stage_mask_count = (int32_t)r.word_stage_mask.size();
-        if (!r.word_stage_mask.empty()) e.word_stage_mask = w.put(r.word_stage_mask.data(), sizeof(uint32_t) * r.word_stage_mask.size());
-    }
-    for (size_t i = 0; i < res.size(); ++i) w.set(h.residues + (uint32_t)(i * sizeof(vpz_entropy_residue)), res[i]);
-
-    h.mappings = w.reserve(sizeof(vpz_entropy_mapping) * su.mappings.size());
-    for (size_t i = 0; i < su.mappings.size(); ++i) {
-        const Mapping &m = su.mappings[i];
-        vpz_entropy_mapping e;
-        memset(&e, 0, sizeof e);
-        e.submaps = (int32_t)m.submap_residue.size();
-        e.coupling_steps = (int32_t)m.coupling_angle.size();
-        for (size_t k = 0; k < m.submap_residue.size(); ++k) {
-            e.submap_floor[k] = m.submap_floor[k];
-            e.submap_residue[k] = m.submap_residue[k];
-        }
-        for (size_t c = 0; c < m.mux.size(); ++c) e.mux[c] = m.mux[c];
-        for (size_t k = 0; k < m.coupling_angle.size(); ++k) {
-            e.coupling_magnitude[k] = m.coupling_magnitude[k];
-            e.coupling_angle[k] = m.coupling_angle[k];
-        }
-        w.set(h.mappings + (uint32_t)(i * sizeof e), e);
-    }
-    h.modes = w.reserve(sizeof(vpz_entropy_mode) * su.modes.size());
-    for (size_t i = 0; i < su.modes.size(); ++i) {
-        const vpz_entropy_mode e = {su.modes[i].block_flag ? 1 : 0, su.modes[i].mapping};
-        w.set(h.modes + (uint32_t)(i * sizeof e), e);
-    }
-    while (w.out.size() & 3) w.out.push_back(0);
-    h.total_bytes = (uint32_t)w.out.size();
-    w.set(at_h, h);
-    return w.out;
-}
-
 int vpzh_gpu_decode_supported(vpzh_stream *s)
 {
     if (!s || !s->su) return 0;
@@ -1879,7 +1893,7 @@ int vpzh_get_entropy_setup(vpzh_stream *s, void *buf, uint64_t capacity, uint64_
     if (!s || !s->su || !size) return VPZH_E_ARG;
     if (!vpzh_gpu_decode_supported(s)) return VPZH_E_UNSUPPORTED;
     try {
-        std::call_once(s->su->image_once, [s] { s->su->image = entropy_image(*s); });
+        std::call_once(s->su->image_once, [s] { s->su->image = entropy_image(*s->su, s->channels, s->size0, s->size1); });
     } catch (const std::exception &e) {
         s->error = e.what();
         return VPZH_E_INVALID_DATA;
@@ -1892,69 +1906,32 @@ int vpzh_get_entropy_setup(vpzh_stream *s, void *buf, uint64_t capacity, uint64_
     return VPZH_OK;
 }
 
-// The records decode_range_impl writes, from the header bits of each packet: decode_packet up to `out->granule = pk.granule`
-// (and its catch for "Unused mode index."), plus VPZ_PKT_INTERLEAVED, which only the mapping decides -- the shortcut of
-// decode_packet is taken for every packet of a mapping with one Residue2 submap over more than one channel, silent or not.
+// The records vpzh_decode_range_ex writes (write_record from the same heads), without decoding anything, and the packets'
+// bytes back to back for the device.
 int vpzh_plan_range(vpzh_stream *s, int64_t first, int64_t count, int32_t stream_id, int64_t residue_base,
                     vpz_packet *packets, vpz_entropy_span *spans, uint8_t *payload, int64_t payload_capacity,
                     int64_t *payload_used, int64_t *residue_used)
 {
     if (!s || !s->su || first < 0 || count < 0 || first + count > (int64_t)s->audio.size() || payload_capacity < 0) return VPZH_E_ARG;
-    const SetupBlob &su = *s->su;
     int64_t need = 8;
     for (int64_t k = 0; k < count; ++k) need += (int64_t)s->audio[(size_t)(first + k)].size;
     if (payload_used) *payload_used = need;
     if (payload && payload_capacity < need) return VPZH_E_ARG;
     int64_t off = 0, at = 0;
-    if (packets) {  // (what vpzh_decode_failures reports: the one failure a supported setup has, counted as decode_range_impl counts it)
+    if (packets) {  // (what vpzh_decode_failures reports: the one failure a supported setup has, counted as decode_range counts it)
         s->decode_failures = 0;
         s->first_failed_packet = -1;
     }
     for (int64_t k = 0; k < count; ++k) {
         const OggPacket &pk = s->audio[(size_t)(first + k)];
         if (packets) {
-            vpz_packet *out = &packets[k];
-            memset(out, 0, sizeof *out);
-            out->stream = stream_id;
-            out->granule = -1;
-            out->residue_offset = residue_base + off;
-            if (pk.resync) out->flags |= VPZ_PKT_RESYNC;
-            BitReader p;
-            p.init(pk.data, pk.size);
-            if (p.read_bits(1) != 0) {
-                out->flags |= VPZ_PKT_NOT_DECODED;
-                if (pk.eos) out->flags |= VPZ_PKT_EOS;
-            } else {
-                const int mode_idx = (int)p.read_bits(su.mode_field_bits);
-                if ((unsigned)mode_idx >= su.modes.size()) {
-                    out->flags |= VPZ_PKT_NOT_DECODED;  // the exception's record: no EOS
-                    if (s->decode_failures++ == 0) {
-                        s->first_failed_packet = k;
-                        s->error = "Unused mode index.";
-                    }
-                } else if (p.is_short) {
-                    out->flags |= VPZ_PKT_NOT_DECODED;
-                    if (pk.eos) out->flags |= VPZ_PKT_EOS;
-                } else {
-                    const Mode &mode = su.modes[mode_idx];
-                    if (pk.eos) out->flags |= VPZ_PKT_EOS;
-                    if (mode.block_flag) {
-                        out->flags |= VPZ_PKT_BLOCK_FLAG;
-                        if (p.read_bit()) out->flags |= VPZ_PKT_PREV_FLAG;
-                        if (p.read_bit()) out->flags |= VPZ_PKT_NEXT_FLAG;
-                    }
-                    out->mapping = (uint8_t)mode.mapping;
-                    out->granule = pk.granule;
-                    const Mapping &map = su.mappings[mode.mapping];
-                    if (map.submap_residue.size() == 1 && s->channels > 1 && su.residues[map.submap_residue[0]].type == 2)
-                        out->flags |= VPZ_PKT_INTERLEAVED;
-                }
-            }
+            write_record(pk.head, pk, stream_id, residue_base + off, &packets[k]);
+            if (pk.head.kind == PacketKind::Failed) s->note_failure(k, kUnusedMode);
         }
         if (spans) spans[k] = {at, (int64_t)pk.size};
         if (payload && pk.size) memcpy(payload + at, pk.data, pk.size);
         at += (int64_t)pk.size;
-        off += s->packet_floats(pk);
+        off += pk.head.residue_values;
     }
     if (payload) memset(payload + at, 0, 8);
     if (residue_used) *residue_used = off;

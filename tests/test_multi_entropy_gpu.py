@@ -184,6 +184,18 @@ def test_a_sub_batch_the_device_refuses_takes_the_host_path(monkeypatch):
     assert on_device_streams(on[3]) == 0 and payload_bytes(on[3]) == 0
 
 
+@pytest.mark.parametrize("s16", [False, True])
+def test_caller_areas_packed_with_no_slack(s16):
+    """capacities that are the streams' lengths and offsets packed: the one layout in which a wrong offset or length of a
+    device-decoded member's download overwrites a neighbour's samples instead of a guard gap"""
+    raws = fixtures() * 2
+    off = run(raws, False, s16=s16, streams_per_call=3, capacity_slack=0)
+    on = run(raws, True, s16=s16, streams_per_call=3, capacity_slack=0)
+    assert (off[2]["status"] == 0).all()
+    assert_same(off, on)
+    assert on_device_streams(on[3]) == 8 and on_device_streams(off[3]) == 0
+
+
 def test_an_area_one_sample_too_small_costs_only_its_stream():
     from vorbispizza_amd import multi
     from vorbispizza_amd.front import OggVorbisFile

@@ -16,8 +16,10 @@
 // with other contents: the workers PLAN its streams (vpzh_plan_range: packet records, spans, the packets' bytes) into the slot,
 // and its issuing thread uploads the bytes, entropy-decodes them on the lane's stream (vpz_entropy_decode) into arrays that
 // never leave the device, synthesises from those and downloads every member's PCM.
+//
+// In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
+// Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstddef>
@@ -98,29 +100,90 @@ struct Setup {
     }
 };
 
-struct Lane {  // one context (HIP stream) of a device group and the decoders that live on it
-    vpz_context *ctx = nullptr;
-    std::vector<std::pair<std::shared_ptr<Setup>, vpz_decoder *>> decs;
-    // gpu_entropy: the entropy setups next to the decoders (a setup belongs to a context and serves one call at a time), and
-    // what a device-decoded sub-batch keeps on the device: packet bytes in, residue / posts / counts between the two calls, PCM out
-    std::vector<std::pair<std::shared_ptr<Setup>, vpz_entropy_setup *>> esetups;
-    uint8_t *d_payload = nullptr, *d_residue = nullptr, *d_posts = nullptr, *d_counts = nullptr, *d_pcm = nullptr;
-    size_t cap_payload = 0, cap_residue = 0, cap_posts = 0, cap_counts = 0, cap_pcm = 0;  // (bytes)
+// The one owner of an array of a slot (page-locked host memory) or of a lane (device memory).  It only grows: a request for
+// `need` elements of `elem` bytes gets room for a quarter more and 64, so that jobs of like size do not allocate again.  The
+// old array may go at once: a slot is prepared when no sub-batch holds it, a lane's stream is idle between its sub-batches.
+struct Buffer {
+    bool device = false;
+    void *p = nullptr;
+    size_t bytes = 0;
+    void release(vpz_context *ctx)
+    {
+        if (p && ctx) (void)(device ? vpz_device_free(ctx, p) : vpz_host_free(ctx, p));
+        p = nullptr;
+        bytes = 0;
+    }
+    bool grow(vpz_context *ctx, size_t need, size_t elem)
+    {
+        if (need * elem <= bytes) return true;
+        release(ctx);
+        const size_t want = (need + need / 4 + 64) * elem;
+        if ((device ? vpz_device_alloc(ctx, (uint64_t)want, &p) : vpz_host_alloc(ctx, (uint64_t)want, &p)) != VPZ_OK) p = nullptr;
+        bytes = p ? want : 0;
+        return p != nullptr;
+    }
 };
 
-struct Slot {  // page-locked batch arrays of one sub-batch in flight
-    vpz_packet *packets = nullptr;
-    float *residue = nullptr;            // (cap_residue floats; holds int16 values for a sub-batch whose residue travels as int16)
-    int16_t *posts = nullptr;
-    uint8_t *counts = nullptr;
-    float *f0_amp = nullptr, *f0_coeff = nullptr;
-    vpz_entropy_span *spans = nullptr;   // a device-decoded sub-batch holds packets, spans and payload only
-    uint8_t *payload = nullptr;
-    size_t cap_packets = 0, cap_residue = 0, cap_posts = 0, cap_counts = 0, cap_f0 = 0, cap_f0c = 0, cap_spans = 0, cap_payload = 0;
+// What a context keeps per setup header, looked up by Setup::same: a library of files from many encoders meets many setups, and
+// a context keeps the decoders (and entropy setups: as many) of the last few, not of every one it has seen -- the oldest goes
+template <class T>
+struct SetupCache {
+    static constexpr size_t kKept = 8;
+    void (*destroy)(T *);
+    std::vector<std::pair<std::shared_ptr<Setup>, T *>> kept;
+    T *find(const Setup &st) const
+    {
+        for (const auto &e : kept)
+            if (e.first->same(st)) return e.second;
+        return nullptr;
+    }
+    void keep(const std::shared_ptr<Setup> &st, T *made)
+    {
+        if (kept.size() >= kKept) {
+            destroy(kept.front().second);
+            kept.erase(kept.begin());
+        }
+        kept.emplace_back(st, made);
+    }
+    void clear()
+    {
+        for (const auto &e : kept) destroy(e.second);
+        kept.clear();
+    }
+};
+
+struct Lane {  // one context (HIP stream) of a device group and the decoders that live on it
+    vpz_context *ctx = nullptr;
+    SetupCache<vpz_decoder> decoders{vpz_decoder_destroy, {}};
+    // gpu_entropy: the entropy setups next to the decoders (a setup belongs to a context and serves one call at a time), and
+    // what a device-decoded sub-batch keeps on the device: packet bytes in, residue / posts / counts between the two calls, PCM out
+    SetupCache<vpz_entropy_setup> esetups{vpz_entropy_setup_destroy, {}};
+    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kBuffers };
+    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
+    uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
+    float *residue() const { return static_cast<float *>(buf[kResidue].p); }  // (float32 or int16 values; the ABI's parameter is float-typed)
+    int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
+    uint8_t *counts() const { return static_cast<uint8_t *>(buf[kCounts].p); }
+    char *pcm() const { return static_cast<char *>(buf[kPcm].p); }
+};
+
+struct Slot {  // page-locked batch arrays of one sub-batch in flight (a device-decoded one holds packets, spans and payload only)
+    enum { kPackets, kResidue, kPosts, kCounts, kF0Amp, kF0Coeff, kSpans, kPayload, kBuffers };
+    Buffer buf[kBuffers];
+    vpz_packet *packets() const { return static_cast<vpz_packet *>(buf[kPackets].p); }
+    float *residue_f32() const { return static_cast<float *>(buf[kResidue].p); }  // (one array: a sub-batch's residue travels as float32 ...
+    int16_t *residue_i16() const { return static_cast<int16_t *>(buf[kResidue].p); }  // ... or as int16, see use_i16)
+    int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
+    uint8_t *counts() const { return static_cast<uint8_t *>(buf[kCounts].p); }
+    float *f0_amp() const { return static_cast<float *>(buf[kF0Amp].p); }
+    float *f0_coeff() const { return static_cast<float *>(buf[kF0Coeff].p); }
+    vpz_entropy_span *spans() const { return static_cast<vpz_entropy_span *>(buf[kSpans].p); }
+    uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
     size_t bytes() const
     {
-        return cap_packets * sizeof(vpz_packet) + cap_residue * sizeof(float) + cap_posts * sizeof(int16_t) + cap_counts +
-               (cap_f0 + cap_f0c) * sizeof(float) + cap_spans * sizeof(vpz_entropy_span) + cap_payload;
+        size_t sum = 0;
+        for (const Buffer &b : buf) sum += b.bytes;
+        return sum;
     }
 };
 
@@ -130,35 +193,17 @@ struct Group {
     std::vector<Slot> slots;
 };
 
-template <class T>
-bool grow(vpz_context *ctx, T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return true;
-    if (p) vpz_host_free(ctx, p);
-    p = nullptr;
-    cap = 0;
-    void *q = nullptr;
-    const size_t want = need + need / 4 + 64;
-    if (vpz_host_alloc(ctx, (uint64_t)(want * sizeof(T)), &q) != VPZ_OK) return false;
-    p = static_cast<T *>(q);
-    cap = want;
-    return true;
-}
+constexpr int64_t kCallValues = (int64_t)64 << 20;  // residue values of one synth call (256 MiB as float32), see GroupRun::cut
 
-// the same for a lane's device buffers (bytes); the lane's stream is idle between its sub-batches, so the old one may go
-bool grow_device(vpz_context *ctx, uint8_t *&p, size_t &cap, size_t need)
-{
-    if (need <= cap) return true;
-    if (p) vpz_device_free(ctx, p);
-    p = nullptr;
-    cap = 0;
-    void *q = nullptr;
-    const size_t want = need + need / 4 + 64;
-    if (vpz_device_alloc(ctx, (uint64_t)want, &q) != VPZ_OK) return false;
-    p = static_cast<uint8_t *>(q);
-    cap = want;
-    return true;
-}
+// The VPZM_* test and diagnosis switches of the environment as one vpzm_decode_library call finds them (its GroupRuns carry a copy)
+struct Switches {
+    static int64_t number(const char *name) { return getenv(name) ? atoll(getenv(name)) : 0; }
+    int64_t max_call_values = number("VPZM_MAX_CALL_VALUES") > 0 ? number("VPZM_MAX_CALL_VALUES") : kCallValues;  // (tests: small calls)
+    bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
+    bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
+    bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
+    bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
+};
 
 }  // namespace
 
@@ -179,22 +224,24 @@ struct vpzm_dispatcher {
 
 namespace {
 
-constexpr int kNoDecoder = 1;  // (synth_sub: no decoder for the sub-batch's setup; not a VPZ_* status, those are <= 0)
-constexpr int64_t kCallValues = (int64_t)64 << 20;  // residue values of one synth call (256 MiB as float32), see plan_wave
+constexpr int kNoDecoder = 1;  // (SubCall: no decoder for the sub-batch's setup; not a VPZ_* status, those are <= 0)
 
 struct Job {  // one stream of the library inside its group
     int32_t k = 0;  // index in the caller's arrays
     vpzh_stream *h = nullptr;
     std::shared_ptr<Setup> own;  // its setup-header products, loaded when it is opened
-    int setup = -1;
     int64_t packets = 0, residue_floats = 0, total_samples = 0;
     int64_t payload_bytes = 0, plan_failures = 0;  // gpu_entropy: what its plan needs in the payload area; packets its plan gave up
     int32_t status = VPZM_OK;
     bool finished = false;  // its PCM has been written (or it has its own failure status): what an aborted run leaves alone
+    void close()
+    {
+        if (h) vpzh_close(h);
+        h = nullptr;
+    }
 };
 
 struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
-    int setup = 0;
     std::shared_ptr<Setup> st;           // (its own reference: `setups` grows under the group's mutex while sub-batches are worked on outside it)
     std::vector<int> members;            // indices into jobs
     std::vector<int64_t> pbase, rbase;   // where each member's packets / residue start in the slot's arrays
@@ -216,7 +263,7 @@ struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
 //             synthesised) -- a worker with no decode work opens the next container instead, so the first synth call is under
 //             way a few milliseconds into the job;
 //   synth     `contexts_per_device` issuing threads take the decoded sub-batches in order, one host-memory vpz_decoder_synth call
-//             each: the upload of one overlaps the download of the other's.
+//             each: the upload of one overlaps the download of the other's (SubCall below).
 struct GroupRun {
     vpzm_dispatcher *m;
     Group &G;
@@ -229,11 +276,12 @@ struct GroupRun {
     const int64_t *pcm_offset, *pcm_capacity;
     vpzm_stream_result *results;
     int threads;
+    const Switches sw;
+    int lane_host_threads = std::max(1, std::min(8, threads / std::max(1, (int)G.lanes.size())));  // vpz_decoder_set_host_threads of every lane's decoders: the device's threads / its contexts
     double t_wall = 0, t_decode = 0, t_synth = 0;
     int64_t device_streams = 0, device_payload = 0;  // streams entropy-decoded on the device, their packet bytes
     Clock::time_point t_begin = Clock::now();
     int64_t samples_total = 0;
-    const bool profile = getenv("VPZM_PROFILE") != nullptr;
 
     std::vector<Job> jobs;
     std::vector<std::shared_ptr<Setup>> setups;
@@ -245,16 +293,9 @@ struct GroupRun {
     std::condition_variable cv;
     size_t next_open = 0, next_task = 0, next_synth = 0;
 
-    GroupRun(vpzm_dispatcher *m_, Group &g, int si, int32_t lo_, int32_t hi_, const uint8_t *const *d, const uint64_t *sz, int32_t layout,
-             void *out, const int64_t *off, const int64_t *cap, vpzm_stream_result *res, int thr)
-        : m(m_), G(g), slot_index(si), lo(lo_), hi(hi_), data(d), size(sz), out_layout(layout), pcm_out(out), pcm_offset(off),
-          pcm_capacity(cap), results(res), threads(thr)
-    {
-        lane_host_threads = std::max(1, std::min(8, thr / std::max(1, (int)G.lanes.size())));
-    }
-
     int wave_size() const { return std::max(4 * m->opt.streams_per_call, 2 * m->device_streams_per_call); }
     bool all_planned() const { return waves_planned == (int)wave_left.size(); }
+    Slot &slot_of(size_t b) { return G.slots[b % G.slots.size()]; }
 
     // ---- open: the container walked (pages, CRC, lacing), the three headers parsed, the setup products read out
     void open_one(size_t i)
@@ -267,8 +308,7 @@ struct GroupRun {
         try {
             if (vpzh_open_memory(data[J.k], size[J.k], &J.h) != VPZH_OK) {
                 J.status = VPZM_E_OPEN;
-                if (J.h) vpzh_close(J.h);
-                J.h = nullptr;
+                J.close();
                 return;
             }
             vpzh_info info{};
@@ -296,7 +336,6 @@ struct GroupRun {
     // ---- plan (under `mu`): the streams of one wave grouped by setup header, every group cut into sub-batches
     void plan_wave(int w)
     {
-        const int S = m->opt.streams_per_call;
         const size_t a = (size_t)w * (size_t)wave_size(), b = std::min(jobs.size(), a + (size_t)wave_size());
         std::vector<std::vector<int>> by_setup(setups.size());
         for (size_t i = a; i < b; ++i) {
@@ -314,42 +353,11 @@ struct GroupRun {
                 by_setup.emplace_back();
             }
             J.own.reset();
-            J.setup = at;
             by_setup[(size_t)at].push_back((int)i);
         }
         std::vector<Sub> fresh;
-        // a synth call holds up to streams_per_call streams of one setup and up to kCallValues residue values (a library of whole
-        // songs would otherwise ask for page-locked slots of gigabytes each): a long stream rides with fewer others, or alone
-        int64_t budget = kCallValues;
-        if (const char *e = getenv("VPZM_MAX_CALL_VALUES"))  // (tests: small calls)
-            if (atoll(e) > 0) budget = atoll(e);
-        for (size_t q = 0; q < by_setup.size(); ++q) {
-            const std::vector<int> &v = by_setup[q];
-            Sub sb;
-            auto flush = [&] {
-                if (!sb.members.empty()) fresh.push_back(std::move(sb));
-                sb = Sub();
-            };
-            // (device-resident inputs are not bound by a page-locked slot's size, and one lane per packet wants many packets)
-            const int limit = setups[q]->on_device() ? m->device_streams_per_call : S;
-            for (size_t j = 0; j < v.size(); ++j) {
-                const Job &J = jobs[(size_t)v[j]];
-                if (!sb.members.empty() && ((int)sb.members.size() >= limit || sb.res_floats + J.residue_floats > budget)) flush();
-                if (sb.members.empty()) {
-                    sb.setup = (int)q;
-                    sb.st = setups[q];
-                    sb.on_device = setups[q]->on_device();
-                }
-                sb.members.push_back(v[j]);
-                sb.pbase.push_back(sb.n_packets);
-                sb.rbase.push_back(sb.res_floats);
-                sb.ybase.push_back(sb.payload_bytes);
-                sb.n_packets += J.packets;
-                sb.res_floats += J.residue_floats;
-                sb.payload_bytes += (J.payload_bytes + 7) & ~(int64_t)7;
-            }
-            flush();
-        }
+        for (size_t q = 0; q < by_setup.size(); ++q)
+            for (Sub &sb : cut(setups[q], by_setup[q])) fresh.push_back(std::move(sb));
         std::sort(fresh.begin(), fresh.end(), [](const Sub &x, const Sub &y) { return x.members[0] < y.members[0]; });
         for (Sub &sb : fresh) {
             const int bi = (int)subs.size();
@@ -359,78 +367,112 @@ struct GroupRun {
         ++waves_planned;
     }
 
+    // The cutting rule: the streams `v` of one setup, in order, become sub-batches.  A synth call holds up to streams_per_call streams
+    // and up to kCallValues residue values (a library of whole songs would otherwise ask for page-locked slots of gigabytes each):
+    // a long stream rides with fewer others, or alone
+    std::vector<Sub> cut(const std::shared_ptr<Setup> &st, const std::vector<int> &v) const
+    {
+        // (device-resident inputs are not bound by a page-locked slot's size, and one lane per packet wants many packets)
+        const int limit = st->on_device() ? m->device_streams_per_call : m->opt.streams_per_call;
+        std::vector<Sub> out;
+        for (int i : v) {
+            const Job &J = jobs[(size_t)i];
+            if (out.empty() || (int)out.back().members.size() >= limit || out.back().res_floats + J.residue_floats > sw.max_call_values) {
+                out.emplace_back();
+                out.back().st = st;
+                out.back().on_device = st->on_device();
+            }
+            Sub &sb = out.back();
+            sb.members.push_back(i);
+            sb.pbase.push_back(sb.n_packets);
+            sb.rbase.push_back(sb.res_floats);
+            sb.ybase.push_back(sb.payload_bytes);
+            sb.n_packets += J.packets;
+            sb.res_floats += J.residue_floats;
+            sb.payload_bytes += (J.payload_bytes + 7) & ~(int64_t)7;
+        }
+        return out;
+    }
+
     // the residue of a sub-batch travels as int16 when its setup header guarantees integers (and the caller has not asked for floats)
     bool use_i16(const Setup &st) const { return st.integral && !m->opt.float_residue; }
 
     // (the functions below run with `mu` RELEASED: they get their sub-batch by reference -- a deque's elements stay where they are, but
     // indexing `subs` / `setups` while plan_wave appends to them is a race)
-    bool prep_slot(size_t b, Sub &sb)  // (one thread prepares a given sub-batch)
+    bool prepare(size_t b, Sub &sb)  // (one thread prepares a given sub-batch, before any of its members is decoded)
     {
-        Slot &sl = G.slots[b % G.slots.size()];
+        Slot &sl = slot_of(b);
         const Setup &st = *sb.st;
-        const size_t C = (size_t)st.info.channels, rec = (size_t)sb.n_packets * C;
-        vpz_context *ctx = G.lanes[0].ctx;
-        if (sb.on_device)  // (no residue, posts or counts on the host: those arrays are born on the device)
-            return grow(ctx, sl.packets, sl.cap_packets, (size_t)sb.n_packets) && grow(ctx, sl.spans, sl.cap_spans, (size_t)sb.n_packets) &&
-                   grow(ctx, sl.payload, sl.cap_payload, (size_t)sb.payload_bytes);
-        // (the slot's residue array is float-typed: int16 values take half the elements)
+        const size_t n = (size_t)sb.n_packets, rec = n * (size_t)st.info.channels;
+        auto room = [&](int which, size_t need, size_t elem) { return sl.buf[which].grow(G.lanes[0].ctx, need, elem); };
+        // (the residue array is counted in floats: int16 values take half the elements)
         const size_t res_elems = use_i16(st) ? ((size_t)sb.res_floats + 1) / 2 : (size_t)sb.res_floats;
-        bool ok = grow(ctx, sl.packets, sl.cap_packets, (size_t)sb.n_packets) && grow(ctx, sl.residue, sl.cap_residue, res_elems) &&
-                  grow(ctx, sl.posts, sl.cap_posts, rec * 64) && grow(ctx, sl.counts, sl.cap_counts, rec);
-        if (ok && st.f0_stride > 0)
-            ok = grow(ctx, sl.f0_amp, sl.cap_f0, rec) && grow(ctx, sl.f0_coeff, sl.cap_f0c, rec * (size_t)st.f0_stride);
+        bool ok = room(Slot::kPackets, n, sizeof(vpz_packet));
+        if (sb.on_device)  // (no residue, posts or counts on the host: those arrays are born on the device)
+            ok = ok && room(Slot::kSpans, n, sizeof(vpz_entropy_span)) && room(Slot::kPayload, (size_t)sb.payload_bytes, 1);
+        else
+            ok = ok && room(Slot::kResidue, res_elems, sizeof(float)) && room(Slot::kPosts, rec * 64, sizeof(int16_t)) && room(Slot::kCounts, rec, 1);
+        if (ok && !sb.on_device && st.f0_stride > 0)
+            ok = room(Slot::kF0Amp, rec, sizeof(float)) && room(Slot::kF0Coeff, rec * (size_t)st.f0_stride, sizeof(float));
+        if (!ok) fail_members(sb, VPZM_E_SYNTH, "vpzm_decode_library: page-locked batch arrays could not be allocated");
         return ok;
     }
-
-    // the plan of one member of a device-decoded sub-batch: packet records, spans and the packets' bytes into the slot.  The container
-    // stays open until the sub-batch has been issued (should the device refuse it, its members are decoded here after all)
-    void plan_member(size_t b, Sub &sb, int j)
+    // a sub-batch that cannot go on: its members fail with `status` -- those that have a failure status of their own keep it
+    void fail_members(const Sub &sb, int32_t status, const char *text)
     {
-        Job &J = jobs[(size_t)sb.members[(size_t)j]];
-        if (J.status != VPZM_OK) return;
-        Slot &sl = G.slots[b % G.slots.size()];
-        const int64_t pb = sb.pbase[(size_t)j], yb = sb.ybase[(size_t)j];
-        int rc = VPZH_E_ARG;
-        try {
-            rc = vpzh_plan_range(J.h, 0, J.packets, j, sb.rbase[(size_t)j], sl.packets + pb, sl.spans + pb, sl.payload + yb, J.payload_bytes,
-                                 nullptr, nullptr);
-            if (rc == VPZH_OK) {
-                for (int64_t p = 0; p < J.packets; ++p) sl.spans[pb + p].offset += yb;  // (spans count from the sub-batch's payload)
-                J.plan_failures = vpzh_decode_failures(J.h, nullptr);
-            }
-        } catch (...) {
-            rc = VPZH_E_INVALID_DATA;
-        }
-        if (rc != VPZH_OK) J.status = VPZM_E_OPEN;
+        for (int mi : sb.members)
+            if (jobs[(size_t)mi].status == VPZM_OK) jobs[(size_t)mi].status = status;
+        m->fail(text);
     }
 
+    // the plan of one member of a device-decoded sub-batch: packet records, spans and the packets' bytes into the slot
+    int plan_member(Job &J, Slot &sl, const Sub &sb, int j)
+    {
+        const int64_t pb = sb.pbase[(size_t)j], yb = sb.ybase[(size_t)j];
+        const int rc = vpzh_plan_range(J.h, 0, J.packets, j, sb.rbase[(size_t)j], sl.packets() + pb, sl.spans() + pb, sl.payload() + yb,
+                                       J.payload_bytes, nullptr, nullptr);
+        if (rc != VPZH_OK) return rc;
+        for (int64_t p = 0; p < J.packets; ++p) sl.spans()[pb + p].offset += yb;  // (spans count from the sub-batch's payload)
+        J.plan_failures = vpzh_decode_failures(J.h, nullptr);
+        return rc;
+    }
+    // ... and the entropy decode of one member of a host-decoded one: records, residue, posts, counts and Floor0 data into the slot
+    int decode_member_on_host(Job &J, Slot &sl, const Sub &sb, int j)
+    {
+        const Setup &st = *sb.st;
+        const size_t C = (size_t)st.info.channels;
+        const int64_t pb = sb.pbase[(size_t)j], rb = sb.rbase[(size_t)j];
+        float *amp_at = st.f0_stride ? sl.f0_amp() + (size_t)pb * C : nullptr;
+        float *coeff_at = st.f0_stride ? sl.f0_coeff() + (size_t)pb * C * (size_t)st.f0_stride : nullptr;
+        const int rc = use_i16(st) ? vpzh_decode_range_i16(J.h, 0, J.packets, j, rb, sl.packets() + pb, sl.residue_i16() + rb, sl.posts() + (size_t)pb * 64 * C,
+                                                           sl.counts() + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride)
+                                   : vpzh_decode_range_ex(J.h, 0, J.packets, j, rb, sl.packets() + pb, sl.residue_f32() + rb, sl.posts() + (size_t)pb * 64 * C,
+                                                          sl.counts() + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride);
+        if (rc == VPZH_OK) results[J.k].skipped_packets += vpzh_decode_failures(J.h, nullptr);
+        return rc;
+    }
+    // one member's decode task.  A container that does not decode costs its stream (VPZM_E_OPEN).  A planned member's container stays
+    // open until the sub-batch has been issued (should the device refuse it, its members are decoded here after all); a decoded one's goes
     void decode_member(size_t b, Sub &sb, int j)
     {
-        if (sb.on_device) return plan_member(b, sb, j);
         Job &J = jobs[(size_t)sb.members[(size_t)j]];
         if (J.status == VPZM_OK) {
-            Slot &sl = G.slots[b % G.slots.size()];
-            const Setup &st = *sb.st;
-            const size_t C = (size_t)st.info.channels;
-            const int64_t pb = sb.pbase[(size_t)j], rb = sb.rbase[(size_t)j];
             int rc = VPZH_E_ARG;
             try {
-                float *amp_at = st.f0_stride ? sl.f0_amp + (size_t)pb * C : nullptr;
-                float *coeff_at = st.f0_stride ? sl.f0_coeff + (size_t)pb * C * (size_t)st.f0_stride : nullptr;
-                if (use_i16(st))
-                    rc = vpzh_decode_range_i16(J.h, 0, J.packets, j, rb, sl.packets + pb, reinterpret_cast<int16_t *>(sl.residue) + rb,
-                                               sl.posts + (size_t)pb * 64 * C, sl.counts + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride);
-                else
-                    rc = vpzh_decode_range_ex(J.h, 0, J.packets, j, rb, sl.packets + pb, sl.residue + rb, sl.posts + (size_t)pb * 64 * C,
-                                              sl.counts + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride);
-                if (rc == VPZH_OK) results[J.k].skipped_packets += vpzh_decode_failures(J.h, nullptr);
+                rc = sb.on_device ? plan_member(J, slot_of(b), sb, j) : decode_member_on_host(J, slot_of(b), sb, j);
             } catch (...) {
                 rc = VPZH_E_INVALID_DATA;
             }
             if (rc != VPZH_OK) J.status = VPZM_E_OPEN;
         }
-        if (J.h) vpzh_close(J.h);  // (the container's packets are not needed any more)
-        J.h = nullptr;
+        if (!sb.on_device) J.close();
+    }
+
+    // a whole sub-batch on the calling thread (a sub-batch the device did not take, the run without threads): the arrays, then every member
+    void decode_sub(size_t b, Sub &sb)
+    {
+        if (!prepare(b, sb)) return;
+        for (size_t j = 0; j < sb.members.size(); ++j) decode_member(b, sb, (int)j);
     }
 
     // ---- the workers: decode what can be decoded, else open the next container, else wait
@@ -451,7 +493,7 @@ struct GroupRun {
                     decode_member(b, sb, j);
                     lk.lock();
                     if (++sb.decoded == (int)sb.members.size()) {
-                        if (profile && sb.on_device)
+                        if (sw.profile && sb.on_device)
                             fprintf(stderr, "[vpzm] group %d: sub-batch %zu planned at %.2f ms\n", slot_index, b, seconds_since(t_begin) * 1e3);
                         cv.notify_all();
                     }
@@ -460,12 +502,8 @@ struct GroupRun {
                 if (!sb.prepping && (b < B || subs[b - B].synth_done)) {  // its slot is free: get the arrays ready
                     sb.prepping = true;
                     lk.unlock();
-                    const bool ok = prep_slot(b, sb);
+                    (void)prepare(b, sb);  // (without arrays its members have their status: decode_member passes them by)
                     lk.lock();
-                    if (!ok) {
-                        for (int mi : sb.members) jobs[(size_t)mi].status = VPZM_E_SYNTH;
-                        m->fail("vpzm_decode_library: page-locked batch arrays could not be allocated");
-                    }
                     sb.prepped = true;
                     cv.notify_all();
                     continue;
@@ -522,12 +560,10 @@ struct GroupRun {
             abort_run("vpzm_decode_library: a pipeline thread failed");
         }
     }
-    int lane_host_threads = 1;   // vpz_decoder_set_host_threads of every lane's decoders: the device's threads / its contexts
 
     vpz_decoder *decoder_for(Lane &L, const std::shared_ptr<Setup> &st)
     {
-        for (auto &p : L.decs)
-            if (p.first->same(*st)) return p.second;
+        if (vpz_decoder *dec = L.decoders.find(*st)) return dec;
         vpz_stream_config cfg{};
         cfg.channels = st->info.channels;
         cfg.block_size0 = st->info.block_size0;
@@ -547,13 +583,7 @@ struct GroupRun {
         // The integer half of a synth call may fork over a pool of the decoder's context (batches of whole songs do): every lane its
         // share of the device's host threads, not a pool for the whole machine each -- the decode workers need the CPUs
         (void)vpz_decoder_set_host_threads(dec, lane_host_threads);
-        // (a library of files from many encoders: a context keeps the decoders of the last few setups, not of every one it has seen)
-        constexpr size_t kDecodersPerContext = 8;
-        if (L.decs.size() >= kDecodersPerContext) {
-            vpz_decoder_destroy(L.decs.front().second);
-            L.decs.erase(L.decs.begin());
-        }
-        L.decs.emplace_back(st, dec);
+        L.decoders.keep(st, dec);
         return dec;
     }
 
@@ -579,285 +609,7 @@ struct GroupRun {
             synth_sub(L, b, *sp);
         }
     }
-
-    vpz_entropy_setup *entropy_setup_for(Lane &L, const std::shared_ptr<Setup> &st)
-    {
-        for (auto &p : L.esetups)
-            if (p.first->same(*st)) return p.second;
-        vpz_entropy_setup *es = nullptr;
-        if (vpz_entropy_setup_create(L.ctx, st->image.data(), (uint64_t)st->image.size(), &es) != VPZ_OK) return nullptr;  // (refused: the host path)
-        constexpr size_t kSetupsPerContext = 8;  // (as many as decoders)
-        if (L.esetups.size() >= kSetupsPerContext) {
-            vpz_entropy_setup_destroy(L.esetups.front().second);
-            L.esetups.erase(L.esetups.begin());
-        }
-        L.esetups.emplace_back(st, es);
-        return es;
-    }
-
-    // ---- a device-decoded sub-batch's first two steps on the lane's stream: the packet bytes go up, vpz_entropy_decode writes residue,
-    // posts and counts into the lane's device arrays (asynchronous: the synth call that follows on the same stream consumes them without
-    // a synchronise).  false: the device path is not to be had for this sub-batch (no memory, an image the library refuses, a failed
-    // call) -- nothing of the job has changed, the sub-batch takes the host path
-    bool entropy_on_device(Lane &L, const Sub &sb, Slot &sl, int64_t n_pk, size_t pcm_bytes, double &t_upload, double &t_entropy)
-    {
-        if (const char *e = getenv("VPZM_FAIL_GPU_ENTROPY"))  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
-            if (atoi(e) != 0) return false;
-        const Setup &st = *sb.st;
-        const size_t rec = (size_t)n_pk * (size_t)st.info.channels, esize = use_i16(st) ? sizeof(int16_t) : sizeof(float);
-        if (!grow_device(L.ctx, L.d_payload, L.cap_payload, (size_t)sb.payload_bytes) ||
-            !grow_device(L.ctx, L.d_residue, L.cap_residue, (size_t)sb.res_floats * esize) ||
-            !grow_device(L.ctx, L.d_posts, L.cap_posts, rec * 64 * sizeof(int16_t)) || !grow_device(L.ctx, L.d_counts, L.cap_counts, rec) ||
-            !grow_device(L.ctx, L.d_pcm, L.cap_pcm, pcm_bytes))
-            return false;
-        vpz_entropy_setup *es = entropy_setup_for(L, sb.st);
-        if (!es) return false;
-        const auto t0 = Clock::now();
-        if (vpz_memcpy_h2d(L.ctx, L.d_payload, sl.payload, (uint64_t)sb.payload_bytes) != VPZ_OK) return false;
-        t_upload = seconds_since(t0);
-        const auto t1 = Clock::now();
-        if (vpz_entropy_decode(es, n_pk, sl.packets, sl.spans, L.d_payload, sb.payload_bytes, use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32,
-                               L.d_residue, sb.res_floats, reinterpret_cast<int16_t *>(L.d_posts), L.d_counts, (int64_t)rec,
-                               VPZ_MEM_DEVICE) != VPZ_OK)
-            return false;
-        if (profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the stage's own time; otherwise nothing waits here)
-        t_entropy = seconds_since(t1);
-        return true;
-    }
-
-    // the host path after all, for a sub-batch the device did not take: its slot gets the host arrays and the issuing thread decodes
-    // the members (their containers are still open)
-    void decode_on_host_after_all(size_t b, Sub &sb)
-    {
-        sb.on_device = false;
-        if (!prep_slot(b, sb)) {
-            for (int mi : sb.members)
-                if (jobs[(size_t)mi].status == VPZM_OK) jobs[(size_t)mi].status = VPZM_E_SYNTH;
-            m->fail("vpzm_decode_library: page-locked batch arrays could not be allocated");
-            return;
-        }
-        for (size_t j = 0; j < sb.members.size(); ++j) decode_member(b, sb, (int)j);
-    }
-
-    void synth_sub(Lane &L, size_t b, Sub &sb)
-    {
-        const int S = m->call_streams();
-        std::vector<int64_t> offs((size_t)S), written((size_t)S), caps((size_t)S, 0);
-        std::vector<int32_t> status;
-        Slot &sl = G.slots[b % G.slots.size()];
-        const Setup &st = *sb.st;
-        const int C = st.info.channels;
-        const size_t elem = out_layout == VPZ_OUT_INTERLEAVED_S16 ? sizeof(int16_t) : sizeof(float);
-        bool any = false, all_ok = true;
-        int64_t cap = 0, base = INT64_MAX, n_pk = 0;
-        // a member whose container did not decode leaves its packets out (rare): the arrays are re-packed stream by stream,
-        // stream ids kept, so that vpz_decoder_synth sees only decoded packets; their residue stays where it is
-        auto repack = [&] {
-            any = false;
-            all_ok = true;
-            for (int mi : sb.members) {
-                if (jobs[(size_t)mi].status == VPZM_OK) any = true;
-                else all_ok = false;
-            }
-            n_pk = sb.n_packets;
-            if (!any || all_ok) return;
-            int64_t w = 0;
-            for (size_t j = 0; j < sb.members.size(); ++j) {
-                const Job &J = jobs[(size_t)sb.members[j]];
-                if (J.status != VPZM_OK) continue;
-                const int64_t pb = sb.pbase[j];
-                if (w != pb) {
-                    memmove(sl.packets + w, sl.packets + pb, sizeof(vpz_packet) * (size_t)J.packets);
-                    if (sb.on_device) {  // (the device arrays are written for the packets as they lie now)
-                        memmove(sl.spans + w, sl.spans + pb, sizeof(vpz_entropy_span) * (size_t)J.packets);
-                    } else {
-                        memmove(sl.posts + (size_t)w * 64 * C, sl.posts + (size_t)pb * 64 * C, sizeof(int16_t) * 64 * (size_t)C * (size_t)J.packets);
-                        memmove(sl.counts + (size_t)w * C, sl.counts + (size_t)pb * C, (size_t)C * (size_t)J.packets);
-                        if (st.f0_stride) {
-                            memmove(sl.f0_amp + (size_t)w * C, sl.f0_amp + (size_t)pb * C, sizeof(float) * (size_t)C * (size_t)J.packets);
-                            memmove(sl.f0_coeff + (size_t)w * C * st.f0_stride, sl.f0_coeff + (size_t)pb * C * st.f0_stride,
-                                    sizeof(float) * (size_t)C * st.f0_stride * (size_t)J.packets);
-                        }
-                    }
-                }
-                w += J.packets;
-            }
-            n_pk = w;
-        };
-        repack();
-        const auto t0 = Clock::now();
-        double t_upload = 0, t_entropy = 0, t_download = 0;
-        int64_t on_device_streams = 0, on_device_payload = 0;
-        if (sb.on_device && any && n_pk > 0) {
-            // the members' areas of the lane's device PCM array, back to back: a stream produces at most block_size1 / 2 samples per
-            // packet, so an area need not be larger than that whatever the caller's is (one block of slack each)
-            size_t pcm_elems = 0;
-            for (size_t j = 0; j < sb.members.size(); ++j) {
-                const Job &J = jobs[(size_t)sb.members[j]];
-                if (J.status == VPZM_OK) pcm_elems += (size_t)(std::min(pcm_capacity[J.k], J.packets * (st.info.block_size1 / 2)) + st.info.block_size1) * (size_t)C;
-            }
-            if (entropy_on_device(L, sb, sl, n_pk, pcm_elems * elem, t_upload, t_entropy)) {
-                for (size_t j = 0; j < sb.members.size(); ++j) {
-                    const Job &J = jobs[(size_t)sb.members[j]];
-                    if (J.status != VPZM_OK) continue;
-                    ++on_device_streams;
-                    on_device_payload += J.payload_bytes;
-                    results[J.k].skipped_packets += J.plan_failures;  // (an unused mode number: the plan's "not decoded", counted as the host decode counts it)
-                }
-            } else {
-                decode_on_host_after_all(b, sb);
-                repack();
-            }
-        }
-        const bool dev = sb.on_device;
-        // (a host-memory call sees the sub-batch's part of the caller's PCM array: it mirrors its output extent on the
-        // device, so the offsets handed over start at the sub-batch's lowest one)
-        for (size_t j = 0; j < sb.members.size(); ++j) base = std::min(base, pcm_offset[jobs[(size_t)sb.members[j]].k]);
-        int64_t dev_at = 0;
-        for (size_t j = 0; j < sb.members.size(); ++j) {
-            const Job &J = jobs[(size_t)sb.members[j]];
-            offs[j] = dev ? dev_at : pcm_offset[J.k] - base;
-            if (J.status == VPZM_OK) {
-                // (every stream has its own area: files of one encoder setting share a setup header and differ in length)
-                caps[j] = pcm_capacity[J.k];
-                if (dev) {
-                    caps[j] = std::min(caps[j], J.packets * (st.info.block_size1 / 2));
-                    dev_at += (caps[j] + st.info.block_size1) * C;
-                }
-                cap = std::max(cap, caps[j]);
-            }
-        }
-        void *out_at = dev ? static_cast<void *>(L.d_pcm) : static_cast<char *>(pcm_out) + elem * (size_t)base;
-        const float *residue = dev ? reinterpret_cast<const float *>(L.d_residue) : sl.residue;
-        const int16_t *posts = dev ? reinterpret_cast<const int16_t *>(L.d_posts) : sl.posts;
-        const uint8_t *counts = dev ? L.d_counts : sl.counts;
-        int rc = VPZ_OK;
-        std::vector<int> member_rc(sb.members.size(), VPZ_OK);  // (a sub-batch is one synth call; after a failed one, a call per member)
-        static const bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;  // (diagnosis: the decode side of the pipeline alone)
-        if (any && n_pk > 0 && !no_synth) {
-            vpz_decoder *dec = decoder_for(L, sb.st);
-            std::vector<int64_t> wr((size_t)S);
-            // one synth call over the slot's packets [p0, p0 + n): the records, the Floor0 data and the statuses move with p0, the
-            // residue offsets are the slot's.  A device-decoded sub-batch's call reads the lane's device arrays, laid out the same way
-            auto call = [&](int64_t p0, int64_t n) -> int {
-                int r = dec ? VPZ_OK : VPZ_E_NOMEM;
-                // the decoder is re-used for new streams: back to what a StreamDecoder is after ProcessHeaderPackets
-                // (`_currentPosition = 0; _hasPosition = true`, StreamDecoder.cs:165-168) -- a bare reset would leave the position to be
-                // picked up from the first granule the way a seek does (:459-463), which moves the EOS trim (:658-666)
-                if (r == VPZ_OK) r = vpz_decoder_reset(dec, -1);
-                for (int sidx = 0; sidx < S && r == VPZ_OK; ++sidx) r = vpz_decoder_set_position(dec, sidx, 0);
-                if (r == VPZ_OK && st.f0_stride > 0)
-                    r = vpz_decoder_set_floor0_data(dec, sl.f0_amp + (size_t)p0 * C, sl.f0_coeff + (size_t)p0 * C * st.f0_stride, st.f0_stride);
-                if (r == VPZ_OK) r = vpz_decoder_set_residue_format(dec, use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32);
-                if (r == VPZ_OK) r = vpz_decoder_set_stream_capacities(dec, caps.data(), S);
-                if (r == VPZ_OK)
-                    r = vpz_decoder_synth(dec, n, sl.packets + p0, residue, sb.res_floats, posts + (size_t)p0 * 64 * C, counts + (size_t)p0 * C,
-                                          n * C, dev ? VPZ_MEM_DEVICE : VPZ_MEM_HOST, out_at, offs.data(), cap, out_layout, 0, wr.data());
-                if (r != VPZ_OK) m->fail(std::string("vpz_decoder_synth: ") + (dec ? vpz_context_last_error(L.ctx) : "no decoder"));
-                int64_t not_ok = 0;
-                if (r == VPZ_OK && vpz_decoder_last_packet_status(dec, nullptr, 0, &not_ok) == VPZ_OK && not_ok > 0) {
-                    status.assign((size_t)n, 0);
-                    vpz_decoder_last_packet_status(dec, status.data(), n, nullptr);
-                    for (int64_t p = 0; p < n; ++p)
-                        if (status[(size_t)p] != VPZ_OK) {
-                            const int32_t sid = sl.packets[p0 + p].stream;
-                            if (sid >= 0 && (size_t)sid < sb.members.size()) results[jobs[(size_t)sb.members[(size_t)sid]].k].skipped_packets += 1;
-                        }
-                }
-                return r;
-            };
-            // (VPZM_FAIL_BATCH_CALLS=1, tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-            const char *fb = getenv("VPZM_FAIL_BATCH_CALLS");
-            const bool fail_batch = fb && atoi(fb) != 0;
-            rc = !dec ? kNoDecoder : fail_batch ? VPZ_E_CAPACITY : call(0, n_pk);
-            if (rc == VPZ_OK) {
-                written = wr;
-            } else if (rc == kNoDecoder) {
-                // vpz_decoder_create refused the setup (its text is in vpzm_last_error): no member of it can be synthesised
-                std::fill(member_rc.begin(), member_rc.end(), kNoDecoder);
-            } else {
-                // "a stream that fails costs only itself": whatever one member's packets did to the call, the others get a call
-                // of their own (the packets lie member by member; a device-decoded sub-batch's arrays are not decoded again)
-                for (int64_t p = 0; p < n_pk;) {
-                    const int32_t sid = sl.packets[p].stream;
-                    int64_t q = p;
-                    while (q < n_pk && sl.packets[q].stream == sid) ++q;
-                    if (sid >= 0 && (size_t)sid < sb.members.size()) {
-                        member_rc[(size_t)sid] = q - p == n_pk && !fail_batch ? rc : call(p, q - p);
-                        if (member_rc[(size_t)sid] == VPZ_OK) written[(size_t)sid] = wr[(size_t)sid];
-                    }
-                    p = q;
-                }
-            }
-        }
-        double t_call = seconds_since(t0) - t_upload - t_entropy;
-        if (dev && any && n_pk > 0) {
-            if (profile) {
-                (void)vpz_context_synchronize(L.ctx);
-                t_call = seconds_since(t0) - t_upload - t_entropy;
-            }
-            // every member's PCM to the caller's area, what samples_written says and no more; neighbours whose areas touch on both sides
-            // (capacities that are the streams' lengths, offsets packed) go as one copy
-            const auto t1 = Clock::now();
-            for (size_t j = 0; j < sb.members.size();) {
-                const Job &J = jobs[(size_t)sb.members[j]];
-                if (J.status != VPZM_OK || member_rc[j] != VPZ_OK || written[j] <= 0) {
-                    ++j;
-                    continue;
-                }
-                const int64_t src = offs[j], dst = pcm_offset[J.k];
-                int64_t n = written[j] * C;
-                size_t q = j + 1;
-                for (; q < sb.members.size(); ++q) {
-                    const Job &N = jobs[(size_t)sb.members[q]];
-                    if (N.status != VPZM_OK || member_rc[q] != VPZ_OK || written[q] <= 0 || offs[q] != src + n || pcm_offset[N.k] != dst + n) break;
-                    n += written[q] * C;
-                }
-                if (vpz_memcpy_d2h(L.ctx, static_cast<char *>(pcm_out) + elem * (size_t)dst, L.d_pcm + elem * (size_t)src, (uint64_t)n * elem) != VPZ_OK) {
-                    m->fail(std::string("vpz_memcpy_d2h: ") + vpz_context_last_error(L.ctx));
-                    for (size_t r = j; r < q; ++r) member_rc[r] = VPZ_E_HIP;
-                }
-                j = q;
-            }
-            // (the slot's packet records and the lane's arrays are free again once the stream has drained)
-            if (vpz_context_synchronize(L.ctx) != VPZ_OK)
-                for (size_t j = 0; j < sb.members.size(); ++j)
-                    if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
-            t_download = seconds_since(t1);
-        }
-        for (int mi : sb.members) {  // (a device-decoded sub-batch's containers were kept open for the host path after all)
-            Job &J = jobs[(size_t)mi];
-            if (J.h) vpzh_close(J.h);
-            J.h = nullptr;
-        }
-        const double dt = seconds_since(t0);
-        if (profile) {
-            if (dev)
-                fprintf(stderr, "[vpzm] group %d: sub-batch %zu on the device done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, download %.2f ms; %lld packets, %lld payload bytes)\n",
-                        slot_index, b, seconds_since(t_begin) * 1e3, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, t_download * 1e3,
-                        (long long)n_pk, (long long)sb.payload_bytes);
-            else
-                fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets)\n", slot_index, b,
-                        seconds_since(t_begin) * 1e3, dt * 1e3, (long long)n_pk);
-        }
-        std::lock_guard<std::mutex> lk(mu);
-        t_synth += dt;
-        device_streams += on_device_streams;
-        device_payload += on_device_payload;
-        for (size_t j = 0; j < sb.members.size(); ++j) {
-            Job &J = jobs[(size_t)sb.members[j]];
-            if (J.status != VPZM_OK) continue;
-            J.finished = true;
-            if (member_rc[j] != VPZ_OK) {
-                J.status = member_rc[j] == kNoDecoder ? VPZM_E_SETUP : member_rc[j] == VPZ_E_CAPACITY ? VPZM_E_CAPACITY : VPZM_E_SYNTH;
-                continue;
-            }
-            results[J.k].samples = written[j];
-            samples_total += written[j] * C;
-        }
-        sb.synth_done = true;
-        cv.notify_all();
-    }
+    void synth_sub(Lane &L, size_t b, Sub &sb);  // (SubCall's stages, below)
 
     // run() for a thread of its own: whatever it throws before its pipeline stands (the job table's allocation) becomes the
     // statuses of the group's streams, never an exception out of the thread
@@ -895,16 +647,12 @@ struct GroupRun {
         } catch (...) {
         }
         if (workers == 0) {
-            // no thread could be started: everything in order on this one
+            // no thread could be started: the stages in order on this one, a sub-batch at a time
             guarded([this] {
                 for (size_t i = 0; i < jobs.size(); ++i) open_one(i);
                 for (int w = 0; w < (int)wave_left.size(); ++w) plan_wave(w);
                 for (size_t b = 0; b < subs.size(); ++b) {
-                    if (!prep_slot(b, subs[b])) {
-                        for (int mi : subs[b].members) jobs[(size_t)mi].status = VPZM_E_SYNTH;
-                        m->fail("vpzm_decode_library: page-locked batch arrays could not be allocated");
-                    }
-                    for (size_t j = 0; j < subs[b].members.size(); ++j) decode_member(b, subs[b], (int)j);
+                    decode_sub(b, subs[b]);
                     subs[b].decoded = (int)subs[b].members.size();
                     synth_sub(G.lanes[0], b, subs[b]);
                 }
@@ -919,8 +667,7 @@ struct GroupRun {
         }
         for (std::thread &t : pool) t.join();
         for (Job &J : jobs) {
-            if (J.h) vpzh_close(J.h);
-            J.h = nullptr;
+            J.close();
             if (aborted && J.status == VPZM_OK && !J.finished) {  // (an aborted run: no PCM, no count -- the stream has no result)
                 J.status = VPZM_E_SYNTH;
                 results[J.k].samples = 0;
@@ -930,6 +677,268 @@ struct GroupRun {
         t_wall = seconds_since(t_begin);
     }
 };
+
+// One sub-batch's synth step on its issuing thread, stage by stage (GroupRun::synth_sub runs them; the model is SynthCall in
+// vpz_decoder.hip).  Two routes: a host-decoded sub-batch's arrays lie in its slot and its PCM goes straight into the caller's array;
+// a device-decoded one's packet bytes go up, vpz_entropy_decode writes the lane's device arrays, the synth call reads those and writes
+// the lane's device PCM array, and every member's PCM comes down.  `sb.on_device` says which; decode_on_device may clear it.
+struct SubCall {
+    GroupRun &R;
+    Lane &L;
+    const size_t b;
+    Sub &sb;
+    Slot &sl = R.slot_of(b);
+    const Setup &st = *sb.st;
+    const int C = st.info.channels, S = R.m->call_streams();  // channels; the streams a decoder is created for
+    const size_t elem = R.out_layout == VPZ_OUT_INTERLEAVED_S16 ? sizeof(int16_t) : sizeof(float);  // bytes of a PCM sample
+    bool any = false;  // ---- repack: a member is left ...
+    int64_t n_pk = 0;  // ... and the packets of those that are
+    // ---- place_outputs: every member's area (offset and capacity in samples), where the areas start, the largest capacity, all the areas
+    std::vector<int64_t> offs = std::vector<int64_t>((size_t)S), caps = offs;
+    void *out_at = nullptr;
+    int64_t cap = 0, pcm_elems = 0;
+    // ---- the calls: samples of every member (of the calls that stand, of the last call), every member's own status
+    vpz_decoder *dec = nullptr;
+    std::vector<int64_t> written = offs, wr = offs;
+    std::vector<int> member_rc = std::vector<int>(sb.members.size(), VPZ_OK);  // (a sub-batch is one synth call; after a failed one, a call per member)
+    Clock::time_point t0 = Clock::now();
+    double t_upload = 0, t_entropy = 0, t_call = 0, t_download = 0;
+
+    Job &job(size_t j) const { return R.jobs[(size_t)sb.members[j]]; }
+    bool live(size_t j) const { return job(j).status == VPZM_OK; }
+    bool has_call() const { return any && n_pk > 0; }
+
+    // a member whose container did not decode leaves its packets out (rare): the arrays are re-packed stream by stream,
+    // stream ids kept, so that vpz_decoder_synth sees only decoded packets; their residue stays where it is
+    void repack()
+    {
+        bool all_ok = true;
+        any = false;
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            if (live(j)) any = true;
+            else all_ok = false;
+        }
+        n_pk = sb.n_packets;
+        if (!any || all_ok) return;
+        int64_t w = 0;
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            const Job &J = job(j);
+            if (J.status != VPZM_OK) continue;
+            const int64_t pb = sb.pbase[j];
+            if (w != pb) {
+                memmove(sl.packets() + w, sl.packets() + pb, sizeof(vpz_packet) * (size_t)J.packets);
+                if (sb.on_device) {  // (the device arrays are written for the packets as they lie now)
+                    memmove(sl.spans() + w, sl.spans() + pb, sizeof(vpz_entropy_span) * (size_t)J.packets);
+                } else {
+                    memmove(sl.posts() + (size_t)w * 64 * C, sl.posts() + (size_t)pb * 64 * C, sizeof(int16_t) * 64 * (size_t)C * (size_t)J.packets);
+                    memmove(sl.counts() + (size_t)w * C, sl.counts() + (size_t)pb * C, (size_t)C * (size_t)J.packets);
+                    if (st.f0_stride) {
+                        memmove(sl.f0_amp() + (size_t)w * C, sl.f0_amp() + (size_t)pb * C, sizeof(float) * (size_t)C * (size_t)J.packets);
+                        memmove(sl.f0_coeff() + (size_t)w * C * st.f0_stride, sl.f0_coeff() + (size_t)pb * C * st.f0_stride,
+                                sizeof(float) * (size_t)C * st.f0_stride * (size_t)J.packets);
+                    }
+                }
+            }
+            w += J.packets;
+        }
+        n_pk = w;
+    }
+
+    // Every stream has its own area (files of one encoder setting share a setup header and differ in length).  Host route: a host-memory
+    // call sees the sub-batch's part of the caller's PCM array (it mirrors its output extent on the device), so the offsets handed over
+    // start at the sub-batch's lowest one, and a capacity is the caller's.  Device route: the areas lie back to back in the lane's device PCM
+    // array; a stream produces at most block_size1 / 2 samples per packet, so an area need not be larger than that, plus one block of slack.
+    void place_outputs()
+    {
+        const bool dev = sb.on_device;
+        int64_t base = INT64_MAX, dev_at = 0;
+        for (size_t j = 0; j < sb.members.size(); ++j) base = std::min(base, R.pcm_offset[job(j).k]);
+        cap = 0;
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            const Job &J = job(j);
+            offs[j] = dev ? dev_at : R.pcm_offset[J.k] - base;
+            caps[j] = 0;
+            if (J.status != VPZM_OK) continue;
+            caps[j] = dev ? std::min(R.pcm_capacity[J.k], J.packets * (st.info.block_size1 / 2)) : R.pcm_capacity[J.k];
+            if (dev) dev_at += (caps[j] + st.info.block_size1) * C;
+            cap = std::max(cap, caps[j]);
+        }
+        pcm_elems = dev_at;
+        out_at = dev ? nullptr : static_cast<char *>(R.pcm_out) + elem * (size_t)base;  // (the lane's array: once decode_on_device has grown it)
+    }
+
+    // A device-decoded sub-batch's first two steps on the lane's stream: the packet bytes go up, vpz_entropy_decode writes residue,
+    // posts and counts into the lane's device arrays (asynchronous: the synth call that follows on the same stream consumes them without
+    // a synchronise).  false: the device path is not to be had for this sub-batch (no memory, an image the library refuses, a failed
+    // call) -- nothing of the job has changed, the sub-batch takes the host path
+    bool decode_on_device()
+    {
+        if (R.sw.fail_gpu_entropy) return false;
+        const bool i16 = R.use_i16(st);
+        const size_t rec = (size_t)n_pk * (size_t)C;
+        auto room = [&](int which, size_t bytes) { return L.buf[which].grow(L.ctx, bytes, 1); };
+        if (!room(Lane::kPayload, (size_t)sb.payload_bytes) || !room(Lane::kResidue, (size_t)sb.res_floats * (i16 ? sizeof(int16_t) : sizeof(float))) ||
+            !room(Lane::kPosts, rec * 64 * sizeof(int16_t)) || !room(Lane::kCounts, rec) || !room(Lane::kPcm, (size_t)pcm_elems * elem))
+            return false;
+        vpz_entropy_setup *es = L.esetups.find(st);
+        if (!es) {
+            if (vpz_entropy_setup_create(L.ctx, st.image.data(), (uint64_t)st.image.size(), &es) != VPZ_OK) return false;  // (refused: the host path)
+            L.esetups.keep(sb.st, es);
+        }
+        const auto t_up = Clock::now();
+        if (vpz_memcpy_h2d(L.ctx, L.payload(), sl.payload(), (uint64_t)sb.payload_bytes) != VPZ_OK) return false;
+        t_upload = seconds_since(t_up);
+        const auto t_en = Clock::now();
+        if (vpz_entropy_decode(es, n_pk, sl.packets(), sl.spans(), L.payload(), sb.payload_bytes, i16 ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32,
+                               L.residue(), sb.res_floats, L.posts(), L.counts(), (int64_t)rec, VPZ_MEM_DEVICE) != VPZ_OK)
+            return false;
+        if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the stage's own time; otherwise nothing waits here)
+        t_entropy = seconds_since(t_en);
+        out_at = L.pcm();
+        return true;
+    }
+
+    // the host path after all: the slot gets the host arrays, this thread decodes the members (their containers are still open), and
+    // the sub-batch is packed and placed again as the host-decoded one it now is
+    void decode_on_host()
+    {
+        sb.on_device = false;
+        R.decode_sub(b, sb);
+        repack();
+        place_outputs();
+    }
+
+    // one synth call over the slot's packets [p0, p0 + n): the records, the Floor0 data and the statuses move with p0, the
+    // residue offsets are the slot's.  A device-decoded sub-batch's call reads the lane's device arrays, laid out the same way
+    int call(int64_t p0, int64_t n)
+    {
+        const bool dev = sb.on_device;
+        const int16_t *posts = dev ? L.posts() : sl.posts();
+        const uint8_t *counts = dev ? L.counts() : sl.counts();
+        // the decoder is re-used for new streams: back to what a StreamDecoder is after ProcessHeaderPackets
+        // (`_currentPosition = 0; _hasPosition = true`, StreamDecoder.cs:165-168) -- a bare reset would leave the position to be
+        // picked up from the first granule the way a seek does (:459-463), which moves the EOS trim (:658-666)
+        int r = vpz_decoder_reset(dec, -1);
+        for (int sidx = 0; sidx < S && r == VPZ_OK; ++sidx) r = vpz_decoder_set_position(dec, sidx, 0);
+        if (r == VPZ_OK && st.f0_stride > 0)
+            r = vpz_decoder_set_floor0_data(dec, sl.f0_amp() + (size_t)p0 * C, sl.f0_coeff() + (size_t)p0 * C * st.f0_stride, st.f0_stride);
+        if (r == VPZ_OK) r = vpz_decoder_set_residue_format(dec, R.use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32);
+        if (r == VPZ_OK) r = vpz_decoder_set_stream_capacities(dec, caps.data(), S);
+        if (r == VPZ_OK)
+            r = vpz_decoder_synth(dec, n, sl.packets() + p0, dev ? L.residue() : sl.residue_f32(), sb.res_floats, posts + (size_t)p0 * 64 * C,
+                                  counts + (size_t)p0 * C, n * C, dev ? VPZ_MEM_DEVICE : VPZ_MEM_HOST, out_at, offs.data(), cap, R.out_layout, 0,
+                                  wr.data());
+        if (r != VPZ_OK) R.m->fail(std::string("vpz_decoder_synth: ") + vpz_context_last_error(L.ctx));
+        int64_t not_ok = 0;
+        if (r == VPZ_OK && vpz_decoder_last_packet_status(dec, nullptr, 0, &not_ok) == VPZ_OK && not_ok > 0) {
+            std::vector<int32_t> status((size_t)n, 0);
+            vpz_decoder_last_packet_status(dec, status.data(), n, nullptr);
+            for (int64_t p = 0; p < n; ++p)
+                if (status[(size_t)p] != VPZ_OK) {
+                    const int32_t sid = sl.packets()[p0 + p].stream;
+                    if (sid >= 0 && (size_t)sid < sb.members.size()) R.results[job((size_t)sid).k].skipped_packets += 1;
+                }
+        }
+        return r;
+    }
+
+    // the sub-batch as ONE synth call
+    void call_batch()
+    {
+        if (!has_call() || R.sw.no_synth) return;
+        dec = R.decoder_for(L, sb.st);
+        const int rc = !dec ? kNoDecoder : R.sw.fail_batch_calls ? VPZ_E_CAPACITY : call(0, n_pk);
+        if (rc == VPZ_OK) written = wr;
+        else if (rc == kNoDecoder) std::fill(member_rc.begin(), member_rc.end(), kNoDecoder);  // (vpz_decoder_create's text is in vpzm_last_error)
+        else call_members(rc);
+    }
+
+    // "a stream that fails costs only itself": whatever one member's packets did to the call, the others get a call
+    // of their own (the packets lie member by member; a device-decoded sub-batch's arrays are not decoded again)
+    void call_members(int batch_rc)
+    {
+        const vpz_packet *packets = sl.packets();
+        for (int64_t p = 0; p < n_pk;) {
+            const int32_t sid = packets[p].stream;
+            int64_t q = p;
+            while (q < n_pk && packets[q].stream == sid) ++q;
+            if (sid >= 0 && (size_t)sid < sb.members.size()) {
+                member_rc[(size_t)sid] = q - p == n_pk && !R.sw.fail_batch_calls ? batch_rc : call(p, q - p);
+                if (member_rc[(size_t)sid] == VPZ_OK) written[(size_t)sid] = wr[(size_t)sid];
+            }
+            p = q;
+        }
+    }
+
+    // device route: every member's PCM to the caller's area, what samples_written says and no more -- one copy per member that has
+    // samples (the areas in the lane's array have a block of slack between them, the caller's areas whatever the caller likes)
+    void download()
+    {
+        const bool down = sb.on_device && has_call();
+        if (down && R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the call's own time)
+        t_call = seconds_since(t0) - t_upload - t_entropy;
+        if (!down) return;
+        const auto t_down = Clock::now();
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            if (!live(j) || member_rc[j] != VPZ_OK || written[j] <= 0) continue;
+            if (vpz_memcpy_d2h(L.ctx, static_cast<char *>(R.pcm_out) + elem * (size_t)R.pcm_offset[job(j).k], L.pcm() + elem * (size_t)offs[j],
+                               (uint64_t)(written[j] * C) * elem) != VPZ_OK) {
+                R.m->fail(std::string("vpz_memcpy_d2h: ") + vpz_context_last_error(L.ctx));
+                member_rc[j] = VPZ_E_HIP;
+            }
+        }
+        // (the slot's packet records and the lane's arrays are free again once the stream has drained)
+        if (vpz_context_synchronize(L.ctx) != VPZ_OK)
+            for (size_t j = 0; j < sb.members.size(); ++j)
+                if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
+        t_download = seconds_since(t_down);
+    }
+
+    // the profile line, then under the group's mutex: the members' results, the group's sums, the slot handed back
+    void account()
+    {
+        for (size_t j = 0; j < sb.members.size(); ++j) job(j).close();  // (a device-decoded sub-batch's containers were kept open for the host path after all)
+        const double dt = seconds_since(t0), at_ms = seconds_since(R.t_begin) * 1e3;
+        if (R.sw.profile && sb.on_device)
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu on the device done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, download %.2f ms; %lld packets, %lld payload bytes)\n",
+                    R.slot_index, b, at_ms, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, t_download * 1e3, (long long)n_pk, (long long)sb.payload_bytes);
+        else if (R.sw.profile)
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets)\n", R.slot_index, b, at_ms, dt * 1e3,
+                    (long long)n_pk);
+        std::lock_guard<std::mutex> lk(R.mu);
+        R.t_synth += dt;
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            Job &J = job(j);
+            if (J.status != VPZM_OK) continue;
+            J.finished = true;
+            if (sb.on_device && has_call()) {  // (it was entropy-decoded on the device)
+                ++R.device_streams;
+                R.device_payload += J.payload_bytes;
+                R.results[J.k].skipped_packets += J.plan_failures;  // (an unused mode number: the plan's "not decoded", counted as the host decode counts it)
+            }
+            if (member_rc[j] != VPZ_OK) {
+                J.status = member_rc[j] == kNoDecoder ? VPZM_E_SETUP : member_rc[j] == VPZ_E_CAPACITY ? VPZM_E_CAPACITY : VPZM_E_SYNTH;
+                continue;
+            }
+            R.results[J.k].samples = written[j];
+            R.samples_total += written[j] * C;
+        }
+        sb.synth_done = true;
+        R.cv.notify_all();
+    }
+};
+
+void GroupRun::synth_sub(Lane &L, size_t b, Sub &sb)
+{
+    SubCall c{*this, L, b, sb};
+    c.repack();
+    c.t0 = Clock::now();
+    c.place_outputs();
+    if (sb.on_device && c.has_call() && !c.decode_on_device()) c.decode_on_host();
+    c.call_batch();
+    c.download();
+    c.account();
+}
 
 }  // namespace
 
@@ -986,23 +995,12 @@ void vpzm_destroy(vpzm_dispatcher *m)
 {
     if (!m) return;
     for (Group &G : m->groups) {
-        vpz_context *ctx0 = G.lanes.empty() ? nullptr : G.lanes[0].ctx;
-        for (Slot &s : G.slots) {
-            if (!ctx0) break;
-            vpz_host_free(ctx0, s.packets);
-            vpz_host_free(ctx0, s.residue);
-            vpz_host_free(ctx0, s.posts);
-            vpz_host_free(ctx0, s.counts);
-            vpz_host_free(ctx0, s.f0_amp);
-            vpz_host_free(ctx0, s.f0_coeff);
-            vpz_host_free(ctx0, s.spans);
-            vpz_host_free(ctx0, s.payload);
-        }
+        for (Slot &s : G.slots)  // (page-locked memory is a context's: the slots' came from the group's first)
+            for (Buffer &b : s.buf) b.release(G.lanes.empty() ? nullptr : G.lanes[0].ctx);
         for (Lane &L : G.lanes) {
-            for (auto &p : L.decs) vpz_decoder_destroy(p.second);
-            for (auto &p : L.esetups) vpz_entropy_setup_destroy(p.second);
-            for (uint8_t *d : {L.d_payload, L.d_residue, L.d_posts, L.d_counts, L.d_pcm})
-                if (d && L.ctx) vpz_device_free(L.ctx, d);
+            L.decoders.clear();
+            L.esetups.clear();
+            for (Buffer &b : L.buf) b.release(L.ctx);
             if (L.ctx) vpz_context_destroy(L.ctx);
         }
     }
@@ -1028,14 +1026,15 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
     const auto t0 = Clock::now();
     const int D = (int)m->groups.size();
     const int per_device = std::max(1, m->opt.host_threads / D);
+    const Switches sw;
     std::vector<std::unique_ptr<GroupRun>> runs;
     std::vector<std::thread> threads;
     try {
         for (int d = 0; d < D; ++d) {
             // shard_range (vorbispizza_amd/sharding.py): contiguous, sizes differ by at most one
             const int32_t lo = (int32_t)((int64_t)n * d / D), hi = (int32_t)((int64_t)n * (d + 1) / D);
-            runs.emplace_back(new GroupRun(m, m->groups[(size_t)d], d, lo, hi, data, size, out_layout, pcm_out, pcm_offset,
-                                           pcm_capacity, results, per_device));
+            runs.emplace_back(new GroupRun{m, m->groups[(size_t)d], d, lo, hi, data, size, out_layout, pcm_out, pcm_offset,
+                                           pcm_capacity, results, per_device, sw});
         }
         for (int d = 1; d < D; ++d) threads.emplace_back([&runs, d] { runs[(size_t)d]->run_guarded(); });
         runs[0]->run_guarded();

@@ -90,7 +90,12 @@ int vpzh_decode_range_ex(vpzh_stream *s, int64_t first, int64_t count, int32_t s
 /* The residue as 16-bit integers.  A residue value is a sum of at most one codebook value per cascade stage; libvorbis' residue books
  * are integer lattices, so for its streams every value is a (small) integer, the same in float32 and in int16 -- and half the bytes on
  * their way to the device (vpz_decoder_set_residue_format(VPZ_RESIDUE_I16)).  vpzh_residue_is_integral: 1 when the setup header
- * guarantees it (every residue value book holds integers only, the worst-case sum stays below 2^15), else 0.
+ * guarantees it, else 0: every residue value book holds integers only; per residue 2 * stages * (the largest sum of magnitudes of
+ * one entry) stays below 2^15; and so does what accumulates over the submaps of every mapping -- the decode keeps the reference's
+ * quirk of one decode buffer for all submaps, never cleared, so a residue of type 0 / 1 adds on top of what earlier submaps left
+ * in the same rows and one of type 2 overwrites its rows: per row, the sum over the type-0/1 submaps that reach it since the last
+ * type-2 submap covering it of stages * (largest entry sum for type 0, largest table magnitude for type 1).  Conservative for
+ * mappings of several type-0/1 submaps; a mapping of one submap or of type-2 submaps only (libvorbis') is decided per residue.
  * vpzh_decode_range_i16: vpzh_decode_range_ex with `residue` as int16 values (offsets and counts in VALUES); VPZH_E_ARG for a stream
  * whose residue is not integral. */
 int vpzh_residue_is_integral(vpzh_stream *s);

@@ -258,3 +258,24 @@ def test_the_entropy_kernels_use_no_scratch():
     assert sum("entropy_decode_kernel" in n for n in names) == 2 and sum("entropy_zero_kernel" in n for n in names) == 2
     for k in ks:
         assert k.get("scratch", 1) == 0, k["demangled"]
+
+
+def test_an_ordered_book_with_32_bit_codes_gives_an_image_the_device_accepts(front):
+    """An ordered book's max_bits is one more than its longest code (33 with 32-bit codes; the count of Codebook.cs:60-66); the
+    device peeks 32 bits at most (vpz_entropy_setup_create refuses more), and decode_scalar compares 32 bits only: the image
+    says min(max_bits, 32) for a stream that vpzh_gpu_decode_supported accepts."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_streams as es
+    seen = []
+    for longest in (31, 32):
+        f = front.OggVorbisFile(es.long_codes(longest, packets=2)[0])
+        assert f.gpu_decode_supported
+        img = f.entropy_setup()
+        book_count = struct.unpack_from("<i", img, 32)[0]
+        books = struct.unpack_from("<I", img, 52)[0]
+        assert book_count == 3
+        bits = [struct.unpack_from("<i", img, books + 48 * k + 8)[0] for k in range(book_count)]
+        assert all(0 < b <= 32 for b in bits), bits
+        seen.append(bits[0])
+        f.close()
+    assert seen == [32, 32]  # (the ordered floor book: 31 + 1, and 32 + 1 held to 32)

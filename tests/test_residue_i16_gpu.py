@@ -105,3 +105,39 @@ def test_the_dispatcher_ships_integral_residues_as_int16_and_floats_on_request(c
     assert (a[2]["status"] == 0).all() and (b[2]["status"] == 0).all()
     assert np.array_equal(a[2]["samples"], b[2]["samples"]) and a[2]["samples"].min() > 0
     assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32))
+
+
+def test_residues_that_accumulate_beyond_int16_are_shipped_as_floats(ctx):
+    """Sixteen one-channel submaps of +-8000 (tests/edge_streams.py): every residue alone passes the 16-bit bound, the sum the
+    reference's never-cleared decode buffer builds up in row 0 reaches 72000.  The dispatcher and the reader, both with their
+    defaults, must give the bits of the float32 hand-over -- the front end has to say that this stream is not integral."""
+    import edge_streams as es
+    from test_multi_gpu import run_dispatcher
+    from vorbispizza_amd.front import OggVorbisFile, VorbisReader
+    raw, exps, _ = es.accumulating_stream(list(range(16)), 8000)
+    assert float(np.abs(es.expected_residue(exps)).max()) >= 32768
+    f = OggVorbisFile(raw)
+    assert f.decode_packets()[1].tobytes() == es.expected_residue(exps).tobytes()
+    raws = [raw] * 3
+    ref = run_dispatcher([0], raws, host_threads=2, float_residue=True)
+    assert (ref[2]["status"] == 0).all() and ref[2]["samples"].min() > 0
+    assert np.abs(ref[0]).max() > 0 and np.isfinite(ref[0]).all()
+    for opt in ({}, {"gpu_entropy": True}):
+        got = run_dispatcher([0], raws, host_threads=2, **opt)
+        assert (got[2]["status"] == 0).all() and np.array_equal(got[2]["samples"], ref[2]["samples"]), opt
+        assert np.array_equal(got[0].view(np.uint32), ref[0].view(np.uint32)), opt
+    # the reader clips by default: against the clipped float32 run
+    clipped = run_dispatcher([0], [raw], host_threads=2, float_residue=True, clip_samples=True)
+    n = int(clipped[2]["samples"][0])
+    rdr = VorbisReader(ctx, raw)
+    buf = np.zeros(16 * 64, dtype=np.float32)
+    chunks = []
+    while True:
+        k = rdr.ReadSamples(buf)
+        if k == 0:
+            break
+        chunks.append(buf[: k * 16].copy())
+    rdr.Dispose()
+    got = np.concatenate(chunks)
+    assert got.size == n * 16 and np.array_equal(got.view(np.uint32), clipped[0][: n * 16].view(np.uint32))
+    f.close()

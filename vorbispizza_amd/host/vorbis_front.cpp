@@ -119,8 +119,9 @@ struct Codebook {
     std::vector<float> lookup;
     // the same values as 16-bit integers, when every one of them is one (bit for bit: no fraction, no -0.0, |v| < 2^15) -- else empty;
     // entry_l1: the largest sum of magnitudes over an entry's dimensions (what one vector can add to ONE bin at most, Residue0's quirk included)
+    // max_abs: the largest magnitude in the table (what a vector that tiles its partition adds to a bin, Residue1.cs:12-34)
     std::vector<int16_t> lookup_i16;
-    double entry_l1 = 0.0;
+    double entry_l1 = 0.0, max_abs = 0.0;
     template <class T> const T *values() const;
     // prefix table of the first `prefix_bits` bits of a code (Huffman.cs:24-105), one 32-bit word per entry:
     // value << 6 | length, 0 = the code is longer than the table (overflow list).  4 KiB per book instead of the 16 KiB of
@@ -316,7 +317,11 @@ struct Codebook {
         }
         for (int idx = 0; idx < entries && dimensions > 0; ++idx) {
             double l1 = 0.0;
-            for (int i = 0; i < dimensions; ++i) l1 += fabs((double)lookup[(size_t)idx * dimensions + i]);
+            for (int i = 0; i < dimensions; ++i) {
+                const double a = fabs((double)lookup[(size_t)idx * dimensions + i]);
+                l1 += a;
+                max_abs = std::max(max_abs, a);
+            }
             entry_l1 = std::max(entry_l1, l1);
         }
     }
@@ -1002,11 +1007,20 @@ void write_record(const PacketHead &h, const OggPacket &pk, int32_t stream_id, i
     out->residue_offset = residue_off;
 }
 
-// Is every residue value of this stream an integer that fits 16 bits?  A residue is a sum, per bin, of at most one codebook value per
+// Is every residue value of this stream an integer that fits 16 bits?  A residue adds, per bin, at most one codebook value per
 // cascade stage (Residue0.cs:144-205); libvorbis' residue books are integer lattices, so for its streams the answer is yes and
 // the vector can travel as int16 -- exactly: sums of integers below 2^24 are the same in float32 -- at half the bytes.  Decided
-// from the setup header alone, conservatively: every value book any residue names must hold integers only, and the worst case --
-// the largest magnitude of any of a residue's books, times its stages -- must stay below 2^15.
+// from the setup header alone, conservatively (residue_integral below):
+//   (1) every value book any residue names must hold integers only;
+//   (2) per residue, the bound B = 2 * (the largest entry_l1 of its books) * (its stages) must stay below 2^15;
+//   (3) per mapping, what ACCUMULATES must stay below 2^15 too.  decode_packet reuses one decode buffer for every submap of a
+//       mapping without clearing it (Mapping.cs:132-163): a type-0/1 submap of `count` channels adds its residue to rows
+//       0..count-1 on top of what earlier submaps left there, a type-2 submap overwrites rows 0..count-1.  One decode of a
+//       residue adds to a bin at most A = (the largest entry_l1 of its books for type 0, the largest magnitude in its books'
+//       tables for types 1 / 2, whose vectors tile the partitions: one value per bin and stage) * (its stages).  A row's
+//       bound is the sum of A over the type-0/1 submaps that reach it since the last type-2 submap that covers it, taken
+//       after every submap (each row is handed out after each).  With one submap, or with type-2 submaps only, A <= B
+//       and (2) decides alone.
 // A residue whose value books do not tile its partitions -- a book of more dimensions than a partition has bins, or of a
 // dimension that does not divide the partition size: the reference decodes such setups (Residue0.cs:171-203 steps by the book's
 // dimensions whatever the partition size) -- lets one vector cover several of the following partitions and overhang the
@@ -1025,23 +1039,49 @@ bool residue_tiles_its_partitions(const SetupBlob &su, const Residue &r)
     return true;
 }
 
+// Rules (1) and (2) for residue `r`: false when it fails them; `adds`: A of rule (3)
+bool residue_bin_bounds(const SetupBlob &su, const Residue &r, double *adds)
+{
+    if (!residue_tiles_its_partitions(su, r)) return false;
+    double worst = 0.0, worst_value = 0.0;
+    for (size_t cl = 0; cl < r.books.size(); ++cl)
+        for (size_t st = 0; st < r.books[cl].size(); ++st) {
+            if (!(r.cascade[cl] & (1u << st))) continue;  // (no book at this stage of the class)
+            const size_t b = r.books[cl][st];
+            if (b >= su.books.size()) return false;
+            const Codebook &cb = su.books[b];
+            if (cb.lookup_i16.empty()) return false;  // (a fraction, a -0.0 or a value beyond 16 bits in the table)
+            worst = std::max(worst, cb.entry_l1);
+            worst_value = std::max(worst_value, cb.max_abs);
+        }
+    // per stage a bin takes one vector's value -- two where a partition's last vector overhangs into the next partition
+    // (Residue1.cs:12-34), the sum of an entry's dimensions for residue type 0 (Residue0.cs:208-231): entry_l1 covers all three
+    *adds = (r.type == 0 ? worst : worst_value) * std::max(1, r.max_stages);
+    return worst * 2.0 * std::max(1, r.max_stages) < 32768.0;
+}
+
 bool residue_integral(const SetupBlob &su)
 {
-    for (const Residue &r : su.residues) {
-        if (!residue_tiles_its_partitions(su, r)) return false;
-        double worst = 0.0;
-        for (size_t cl = 0; cl < r.books.size(); ++cl)
-            for (size_t st = 0; st < r.books[cl].size(); ++st) {
-                if (!(r.cascade[cl] & (1u << st))) continue;  // (no book at this stage of the class)
-                const size_t b = r.books[cl][st];
-                if (b >= su.books.size()) return false;
-                const Codebook &cb = su.books[b];
-                if (cb.lookup_i16.empty()) return false;  // (a fraction, a -0.0 or a value beyond 16 bits in the table)
-                worst = std::max(worst, cb.entry_l1);
+    std::vector<double> adds(su.residues.size(), 0.0);
+    for (size_t i = 0; i < su.residues.size(); ++i)
+        if (!residue_bin_bounds(su, su.residues[i], &adds[i])) return false;
+    // rule (3): what accumulates in the rows of decode_packet's decode buffer over the submaps of a mapping
+    for (const Mapping &m : su.mappings) {
+        const size_t submaps = m.submap_residue.size();
+        if (submaps < 2) continue;
+        std::vector<size_t> count(submaps, 0);
+        for (uint8_t s : m.mux)
+            if (s < submaps) ++count[s];
+        const size_t rows = *std::max_element(count.begin(), count.end());
+        for (size_t row = 0; row < rows; ++row) {
+            double acc = 0.0;
+            for (size_t i = 0; i < submaps; ++i) {
+                const size_t ri = m.submap_residue[i];
+                if (count[i] <= row || ri >= su.residues.size()) continue;  // (the submap does not reach this row)
+                acc = su.residues[ri].type == 2 ? adds[ri] : acc + adds[ri];
+                if (acc >= 32768.0) return false;
             }
-        // per stage a bin takes one vector's value -- two where a partition's last vector overhangs into the next partition
-        // (Residue1.cs:12-34), the sum of an entry's dimensions for residue type 0 (Residue0.cs:208-231): entry_l1 covers all three
-        if (worst * 2.0 * std::max(1, r.max_stages) >= 32768.0) return false;
+        }
     }
     return true;
 }
@@ -1125,7 +1165,11 @@ std::vector<uint8_t> entropy_image(const SetupBlob &su, int channels, int size0,
         vpz_entropy_book &b = books[i];
         b.dimensions = cb.dimensions;
         b.entries = cb.entries;
-        b.max_bits = cb.max_bits;
+        // An ORDERED book's max_bits is one more than its longest code (init_tree keeps Codebook.cs:60-66's count, which steps
+        // past the last length): 33 for a book with 32-bit codes, and vpz_entropy_setup_create refuses a peek of more than
+        // 32 bits.  decode_scalar compares the low 32 bits of its peek only (`int d`), and a peek of 32 bits is the low 32
+        // bits of one of 33 -- both come up empty together --, so the image says 32: the same entries, bit for bit.
+        b.max_bits = std::min(cb.max_bits, 32);
         b.prefix_bits = cb.prefix.empty() ? 0 : cb.prefix_bits;
         b.prefix_count = (int32_t)cb.prefix.size();
         if (!cb.prefix.empty()) b.prefix = w.put(cb.prefix.data(), sizeof(uint32_t) * cb.prefix.size());

@@ -1,11 +1,18 @@
 #!/usr/bin/env python3
 """The 1024-stream job through the in-process dispatcher under several thread / slot / sub-batch settings (one GPU, N groups).
 
-    dispatcher_probe.py [--gpu-entropy | --ab] [--reps N] [--s16-only] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py [--gpu-entropy | --mixed | --ab] [--setups K] [--reps N] [--s16-only] groups,threads,streams_per_call,contexts,slots ...
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
+--mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
 --ab: for every setting TWO dispatchers in this process, the option off and on, take the job in turn, --reps times each
-(default 5): medians and extremes of both, and the PCM of the two compared."""
+(default 5): medians and extremes of both, and the PCM of the two compared.  The option is gpu_entropy; with --mixed it is
+mixed_setups, gpu_entropy on in both.
+--setups K: the mixed-library job instead of the two fixtures' -- STREAMS streams drawn round-robin from K stereo 256/2048 setups of
+the writer (tests/synthetic_streams.py: stereo_coupled_res2(2 + 10 k), --setup-packets packets each, default 300) and the two
+fixtures.  Building them takes seconds each: with VPZ_PROBE_CACHE=DIR they are kept there.
+A line "counts" follows every result: sub_batches, device-decoded and mixed ones, decoders_created of the last call (a build
+without vpzm_last_call_counts, taken through VPZ_LIB_DIR, prints none)."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -15,6 +22,9 @@ from vorbispizza_amd import multi
 ap = argparse.ArgumentParser()
 ap.add_argument("--gpu-entropy", action="store_true")
 ap.add_argument("--ab", action="store_true")
+ap.add_argument("--mixed", action="store_true")
+ap.add_argument("--setups", type=int, default=0)
+ap.add_argument("--setup-packets", type=int, default=300)
 ap.add_argument("--reps", type=int, default=0)
 ap.add_argument("--s16-only", action="store_true")
 ap.add_argument("settings", nargs="+")
@@ -22,9 +32,45 @@ args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
 raws = [np.frombuffer(open(os.path.join(ROOT, "tests", "golden", n), "rb").read(), dtype=np.uint8) for n, _ in bench.REAL_FIXTURES]
 caps1 = [smp + 2048 for _, smp in bench.REAL_FIXTURES]
-datas = [raws[i % 2] for i in range(streams)]
-caps = np.array([caps1[i % 2] for i in range(streams)], dtype=np.int64)
+
+
+def writer_stream(k, packets):
+    """stereo_coupled_res2(2 + 10 k) with `packets` packets, as a uint8 array (kept under VPZ_PROBE_CACHE when that is set)"""
+    cache = os.environ.get("VPZ_PROBE_CACHE")
+    path = os.path.join(cache, "stereo_%d_%d.ogg" % (2 + 10 * k, packets)) if cache else None
+    if path and os.path.exists(path):
+        return np.frombuffer(open(path, "rb").read(), dtype=np.uint8)
+    import synthetic_streams as ss
+    st, rng = ss.stereo_coupled_res2(2 + 10 * k)
+    raw = bytes(st.build(rng, packets)[0])
+    if path:
+        os.makedirs(cache, exist_ok=True)
+        open(path, "wb").write(raw)
+    return np.frombuffer(raw, dtype=np.uint8)
+
+
+if args.setups:
+    from vorbispizza_amd.front import OggVorbisFile
+    raws += [writer_stream(k, args.setup_packets) for k in range(args.setups)]
+    for r in raws[2:]:
+        f = OggVorbisFile(r.tobytes())
+        assert f.gpu_decode_supported and f.channels == 2
+        caps1.append(int(f.total_samples) + 2048)
+        f.close()
+    pick = [2 + i % args.setups for i in range(streams - 2)] + [0, 1]
+else:
+    pick = [i % 2 for i in range(streams)]
+datas = [raws[i] for i in pick]
+caps = np.array([caps1[i] for i in pick], dtype=np.int64)
 offs = np.concatenate([[0], np.cumsum(caps * 2)[:-1]]).astype(np.int64)
+
+
+def counts_line(d):
+    if not hasattr(multi.lib(), "vpzm_last_call_counts"):
+        return ""
+    c = d.call_counts()
+    return "\n    counts: %d sub-batches (%d device-decoded, %d mixed, at most %d setups in one), %d decoders created in the last call" % (
+        c.sub_batches, c.device_decoded_sub_batches, c.mixed_sub_batches, c.max_setups_per_sub_batch, c.decoders_created)
 
 
 def describe(walls):
@@ -37,8 +83,8 @@ for s16 in ((True,) if args.s16_only else (False, True)):
         what = "%s groups %d threads %3d streams/call %2d contexts %d slots %d" % ("s16" if s16 else "f32", groups, thr, spc, ctxs, slots)
         if args.ab:
             ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
-                                   gpu_entropy=g) for g in (False, True)]
-            walls, sums = ([], []), [None, None]
+                                   gpu_entropy=g or args.mixed, **({"mixed_setups": g} if args.mixed else {})) for g in (False, True)]
+            walls, sums, lines = ([], []), [None, None], ["", ""]
             for d in ds:  # (one pass each that does not count: slots, decoders and device arrays are allocated in it)
                 d.decode_library(datas, pcm, offs, caps, s16=s16)
             for _ in range(args.reps or 5):
@@ -49,15 +95,18 @@ for s16 in ((True,) if args.s16_only else (False, True)):
                     walls[i].append(st.wall_s)
                     sums[i] = (int(pcm.view(np.uint16).astype(np.uint64).sum()), int(res["samples"].sum()), st.pinned_mib,
                                int(sum(st.device_gpu_entropy_streams)), int(sum(st.device_payload_bytes)), st.device_decode_s[0])
-            for d in ds:
+            for i, d in enumerate(ds):
+                lines[i] = counts_line(d)
                 d.close()
             assert sums[0][:2] == sums[1][:2], "the two dispatchers' PCM differs"
-            print("%s:\n    gpu_entropy off: %s, host decode until %.1f ms, pinned %d MiB\n    gpu_entropy on:  %s, plan until %.1f ms, pinned %d MiB, "
-                  "%d streams on the device, %.1f MB of packet bytes" % (what, describe(walls[0]), sums[0][5] * 1e3, sums[0][2], describe(walls[1]),
-                                                                           sums[1][5] * 1e3, sums[1][2], sums[1][3], sums[1][4] / 1e6), flush=True)
+            name = "mixed_setups" if args.mixed else "gpu_entropy"
+            print("%s:\n    %s off: %s, host decode until %.1f ms, pinned %d MiB%s\n    %s on:  %s, plan until %.1f ms, pinned %d MiB, "
+                  "%d streams on the device, %.1f MB of packet bytes%s" % (what, name, describe(walls[0]), sums[0][5] * 1e3, sums[0][2], lines[0], name,
+                                                                         describe(walls[1]), sums[1][5] * 1e3, sums[1][2], sums[1][3], sums[1][4] / 1e6,
+                                                                         lines[1]), flush=True)
             continue
         d = multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
-                             gpu_entropy=args.gpu_entropy)
+                             gpu_entropy=args.gpu_entropy or args.mixed, **({"mixed_setups": True} if args.mixed else {}))
         best, walls = None, []
         for _ in range(args.reps or 3):
             res, st = d.decode_library(datas, pcm, offs, caps, s16=s16)
@@ -65,9 +114,10 @@ for s16 in ((True,) if args.s16_only else (False, True)):
             walls.append(st.wall_s)
             if best is None or st.wall_s < best[0]:
                 best = (st.wall_s, st.device_decode_s[0], st.device_synth_s[0])
+        line = counts_line(d)
         d.close()
         tot = int(res["samples"].sum()) * 2
-        print("%s%s: %.1f ms = %.2f Gsamples/s (decode until %.1f, synth sum %.1f; %s)"
-              % (what, " gpu_entropy" if args.gpu_entropy else "", best[0] * 1e3, tot / best[0] / 1e9, best[1] * 1e3, best[2] * 1e3,
-                 describe(walls[1:] or walls)), flush=True)
+        print("%s%s: %.1f ms = %.2f Gsamples/s (decode until %.1f, synth sum %.1f; %s)%s"
+              % (what, " mixed_setups" if args.mixed else " gpu_entropy" if args.gpu_entropy else "", best[0] * 1e3, tot / best[0] / 1e9, best[1] * 1e3,
+                 best[2] * 1e3, describe(walls[1:] or walls), line), flush=True)
     del pcm

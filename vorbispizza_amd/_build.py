@@ -48,6 +48,7 @@ def _deps(src):
             deps.append(os.path.join(CSRC, name))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_synth.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_entropy.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_entropy_group.h"))
     return deps
 
 
@@ -64,7 +65,8 @@ def build_host(force=False, verbose=False):
     inc = os.path.join(_HERE, "..", "include")
     deps = srcs + [os.path.join(inc, "vorbispizza_front.h"), os.path.join(inc, "vorbispizza_reader.h"),
                    os.path.join(inc, "vorbispizza_multi.h"), os.path.join(inc, "vorbispizza_synth.h"),
-                   os.path.join(inc, "vorbispizza_entropy.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_entropy.h"), os.path.join(inc, "vorbispizza_entropy_group.h"),
+                   os.path.join(inc, "vorbispizza_multi_mixed.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

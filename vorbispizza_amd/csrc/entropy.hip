@@ -14,320 +14,14 @@
 #include <vector>
 
 #include "vpz_internal.hpp"
-#include "../../include/vorbispizza_entropy.h"
+#include "entropy_decode.hpp"
+#include "../../include/vorbispizza_entropy_group.h"
 
 namespace vpz {
 namespace {
 
-// what the kernels know of a packet (24 bytes): where its bits are, where its residue goes, its flags and mapping
-struct PacketDesc {
-    int64_t payload_bit;     // bit offset of the packet in the payload
-    int64_t residue_offset;  // value offset of its residue
-    uint32_t size;           // bytes
-    uint32_t info;           // flags | mapping << 8
-};
-
 constexpr int kBlock = 256;
 constexpr int64_t kSmallLaunch = 65536;  // packets below which entropy_decode_kernel is launched with one wave per workgroup
-
-// 256 one-bit flags in registers (a runtime-indexed array would live in scratch memory): channels of a packet
-struct Mask256 {
-    uint64_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-    __host__ __device__ bool get(int i) const
-    {
-        const uint64_t w = i < 64 ? m0 : i < 128 ? m1 : i < 192 ? m2 : m3;
-        return (w >> (i & 63)) & 1u;
-    }
-    __host__ __device__ void put(int i, bool v)
-    {
-        const uint64_t bit = 1ull << (i & 63);
-        if (i < 64) m0 = v ? (m0 | bit) : (m0 & ~bit);
-        else if (i < 128) m1 = v ? (m1 | bit) : (m1 & ~bit);
-        else if (i < 192) m2 = v ? (m2 | bit) : (m2 & ~bit);
-        else m3 = v ? (m3 | bit) : (m3 & ~bit);
-    }
-};
-
-// BitReader (host: try_peek / skip / read_bits): LSB first; a peek near the end returns the bits that are left,
-// zero-padded; a skip past the end stops at the end.  Two aligned words of the payload per peek.
-struct Bits {
-    const uint32_t *words;
-    uint64_t base;  // bit offset of the packet in the payload
-    uint32_t pos, total;
-
-    __host__ __device__ uint32_t peek(int count, int &n) const
-    {
-        const uint32_t rem = total - pos;
-        n = rem < (uint32_t)count ? (int)rem : count;
-        if (n <= 0) {
-            n = 0;
-            return 0;
-        }
-        const uint64_t ab = base + pos;
-        const uint64_t q = ab >> 5;
-        const uint64_t w = (uint64_t)words[q] | ((uint64_t)words[q + 1] << 32);
-        const uint32_t v = (uint32_t)(w >> (ab & 31));
-        return n >= 32 ? v : (v & ((1u << n) - 1u));
-    }
-    __host__ __device__ void skip(uint32_t count)
-    {
-        const uint32_t rem = total - pos;
-        pos = rem >= count ? pos + count : total;
-    }
-    __host__ __device__ uint32_t read(int count)
-    {
-        int n;
-        const uint32_t v = peek(count, n);
-        pos += (uint32_t)n;
-        return v;
-    }
-};
-
-template <class T> __host__ __device__ const T *at(const uint8_t *img, uint32_t off) { return reinterpret_cast<const T *>(img + off); }
-
-// Codebook::decode_scalar: the prefix table, then the overflow list in the host's order; -1 on a miss
-__host__ __device__ int decode_scalar(const uint8_t *img, const vpz_entropy_book *b, Bits &p)
-{
-    int n;
-    const int prefix_count = b->prefix_count;
-    const uint32_t data = p.peek(b->prefix_bits, n);
-    if (n != 0 && prefix_count != 0) {
-        const uint32_t e = at<uint32_t>(img, b->prefix)[data];
-        if (e & 63u) {
-            p.skip(e & 63u);
-            return (int)(e >> 6);
-        }
-    }
-    const uint32_t d = p.peek(b->max_bits, n);
-    if (n != 0) {
-        const vpz_entropy_code *c = at<vpz_entropy_code>(img, b->overflow);
-        const int count = b->overflow_count;
-        for (int k = 0; k < count; ++k) {
-            if (c[k].bits == (d & c[k].mask)) {
-                p.skip(c[k].length);
-                return (int)c[k].value;
-            }
-        }
-    }
-    return -1;
-}
-
-__host__ __device__ inline int16_t clamp16(int v) { return (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v)); }
-
-// Floor1::unpack -> the post count; posts are written to `out` as they are read (the record was zeroed), so that a
-// miss leaves what was read before it, as the host's `raw` array does
-__host__ __device__ int floor1_unpack(const uint8_t *img, const vpz_entropy_book *books, const vpz_entropy_floor1 *f, Bits &p,
-                             int16_t *out)
-{
-    if (!p.read(1)) return 0;
-    const int y_bits = f->y_bits;
-    int post_count = 2;
-    out[0] = clamp16((int)p.read(y_bits));
-    out[1] = clamp16((int)p.read(y_bits));
-    const int parts = f->partition_count;
-    for (int i = 0; i < parts; ++i) {
-        const int cls = f->partition_class[i];
-        const int cdim = f->class_dimensions[cls];
-        const int cbits = f->class_subclasses[cls];
-        const uint32_t csub = (1u << cbits) - 1u;
-        uint32_t cval = 0;
-        if (cbits > 0) {
-            const int v = decode_scalar(img, books + f->class_masterbooks[cls], p);
-            if (v == -1) return 0;
-            cval = (uint32_t)v;
-        }
-        for (int j = 0; j < cdim; ++j) {
-            const int book_idx = f->subclass_books[cls * 8 + (cval & csub)];
-            cval >>= cbits;
-            int post = 0;
-            if (book_idx >= 0) {
-                post = decode_scalar(img, books + book_idx, p);
-                if (post == -1) return 0;
-            }
-            if (post_count < 64) out[post_count] = clamp16(post);
-            ++post_count;
-        }
-    }
-    return post_count;
-}
-
-template <class T> __host__ __device__ const T *values(const uint8_t *img, const vpz_entropy_book *b);
-template <> __host__ __device__ const float *values<float>(const uint8_t *img, const vpz_entropy_book *b) { return at<float>(img, b->lookup_f32); }
-template <> __host__ __device__ const int16_t *values<int16_t>(const uint8_t *img, const vpz_entropy_book *b) { return at<int16_t>(img, b->lookup_i16); }
-
-// Residue::write_vectors: type 0 sums an entry into ONE bin, every partial sum rounded (quirk q9); types 1 / 2 add the
-// vector to consecutive bins.  true: the packet ran out
-template <class T>
-__host__ __device__ bool write_vectors(const uint8_t *img, const vpz_entropy_book *cb, Bits &p, T *chan, int chan_len, int offset, int type,
-                              int partition_size)
-{
-    const T *lookup = values<T>(img, cb);
-    const int dim = cb->dimensions;
-    if (type == 0) {
-        const int steps = partition_size / dim;
-        for (int step = 0; step < steps; ++step) {
-            const int entry = decode_scalar(img, cb, p);
-            if (entry == -1) return true;
-            T r = 0;
-            const T *lk = lookup + (size_t)entry * dim;
-            for (int d = 0; d < dim; ++d) r = (T)(r + lk[d]);
-            if (offset + step < chan_len) chan[offset + step] = (T)(chan[offset + step] + r);
-        }
-        return false;
-    }
-    for (int i = 0; i < partition_size;) {
-        const int entry = decode_scalar(img, cb, p);
-        if (entry == -1) return true;
-        const T *lk = lookup + (size_t)entry * dim;
-        if (offset + i + dim > chan_len) return true;  // (never: the image's value books tile their partitions)
-        for (int j = 0; j < dim; ++j) chan[offset + i + j] = (T)(chan[offset + i + j] + lk[j]);
-        i += dim;
-    }
-    return false;
-}
-
-// Residue::decode: `count` vectors at `stride`; a class word that misses abandons every remaining stage, a vector that
-// misses keeps the vectors already added.  cache: the class words of this decode (count * partition words)
-template <class T>
-__host__ __device__ void residue_decode(const uint8_t *img, const vpz_entropy_book *books, const vpz_entropy_residue *r, Bits &p,
-                               const Mask256 &dnd, int count, int block_size, T *buffer, int stride, int32_t *cache)
-{
-    const int half = block_size / 2;
-    const int b = r->begin < half ? r->begin : half;
-    const int e = r->end < half ? r->end : half;
-    const int n = e - b;
-    if (n <= 0) return;
-    const int psize = r->partition_size;
-    const int partition_count = n / psize;
-    const vpz_entropy_book *cb = books + r->class_book;
-    const int dim = cb->dimensions;
-    const int partition_words = (partition_count + dim - 1) / dim;
-    const int words = r->decode_map_count / dim;
-    const int16_t *stage_book = at<int16_t>(img, r->stage_book);
-    const uint8_t *decode_map = img + r->decode_map;
-    const int max_stages = r->max_stages, type = r->type;
-    for (int stage = 0; stage < max_stages; ++stage) {
-        for (int partition_idx = 0, entry_idx = 0; partition_idx < partition_count; ++entry_idx) {
-            if (stage == 0) {
-                for (int ch = 0; ch < count; ++ch) {
-                    if (dnd.get(ch)) continue;
-                    const int idx = decode_scalar(img, cb, p);
-                    if (idx < 0 || idx >= words) return;
-                    cache[ch * partition_words + entry_idx] = idx;
-                }
-            }
-            for (int dim_idx = 0; partition_idx < partition_count && dim_idx < dim; ++dim_idx, ++partition_idx) {
-                const int offset = b + partition_idx * psize;
-                for (int ch = 0; ch < count; ++ch) {
-                    if (dnd.get(ch)) continue;
-                    const int idx = decode_map[cache[ch * partition_words + entry_idx] * dim + dim_idx];
-                    const int bk = stage < 8 ? stage_book[idx * 8 + stage] : -1;
-                    if (bk < 0) continue;
-                    if (write_vectors<T>(img, books + bk, p, buffer + (size_t)ch * stride, stride, offset, type, psize)) return;
-                }
-            }
-        }
-    }
-}
-
-// decode_packet from the floors on, for packet k
-template <class T>
-__host__ __device__ void decode_one_packet(const uint8_t *img, const PacketDesc *pk, int64_t k, const uint32_t *payload, T *residue,
-                                           int16_t *posts, uint8_t *post_counts, int32_t *cache, int cache_words, T *dbuf)
-{
-    const vpz_entropy_image_header *h = at<vpz_entropy_image_header>(img, 0);
-    const int channels = h->channels;
-    const PacketDesc d = pk[k];
-    const uint32_t flags = d.info & 0xffu;
-    const int64_t rec = k * channels;
-    if (flags & VPZ_PKT_NOT_DECODED) {
-        for (int c = 0; c < channels; ++c) post_counts[rec + c] = 0;
-        return;
-    }
-    const bool bf = flags & VPZ_PKT_BLOCK_FLAG;
-    const int block_size = bf ? h->block_size1 : h->block_size0;
-    const int half = block_size / 2;
-    const vpz_entropy_book *books = at<vpz_entropy_book>(img, h->books);
-    const vpz_entropy_floor1 *floors = at<vpz_entropy_floor1>(img, h->floors);
-    const vpz_entropy_residue *residues = at<vpz_entropy_residue>(img, h->residues);
-    const vpz_entropy_mapping *map = at<vpz_entropy_mapping>(img, h->mappings) + (d.info >> 8);
-    Bits p;
-    p.words = payload;
-    p.base = (uint64_t)d.payload_bit;
-    p.total = d.size * 8u;
-    // the floors begin after the header bits, or where the packet ends: the CPU front end's decode_packet starts at the same
-    // bit (PacketHead::header_bits of host/vorbis_front.cpp, the same sum)
-    const uint32_t header_bits = 1u + (uint32_t)h->mode_field_bits + (bf ? 2u : 0u);  // type bit, mode, window flags
-    p.pos = header_bits < p.total ? header_bits : p.total;
-
-    // floors, Mapping.cs:109-118
-    Mask256 no_execute;
-    for (int ch = 0; ch < channels; ++ch) {
-        const int fl = map->submap_floor[map->mux[ch]];
-        int pc = floor1_unpack(img, books, floors + fl, p, posts + (rec + ch) * 64);
-        if (pc > 64) pc = 64;
-        post_counts[rec + ch] = (uint8_t)pc;
-        no_execute.put(ch, pc == 0);
-    }
-    // coupling fix-up, Mapping.cs:121-130
-    const int steps = map->coupling_steps;
-    for (int i = 0; i < steps; ++i) {
-        const int mag = map->coupling_magnitude[i], ang = map->coupling_angle[i];
-        if (!(no_execute.get(mag) && no_execute.get(ang))) {
-            no_execute.put(mag, false);
-            no_execute.put(ang, false);
-        }
-    }
-    // residues, Mapping.cs:132-163
-    T *dst = residue + d.residue_offset;
-    int32_t *words = cache + k * cache_words;
-    const int submaps = map->submaps;
-    if (submaps == 1) {
-        // one submap: every channel is a member in order and the decode buffer starts cleared -- decoding straight into
-        // the zeroed output is decode_packet's copy of it (the Residue2 shortcut for more than one channel included)
-        const vpz_entropy_residue *r = residues + map->submap_residue[0];
-        if (r->type == 2) {
-            bool any = false;
-            for (int ch = 0; ch < channels; ++ch) any |= !no_execute.get(ch);
-            if (any) residue_decode<T>(img, books, r, p, Mask256(), 1, block_size * channels, dst, half * channels, words);
-        } else {
-            residue_decode<T>(img, books, r, p, no_execute, channels, block_size, dst, half, words);
-        }
-        return;
-    }
-    // several submaps: decode_packet's decode buffer, reused by every submap without clearing (rows of `half` values:
-    // nothing of a tiling residue reaches beyond), and the Residue2 temporary after it
-    T *buf = dbuf + 2 * d.residue_offset;
-    T *tmp = buf + (size_t)channels * half;
-    for (int i = 0; i < channels * half; ++i) buf[i] = 0;
-    for (int i = 0; i < submaps; ++i) {
-        Mask256 dnd;
-        int count = 0;
-        for (int j = 0; j < channels; ++j)
-            if (map->mux[j] == i) dnd.put(count++, no_execute.get(j));
-        if (count == 0) continue;
-        const vpz_entropy_residue *r = residues + map->submap_residue[i];
-        if (r->type == 2) {  // Residue2.cs:12-52
-            bool any = false;
-            for (int kk = 0; kk < count; ++kk) any |= !dnd.get(kk);
-            if (!any) {
-                for (int kk = 0; kk < count * half; ++kk) buf[kk] = 0;
-            } else {
-                for (int kk = 0; kk < count * half; ++kk) tmp[kk] = 0;
-                residue_decode<T>(img, books, r, p, Mask256(), 1, block_size * count, tmp, half * count, words);
-                for (int kk = 0; kk < count; ++kk)
-                    for (int bb = 0; bb < half; ++bb) buf[kk * half + bb] = tmp[bb * count + kk];
-            }
-        } else {
-            residue_decode<T>(img, books, r, p, dnd, count, block_size, buf, half, words);
-        }
-        for (int j = 0, kk = 0; j < channels; ++j)
-            if (map->mux[j] == i) {
-                for (int bb = 0; bb < half; ++bb) dst[(size_t)j * half + bb] = buf[kk * half + bb];
-                ++kk;
-            }
-    }
-}
 
 // one lane per packet
 template <class T>
@@ -337,7 +31,28 @@ __global__ void __launch_bounds__(kBlock) entropy_decode_kernel(const uint8_t *_
                                                                 T *dbuf)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (the workgroup's size is the launch's choice, kBlock at most)
-    if (k < n_packets) decode_one_packet<T>(img, pk, k, payload, residue, posts, post_counts, cache, cache_words, dbuf);
+    if (k >= n_packets) return;
+    const PacketDesc d = pk[k];
+    decode_one_packet<T>(img, d, k, payload, residue, posts, post_counts, cache, cache_words, dbuf);
+}
+
+// A group call: one lane per entry of the lane list (entropy_decode.hpp), whose runs start on whole waves -- the setup of a wave is
+// one, read once and made scalar, so that the image's address, its header fields and record arrays stay in scalar registers as
+// they do above, where the image is a kernel argument.  (Both launch sizes are multiples of the wave size.)
+// (The table's entries are typed as addresses of global memory: of a plain pointer read from memory the compiler knows no address
+// space, and every load from the image would be a flat one.)
+using ImageAddress = const __attribute__((address_space(1))) uint8_t *;
+template <class T>
+__global__ void __launch_bounds__(kBlock) entropy_group_kernel(const ImageAddress *__restrict__ images, const PacketDesc *__restrict__ lanes,
+                                                               const int64_t *__restrict__ lane_packet, int64_t n_lanes,
+                                                               const uint32_t *__restrict__ payload, T *residue, int16_t *posts,
+                                                               uint8_t *post_counts, int32_t *cache, int cache_words, T *dbuf)
+{
+    const int64_t l = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (l >= n_lanes) return;
+    const PacketDesc d = lanes[l];
+    const uint8_t *img = (const uint8_t *)images[__builtin_amdgcn_readfirstlane((int)lane_setup(d.info))];
+    decode_group_lane<T>(img, d, lane_packet[l], payload, residue, posts, post_counts, cache, cache_words, dbuf);
 }
 
 // the residue regions of the decoded packets, zeroed with whole rows (a workgroup per packet)
@@ -357,16 +72,23 @@ __global__ void __launch_bounds__(kBlock) entropy_zero_kernel(const PacketDesc *
 }  // namespace
 }  // namespace vpz
 
-struct vpz_entropy_setup {
-    vpz::Context *ctx = nullptr;
+namespace vpz {
+namespace {
+
+// a validated setup image and what the launches need to know of it
+struct EntropyImage {
     std::vector<uint8_t> image;       // the validated image (host copy)
     vpz_entropy_image_header h{};
     uint8_t *d_image = nullptr;
     bool i16_ok = false;              // every residue value book has its int16 table and the image says integral
     bool multi_submap = false;        // some mapping has several submaps: the decode buffer is needed
     int cache_words = 1;              // class words one packet's residue decode keeps, at most
-    // per call
-    vpz::PacketDesc *h_desc = nullptr, *d_desc = nullptr;
+};
+
+// what a call needs on the device, kept between the calls of one setup or one group
+struct CallScratch {
+    PacketDesc *h_desc = nullptr, *d_desc = nullptr;    // the packet descriptors (a group: its lane list)
+    int64_t *h_index = nullptr, *d_index = nullptr;     // a group: the packet of every lane
     size_t desc_cap = 0;
     hipEvent_t desc_done = nullptr;
     bool desc_pending = false;
@@ -377,6 +99,27 @@ struct vpz_entropy_setup {
     void *d_residue = nullptr; size_t residue_bytes = 0;
     void *d_posts = nullptr; size_t posts_bytes = 0;
     void *d_counts = nullptr; size_t counts_bytes = 0;
+};
+
+}  // namespace
+}  // namespace vpz
+
+struct vpz_entropy_setup {
+    vpz::Context *ctx = nullptr;
+    vpz::EntropyImage img;
+    vpz::CallScratch call;
+};
+
+struct vpz_entropy_group {
+    vpz::Context *ctx = nullptr;
+    std::vector<vpz::EntropyImage> images;
+    void *d_table = nullptr;            // the images' device addresses (ImageAddress[n_setups])
+    int channels = 0, block_size0 = 0, block_size1 = 0;
+    bool i16_ok = true;                 // every setup allows the int16 residue
+    bool multi_submap = false;          // any setup needs the decode buffer
+    int cache_words = 1;                // the largest any setup needs
+    std::vector<vpz::PacketDesc> desc;  // per call: the packets' descriptors before they are ordered
+    vpz::CallScratch call;
 };
 
 namespace {
@@ -393,7 +136,7 @@ bool pow2_block(int n) { return n >= 64 && n <= 8192 && (n & (n - 1)) == 0; }
 
 // every check the kernels rely on: nothing they index with a value from the image or the bit stream can leave the image
 // or a packet's residue region
-bool validate(vpz_entropy_setup &S, std::string &why)
+bool validate(vpz::EntropyImage &S, std::string &why)
 {
     const std::vector<uint8_t> &img = S.image;
 #define REQUIRE(cond, text) do { if (!(cond)) { why = text; return false; } } while (0)
@@ -520,6 +263,187 @@ int grow(vpz::Context *ctx, void **buf, size_t *have, size_t need)
     return vpz::ensure_stage(ctx, buf, have, need < 16 ? 16 : need);
 }
 
+int upload_image(vpz::Context *ctx, vpz::EntropyImage &I)
+{
+    VPZ_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&I.d_image), I.image.size()));
+    VPZ_HIP_TRY(ctx, hipMemcpy(I.d_image, I.image.data(), I.image.size(), hipMemcpyHostToDevice));
+    return VPZ_OK;
+}
+
+void release(vpz::CallScratch &K)
+{
+    for (void *p : {(void *)K.d_desc, (void *)K.d_index, K.d_cache, K.d_dbuf, K.d_payload, K.d_residue, K.d_posts, K.d_counts})
+        if (p) (void)hipFree(p);
+    if (K.h_desc) (void)hipHostFree(K.h_desc);
+    if (K.h_index) (void)hipHostFree(K.h_index);
+    if (K.desc_done) (void)hipEventDestroy(K.desc_done);
+    K = vpz::CallScratch();
+}
+
+// the arguments both decode calls check alike, before anything that knows a setup
+int check_call(vpz::Context *ctx, const char *who, int64_t n_packets, const vpz_packet *packets, const vpz_entropy_span *spans,
+               const uint8_t *payload, int64_t payload_bytes, int32_t residue_format, bool i16_ok, const void *residue,
+               int64_t residue_values, const int16_t *posts, const uint8_t *post_counts, int64_t n_records, int channels,
+               int32_t mem_space)
+{
+    auto fail = [&](const char *text) { return set_error(ctx, VPZ_E_INVALID_ARG, (std::string(who) + ": " + text).c_str()); };
+    if (n_packets < 0 || payload_bytes < 0 || residue_values < 0 || n_records < 0) return fail("negative count or extent");
+    if (mem_space != VPZ_MEM_HOST && mem_space != VPZ_MEM_DEVICE) return fail("bad mem_space");
+    if (residue_format != VPZ_RESIDUE_F32 && residue_format != VPZ_RESIDUE_I16) return fail("bad residue format");
+    if (residue_format == VPZ_RESIDUE_I16 && !i16_ok) return fail("int16 residue for a setup whose residue is not integral");
+    if (n_packets == 0) return VPZ_OK;
+    if (!packets || !spans || !payload || !posts || !post_counts) return fail("null argument");
+    if (n_packets > (int64_t)1 << 40 || n_records < n_packets * channels) return fail("fewer post records than packets * channels");
+    const size_t esize = residue_format == VPZ_RESIDUE_I16 ? 2 : 4;
+    if (mem_space == VPZ_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(payload) & 3) || (reinterpret_cast<uintptr_t>(residue) & (esize - 1)) ||
+                                        (reinterpret_cast<uintptr_t>(posts) & 1)))
+        return fail("misaligned device buffer");
+    return VPZ_OK;
+}
+
+// the bounds of packet k that no setup decides: its span; for a decoded packet, its residue of `len` values
+const char *check_packet(const vpz_packet &p, const vpz_entropy_span &sp, int64_t payload_bytes, int channels, int block_size0,
+                         int block_size1, int64_t residue_values)
+{
+    if (sp.offset < 0 || sp.size < 0 || sp.size >= ((int64_t)1 << 28) || sp.offset > payload_bytes - sp.size - 8)
+        return "a packet's span lies outside the payload";
+    if (p.flags & VPZ_PKT_NOT_DECODED) return nullptr;
+    const int64_t len = (int64_t)channels * ((p.flags & VPZ_PKT_BLOCK_FLAG) ? block_size1 : block_size0) / 2;
+    if (p.residue_offset < 0 || p.residue_offset > residue_values - len) return "a packet's residue lies beyond residue_values";
+    return nullptr;
+}
+
+vpz::PacketDesc describe(const vpz_packet &p, const vpz_entropy_span &sp, uint32_t mapping, uint32_t setup)
+{
+    return vpz::PacketDesc{sp.offset * 8, p.residue_offset, (uint32_t)sp.size, (uint32_t)p.flags | (mapping << 8) | (setup << 16)};
+}
+
+// room for n descriptors (and, for a group, n lane indices) in the page-locked buffer; the previous call's copy has left it
+int desc_room(vpz::Context *ctx, vpz::CallScratch &K, int64_t n, bool with_index)
+{
+    if (K.desc_pending) {
+        VPZ_HIP_TRY(ctx, hipEventSynchronize(K.desc_done));
+        K.desc_pending = false;
+    }
+    if (K.desc_cap >= (size_t)n) return VPZ_OK;
+    if (K.h_desc) VPZ_HIP_TRY(ctx, hipHostFree(K.h_desc));
+    K.h_desc = nullptr;
+    if (K.d_desc) VPZ_HIP_TRY(ctx, hipFree(K.d_desc));
+    K.d_desc = nullptr;
+    if (K.h_index) VPZ_HIP_TRY(ctx, hipHostFree(K.h_index));
+    K.h_index = nullptr;
+    if (K.d_index) VPZ_HIP_TRY(ctx, hipFree(K.d_index));
+    K.d_index = nullptr;
+    K.desc_cap = 0;
+    const size_t cap = (size_t)n + (size_t)n / 4;
+    VPZ_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&K.h_desc), cap * sizeof(vpz::PacketDesc)));
+    VPZ_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&K.d_desc), cap * sizeof(vpz::PacketDesc)));
+    if (with_index) {
+        VPZ_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&K.h_index), cap * sizeof(int64_t)));
+        VPZ_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&K.d_index), cap * sizeof(int64_t)));
+    }
+    K.desc_cap = cap;
+    return VPZ_OK;
+}
+
+int upload_descs(vpz::Context *ctx, vpz::CallScratch &K, int64_t n, bool with_index)
+{
+    hipStream_t st = ctx->stream;
+    VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.d_desc, K.h_desc, sizeof(vpz::PacketDesc) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (with_index) VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.d_index, K.h_index, sizeof(int64_t) * (size_t)n, hipMemcpyHostToDevice, st));
+    VPZ_HIP_TRY(ctx, hipEventRecord(K.desc_done, st));
+    K.desc_pending = true;
+    return VPZ_OK;
+}
+
+// the buffers the kernels work on: the caller's (VPZ_MEM_DEVICE) or the staging copies (VPZ_MEM_HOST)
+struct Buffers {
+    const uint8_t *payload;
+    void *residue;
+    int16_t *posts;
+    uint8_t *counts;
+};
+
+// the class-word cache and the decode buffer, the staging copies in, the post records cleared
+int stage_in(vpz::Context *ctx, vpz::CallScratch &K, int64_t n_packets, int channels, int cache_words, bool multi_submap, size_t esize,
+             int32_t mem_space, const uint8_t *payload, int64_t payload_bytes, void *residue, int64_t residue_values, int16_t *posts,
+             uint8_t *post_counts, Buffers &B)
+{
+    hipStream_t st = ctx->stream;
+    int rc;
+    if ((rc = grow(ctx, &K.d_cache, &K.cache_bytes, sizeof(int32_t) * (size_t)n_packets * cache_words)) != VPZ_OK) return rc;
+    if (multi_submap && (rc = grow(ctx, &K.d_dbuf, &K.dbuf_bytes, 2 * esize * (size_t)residue_values)) != VPZ_OK) return rc;
+    B = Buffers{payload, residue, posts, post_counts};
+    const size_t recs = (size_t)n_packets * channels;
+    if (mem_space == VPZ_MEM_HOST) {
+        if ((rc = grow(ctx, &K.d_payload, &K.payload_bytes, (size_t)payload_bytes + 8)) != VPZ_OK) return rc;
+        if ((rc = grow(ctx, &K.d_residue, &K.residue_bytes, esize * (size_t)residue_values)) != VPZ_OK) return rc;
+        if ((rc = grow(ctx, &K.d_posts, &K.posts_bytes, recs * 64 * sizeof(int16_t))) != VPZ_OK) return rc;
+        if ((rc = grow(ctx, &K.d_counts, &K.counts_bytes, recs)) != VPZ_OK) return rc;
+        VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.d_payload, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, st));
+        // (the whole extent goes both ways: what no packet writes comes back as it was)
+        if (residue && residue_values)
+            VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.d_residue, residue, esize * (size_t)residue_values, hipMemcpyHostToDevice, st));
+        B = Buffers{static_cast<const uint8_t *>(K.d_payload), K.d_residue, static_cast<int16_t *>(K.d_posts),
+                    static_cast<uint8_t *>(K.d_counts)};
+    }
+    VPZ_HIP_TRY(ctx, hipMemsetAsync(B.posts, 0, recs * 64 * sizeof(int16_t), st));
+    return VPZ_OK;
+}
+
+// after the launches: their status; VPZ_MEM_HOST: the staging copies out and a synchronise
+int stage_out(vpz::Context *ctx, vpz::CallScratch &K, int64_t n_packets, int channels, size_t esize, int32_t mem_space, void *residue,
+              int64_t residue_values, int16_t *posts, uint8_t *post_counts)
+{
+    hipStream_t st = ctx->stream;
+    VPZ_HIP_TRY(ctx, hipGetLastError());
+    if (mem_space != VPZ_MEM_HOST) return VPZ_OK;
+    const size_t recs = (size_t)n_packets * channels;
+    if (residue && residue_values)
+        VPZ_HIP_TRY(ctx, hipMemcpyAsync(residue, K.d_residue, esize * (size_t)residue_values, hipMemcpyDeviceToHost, st));
+    VPZ_HIP_TRY(ctx, hipMemcpyAsync(posts, K.d_posts, recs * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+    VPZ_HIP_TRY(ctx, hipMemcpyAsync(post_counts, K.d_counts, recs, hipMemcpyDeviceToHost, st));
+    VPZ_HIP_TRY(ctx, hipStreamSynchronize(st));
+    return VPZ_OK;
+}
+
+// One lane per packet, and a launch's time is the latency of its slowest lane's chain: a small launch gains from spreading its
+// waves over the CUs (a wave per workgroup: 39 000 packets are 600 workgroups on 256 CUs instead of 150 that hold four waves
+// each).  Launches of 2 900 to 39 000 packets: 2.62 / 2.73 / 2.99 ms at 64 lanes against 3.08 / 3.11 / 3.25 ms at 256
+// (tools/kbench_entropy.py, 16 / 64 / 128 streams); nothing larger was measured, so larger launches keep kBlock.
+unsigned launch_block(int64_t lanes) { return lanes < vpz::kSmallLaunch ? 64u : (unsigned)vpz::kBlock; }
+
+template <class T>
+void launch_setup(vpz_entropy_setup *S, int64_t n_packets, bool any_decoded, const Buffers &B, hipStream_t st)
+{
+    const vpz_entropy_image_header &h = S->img.h;
+    const unsigned zero_grid = (unsigned)std::min<int64_t>(n_packets, 8192);
+    const unsigned block = launch_block(n_packets);
+    const unsigned grid = (unsigned)((n_packets + block - 1) / block);
+    if (any_decoded)
+        hipLaunchKernelGGL(vpz::entropy_zero_kernel<T>, dim3(zero_grid), dim3(vpz::kBlock), 0, st, S->call.d_desc, n_packets, h.channels,
+                           h.block_size0 / 2, h.block_size1 / 2, static_cast<T *>(B.residue));
+    hipLaunchKernelGGL(vpz::entropy_decode_kernel<T>, dim3(grid), dim3(block), 0, st, S->img.d_image, S->call.d_desc, n_packets,
+                       reinterpret_cast<const uint32_t *>(B.payload), static_cast<T *>(B.residue), B.posts, B.counts,
+                       static_cast<int32_t *>(S->call.d_cache), S->img.cache_words, static_cast<T *>(S->call.d_dbuf));
+}
+
+// the same two passes over a group's lane list
+template <class T>
+void launch_group(vpz_entropy_group *G, int64_t n_lanes, bool any_decoded, const Buffers &B, hipStream_t st)
+{
+    const unsigned zero_grid = (unsigned)std::min<int64_t>(n_lanes, 8192);
+    const unsigned block = launch_block(n_lanes);
+    const unsigned grid = (unsigned)((n_lanes + block - 1) / block);
+    if (any_decoded)
+        hipLaunchKernelGGL(vpz::entropy_zero_kernel<T>, dim3(zero_grid), dim3(vpz::kBlock), 0, st, G->call.d_desc, n_lanes, G->channels,
+                           G->block_size0 / 2, G->block_size1 / 2, static_cast<T *>(B.residue));
+    hipLaunchKernelGGL(vpz::entropy_group_kernel<T>, dim3(grid), dim3(block), 0, st, static_cast<const vpz::ImageAddress *>(G->d_table), G->call.d_desc, G->call.d_index,
+                       n_lanes,
+                       reinterpret_cast<const uint32_t *>(B.payload), static_cast<T *>(B.residue), B.posts, B.counts,
+                       static_cast<int32_t *>(G->call.d_cache), G->cache_words, static_cast<T *>(G->call.d_dbuf));
+}
+
 }  // namespace
 
 extern "C" {
@@ -534,16 +458,21 @@ int vpz_entropy_setup_create(vpz_context *c, const void *image, uint64_t size, v
     vpz_entropy_setup *S = new (std::nothrow) vpz_entropy_setup();
     if (!S) return VPZ_E_NOMEM;
     S->ctx = ctx;
-    S->image.assign(static_cast<const uint8_t *>(image), static_cast<const uint8_t *>(image) + size);
-    std::string why;
-    if (!validate(*S, why)) {
+    try {  // (the host copy, validate's tables, the error text: no exception leaves the C ABI)
+        S->img.image.assign(static_cast<const uint8_t *>(image), static_cast<const uint8_t *>(image) + size);
+        std::string why;
+        if (!validate(S->img, why)) {
+            delete S;
+            return set_error(ctx, VPZ_E_INVALID_ARG, ("vpz_entropy_setup_create: " + why).c_str());
+        }
+    } catch (const std::bad_alloc &) {
         delete S;
-        return set_error(ctx, VPZ_E_INVALID_ARG, ("vpz_entropy_setup_create: " + why).c_str());
+        return VPZ_E_NOMEM;
     }
     hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&S->d_image), S->image.size());
-    if (e == hipSuccess) e = hipMemcpy(S->d_image, S->image.data(), S->image.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&S->desc_done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&S->img.d_image), S->img.image.size());
+    if (e == hipSuccess) e = hipMemcpy(S->img.d_image, S->img.image.data(), S->img.image.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&S->call.desc_done, hipEventDisableTiming);
     if (e != hipSuccess) {
         vpz_entropy_setup_destroy(S);
         return set_error(ctx, VPZ_E_HIP, "vpz_entropy_setup_create", e);
@@ -556,139 +485,186 @@ void vpz_entropy_setup_destroy(vpz_entropy_setup *S)
 {
     if (!S) return;
     if (S->ctx) (void)hipStreamSynchronize(S->ctx->stream);
-    for (void *p : {(void *)S->d_image, (void *)S->d_desc, S->d_cache, S->d_dbuf, S->d_payload, S->d_residue, S->d_posts, S->d_counts})
-        if (p) (void)hipFree(p);
-    if (S->h_desc) (void)hipHostFree(S->h_desc);
-    if (S->desc_done) (void)hipEventDestroy(S->desc_done);
+    if (S->img.d_image) (void)hipFree(S->img.d_image);
+    release(S->call);
     delete S;
 }
 
 int vpz_entropy_decode(vpz_entropy_setup *S, int64_t n_packets, const vpz_packet *packets, const vpz_entropy_span *spans,
                        const uint8_t *payload, int64_t payload_bytes, int32_t residue_format, void *residue,
                        int64_t residue_values, int16_t *posts, uint8_t *post_counts, int64_t n_records, int32_t mem_space)
-{
+try {
     if (!S) return VPZ_E_INVALID_ARG;
     vpz::Context *ctx = S->ctx;
-    const vpz_entropy_image_header &h = S->h;
+    const vpz_entropy_image_header &h = S->img.h;
     const int C = h.channels;
-    if (n_packets < 0 || payload_bytes < 0 || residue_values < 0 || n_records < 0)
-        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: negative count or extent");
-    if (mem_space != VPZ_MEM_HOST && mem_space != VPZ_MEM_DEVICE) return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: bad mem_space");
-    if (residue_format != VPZ_RESIDUE_F32 && residue_format != VPZ_RESIDUE_I16)
-        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: bad residue format");
-    if (residue_format == VPZ_RESIDUE_I16 && !S->i16_ok)
-        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: int16 residue for a setup whose residue is not integral");
-    if (n_packets == 0) return VPZ_OK;
-    if (!packets || !spans || !payload || !posts || !post_counts)
-        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: null argument");
-    if (n_packets > (int64_t)1 << 40 || n_records < n_packets * C)
-        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: fewer post records than packets * channels");
+    int rc = check_call(ctx, "vpz_entropy_decode", n_packets, packets, spans, payload, payload_bytes, residue_format, S->img.i16_ok, residue,
+                        residue_values, posts, post_counts, n_records, C, mem_space);
+    if (rc != VPZ_OK || n_packets == 0) return rc;
     const size_t esize = residue_format == VPZ_RESIDUE_I16 ? 2 : 4;
-    if (mem_space == VPZ_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(payload) & 3) || (reinterpret_cast<uintptr_t>(residue) & (esize - 1)) ||
-                                        (reinterpret_cast<uintptr_t>(posts) & 1)))
-        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: misaligned device buffer");
     // every bound first: an invalid batch writes nothing
     bool any_decoded = false;
     for (int64_t k = 0; k < n_packets; ++k) {
-        const vpz_entropy_span &sp = spans[k];
-        if (sp.offset < 0 || sp.size < 0 || sp.size >= ((int64_t)1 << 28) || sp.offset > payload_bytes - sp.size - 8)
-            return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: a packet's span lies outside the payload");
         const vpz_packet &p = packets[k];
+        if (const char *why = check_packet(p, spans[k], payload_bytes, C, h.block_size0, h.block_size1, residue_values))
+            return set_error(ctx, VPZ_E_INVALID_ARG, (std::string("vpz_entropy_decode: ") + why).c_str());
         if (p.flags & VPZ_PKT_NOT_DECODED) continue;
         any_decoded = true;
         if (p.mapping >= h.mapping_count) return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: packet mapping index out of range");
-        const int64_t len = (int64_t)C * ((p.flags & VPZ_PKT_BLOCK_FLAG) ? h.block_size1 : h.block_size0) / 2;
-        if (p.residue_offset < 0 || p.residue_offset > residue_values - len)
-            return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: a packet's residue lies beyond residue_values");
     }
     if (any_decoded && !residue) return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_decode: null residue");
 
     VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    vpz::CallScratch &K = S->call;
+    if ((rc = desc_room(ctx, K, n_packets, false)) != VPZ_OK) return rc;
+    for (int64_t k = 0; k < n_packets; ++k) K.h_desc[k] = describe(packets[k], spans[k], packets[k].mapping, 0);
+    if ((rc = upload_descs(ctx, K, n_packets, false)) != VPZ_OK) return rc;
+    Buffers B;
+    if ((rc = stage_in(ctx, K, n_packets, C, S->img.cache_words, S->img.multi_submap, esize, mem_space, payload, payload_bytes, residue,
+                       residue_values, posts, post_counts, B)) != VPZ_OK)
+        return rc;
+    if (residue_format == VPZ_RESIDUE_I16) launch_setup<int16_t>(S, n_packets, any_decoded, B, ctx->stream);
+    else launch_setup<float>(S, n_packets, any_decoded, B, ctx->stream);
+    return stage_out(ctx, K, n_packets, C, esize, mem_space, residue, residue_values, posts, post_counts);
+} catch (const std::bad_alloc &) {  // (the descriptors, an error text: no exception leaves the C ABI)
+    return VPZ_E_NOMEM;
+}
+
+}  // extern "C"
+
+namespace {
+
+// vpz_entropy_group_create once its arguments are there: the images validated and uploaded into *G (may throw std::bad_alloc;
+// whatever it returns or throws, the caller destroys a group that is not VPZ_OK)
+int fill_group(vpz::Context *ctx, vpz_entropy_group *G, const void *const *images, const uint64_t *sizes, int32_t n_setups)
+{
+    G->images.resize(n_setups);
+    auto refuse = [&](const std::string &why) { return set_error(ctx, VPZ_E_INVALID_ARG, ("vpz_entropy_group_create: " + why).c_str()); };
+    for (int s = 0; s < n_setups; ++s) {
+        vpz::EntropyImage &I = G->images[s];
+        if (!images[s] || sizes[s] > (1ull << 31)) return refuse("image " + std::to_string(s) + ": null or too large");
+        I.image.assign(static_cast<const uint8_t *>(images[s]), static_cast<const uint8_t *>(images[s]) + sizes[s]);
+        std::string why;
+        if (!validate(I, why)) return refuse("image " + std::to_string(s) + ": " + why);
+        const vpz_entropy_image_header &h0 = G->images[0].h;
+        if (I.h.channels != h0.channels || I.h.block_size0 != h0.block_size0 || I.h.block_size1 != h0.block_size1)
+            return refuse("image " + std::to_string(s) + ": channels or block sizes differ from image 0");
+        G->i16_ok = G->i16_ok && I.i16_ok;
+        G->multi_submap = G->multi_submap || I.multi_submap;
+        G->cache_words = std::max(G->cache_words, I.cache_words);
+    }
+    G->channels = G->images[0].h.channels;
+    G->block_size0 = G->images[0].h.block_size0;
+    G->block_size1 = G->images[0].h.block_size1;
+    auto upload = [&]() -> int {
+        VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::vector<const uint8_t *> table(n_setups);
+        for (int s = 0; s < n_setups; ++s) {
+            const int rc = upload_image(ctx, G->images[s]);
+            if (rc != VPZ_OK) return rc;
+            table[s] = G->images[s].d_image;
+        }
+        VPZ_HIP_TRY(ctx, hipMalloc(&G->d_table, sizeof(uint8_t *) * (size_t)n_setups));
+        VPZ_HIP_TRY(ctx, hipMemcpy(G->d_table, table.data(), sizeof(uint8_t *) * (size_t)n_setups, hipMemcpyHostToDevice));
+        VPZ_HIP_TRY(ctx, hipEventCreateWithFlags(&G->call.desc_done, hipEventDisableTiming));
+        return VPZ_OK;
+    };
+    return upload();
+}
+
+}  // namespace
+
+extern "C" {
+
+int vpz_entropy_group_create(vpz_context *c, const void *const *images, const uint64_t *sizes, int32_t n_setups, vpz_entropy_group **out)
+{
+    if (!c || !out) return VPZ_E_INVALID_ARG;
+    *out = nullptr;
+    vpz::Context *ctx = &c->impl;
+    if (!images || !sizes) return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_group_create: null argument");
+    if (n_setups < 1 || n_setups > VPZ_ENTROPY_GROUP_MAX_SETUPS)
+        return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_entropy_group_create: n_setups outside 1 .. 256");
+    vpz_entropy_group *G = new (std::nothrow) vpz_entropy_group();
+    if (!G) return VPZ_E_NOMEM;
+    G->ctx = ctx;
     int rc;
-    // the packet descriptors, through a page-locked buffer (the previous call's copy has left it)
-    if (S->desc_pending) {
-        VPZ_HIP_TRY(ctx, hipEventSynchronize(S->desc_done));
-        S->desc_pending = false;
+    try {
+        rc = fill_group(ctx, G, images, sizes, n_setups);
+    } catch (const std::bad_alloc &) {  // (no exception leaves the C ABI)
+        rc = VPZ_E_NOMEM;
     }
-    if (S->desc_cap < (size_t)n_packets) {
-        if (S->h_desc) VPZ_HIP_TRY(ctx, hipHostFree(S->h_desc));
-        if (S->d_desc) VPZ_HIP_TRY(ctx, hipFree(S->d_desc));
-        S->h_desc = nullptr;
-        S->d_desc = nullptr;
-        S->desc_cap = 0;
-        const size_t cap = (size_t)n_packets + (size_t)n_packets / 4;
-        VPZ_HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void **>(&S->h_desc), cap * sizeof(vpz::PacketDesc)));
-        VPZ_HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&S->d_desc), cap * sizeof(vpz::PacketDesc)));
-        S->desc_cap = cap;
+    if (rc != VPZ_OK) {
+        vpz_entropy_group_destroy(G);  // (nothing stays allocated)
+        return rc;
     }
+    *out = G;
+    return VPZ_OK;
+}
+
+void vpz_entropy_group_destroy(vpz_entropy_group *G)
+{
+    if (!G) return;
+    if (G->ctx) (void)hipStreamSynchronize(G->ctx->stream);
+    for (vpz::EntropyImage &I : G->images)
+        if (I.d_image) (void)hipFree(I.d_image);
+    if (G->d_table) (void)hipFree(G->d_table);
+    release(G->call);
+    delete G;
+}
+
+int vpz_entropy_group_decode(vpz_entropy_group *G, int32_t n_streams, const uint8_t *stream_setup, const uint8_t *stream_mapping_base,
+                             int64_t n_packets, const vpz_packet *packets, const vpz_entropy_span *spans, const uint8_t *payload,
+                             int64_t payload_bytes, int32_t residue_format, void *residue, int64_t residue_values, int16_t *posts,
+                             uint8_t *post_counts, int64_t n_records, int32_t mem_space)
+try {
+    if (!G) return VPZ_E_INVALID_ARG;
+    vpz::Context *ctx = G->ctx;
+    const int C = G->channels, n_setups = (int)G->images.size();
+    auto fail = [&](const char *why) { return set_error(ctx, VPZ_E_INVALID_ARG, (std::string("vpz_entropy_group_decode: ") + why).c_str()); };
+    if (n_streams < 0) return fail("negative stream count");
+    int rc = check_call(ctx, "vpz_entropy_group_decode", n_packets, packets, spans, payload, payload_bytes, residue_format, G->i16_ok, residue,
+                        residue_values, posts, post_counts, n_records, C, mem_space);
+    if (rc != VPZ_OK) return rc;
+    if (n_streams > 0 && (!stream_setup || !stream_mapping_base)) return fail("null argument");
+    for (int32_t s = 0; s < n_streams; ++s)
+        if (stream_setup[s] >= n_setups) return fail("a stream's setup index out of range");
+    if (n_packets == 0) return VPZ_OK;
+    const size_t esize = residue_format == VPZ_RESIDUE_I16 ? 2 : 4;
+    // every bound first: an invalid batch writes nothing.  The descriptors are written on the way, in packet order
+    bool any_decoded = false;
+    G->desc.resize((size_t)n_packets);
+    int64_t per_setup[VPZ_ENTROPY_GROUP_MAX_SETUPS] = {0}, start[VPZ_ENTROPY_GROUP_MAX_SETUPS];
     for (int64_t k = 0; k < n_packets; ++k) {
         const vpz_packet &p = packets[k];
-        vpz::PacketDesc &d = S->h_desc[k];
-        d.payload_bit = spans[k].offset * 8;
-        d.residue_offset = p.residue_offset;
-        d.size = (uint32_t)spans[k].size;
-        d.info = (uint32_t)p.flags | ((uint32_t)p.mapping << 8);
+        if (p.stream < 0 || p.stream >= n_streams) return fail("a packet's stream index out of range");
+        if (const char *why = check_packet(p, spans[k], payload_bytes, C, G->block_size0, G->block_size1, residue_values)) return fail(why);
+        const int setup = stream_setup[p.stream];
+        int mapping = 0;  // (a packet that is not decoded reads no mapping)
+        if (!(p.flags & VPZ_PKT_NOT_DECODED)) {
+            any_decoded = true;
+            mapping = (int)p.mapping - (int)stream_mapping_base[p.stream];
+            if (mapping < 0 || mapping >= G->images[setup].h.mapping_count) return fail("packet mapping index outside its setup's mappings");
+        }
+        G->desc[k] = describe(p, spans[k], (uint32_t)mapping, (uint32_t)setup);
+        ++per_setup[setup];
     }
-    VPZ_HIP_TRY(ctx, hipMemcpyAsync(S->d_desc, S->h_desc, sizeof(vpz::PacketDesc) * (size_t)n_packets, hipMemcpyHostToDevice, st));
-    VPZ_HIP_TRY(ctx, hipEventRecord(S->desc_done, st));
-    S->desc_pending = true;
-    if ((rc = grow(ctx, &S->d_cache, &S->cache_bytes, sizeof(int32_t) * (size_t)n_packets * S->cache_words)) != VPZ_OK) return rc;
-    if (S->multi_submap && (rc = grow(ctx, &S->d_dbuf, &S->dbuf_bytes, 2 * esize * (size_t)residue_values)) != VPZ_OK) return rc;
+    if (any_decoded && !residue) return fail("null residue");
+    const int64_t n_lanes = vpz::lane_list_starts(n_setups, per_setup, start);
 
-    const uint8_t *d_payload = payload;
-    void *d_residue = residue;
-    int16_t *d_posts = posts;
-    uint8_t *d_counts = post_counts;
-    const size_t recs = (size_t)n_packets * C;
-    if (mem_space == VPZ_MEM_HOST) {
-        if ((rc = grow(ctx, &S->d_payload, &S->payload_bytes, (size_t)payload_bytes + 8)) != VPZ_OK) return rc;
-        if ((rc = grow(ctx, &S->d_residue, &S->residue_bytes, esize * (size_t)residue_values)) != VPZ_OK) return rc;
-        if ((rc = grow(ctx, &S->d_posts, &S->posts_bytes, recs * 64 * sizeof(int16_t))) != VPZ_OK) return rc;
-        if ((rc = grow(ctx, &S->d_counts, &S->counts_bytes, recs)) != VPZ_OK) return rc;
-        VPZ_HIP_TRY(ctx, hipMemcpyAsync(S->d_payload, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, st));
-        // (the whole extent goes both ways: what no packet writes comes back as it was)
-        if (residue && residue_values)
-            VPZ_HIP_TRY(ctx, hipMemcpyAsync(S->d_residue, residue, esize * (size_t)residue_values, hipMemcpyHostToDevice, st));
-        d_payload = static_cast<const uint8_t *>(S->d_payload);
-        d_residue = S->d_residue;
-        d_posts = static_cast<int16_t *>(S->d_posts);
-        d_counts = static_cast<uint8_t *>(S->d_counts);
-    }
-    VPZ_HIP_TRY(ctx, hipMemsetAsync(d_posts, 0, recs * 64 * sizeof(int16_t), st));
-    const unsigned zero_grid = (unsigned)std::min<int64_t>(n_packets, 8192);
-    // One lane per packet, and a launch's time is the latency of its slowest lane's chain: a small launch gains from spreading its
-    // waves over the CUs (a wave per workgroup: 39 000 packets are 600 workgroups on 256 CUs instead of 150 that hold four waves
-    // each).  Launches of 2 900 to 39 000 packets: 2.62 / 2.73 / 2.99 ms at 64 lanes against 3.08 / 3.11 / 3.25 ms at 256
-    // (tools/kbench_entropy.py, 16 / 64 / 128 streams); nothing larger was measured, so larger launches keep kBlock.
-    const unsigned block = n_packets < vpz::kSmallLaunch ? 64u : (unsigned)vpz::kBlock;
-    const unsigned grid = (unsigned)((n_packets + block - 1) / block);
-    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_payload);
-    int32_t *cache = static_cast<int32_t *>(S->d_cache);
-    if (residue_format == VPZ_RESIDUE_I16) {
-        if (any_decoded)
-            hipLaunchKernelGGL(vpz::entropy_zero_kernel<int16_t>, dim3(zero_grid), dim3(vpz::kBlock), 0, st, S->d_desc, n_packets, C,
-                               h.block_size0 / 2, h.block_size1 / 2, static_cast<int16_t *>(d_residue));
-        hipLaunchKernelGGL(vpz::entropy_decode_kernel<int16_t>, dim3(grid), dim3(block), 0, st, S->d_image, S->d_desc, n_packets,
-                           words, static_cast<int16_t *>(d_residue), d_posts, d_counts, cache, S->cache_words,
-                           static_cast<int16_t *>(S->d_dbuf));
-    } else {
-        if (any_decoded)
-            hipLaunchKernelGGL(vpz::entropy_zero_kernel<float>, dim3(zero_grid), dim3(vpz::kBlock), 0, st, S->d_desc, n_packets, C,
-                               h.block_size0 / 2, h.block_size1 / 2, static_cast<float *>(d_residue));
-        hipLaunchKernelGGL(vpz::entropy_decode_kernel<float>, dim3(grid), dim3(block), 0, st, S->d_image, S->d_desc, n_packets,
-                           words, static_cast<float *>(d_residue), d_posts, d_counts, cache, S->cache_words,
-                           static_cast<float *>(S->d_dbuf));
-    }
-    VPZ_HIP_TRY(ctx, hipGetLastError());
-    if (mem_space == VPZ_MEM_HOST) {
-        if (residue && residue_values)
-            VPZ_HIP_TRY(ctx, hipMemcpyAsync(residue, S->d_residue, esize * (size_t)residue_values, hipMemcpyDeviceToHost, st));
-        VPZ_HIP_TRY(ctx, hipMemcpyAsync(posts, S->d_posts, recs * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-        VPZ_HIP_TRY(ctx, hipMemcpyAsync(post_counts, S->d_counts, recs, hipMemcpyDeviceToHost, st));
-        VPZ_HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return VPZ_OK;
+    VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    vpz::CallScratch &K = G->call;
+    if ((rc = desc_room(ctx, K, n_lanes, true)) != VPZ_OK) return rc;
+    vpz::lane_list_fill(n_setups, start, n_packets, G->desc.data(), n_lanes, K.h_desc, K.h_index);
+    if ((rc = upload_descs(ctx, K, n_lanes, true)) != VPZ_OK) return rc;
+    Buffers B;
+    if ((rc = stage_in(ctx, K, n_packets, C, G->cache_words, G->multi_submap, esize, mem_space, payload, payload_bytes, residue,
+                       residue_values, posts, post_counts, B)) != VPZ_OK)
+        return rc;
+    if (residue_format == VPZ_RESIDUE_I16) launch_group<int16_t>(G, n_lanes, any_decoded, B, ctx->stream);
+    else launch_group<float>(G, n_lanes, any_decoded, B, ctx->stream);
+    return stage_out(ctx, K, n_packets, C, esize, mem_space, residue, residue_values, posts, post_counts);
+} catch (const std::bad_alloc &) {  // (the descriptors, an error text: no exception leaves the C ABI)
+    return VPZ_E_NOMEM;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""ctypes binding of include/vorbispizza_entropy.h -- the entropy decode of Vorbis audio packets on the GPU -- and
-decode_to_pcm, the whole path of one file on the device: plan (CPU, vpzh_plan_range) -> vpz_entropy_decode ->
+"""ctypes binding of include/vorbispizza_entropy.h -- the entropy decode of Vorbis audio packets on the GPU --, of
+include/vorbispizza_entropy_group.h -- the same for streams of different setups in one call -- and decode_to_pcm, the whole path of one file on the device: plan (CPU, vpzh_plan_range) -> vpz_entropy_decode ->
 vpz_decoder_synth, no residue crossing the host link."""
 import ctypes as C
 
@@ -19,6 +19,14 @@ _SIGNATURES = [
                                      C.c_int32]),
 ]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
+_GROUP_SIGNATURES = [
+    ("vpz_entropy_group_create", C.c_int, [_vp, _vp, _vp, C.c_int32, C.POINTER(_vp)]),
+    ("vpz_entropy_group_destroy", None, [_vp]),
+    ("vpz_entropy_group_decode", C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp, C.c_int64, _vp,
+                                           _vp, C.c_int64, C.c_int32]),
+]
+GROUP_EXPORTED_SYMBOLS = [s[0] for s in _GROUP_SIGNATURES]
+GROUP_MAX_SETUPS = 256
 _lib = None
 
 
@@ -26,7 +34,9 @@ def lib():
     global _lib
     if _lib is None:
         L = capi.lib()
-        for name, restype, argtypes in _SIGNATURES:
+        for name, restype, argtypes in _SIGNATURES + _GROUP_SIGNATURES:
+            if name in GROUP_EXPORTED_SYMBOLS and not hasattr(L, name):
+                continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has no group: using one raises)
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes
@@ -80,6 +90,65 @@ class EntropySetup:
     def decode(self, packets, spans, payload, residue, posts, post_counts, mem_space=capi.MEM_HOST, residue_format=None):
         """decode_raw that raises SynthError on a failed status."""
         rc = self.decode_raw(packets, spans, payload, residue, posts, post_counts, mem_space, residue_format)
+        if rc != capi.OK:
+            raise capi.SynthError(rc, self.ctx.last_error())
+
+
+class EntropyGroup:
+    """vpz_entropy_group: validated setup images of one class (channels, block sizes) on the context's device, for
+    batches whose streams each name their setup."""
+
+    def __init__(self, ctx, images):
+        self.ctx = ctx
+        self._images = [np.frombuffer(bytes(im), dtype=np.uint8) for im in images]
+        n = len(self._images)
+        ptrs = (C.c_void_p * max(1, n))(*[im.ctypes.data for im in self._images])
+        sizes = (C.c_uint64 * max(1, n))(*[im.size for im in self._images])
+        self._h = _vp()
+        rc = lib().vpz_entropy_group_create(ctx._h, ptrs, sizes, n, C.byref(self._h))
+        if rc != capi.OK:
+            self._h = None
+            raise capi.SynthError(rc, ctx.last_error())
+        self.n_setups = n
+        self.channels, self.block_size0, self.block_size1 = (int(v) for v in self._images[0][12:24].view(np.int32))
+        import weakref
+        ctx._children.append(weakref.ref(self))
+
+    def close(self):
+        if self._h and self.ctx._h:
+            lib().vpz_entropy_group_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def decode_raw(self, stream_setup, stream_mapping_base, packets, spans, payload, residue, posts, post_counts, mem_space,
+                   residue_format=None, payload_bytes=None, residue_values=None, n_records=None):
+        """Thin call of vpz_entropy_group_decode: EntropySetup.decode_raw's arguments after stream_setup / stream_mapping_base
+        (one uint8 entry per stream; packets[k]["stream"] indexes them).  Returns the status without raising."""
+        stream_setup = np.ascontiguousarray(stream_setup, dtype=np.uint8)
+        stream_mapping_base = np.ascontiguousarray(stream_mapping_base, dtype=np.uint8)
+        assert stream_setup.size == stream_mapping_base.size
+        packets = np.ascontiguousarray(packets, dtype=capi.PACKET_DTYPE)
+        spans = np.ascontiguousarray(spans, dtype=np.int64).reshape(-1, 2)
+        if residue_format is None:
+            residue_format = capi.RESIDUE_I16 if str(getattr(residue, "dtype", "")) in ("int16", "torch.int16") else capi.RESIDUE_F32
+        if mem_space == capi.MEM_DEVICE:
+            capi._sync_producer(payload, residue, posts, post_counts)
+        return lib().vpz_entropy_group_decode(
+            self._h, stream_setup.size, capi._ptr(stream_setup), capi._ptr(stream_mapping_base), len(packets), capi._ptr(packets),
+            capi._ptr(spans), capi._ptr(payload), capi._numel(payload) if payload_bytes is None else payload_bytes,
+            int(residue_format), capi._ptr(residue), capi._numel(residue) if residue_values is None else residue_values,
+            capi._ptr(posts), capi._ptr(post_counts), capi._numel(post_counts) if n_records is None else n_records, int(mem_space))
+
+    def decode(self, stream_setup, stream_mapping_base, packets, spans, payload, residue, posts, post_counts,
+               mem_space=capi.MEM_HOST, residue_format=None):
+        """decode_raw that raises SynthError on a failed status."""
+        rc = self.decode_raw(stream_setup, stream_mapping_base, packets, spans, payload, residue, posts, post_counts, mem_space,
+                             residue_format)
         if rc != capi.OK:
             raise capi.SynthError(rc, self.ctx.last_error())
 

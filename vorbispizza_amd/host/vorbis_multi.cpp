@@ -17,9 +17,15 @@
 // and its issuing thread uploads the bytes, entropy-decodes them on the lane's stream (vpz_entropy_decode) into arrays that
 // never leave the device, synthesises from those and downloads every member's PCM.
 //
+// With vpzm_set_mixed_setups (include/vorbispizza_multi_mixed.h) on top of that, the streams of device-decodable setups that agree in
+// channels, block sizes and residue type are cut into sub-batches together: such a sub-batch's setup is a MERGED one (Setup::parts),
+// its records carry mapping indices of the merged setup, vpz_entropy_group_decode decodes it and a decoder of the merged setup
+// synthesises it.
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstddef>
@@ -35,6 +41,8 @@
 #include <vector>
 
 #include "../../include/vorbispizza_multi.h"
+#include "../../include/vorbispizza_multi_mixed.h"
+#include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
 
@@ -51,6 +59,13 @@ struct Setup {
     int f0_stride = 0;
     bool integral = false;  // every residue value is an integer of 16 bits: the residue travels as int16 (half the link bytes)
     std::vector<uint8_t> image;  // gpu_entropy, a setup the device can decode: its entropy setup image (else empty)
+    // mixed_setups, a MERGED setup: the union of the Floor1 configurations of `parts` (equal ones shared) and their mappings back to
+    // back with channel_floor remapped -- the C++ counterpart of sharding.merge_setups; part q's mapping i is mapping_base[q] + i.
+    // It has no image of its own: the parts' images, in order, are its entropy group's
+    std::vector<std::shared_ptr<Setup>> parts;
+    std::vector<int> mapping_base;
+    static constexpr size_t kMergedMost = 256;   // mappings (a record's index is a byte) and parts (a group's images) of a merged setup
+    static constexpr size_t kMergedFloors = 64;  // ... and its floors: what vpz_decoder_create accepts
 
     bool load(vpzh_stream *h, bool gpu_entropy)
     {
@@ -75,7 +90,71 @@ struct Setup {
         }
         return true;
     }
-    bool on_device() const { return !image.empty(); }
+    bool on_device() const { return !image.empty() || !parts.empty(); }
+    // the merge class: two setups may share a merged setup (a decoder, an entropy group)
+    bool same_class(const Setup &o) const
+    {
+        return info.channels == o.info.channels && info.block_size0 == o.info.block_size0 && info.block_size1 == o.info.block_size1 &&
+               integral == o.integral && on_device() && o.on_device();
+    }
+    int part_of(const Setup &o) const
+    {
+        for (size_t q = 0; q < parts.size(); ++q)
+            if (parts[q]->same(o)) return (int)q;
+        return -1;
+    }
+    static bool same_floor1(const vpz_floor1_config &a, const vpz_floor1_config &b)
+    {
+        return a.x_count == b.x_count && a.multiplier == b.multiplier &&
+               memcmp(a.x_list, b.x_list, sizeof(int32_t) * (size_t)std::max(0, a.x_count)) == 0;
+    }
+    // where floor f lies in the union: in `floors`, or behind them in `fresh` (those of the coming part that the union does not have yet;
+    // floors.size() + fresh.size(): in neither)
+    size_t floor_in_union(const vpz_floor1_config &f, const std::vector<vpz_floor1_config> &fresh) const
+    {
+        size_t at = 0;
+        while (at < floors.size() && !same_floor1(floors[at], f)) ++at;
+        if (at < floors.size()) return at;
+        for (at = 0; at < fresh.size() && !same_floor1(fresh[at], f); ++at) {}
+        return floors.size() + at;
+    }
+    // a merged setup can take one more part: with it, it holds at most `most_mappings` mappings (kMergedMost at the most), kMergedFloors
+    // floors and kMergedMost parts -- an empty one takes any part (a single setup is what a decoder was created from before)
+    bool fits(const Setup &o, size_t most_mappings) const
+    {
+        if (parts.empty()) return true;
+        std::vector<vpz_floor1_config> fresh;
+        for (const vpz_floor1_config &f : o.floors)
+            if (floor_in_union(f, fresh) == floors.size() + fresh.size()) fresh.push_back(f);
+        return mappings.size() + o.mappings.size() <= std::min(most_mappings, kMergedMost) && floors.size() + fresh.size() <= kMergedFloors &&
+               parts.size() < kMergedMost;
+    }
+    // ... and takes it (the caller has asked `fits`)
+    void add_part(const std::shared_ptr<Setup> &o)
+    {
+        std::vector<vpz_floor1_config> fresh;
+        std::vector<uint8_t> remap(o->floors.size(), 0);
+        for (size_t i = 0; i < o->floors.size(); ++i) {
+            const size_t at = floor_in_union(o->floors[i], fresh);
+            if (at == floors.size() + fresh.size()) fresh.push_back(o->floors[i]);
+            remap[i] = (uint8_t)at;
+        }
+        if (parts.empty()) {
+            info = o->info;
+            integral = o->integral;
+        }
+        mapping_base.push_back((int)mappings.size());
+        for (vpz_mapping_config mc : o->mappings) {
+            for (int c = 0; c < info.channels; ++c) mc.channel_floor[c] = remap[mc.channel_floor[c]];
+            mappings.push_back(mc);
+        }
+        floors.insert(floors.end(), fresh.begin(), fresh.end());
+        floors0.assign(floors.size(), vpz_floor0_config{});
+        floor_types.assign(floors.size(), 1);  // (the device decodes no type-0 floor: a merge class has none)
+        info.floor_count = (int32_t)floors.size();
+        info.mapping_count = (int32_t)mappings.size();
+        parts.push_back(o);
+    }
     // the same decoder serves two streams iff everything it was created from is the same
     bool same(const Setup &o) const
     {
@@ -83,15 +162,14 @@ struct Setup {
             floors.size() != o.floors.size() || mappings.size() != o.mappings.size() || floor_types != o.floor_types || integral != o.integral)
             return false;
         // (the synthesis does not know the codebooks, the device's entropy decode does: equal setup headers give equal images)
-        if (image != o.image) return false;
+        if (image != o.image || parts.size() != o.parts.size()) return false;
+        for (size_t q = 0; q < parts.size(); ++q)
+            if (parts[q]->image != o.parts[q]->image) return false;
         for (size_t i = 0; i < floors.size(); ++i) {
             if (floor_types[i] == 0) {
                 if (memcmp(&floors0[i], &o.floors0[i], sizeof floors0[i]) != 0) return false;
-            } else {
-                const vpz_floor1_config &a = floors[i], &b = o.floors[i];
-                if (a.x_count != b.x_count || a.multiplier != b.multiplier ||
-                    memcmp(a.x_list, b.x_list, sizeof(int32_t) * (size_t)std::max(0, a.x_count)) != 0)
-                    return false;
+            } else if (!same_floor1(floors[i], o.floors[i])) {
+                return false;
             }
         }
         for (size_t i = 0; i < mappings.size(); ++i)
@@ -158,6 +236,7 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     // gpu_entropy: the entropy setups next to the decoders (a setup belongs to a context and serves one call at a time), and
     // what a device-decoded sub-batch keeps on the device: packet bytes in, residue / posts / counts between the two calls, PCM out
     SetupCache<vpz_entropy_setup> esetups{vpz_entropy_setup_destroy, {}};
+    SetupCache<vpz_entropy_group> egroups{vpz_entropy_group_destroy, {}};  // mixed_setups: the groups of the merged setups, kept alike
     enum { kPayload, kResidue, kPosts, kCounts, kPcm, kBuffers };
     Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
@@ -199,6 +278,7 @@ constexpr int64_t kCallValues = (int64_t)64 << 20;  // residue values of one syn
 struct Switches {
     static int64_t number(const char *name) { return getenv(name) ? atoll(getenv(name)) : 0; }
     int64_t max_call_values = number("VPZM_MAX_CALL_VALUES") > 0 ? number("VPZM_MAX_CALL_VALUES") : kCallValues;  // (tests: small calls)
+    int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
@@ -212,6 +292,8 @@ struct vpzm_dispatcher {
     vpzm_options opt{};
     int device_streams_per_call = 0;  // gpu_entropy: streams of a device-decoded call (opt.streams_per_call: of a host-decoded one)
     int call_streams() const { return std::max(opt.streams_per_call, device_streams_per_call); }  // what a decoder is created for
+    bool mixed_setups = false;        // vpzm_set_mixed_setups: device-decoded sub-batches may hold streams of several setups
+    vpzm_call_counts counts{};        // of the last vpzm_decode_library call
     std::string error;
     std::mutex err_mu;
     std::mutex call_mu;  // vpzm_decode_library holds it: calls from several host threads take the dispatcher in turn
@@ -232,6 +314,7 @@ struct Job {  // one stream of the library inside its group
     std::shared_ptr<Setup> own;  // its setup-header products, loaded when it is opened
     int64_t packets = 0, residue_floats = 0, total_samples = 0;
     int64_t payload_bytes = 0, plan_failures = 0;  // gpu_entropy: what its plan needs in the payload area; packets its plan gave up
+    int part = 0;  // mixed_setups: which part of its class's merged setup its own setup is
     int32_t status = VPZM_OK;
     bool finished = false;  // its PCM has been written (or it has its own failure status): what an aborted run leaves alone
     void close()
@@ -246,6 +329,9 @@ struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
     std::vector<int> members;            // indices into jobs
     std::vector<int64_t> pbase, rbase;   // where each member's packets / residue start in the slot's arrays
     std::vector<int64_t> ybase;          // ... and its packet bytes in the slot's payload area (a device-decoded sub-batch)
+    std::vector<uint8_t> part;           // a MIXED sub-batch (`st` is a merged setup): each member's part of it; empty otherwise
+    bool mixed() const { return !part.empty(); }
+    int mapping_shift(size_t j) const { return mixed() ? st->mapping_base[part[j]] : 0; }  // what member j's records add to their mapping index
     int64_t n_packets = 0, res_floats = 0, payload_bytes = 0;
     bool on_device = false;              // planned on the host, entropy-decoded on the device
     int decoded = 0;                     // members whose entropy decode is complete (under the group's mutex)
@@ -277,6 +363,7 @@ struct GroupRun {
     vpzm_stream_result *results;
     int threads;
     const Switches sw;
+    const bool mixed;  // the dispatcher's mixed_setups as the call found it, with gpu_entropy
     int lane_host_threads = std::max(1, std::min(8, threads / std::max(1, (int)G.lanes.size())));  // vpz_decoder_set_host_threads of every lane's decoders: the device's threads / its contexts
     double t_wall = 0, t_decode = 0, t_synth = 0;
     int64_t device_streams = 0, device_payload = 0;  // streams entropy-decoded on the device, their packet bytes
@@ -285,6 +372,12 @@ struct GroupRun {
 
     std::vector<Job> jobs;
     std::vector<std::shared_ptr<Setup>> setups;
+    // mixed: the merged setups of this call; setups[q] is part merged_at[q].second of merged[merged_at[q].first] (-1: not looked up yet).
+    // A merged setup only grows, as a copy with one more part: sub-batches cut before keep the one they were cut with
+    std::vector<std::shared_ptr<Setup>> merged;
+    std::vector<std::pair<int, int>> merged_at;
+    int64_t n_device_subs = 0, n_mixed_subs = 0, most_setups = 0;  // vpzm_call_counts, this group's share (under `mu`)
+    std::atomic<int64_t> decoders_created{0};
     std::deque<Sub> subs;                    // (a deque: sub-batches are appended while others are in flight)
     std::vector<std::pair<int, int>> tasks;  // (sub, member) in the order they are decoded
     std::vector<int> wave_left;              // streams of each wave still to be opened
@@ -356,8 +449,31 @@ struct GroupRun {
             by_setup[(size_t)at].push_back((int)i);
         }
         std::vector<Sub> fresh;
-        for (size_t q = 0; q < by_setup.size(); ++q)
-            for (Sub &sb : cut(setups[q], by_setup[q])) fresh.push_back(std::move(sb));
+        std::vector<std::vector<int>> pool;  // mixed: the wave's streams of every merged setup, in job order
+        for (size_t q = 0; q < by_setup.size(); ++q) {
+            if (by_setup[q].empty()) continue;
+            if (!mixed || !setups[q]->on_device()) {
+                for (Sub &sb : cut(setups[q], by_setup[q])) fresh.push_back(std::move(sb));
+                continue;
+            }
+            const std::pair<int, int> at = merge(q);
+            pool.resize(merged.size());
+            for (int i : by_setup[q]) {
+                jobs[(size_t)i].part = at.second;
+                pool[(size_t)at.first].push_back(i);
+            }
+        }
+        for (size_t g = 0; g < pool.size(); ++g) {
+            std::sort(pool[g].begin(), pool[g].end());
+            for (Sub &sb : cut(merged[g], pool[g])) fresh.push_back(std::move(sb));
+        }
+        for (const Sub &sb : fresh) {
+            std::vector<uint8_t> seen = sb.part;
+            std::sort(seen.begin(), seen.end());
+            const int64_t n_setups = sb.mixed() ? std::unique(seen.begin(), seen.end()) - seen.begin() : 1;
+            n_mixed_subs += n_setups > 1;
+            most_setups = std::max(most_setups, n_setups);
+        }
         std::sort(fresh.begin(), fresh.end(), [](const Sub &x, const Sub &y) { return x.members[0] < y.members[0]; });
         for (Sub &sb : fresh) {
             const int bi = (int)subs.size();
@@ -367,7 +483,28 @@ struct GroupRun {
         ++waves_planned;
     }
 
-    // The cutting rule: the streams `v` of one setup, in order, become sub-batches.  A synth call holds up to streams_per_call streams
+    // mixed: where setups[q] lies in the call's merged setups.  It joins the last merged setup of its class, which grows by it; when
+    // that one is full (Setup::fits: mappings, floors, parts), or there is none, it starts another
+    std::pair<int, int> merge(size_t q)
+    {
+        merged_at.resize(setups.size(), {-1, -1});
+        if (merged_at[q].first >= 0) return merged_at[q];
+        int last = -1;
+        for (size_t g = 0; g < merged.size(); ++g)
+            if (merged[g]->same_class(*setups[q])) last = (int)g;
+        const bool grows = last >= 0 && merged[(size_t)last]->fits(*setups[q], (size_t)sw.max_merged_mappings);
+        auto grown = grows ? std::make_shared<Setup>(*merged[(size_t)last]) : std::make_shared<Setup>();
+        grown->add_part(setups[q]);
+        if (grows) {
+            merged[(size_t)last] = grown;
+        } else {
+            merged.push_back(grown);
+            last = (int)merged.size() - 1;
+        }
+        return merged_at[q] = {last, (int)grown->parts.size() - 1};
+    }
+
+    // The cutting rule: the streams `v` of one setup (mixed: of one merged setup), in order, become sub-batches.  A synth call holds up to streams_per_call streams
     // and up to kCallValues residue values (a library of whole songs would otherwise ask for page-locked slots of gigabytes each):
     // a long stream rides with fewer others, or alone
     std::vector<Sub> cut(const std::shared_ptr<Setup> &st, const std::vector<int> &v) const
@@ -390,7 +527,14 @@ struct GroupRun {
             sb.n_packets += J.packets;
             sb.res_floats += J.residue_floats;
             sb.payload_bytes += (J.payload_bytes + 7) & ~(int64_t)7;
+            if (!st->parts.empty()) sb.part.push_back((uint8_t)J.part);
         }
+        // (a merged setup's sub-batch whose members all share one setup takes that setup's route: single image, vpz_entropy_decode)
+        for (Sub &sb : out)
+            if (sb.mixed() && std::count(sb.part.begin(), sb.part.end(), sb.part[0]) == (std::ptrdiff_t)sb.part.size()) {
+                sb.st = st->parts[sb.part[0]];
+                sb.part.clear();
+            }
         return out;
     }
 
@@ -425,6 +569,14 @@ struct GroupRun {
         m->fail(text);
     }
 
+    // A mixed sub-batch's records carry mapping indices of its merged setup: every record of member j, the not-decoded ones included (an
+    // index valid in its own setup stays valid in the merged one), moves by the base of the member's part
+    static void shift_mappings(vpz_packet *pk, int64_t n, int by)
+    {
+        if (by)
+            for (int64_t p = 0; p < n; ++p) pk[p].mapping = (uint8_t)(pk[p].mapping + by);
+    }
+
     // the plan of one member of a device-decoded sub-batch: packet records, spans and the packets' bytes into the slot
     int plan_member(Job &J, Slot &sl, const Sub &sb, int j)
     {
@@ -433,6 +585,7 @@ struct GroupRun {
                                        J.payload_bytes, nullptr, nullptr);
         if (rc != VPZH_OK) return rc;
         for (int64_t p = 0; p < J.packets; ++p) sl.spans()[pb + p].offset += yb;  // (spans count from the sub-batch's payload)
+        shift_mappings(sl.packets() + pb, J.packets, sb.mapping_shift((size_t)j));
         J.plan_failures = vpzh_decode_failures(J.h, nullptr);
         return rc;
     }
@@ -449,6 +602,7 @@ struct GroupRun {
                                    : vpzh_decode_range_ex(J.h, 0, J.packets, j, rb, sl.packets() + pb, sl.residue_f32() + rb, sl.posts() + (size_t)pb * 64 * C,
                                                           sl.counts() + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride);
         if (rc == VPZH_OK) results[J.k].skipped_packets += vpzh_decode_failures(J.h, nullptr);
+        if (rc == VPZH_OK) shift_mappings(sl.packets() + pb, J.packets, sb.mapping_shift((size_t)j));  // (the stream's own handle decoded it from its own setup)
         return rc;
     }
     // one member's decode task.  A container that does not decode costs its stream (VPZM_E_OPEN).  A planned member's container stays
@@ -576,6 +730,7 @@ struct GroupRun {
         cfg.floor_types = st->floor_types.data();
         cfg.floors0 = st->floors0.data();
         vpz_decoder *dec = nullptr;
+        ++decoders_created;
         if (vpz_decoder_create(L.ctx, &cfg, m->call_streams(), &dec) != VPZ_OK) {
             m->fail(std::string("vpz_decoder_create: ") + vpz_context_last_error(L.ctx));
             return nullptr;
@@ -780,18 +935,35 @@ struct SubCall {
         if (!room(Lane::kPayload, (size_t)sb.payload_bytes) || !room(Lane::kResidue, (size_t)sb.res_floats * (i16 ? sizeof(int16_t) : sizeof(float))) ||
             !room(Lane::kPosts, rec * 64 * sizeof(int16_t)) || !room(Lane::kCounts, rec) || !room(Lane::kPcm, (size_t)pcm_elems * elem))
             return false;
-        vpz_entropy_setup *es = L.esetups.find(st);
-        if (!es) {
+        vpz_entropy_setup *es = sb.mixed() ? nullptr : L.esetups.find(st);
+        if (!sb.mixed() && !es) {
             if (vpz_entropy_setup_create(L.ctx, st.image.data(), (uint64_t)st.image.size(), &es) != VPZ_OK) return false;  // (refused: the host path)
             L.esetups.keep(sb.st, es);
         }
+        vpz_entropy_group *eg = sb.mixed() ? L.egroups.find(st) : nullptr;
+        if (sb.mixed() && !eg) {  // (the merged setup's parts in order: a member's part is its setup in the group)
+            std::vector<const void *> images;
+            std::vector<uint64_t> sizes;
+            for (const auto &part : st.parts) {
+                images.push_back(part->image.data());
+                sizes.push_back((uint64_t)part->image.size());
+            }
+            if (vpz_entropy_group_create(L.ctx, images.data(), sizes.data(), (int32_t)images.size(), &eg) != VPZ_OK) return false;
+            L.egroups.keep(sb.st, eg);
+        }
+        std::vector<uint8_t> bases;  // (a mixed sub-batch: the member index is the stream, its part the stream's setup)
+        for (size_t j = 0; j < sb.part.size(); ++j) bases.push_back((uint8_t)sb.mapping_shift(j));
         const auto t_up = Clock::now();
         if (vpz_memcpy_h2d(L.ctx, L.payload(), sl.payload(), (uint64_t)sb.payload_bytes) != VPZ_OK) return false;
         t_upload = seconds_since(t_up);
         const auto t_en = Clock::now();
-        if (vpz_entropy_decode(es, n_pk, sl.packets(), sl.spans(), L.payload(), sb.payload_bytes, i16 ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32,
-                               L.residue(), sb.res_floats, L.posts(), L.counts(), (int64_t)rec, VPZ_MEM_DEVICE) != VPZ_OK)
-            return false;
+        const int32_t format = i16 ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32;
+        const int rc = sb.mixed() ? vpz_entropy_group_decode(eg, (int32_t)sb.part.size(), sb.part.data(), bases.data(), n_pk, sl.packets(), sl.spans(),
+                                                             L.payload(), sb.payload_bytes, format, L.residue(), sb.res_floats, L.posts(),
+                                                             L.counts(), (int64_t)rec, VPZ_MEM_DEVICE)
+                                  : vpz_entropy_decode(es, n_pk, sl.packets(), sl.spans(), L.payload(), sb.payload_bytes, format, L.residue(),
+                                                       sb.res_floats, L.posts(), L.counts(), (int64_t)rec, VPZ_MEM_DEVICE);
+        if (rc != VPZ_OK) return false;
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the stage's own time; otherwise nothing waits here)
         t_entropy = seconds_since(t_en);
         out_at = L.pcm();
@@ -907,6 +1079,7 @@ struct SubCall {
                     (long long)n_pk);
         std::lock_guard<std::mutex> lk(R.mu);
         R.t_synth += dt;
+        R.n_device_subs += sb.on_device && has_call();
         for (size_t j = 0; j < sb.members.size(); ++j) {
             Job &J = job(j);
             if (J.status != VPZM_OK) continue;
@@ -1000,6 +1173,7 @@ void vpzm_destroy(vpzm_dispatcher *m)
         for (Lane &L : G.lanes) {
             L.decoders.clear();
             L.esetups.clear();
+            L.egroups.clear();
             for (Buffer &b : L.buf) b.release(L.ctx);
             if (L.ctx) vpz_context_destroy(L.ctx);
         }
@@ -1014,14 +1188,16 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
                         void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity, vpzm_stream_result *results,
                         vpzm_stats *stats)
 {
-    if (!m || n < 0 || !results || (n > 0 && (!data || !size || !pcm_out || !pcm_offset || !pcm_capacity))) return VPZM_E_ARG;
+    if (!m) return VPZM_E_ARG;
+    // (slots, contexts and decoder caches belong to one call at a time: a second caller waits here, it is not refused)
+    std::lock_guard<std::mutex> one_call(m->call_mu);
+    m->counts = vpzm_call_counts{};  // (of THIS call from here on, however it ends)
+    if (n < 0 || !results || (n > 0 && (!data || !size || !pcm_out || !pcm_offset || !pcm_capacity))) return VPZM_E_ARG;
     if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_INTERLEAVED_S16) return VPZM_E_ARG;
     for (int32_t k = 0; k < n; ++k)
         if (!data[k] || pcm_offset[k] < 0 || pcm_capacity[k] < 0) return VPZM_E_ARG;
     // (the fields appended for gpu_entropy exist for a caller that sets the option; an older caller's struct ends before them)
     if (stats) memset(stats, 0, m->opt.gpu_entropy ? sizeof *stats : offsetof(vpzm_stats, device_gpu_entropy_streams));
-    // (slots, contexts and decoder caches belong to one call at a time: a second caller waits here, it is not refused)
-    std::lock_guard<std::mutex> one_call(m->call_mu);
     m->error.clear();
     const auto t0 = Clock::now();
     const int D = (int)m->groups.size();
@@ -1034,7 +1210,7 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
             // shard_range (vorbispizza_amd/sharding.py): contiguous, sizes differ by at most one
             const int32_t lo = (int32_t)((int64_t)n * d / D), hi = (int32_t)((int64_t)n * (d + 1) / D);
             runs.emplace_back(new GroupRun{m, m->groups[(size_t)d], d, lo, hi, data, size, out_layout, pcm_out, pcm_offset,
-                                           pcm_capacity, results, per_device, sw});
+                                           pcm_capacity, results, per_device, sw, m->mixed_setups && m->opt.gpu_entropy});
         }
         for (int d = 1; d < D; ++d) threads.emplace_back([&runs, d] { runs[(size_t)d]->run_guarded(); });
         runs[0]->run_guarded();
@@ -1047,6 +1223,13 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
         return VPZM_E_NOMEM;
     }
     for (std::thread &t : threads) t.join();
+    for (const auto &run : runs) {
+        m->counts.sub_batches += (int64_t)run->subs.size();
+        m->counts.device_decoded_sub_batches += run->n_device_subs;
+        m->counts.mixed_sub_batches += run->n_mixed_subs;
+        m->counts.max_setups_per_sub_batch = std::max(m->counts.max_setups_per_sub_batch, run->most_setups);
+        m->counts.decoders_created += run->decoders_created;
+    }
     if (stats) {
         stats->wall_s = seconds_since(t0);
         stats->threads_per_device = per_device;
@@ -1066,6 +1249,22 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
             }
         }
     }
+    return VPZM_OK;
+}
+
+int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)
+{
+    if (!m) return VPZM_E_ARG;
+    std::lock_guard<std::mutex> one_call(m->call_mu);
+    m->mixed_setups = on != 0;
+    return VPZM_OK;
+}
+
+int vpzm_last_call_counts(vpzm_dispatcher *m, vpzm_call_counts *out)
+{
+    if (!m || !out) return VPZM_E_ARG;
+    std::lock_guard<std::mutex> one_call(m->call_mu);
+    *out = m->counts;
     return VPZM_OK;
 }
 

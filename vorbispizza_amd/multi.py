@@ -1,6 +1,6 @@
-"""ctypes view of include/vorbispizza_multi.h -- the in-process multi-device dispatcher of libvorbispizza_host.so (one host
-process, one context group per MI355X, streams partitioned contiguously, no collective).  What a C# host P/Invokes;
-tests and bench.py use it from here."""
+"""ctypes view of include/vorbispizza_multi.h and include/vorbispizza_multi_mixed.h -- the in-process multi-device dispatcher of
+libvorbispizza_host.so (one host process, one context group per MI355X, streams partitioned contiguously, no collective).  What a
+C# host P/Invokes; tests and bench.py use it from here."""
 import ctypes as C
 
 import numpy as np
@@ -30,11 +30,17 @@ class Stats(C.Structure):
                 ("device_gpu_entropy_streams", C.c_int64 * 16), ("device_payload_bytes", C.c_int64 * 16)]
 
 
+class CallCounts(C.Structure):  # vpzm_call_counts (vorbispizza_multi_mixed.h)
+    _fields_ = [("sub_batches", C.c_int64), ("device_decoded_sub_batches", C.c_int64), ("mixed_sub_batches", C.c_int64),
+                ("max_setups_per_sub_batch", C.c_int64), ("decoders_created", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
 RESULT_DTYPE = np.dtype([("status", "<i4"), ("device_slot", "<i4"), ("channels", "<i4"), ("sample_rate", "<i4"),
                          ("samples", "<i8"), ("packets", "<i8"), ("skipped_packets", "<i8")])
 assert RESULT_DTYPE.itemsize == C.sizeof(StreamResult)
 
 EXPORTED_SYMBOLS = ["vpzm_create", "vpzm_destroy", "vpzm_last_error", "vpzm_device_count", "vpzm_decode_library"]
+MIXED_EXPORTED_SYMBOLS = ["vpzm_set_mixed_setups", "vpzm_last_call_counts"]  # (vorbispizza_multi_mixed.h)
 _bound = False
 
 
@@ -53,6 +59,11 @@ def lib():
         L.vpzm_device_count.restype = C.c_int
         L.vpzm_decode_library.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(Stats)]
         L.vpzm_decode_library.restype = C.c_int
+        if hasattr(L, "vpzm_set_mixed_setups"):  # (an older build taken through VPZ_LIB_DIR for an A/B run has neither: using one raises)
+            L.vpzm_set_mixed_setups.argtypes = [vp, C.c_int32]
+            L.vpzm_set_mixed_setups.restype = C.c_int
+            L.vpzm_last_call_counts.argtypes = [vp, C.POINTER(CallCounts)]
+            L.vpzm_last_call_counts.restype = C.c_int
         _bound = True
     return L
 
@@ -64,10 +75,12 @@ class MultiError(RuntimeError):
 class Dispatcher:
     """vpzm_dispatcher: one context group per entry of `device_ids` (an id may repeat: several groups on one GPU).
     gpu_entropy: streams whose setup the device can decode (vpzh_gpu_decode_supported) are entropy-decoded there, the others on
-    the host threads in the same call; the PCM is the same bit for bit."""
+    the host threads in the same call; the PCM is the same bit for bit.  mixed_setups (with gpu_entropy): device-decoded
+    sub-batches may hold streams of different setups that agree in channels, block sizes and residue type
+    (vpzm_set_mixed_setups); set_mixed_setups changes it between calls."""
 
     def __init__(self, device_ids, host_threads=0, streams_per_call=0, contexts_per_device=0, clip_samples=False,
-                 slots_per_device=0, float_residue=False, gpu_entropy=False):
+                 slots_per_device=0, float_residue=False, gpu_entropy=False, mixed_setups=False):
         ids = (C.c_int32 * len(device_ids))(*[int(d) for d in device_ids])
         opt = Options(host_threads, streams_per_call, contexts_per_device, 1 if clip_samples else 0, slots_per_device,
                       1 if float_residue else 0, 1 if gpu_entropy else 0)
@@ -77,6 +90,21 @@ class Dispatcher:
             self._h = None
             raise MultiError("vpzm_create failed (status %d)" % rc)
         self.n_devices = len(device_ids)
+        if mixed_setups:
+            self.set_mixed_setups(True)
+
+    def set_mixed_setups(self, on):
+        rc = lib().vpzm_set_mixed_setups(self._h, 1 if on else 0)
+        if rc != OK:
+            raise MultiError("vpzm_set_mixed_setups failed (status %d)" % rc)
+
+    def call_counts(self):
+        """vpzm_last_call_counts: the CallCounts of the last decode_library call"""
+        counts = CallCounts()
+        rc = lib().vpzm_last_call_counts(self._h, C.byref(counts))
+        if rc != OK:
+            raise MultiError("vpzm_last_call_counts failed (status %d)" % rc)
+        return counts
 
     def close(self):
         if getattr(self, "_h", None):

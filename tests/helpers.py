@@ -238,8 +238,8 @@ def floor0_safe_amp(coeff, bark_map_size, amp_ofs):
 
 ALL_LONG = PKT_BLOCK_FLAG | PKT_PREV_FLAG | PKT_NEXT_FLAG
 
-_CUT_LINE = (r"\[vpz host\] cut: [^,]+, by (?P<by>cost|length), R (?P<R>\d+), .*?, (?P<runs>\d+) runs for -?\d+ slots, .*?"
-             r"chained (?P<chained>\d+), runs filled by (?P<fill>the pool|the calling thread) on (?P<fill_threads>\d+) threads, "
+_CUT_LINE = (r"\[vpz host\] cut: [^,]+, by (?P<by>cost|length), R (?P<R>\d+), target (?P<target>-?\d+) eighths, (?P<runs>\d+) runs "
+             r"for -?\d+ slots, .*?heavy below (?P<heavy>-?\d+), .*?chained (?P<chained>\d+), runs filled by (?P<fill>the pool|the calling thread) on (?P<fill_threads>\d+) threads, "
              r"chain sweep on (?P<chain_threads>\d+) threads")
 _CALL_LINE = r"\[vpz host\] packets (?P<packets>\d+): route (?P<route>\w+), .*? pass1 [\d.]+ us \((?P<pass1>parallel|serial)\)"
 
@@ -252,7 +252,7 @@ def host_profile(err):
     assert len(cut) == 1 and len(call) == 1, "expected one cut line and one call line, got:\n" + err[-2000:]
     m = re.search(_CUT_LINE, err).groupdict()
     m.update(re.search(_CALL_LINE, err).groupdict())
-    for k in ("R", "runs", "chained", "fill_threads", "chain_threads", "packets"):
+    for k in ("R", "runs", "chained", "fill_threads", "chain_threads", "packets", "target", "heavy"):
         m[k] = int(m[k])
     return m
 
@@ -274,6 +274,63 @@ def by_length_runs(frames_per_stream, R):
     for s, n in enumerate(frames_per_stream):
         for j, f0 in enumerate(range(0, n, R)):
             runs.append((s, j, min(R, n - f0)))
+    return runs
+
+
+def cost_codes(packets, dual):
+    """DESIGN 4.3 / 4.7, the cost of a stream's packets IN ONE CALL ([(flags, mapping)] in order), in eighths of a long block's pass:
+    a long block 8; a short block alone or at the head of a batch 8 on the stereo / pair routes (`dual`) and 6 in group mode; a short
+    block that rides in a batch 2 / 3.  A short block may ride (`ok`) when it has a predecessor in the call, on the stereo routes
+    always, in group mode when it is Residue2-interleaved and not already floored; it joins its predecessor's batch when that may
+    ride too, is short and has the same mapping (and both are floored or both are not: counted in the total only); a batch holds
+    eight blocks.  Returns ([(is_short, ok, same mapping as a short predecessor)], the stream's total cost)."""
+    w_short, w_member = (8, 2) if dual else (6, 3)
+    codes, units, pos, prev_ok = [], 0, -1, False
+    for i, (fl, mp) in enumerate(packets):
+        short = not fl & PKT_BLOCK_FLAG
+        ok = same = link = False
+        if i > 0:
+            pfl, pmp = packets[i - 1]
+            p_short = not pfl & PKT_BLOCK_FLAG
+            ok = short and not (fl | pfl) & PKT_NOT_DECODED and (dual or bool(fl & PKT_INTERLEAVED and not fl & PKT_NO_FLOOR))
+            same = ok and mp == pmp and p_short
+            link = same and prev_ok and not (fl ^ pfl) & PKT_NO_FLOOR
+        pos = (pos + 1 if link else 0) if ok else -1
+        units += w_member if ok and pos & 7 else (w_short if short else 8)
+        codes.append((short, ok, same))
+        prev_ok = ok
+    return codes, units
+
+
+def by_cost_runs(packets_per_stream, target, r_max, dual, heavy=-1):
+    """The runs of a cut by cost: a run takes frames while its cost stays within the target and it holds fewer
+    than r_max frames (the descriptor area), at least one; inside a run the batches start over.  `heavy` >= 0 (the stereo routes'
+    skew): a run that starts below that much of the call's cost gets target + 2.5 %, the others target - 2.5 %.  Returns
+    [(stream, index within the stream's runs, frames, cost, whether the frame cap and not the cost ended the run)]."""
+    w_short, w_member = (8, 2) if dual else (6, 3)
+    runs, prefix = [], 0
+    for s, packets in enumerate(packets_per_stream):
+        codes, total = cost_codes(packets, dual)
+        f0, j, before = 0, 0, 0
+        while f0 < len(codes):
+            t = target
+            if heavy >= 0:
+                t += target * 25 // 1000 if prefix + before < heavy else -(target * 25 // 1000)
+            n, units, pos, prev_ok, capped = 0, 0, -1, False, False
+            while f0 + n < len(codes):
+                short, ok, same = codes[f0 + n]
+                link = ok and prev_ok and same
+                p = (pos + 1 if link else 0) if ok else -1
+                u = w_member if ok and p & 7 else (w_short if short else 8)
+                if n > 0 and units + u > t:
+                    break
+                if n == r_max:
+                    capped = True
+                    break
+                units, pos, prev_ok, n = units + u, p, ok, n + 1
+            runs.append((s, j, n, units, capped))
+            f0, j, before = f0 + n, j + 1, before + units
+        prefix += total
     return runs
 
 

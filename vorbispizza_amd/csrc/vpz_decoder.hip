@@ -201,6 +201,7 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
     if (const char *e = getenv("VPZ_NO_DIRECT_I16")) D.no_direct_i16 = atoi(e) != 0;  // A/B and bit-equality tests: always widen int16 residue first
     if (const char *e = getenv("VPZ_NO_CHAIN")) D.no_chain = atoi(e) != 0;  // A/B tests: every run recomputes its predecessor block
     if (const char *e = getenv("VPZ_DUAL_RUN")) D.dual_run = std::max(4, atoi(e));
+    if (const char *e = getenv("VPZ_PLAN_SLOTS")) D.plan_slots = std::max<int64_t>(0, atoll(e));  // tests: long runs from small batches
     if (const char *e = getenv("VPZ_SYNTH_ABLATE")) D.ablate = atoi(e);
     if (const char *e = getenv("VPZ_HOST_THREADS")) D.host_threads = atoi(e);
     if (const char *e = getenv("VPZ_NO_EARLY_UPLOAD")) D.no_early_upload = atoi(e) != 0;
@@ -649,6 +650,7 @@ struct SynthCall {
         P.needs_general = synth_needs_general(D.size0, D.size1);
         P.resident_slots = [](const SynthPlan &p) -> int64_t {
             const Decoder &d = p.D;
+            if (d.plan_slots > 0) return d.plan_slots;
             return p.use_dual ? synth_dual_resident_slots(p.facts.any_floor, d.ctx->num_cu)
                    : d.big    ? synth_big_resident_waves(p.facts.any_floor, d.ctx->num_cu, d.size0, d.size1)
                               : synth_resident_waves(p.facts.any_floor, d.ctx->num_cu, d.channels, p.use_group);

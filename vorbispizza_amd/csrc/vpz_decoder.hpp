@@ -139,6 +139,7 @@ struct Decoder {
     int32_t f0_stride = 0;
     PacketInfo packet_info[8];  // Mode.GetPacketInfo by (block | prev << 1 | next << 2) == vpz_packet.flags & 7
     int dual_run = 8;  // preferred run length of the stereo fast path's chained runs (VPZ_DUAL_RUN)
+    int64_t plan_slots = 0;  // VPZ_PLAN_SLOTS=n (tests): the resident slots the run cut plans for, on every route; 0: the kernels' own
     bool no_direct_i16 = false;
     bool no_chain = false;  // VPZ_NO_CHAIN=1 (A/B tests): no run of the stereo fast path takes its predecessor's tail over in LDS
     int ablate = 0;  // VPZ_SYNTH_ABLATE, tuning experiments only

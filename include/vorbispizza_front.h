@@ -66,6 +66,16 @@ int vpzh_get_residue_type(vpzh_stream *s, int index);
 int64_t vpzh_total_samples(vpzh_stream *s);
 int vpzh_seek(vpzh_stream *s, int64_t sample_position, int64_t *first_packet, int64_t *roll_forward);
 
+/* The packets that a window of `count` samples per channel from `start` needs (count < 0: to the end), by vpzh_seek's search.
+ * *samples = min(count, vpzh_total_samples - start): the granule-capped length bounds a window, not the counted one that
+ * vpzh_seek accepts positions up to.  *first_packet and *roll_forward are vpzh_seek(start)'s; *n_packets counts from the pre-roll
+ * packet through the packet that holds sample start + *samples - 1 (0 when *samples is 0); *position is the counted position
+ * after the pre-roll packet, what the decoder's stream is set to (vpz_decoder_set_position) before the window's first packet;
+ * *residue_values is the sum over the window's packets (what vpzh_decode_range_* / vpzh_plan_range use for them).
+ * VPZH_E_ARG when start < 0 or start > vpzh_total_samples. */
+int vpzh_window(vpzh_stream *s, int64_t start, int64_t count, int64_t *first_packet, int64_t *n_packets, int64_t *roll_forward,
+                int64_t *position, int64_t *samples, int64_t *residue_values);
+
 /* Entropy-decodes every audio packet.  packets[audio_packets], residue[residue_floats],
  * posts[audio_packets*channels*64], post_counts[audio_packets*channels].  `stream_id` is written to
  * vpz_packet.stream, `residue_base` is added to every residue_offset.  Packets whose first bit is set

@@ -2,6 +2,7 @@
 """The 1024-stream job through the in-process dispatcher under several thread / slot / sub-batch settings (one GPU, N groups).
 
     dispatcher_probe.py [--gpu-entropy | --mixed | --ab] [--setups K] [--reps N] [--s16-only] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --ranges SAMPLES [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -12,7 +13,11 @@ mixed_setups, gpu_entropy on in both.
 the writer (tests/synthetic_streams.py: stereo_coupled_res2(2 + 10 k), --setup-packets packets each, default 300) and the two
 fixtures.  Building them takes seconds each: with VPZ_PROBE_CACHE=DIR they are kept there.
 A line "counts" follows every result: sub_batches, device-decoded and mixed ones, decoders_created of the last call (a build
-without vpzm_last_call_counts, taken through VPZ_LIB_DIR, prints none)."""
+without vpzm_last_call_counts, taken through VPZ_LIB_DIR, prints none).
+--ranges SAMPLES: one window of SAMPLES samples per stream at a seeded random start, 16-bit PCM, into a dense [streams][SAMPLES][2] array.
+The A/B: vpzm_decode_library of the whole streams followed by slicing on the host (the slicing timed with it) against vpzm_decode_ranges,
+two dispatchers in this process taking turns, --reps times each (default 5), the pair of series run twice; the two dense arrays are
+compared.  Every line gives the median and the extremes of its series: a difference inside the extremes is no difference."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -27,6 +32,7 @@ ap.add_argument("--setups", type=int, default=0)
 ap.add_argument("--setup-packets", type=int, default=300)
 ap.add_argument("--reps", type=int, default=0)
 ap.add_argument("--s16-only", action="store_true")
+ap.add_argument("--ranges", type=int, default=0)
 ap.add_argument("settings", nargs="+")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -76,6 +82,61 @@ def counts_line(d):
 def describe(walls):
     return "median %.1f ms (min %.1f, max %.1f)" % (statistics.median(walls) * 1e3, min(walls) * 1e3, max(walls) * 1e3)
 
+
+def ranges_job(samples):
+    import time
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    starts = np.array([int(rng.integers(0, totals[i] - samples - 64)) for i in pick], dtype=np.int64)  # (issue6test.ogg ends 63 samples short)
+    windows = [(int(a), samples) for a in starts]
+    n = len(datas)
+    whole = torch.empty(int((caps * 2).sum()), dtype=torch.int16, pin_memory=True).numpy()
+    dense = [torch.empty(n * samples * 2, dtype=torch.int16, pin_memory=True).numpy() for _ in range(2)]
+    d_offs, d_caps = np.arange(n, dtype=np.int64) * samples * 2, np.full(n, samples, dtype=np.int64)
+
+    def by_library(d):
+        t0 = time.perf_counter()
+        res, st = d.decode_library(datas, whole, offs, caps, s16=True)
+        out = dense[0].reshape(n, samples * 2)
+        for k in range(n):  # the host's slicing: what a caller of the whole decode does to get its windows
+            out[k] = whole[offs[k] + starts[k] * 2: offs[k] + (starts[k] + samples) * 2]
+        return time.perf_counter() - t0, res, st
+
+    def by_ranges(d):
+        t0 = time.perf_counter()
+        res, st = d.decode_ranges(datas, windows, dense[1], d_offs, d_caps, s16=True)
+        return time.perf_counter() - t0, res, st
+
+    def series(legs, reps):
+        walls = [[] for _ in legs]
+        for _ in range(reps):
+            for i, leg in enumerate(legs):
+                wall, res, st = leg()
+                assert (res["status"] == 0).all()
+                walls[i].append(wall)
+        return walls
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "s16 groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        _, res_lib, _ = by_library(ds[0])  # (one pass each that does not count: slots, decoders and device arrays are allocated in it)
+        _, res, st = by_ranges(ds[1])
+        assert (res["samples"] == samples).all() and np.array_equal(dense[0], dense[1]), "the windows differ from the slices of the whole decode"
+        print("%s:\n    packets decoded: %d of %d (%.1f %%), pinned %d MiB, %d streams on the device" % (
+            what, int(res["packets"].sum()), int(res_lib["packets"].sum()), 100.0 * res["packets"].sum() / res_lib["packets"].sum(), st.pinned_mib,
+            int(sum(st.device_gpu_entropy_streams))), flush=True)
+        for run in (1, 2):
+            walls = series([lambda: by_library(ds[0]), lambda: by_ranges(ds[1])], args.reps or 5)
+            print("    A/B run %d: decode_library + host slicing %s; decode_ranges %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+if args.ranges:
+    ranges_job(args.ranges)
+    sys.exit(0)
 
 for s16 in ((True,) if args.s16_only else (False, True)):
     pcm = torch.empty(int((caps * 2).sum()), dtype=torch.int16 if s16 else torch.float32, pin_memory=True).numpy()

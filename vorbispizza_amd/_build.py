@@ -49,6 +49,7 @@ def _deps(src):
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_synth.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_entropy.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_entropy_group.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm.h"))
     return deps
 
 
@@ -66,7 +67,8 @@ def build_host(force=False, verbose=False):
     deps = srcs + [os.path.join(inc, "vorbispizza_front.h"), os.path.join(inc, "vorbispizza_reader.h"),
                    os.path.join(inc, "vorbispizza_multi.h"), os.path.join(inc, "vorbispizza_synth.h"),
                    os.path.join(inc, "vorbispizza_entropy.h"), os.path.join(inc, "vorbispizza_entropy_group.h"),
-                   os.path.join(inc, "vorbispizza_multi_mixed.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi_mixed.h"), os.path.join(inc, "vorbispizza_multi_ranges.h"),
+                   os.path.join(inc, "vorbispizza_pcm.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

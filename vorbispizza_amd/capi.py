@@ -96,7 +96,12 @@ _SIGNATURES = [
 _DEBUG_SIGNATURES = [
     ("vpz_debug_floor1_indices", C.c_int, [_vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 ]
+# include/vorbispizza_pcm.h (a header of its own: the product header and its ABI version do not change with it)
+_PCM_SIGNATURES = [
+    ("vpz_pcm_download", C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
+PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
 DEBUG_SYMBOLS = [s[0] for s in _DEBUG_SIGNATURES]
 
 _lib = None
@@ -125,7 +130,9 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES:
+        for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + _PCM_SIGNATURES:
+            if (name, restype, argtypes) in _PCM_SIGNATURES and not hasattr(L, name):
+                continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
             fn = getattr(L, name)
             fn.restype = restype
             fn.argtypes = argtypes

@@ -5,6 +5,7 @@
 #include <new>
 
 #include "vpz_internal.hpp"
+#include "../../include/vorbispizza_pcm.h"
 
 namespace vpz {
 
@@ -377,6 +378,15 @@ int vpz_memcpy_d2h(vpz_context *c, void *host_dst, const void *dev_src, uint64_t
     if (!c || (!host_dst && bytes) || (!dev_src && bytes)) return VPZ_E_INVALID_ARG;
     VPZ_HIP_TRY(&c->impl, hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, c->impl.stream));
     VPZ_HIP_TRY(&c->impl, hipStreamSynchronize(c->impl.stream));
+    return VPZ_OK;
+}
+
+// vpz_memcpy_d2h without its synchronise (include/vorbispizza_pcm.h): many small copies queued, one vpz_context_synchronize for all
+int vpz_pcm_download(vpz_context *c, void *host_dst, const void *dev_src, uint64_t bytes)
+{
+    if (!c || (!host_dst && bytes) || (!dev_src && bytes)) return VPZ_E_INVALID_ARG;
+    if (bytes == 0) return VPZ_OK;
+    VPZ_HIP_TRY(&c->impl, hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, c->impl.stream));
     return VPZ_OK;
 }
 

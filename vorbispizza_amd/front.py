@@ -114,6 +114,8 @@ def lib():
         L.vpzh_total_samples.restype = C.c_int64
         L.vpzh_seek.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.vpzh_seek.restype = C.c_int
+        L.vpzh_window.argtypes = [vp, C.c_int64, C.c_int64] + [C.POINTER(C.c_int64)] * 6
+        L.vpzh_window.restype = C.c_int
         L.vpzr_read_samples.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int)]
         L.vpzr_read_samples.restype = C.c_int64
         L.vpzr_read_samples_planar.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int)]
@@ -184,6 +186,15 @@ class OggVorbisFile:
         if lib().vpzh_seek(self._h, int(sample_position), C.byref(first), C.byref(roll)) != 0:
             raise FrontError(lib().vpzh_last_error(self._h).decode())
         return first.value, roll.value
+
+    def window(self, start, count=-1):
+        """vpzh_window: the packets that `count` samples per channel from `start` need (count < 0: to the end), as a dict of
+        first_packet, n_packets, roll_forward, position, samples and residue_values."""
+        out = [C.c_int64() for _ in range(6)]
+        if lib().vpzh_window(self._h, int(start), int(count), *[C.byref(v) for v in out]) != 0:
+            raise FrontError(lib().vpzh_last_error(self._h).decode())
+        names = ("first_packet", "n_packets", "roll_forward", "position", "samples", "residue_values")
+        return dict(zip(names, (v.value for v in out)))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1991,6 +1991,14 @@ int64_t vpzh_total_samples(vpzh_stream *s)
     return total;
 }
 
+// The packet whose span [cum[k - 1], cum[k]) holds a counted position (the last one for the stream's end): the one search of
+// vpzh_seek and vpzh_window.  `cum` has two entries or more and the position lies in [0, cum.back()]
+static size_t packet_holding(const std::vector<int64_t> &cum, int64_t sample_position)
+{
+    size_t k = (size_t)(std::upper_bound(cum.begin() + 1, cum.end(), sample_position) - cum.begin());
+    return k >= cum.size() ? cum.size() - 1 : k;  // position == end of the stream: the last packet, rolled to its end
+}
+
 int vpzh_seek(vpzh_stream *s, int64_t sample_position, int64_t *first_packet, int64_t *roll_forward)
 {
     // PacketProvider.SeekTo(granulePos, preRoll = 1) (:56-84, GetTargetPageInfo :86-160): the packet whose
@@ -2001,10 +2009,33 @@ int vpzh_seek(vpzh_stream *s, int64_t sample_position, int64_t *first_packet, in
         s->error = "The requested seek position extends beyond the stream.";  // SeekOutOfRangeException
         return VPZH_E_ARG;
     }
-    size_t k = (size_t)(std::upper_bound(cum.begin() + 1, cum.end(), sample_position) - cum.begin());
-    if (k >= cum.size()) k = cum.size() - 1;  // position == end of the stream: the last packet, rolled to its end
+    const size_t k = packet_holding(cum, sample_position);
     *first_packet = (int64_t)k - 1;
     *roll_forward = sample_position - cum[k - 1];
+    return VPZH_OK;
+}
+
+int vpzh_window(vpzh_stream *s, int64_t start, int64_t count, int64_t *first_packet, int64_t *n_packets, int64_t *roll_forward,
+                int64_t *position, int64_t *samples, int64_t *residue_values)
+{
+    if (!s || !first_packet || !n_packets || !roll_forward || !position || !samples || !residue_values) return VPZH_E_ARG;
+    const int64_t total = vpzh_total_samples(s);  // (the granule-capped length: what a whole decode delivers, not what vpzh_seek accepts)
+    if (start < 0 || start > total) {
+        s->error = "The requested window starts outside the stream.";
+        return VPZH_E_ARG;
+    }
+    *first_packet = *n_packets = *roll_forward = *position = *residue_values = 0;
+    *samples = count < 0 ? total - start : std::min(count, total - start);
+    if (total == 0) return VPZH_OK;  // (a stream of no samples has the empty window at 0 and nothing to seek in)
+    const std::vector<int64_t> &cum = s->cum_samples;
+    const size_t k = packet_holding(cum, start);
+    *first_packet = (int64_t)k - 1;
+    *roll_forward = start - cum[k - 1];
+    *position = cum[k - 1];
+    if (*samples == 0) return VPZH_OK;
+    // through the packet that holds the window's last sample, from the pre-roll packet on
+    *n_packets = (int64_t)packet_holding(cum, start + *samples - 1) - *first_packet + 1;
+    for (int64_t p = 0; p < *n_packets; ++p) *residue_values += s->audio[(size_t)(*first_packet + p)].head.residue_values;
     return VPZH_OK;
 }
 

@@ -22,6 +22,12 @@
 // its records carry mapping indices of the merged setup, vpz_entropy_group_decode decodes it and a decoder of the merged setup
 // synthesises it.
 //
+// vpzm_decode_ranges (include/vorbispizza_multi_ranges.h) is the same pipeline over a WINDOW of every stream (vpzh_window: the pre-roll
+// packet through the packet of the window's last sample; a Job carries it, and for vpzm_decode_library it is the whole stream).  A
+// ranges call's PCM is staged on both routes -- the lane's device array, or a page-locked array of the slot --
+// and its download trims every member's window out of its area (device route: an asynchronous vpz_pcm_download per member, one
+// synchronise for the sub-batch).
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
@@ -42,6 +48,8 @@
 
 #include "../../include/vorbispizza_multi.h"
 #include "../../include/vorbispizza_multi_mixed.h"
+#include "../../include/vorbispizza_multi_ranges.h"
+#include "../../include/vorbispizza_pcm.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -247,7 +255,8 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
 };
 
 struct Slot {  // page-locked batch arrays of one sub-batch in flight (a device-decoded one holds packets, spans and payload only)
-    enum { kPackets, kResidue, kPosts, kCounts, kF0Amp, kF0Coeff, kSpans, kPayload, kBuffers };
+    // (kStage: a ranges call's host route writes its members' PCM areas here, and `download` copies every window out of them)
+    enum { kPackets, kResidue, kPosts, kCounts, kF0Amp, kF0Coeff, kSpans, kPayload, kStage, kBuffers };
     Buffer buf[kBuffers];
     vpz_packet *packets() const { return static_cast<vpz_packet *>(buf[kPackets].p); }
     float *residue_f32() const { return static_cast<float *>(buf[kResidue].p); }  // (one array: a sub-batch's residue travels as float32 ...
@@ -258,6 +267,7 @@ struct Slot {  // page-locked batch arrays of one sub-batch in flight (a device-
     float *f0_coeff() const { return static_cast<float *>(buf[kF0Coeff].p); }
     vpz_entropy_span *spans() const { return static_cast<vpz_entropy_span *>(buf[kSpans].p); }
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
+    char *stage() const { return static_cast<char *>(buf[kStage].p); }
     size_t bytes() const
     {
         size_t sum = 0;
@@ -274,7 +284,7 @@ struct Group {
 
 constexpr int64_t kCallValues = (int64_t)64 << 20;  // residue values of one synth call (256 MiB as float32), see GroupRun::cut
 
-// The VPZM_* test and diagnosis switches of the environment as one vpzm_decode_library call finds them (its GroupRuns carry a copy)
+// The VPZM_* test and diagnosis switches of the environment as one vpzm_decode_library / vpzm_decode_ranges call finds them (its GroupRuns carry a copy)
 struct Switches {
     static int64_t number(const char *name) { return getenv(name) ? atoll(getenv(name)) : 0; }
     int64_t max_call_values = number("VPZM_MAX_CALL_VALUES") > 0 ? number("VPZM_MAX_CALL_VALUES") : kCallValues;  // (tests: small calls)
@@ -312,7 +322,10 @@ struct Job {  // one stream of the library inside its group
     int32_t k = 0;  // index in the caller's arrays
     vpzh_stream *h = nullptr;
     std::shared_ptr<Setup> own;  // its setup-header products, loaded when it is opened
-    int64_t packets = 0, residue_floats = 0, total_samples = 0;
+    // its WINDOW (vpzh_window; vpzm_decode_library: the whole stream): `packets` packets from `first`, `residue_floats` values in them;
+    // the decoder's stream starts at `position`, and the caller gets `wanted` samples of what they give after dropping `roll`
+    int64_t first = 0, packets = 0, residue_floats = 0, roll = 0, wanted = 0, position = 0;
+    int64_t total_samples = 0;
     int64_t payload_bytes = 0, plan_failures = 0;  // gpu_entropy: what its plan needs in the payload area; packets its plan gave up
     int part = 0;  // mixed_setups: which part of its class's merged setup its own setup is
     int32_t status = VPZM_OK;
@@ -357,6 +370,7 @@ struct GroupRun {
     int32_t lo, hi;  // the group's streams [lo, hi)
     const uint8_t *const *data;
     const uint64_t *size;
+    const vpzm_range *ranges;  // vpzm_decode_ranges: every stream's window (nullptr: vpzm_decode_library, whole streams)
     int32_t out_layout;
     void *pcm_out;
     const int64_t *pcm_offset, *pcm_capacity;
@@ -412,13 +426,24 @@ struct GroupRun {
             R.channels = info.channels;
             R.sample_rate = info.sample_rate;
             R.packets = info.audio_packets;
-            if (J.total_samples > pcm_capacity[J.k]) { J.status = VPZM_E_CAPACITY; return; }
+            J.wanted = J.total_samples;
+            if (ranges) {  // (the window rule is the front end's; a window outside the stream costs its entry alone)
+                int64_t values = 0;
+                if (vpzh_window(J.h, ranges[J.k].start, ranges[J.k].count, &J.first, &J.packets, &J.roll, &J.position, &J.wanted, &values) != VPZH_OK) {
+                    J.status = VPZM_E_RANGE;
+                    R.packets = 0;
+                    return;
+                }
+                J.residue_floats = values;
+                R.packets = J.packets;
+            }
+            if (J.wanted > pcm_capacity[J.k]) { J.status = VPZM_E_CAPACITY; return; }
             if (J.packets > 0) {
                 J.own = std::make_shared<Setup>();
                 if (!J.own->load(J.h, m->opt.gpu_entropy != 0)) J.status = VPZM_E_SETUP;
                 // (the plan's sizes first, without a payload: members' payload bases are known when the sub-batch is cut)
                 if (J.status == VPZM_OK && J.own->on_device() &&
-                    vpzh_plan_range(J.h, 0, J.packets, 0, 0, nullptr, nullptr, nullptr, 0, &J.payload_bytes, nullptr) != VPZH_OK)
+                    vpzh_plan_range(J.h, J.first, J.packets, 0, 0, nullptr, nullptr, nullptr, 0, &J.payload_bytes, nullptr) != VPZH_OK)
                     J.own->image.clear();
             }
         } catch (...) {
@@ -581,7 +606,7 @@ struct GroupRun {
     int plan_member(Job &J, Slot &sl, const Sub &sb, int j)
     {
         const int64_t pb = sb.pbase[(size_t)j], yb = sb.ybase[(size_t)j];
-        const int rc = vpzh_plan_range(J.h, 0, J.packets, j, sb.rbase[(size_t)j], sl.packets() + pb, sl.spans() + pb, sl.payload() + yb,
+        const int rc = vpzh_plan_range(J.h, J.first, J.packets, j, sb.rbase[(size_t)j], sl.packets() + pb, sl.spans() + pb, sl.payload() + yb,
                                        J.payload_bytes, nullptr, nullptr);
         if (rc != VPZH_OK) return rc;
         for (int64_t p = 0; p < J.packets; ++p) sl.spans()[pb + p].offset += yb;  // (spans count from the sub-batch's payload)
@@ -597,9 +622,9 @@ struct GroupRun {
         const int64_t pb = sb.pbase[(size_t)j], rb = sb.rbase[(size_t)j];
         float *amp_at = st.f0_stride ? sl.f0_amp() + (size_t)pb * C : nullptr;
         float *coeff_at = st.f0_stride ? sl.f0_coeff() + (size_t)pb * C * (size_t)st.f0_stride : nullptr;
-        const int rc = use_i16(st) ? vpzh_decode_range_i16(J.h, 0, J.packets, j, rb, sl.packets() + pb, sl.residue_i16() + rb, sl.posts() + (size_t)pb * 64 * C,
+        const int rc = use_i16(st) ? vpzh_decode_range_i16(J.h, J.first, J.packets, j, rb, sl.packets() + pb, sl.residue_i16() + rb, sl.posts() + (size_t)pb * 64 * C,
                                                            sl.counts() + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride)
-                                   : vpzh_decode_range_ex(J.h, 0, J.packets, j, rb, sl.packets() + pb, sl.residue_f32() + rb, sl.posts() + (size_t)pb * 64 * C,
+                                   : vpzh_decode_range_ex(J.h, J.first, J.packets, j, rb, sl.packets() + pb, sl.residue_f32() + rb, sl.posts() + (size_t)pb * 64 * C,
                                                           sl.counts() + (size_t)pb * C, nullptr, amp_at, coeff_at, st.f0_stride);
         if (rc == VPZH_OK) results[J.k].skipped_packets += vpzh_decode_failures(J.h, nullptr);
         if (rc == VPZH_OK) shift_mappings(sl.packets() + pb, J.packets, sb.mapping_shift((size_t)j));  // (the stream's own handle decoded it from its own setup)
@@ -837,6 +862,7 @@ struct GroupRun {
 // vpz_decoder.hip).  Two routes: a host-decoded sub-batch's arrays lie in its slot and its PCM goes straight into the caller's array;
 // a device-decoded one's packet bytes go up, vpz_entropy_decode writes the lane's device arrays, the synth call reads those and writes
 // the lane's device PCM array, and every member's PCM comes down.  `sb.on_device` says which; decode_on_device may clear it.
+// A ranges call (`ranged`) stages the PCM on both routes; `download` brings every member's window from there to the caller's area.
 struct SubCall {
     GroupRun &R;
     Lane &L;
@@ -846,6 +872,7 @@ struct SubCall {
     const Setup &st = *sb.st;
     const int C = st.info.channels, S = R.m->call_streams();  // channels; the streams a decoder is created for
     const size_t elem = R.out_layout == VPZ_OUT_INTERLEAVED_S16 ? sizeof(int16_t) : sizeof(float);  // bytes of a PCM sample
+    const bool ranged = R.ranges != nullptr;  // a vpzm_decode_ranges call: staged PCM on both routes, windows trimmed in `download`
     bool any = false;  // ---- repack: a member is left ...
     int64_t n_pk = 0;  // ... and the packets of those that are
     // ---- place_outputs: every member's area (offset and capacity in samples), where the areas start, the largest capacity, all the areas
@@ -858,6 +885,7 @@ struct SubCall {
     std::vector<int> member_rc = std::vector<int>(sb.members.size(), VPZ_OK);  // (a sub-batch is one synth call; after a failed one, a call per member)
     Clock::time_point t0 = Clock::now();
     double t_upload = 0, t_entropy = 0, t_call = 0, t_download = 0;
+    int member_calls = 0;  // synth calls made for single members after the batch call failed (the profile line says how many)
 
     Job &job(size_t j) const { return R.jobs[(size_t)sb.members[j]]; }
     bool live(size_t j) const { return job(j).status == VPZM_OK; }
@@ -903,9 +931,12 @@ struct SubCall {
     // call sees the sub-batch's part of the caller's PCM array (it mirrors its output extent on the device), so the offsets handed over
     // start at the sub-batch's lowest one, and a capacity is the caller's.  Device route: the areas lie back to back in the lane's device PCM
     // array; a stream produces at most block_size1 / 2 samples per packet, so an area need not be larger than that, plus one block of slack.
+    // A ranges call stages its PCM on both routes, by the device route's rule: the areas back to back in the lane's device array or in
+    // the slot's page-locked stage, `packets * block_size1 / 2` samples and a block of slack each -- a window's packets give up to a
+    // packet of samples more than the caller wants, in front (Job::roll) and behind, so no area of the caller's could take them.
     void place_outputs()
     {
-        const bool dev = sb.on_device;
+        const bool dev = sb.on_device || ranged;  // (the areas are the call's own, not the caller's)
         int64_t base = INT64_MAX, dev_at = 0;
         for (size_t j = 0; j < sb.members.size(); ++j) base = std::min(base, R.pcm_offset[job(j).k]);
         cap = 0;
@@ -914,12 +945,18 @@ struct SubCall {
             offs[j] = dev ? dev_at : R.pcm_offset[J.k] - base;
             caps[j] = 0;
             if (J.status != VPZM_OK) continue;
-            caps[j] = dev ? std::min(R.pcm_capacity[J.k], J.packets * (st.info.block_size1 / 2)) : R.pcm_capacity[J.k];
+            caps[j] = ranged ? J.packets * (st.info.block_size1 / 2)
+                      : dev  ? std::min(R.pcm_capacity[J.k], J.packets * (st.info.block_size1 / 2))
+                             : R.pcm_capacity[J.k];
             if (dev) dev_at += (caps[j] + st.info.block_size1) * C;
             cap = std::max(cap, caps[j]);
         }
         pcm_elems = dev_at;
         out_at = dev ? nullptr : static_cast<char *>(R.pcm_out) + elem * (size_t)base;  // (the lane's array: once decode_on_device has grown it)
+        if (ranged && !sb.on_device && has_call()) {  // (host route of a ranges call: the slot's stage; without it the members fail like a slot without arrays)
+            if (sl.buf[Slot::kStage].grow(R.G.lanes[0].ctx, (size_t)pcm_elems, elem)) out_at = sl.stage();
+            else R.fail_members(sb, VPZM_E_SYNTH, "vpzm_decode_ranges: the page-locked PCM stage could not be allocated");
+        }
     }
 
     // A device-decoded sub-batch's first two steps on the lane's stream: the packet bytes go up, vpz_entropy_decode writes residue,
@@ -991,7 +1028,9 @@ struct SubCall {
         // (`_currentPosition = 0; _hasPosition = true`, StreamDecoder.cs:165-168) -- a bare reset would leave the position to be
         // picked up from the first granule the way a seek does (:459-463), which moves the EOS trim (:658-666)
         int r = vpz_decoder_reset(dec, -1);
-        for (int sidx = 0; sidx < S && r == VPZ_OK; ++sidx) r = vpz_decoder_set_position(dec, sidx, 0);
+        // -- every member's stream at the position its window starts from (Job::position: 0 for a whole stream)
+        for (int sidx = 0; sidx < S && r == VPZ_OK; ++sidx)
+            r = vpz_decoder_set_position(dec, sidx, (size_t)sidx < sb.members.size() ? job((size_t)sidx).position : 0);
         if (r == VPZ_OK && st.f0_stride > 0)
             r = vpz_decoder_set_floor0_data(dec, sl.f0_amp() + (size_t)p0 * C, sl.f0_coeff() + (size_t)p0 * C * st.f0_stride, st.f0_stride);
         if (r == VPZ_OK) r = vpz_decoder_set_residue_format(dec, R.use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32);
@@ -1017,7 +1056,7 @@ struct SubCall {
     // the sub-batch as ONE synth call
     void call_batch()
     {
-        if (!has_call() || R.sw.no_synth) return;
+        if (!has_call() || R.sw.no_synth || !out_at) return;  // (no out_at: a ranges call whose stage could not be had; its members have their status)
         dec = R.decoder_for(L, sb.st);
         const int rc = !dec ? kNoDecoder : R.sw.fail_batch_calls ? VPZ_E_CAPACITY : call(0, n_pk);
         if (rc == VPZ_OK) written = wr;
@@ -1035,32 +1074,44 @@ struct SubCall {
             int64_t q = p;
             while (q < n_pk && packets[q].stream == sid) ++q;
             if (sid >= 0 && (size_t)sid < sb.members.size()) {
-                member_rc[(size_t)sid] = q - p == n_pk && !R.sw.fail_batch_calls ? batch_rc : call(p, q - p);
+                const bool again = q - p != n_pk || R.sw.fail_batch_calls;  // (a member that WAS the batch has had its call)
+                member_rc[(size_t)sid] = again ? call(p, q - p) : batch_rc;
+                member_calls += again;
                 if (member_rc[(size_t)sid] == VPZ_OK) written[(size_t)sid] = wr[(size_t)sid];
             }
             p = q;
         }
     }
 
-    // device route: every member's PCM to the caller's area, what samples_written says and no more -- one copy per member that has
-    // samples (the areas in the lane's array have a block of slack between them, the caller's areas whatever the caller likes)
+    // Every member's PCM from where the call left it to the caller's area -- one copy per member that has samples.  A library call has
+    // something to copy on the device route only (the areas in the lane's array have a block of slack between them, the caller's areas
+    // whatever the caller likes): what samples_written says and no more, a synchronising vpz_memcpy_d2h each.  A ranges call copies on
+    // both routes, and member j gets min(wanted, written - roll) samples from `roll` samples into its area -- what its window's packets
+    // gave after the roll, never more than it asked for; `written` becomes that count.  Its device route queues a vpz_pcm_download per
+    // member and synchronises once; its host route is a memcpy per member from the slot's stage.
     void download()
     {
-        const bool down = sb.on_device && has_call();
-        if (down && R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the call's own time)
+        const bool dev = sb.on_device && has_call();
+        if (dev && R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the call's own time)
         t_call = seconds_since(t0) - t_upload - t_entropy;
-        if (!down) return;
+        if (!dev && !ranged) return;
         const auto t_down = Clock::now();
         for (size_t j = 0; j < sb.members.size(); ++j) {
-            if (!live(j) || member_rc[j] != VPZ_OK || written[j] <= 0) continue;
-            if (vpz_memcpy_d2h(L.ctx, static_cast<char *>(R.pcm_out) + elem * (size_t)R.pcm_offset[job(j).k], L.pcm() + elem * (size_t)offs[j],
-                               (uint64_t)(written[j] * C) * elem) != VPZ_OK) {
-                R.m->fail(std::string("vpz_memcpy_d2h: ") + vpz_context_last_error(L.ctx));
+            if (!live(j) || member_rc[j] != VPZ_OK) continue;
+            const Job &J = job(j);
+            if (ranged) written[j] = std::max<int64_t>(0, std::min(J.wanted, written[j] - J.roll));
+            if (written[j] <= 0) continue;
+            char *to = static_cast<char *>(R.pcm_out) + elem * (size_t)R.pcm_offset[J.k];
+            const size_t from = elem * (size_t)(offs[j] + J.roll * C), bytes = elem * (size_t)(written[j] * C);  // (a whole stream rolls 0)
+            if (!dev) {
+                memcpy(to, static_cast<char *>(out_at) + from, bytes);
+            } else if ((ranged ? vpz_pcm_download(L.ctx, to, L.pcm() + from, bytes) : vpz_memcpy_d2h(L.ctx, to, L.pcm() + from, bytes)) != VPZ_OK) {
+                R.m->fail(std::string(ranged ? "vpz_pcm_download: " : "vpz_memcpy_d2h: ") + vpz_context_last_error(L.ctx));
                 member_rc[j] = VPZ_E_HIP;
             }
         }
         // (the slot's packet records and the lane's arrays are free again once the stream has drained)
-        if (vpz_context_synchronize(L.ctx) != VPZ_OK)
+        if (dev && vpz_context_synchronize(L.ctx) != VPZ_OK)
             for (size_t j = 0; j < sb.members.size(); ++j)
                 if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
         t_download = seconds_since(t_down);
@@ -1072,11 +1123,11 @@ struct SubCall {
         for (size_t j = 0; j < sb.members.size(); ++j) job(j).close();  // (a device-decoded sub-batch's containers were kept open for the host path after all)
         const double dt = seconds_since(t0), at_ms = seconds_since(R.t_begin) * 1e3;
         if (R.sw.profile && sb.on_device)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu on the device done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, download %.2f ms; %lld packets, %lld payload bytes)\n",
-                    R.slot_index, b, at_ms, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, t_download * 1e3, (long long)n_pk, (long long)sb.payload_bytes);
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu on the device done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, download %.2f ms; %lld packets, %lld payload bytes, %d member calls)\n",
+                    R.slot_index, b, at_ms, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, t_download * 1e3, (long long)n_pk, (long long)sb.payload_bytes, member_calls);
         else if (R.sw.profile)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets)\n", R.slot_index, b, at_ms, dt * 1e3,
-                    (long long)n_pk);
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets, %d member calls)\n", R.slot_index, b, at_ms, dt * 1e3,
+                    (long long)n_pk, member_calls);
         std::lock_guard<std::mutex> lk(R.mu);
         R.t_synth += dt;
         R.n_device_subs += sb.on_device && has_call();
@@ -1184,9 +1235,10 @@ void vpzm_destroy(vpzm_dispatcher *m)
 const char *vpzm_last_error(vpzm_dispatcher *m) { return m ? m->error.c_str() : "null dispatcher"; }
 int vpzm_device_count(vpzm_dispatcher *m) { return m ? (int)m->groups.size() : 0; }
 
-int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, int32_t out_layout,
-                        void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity, vpzm_stream_result *results,
-                        vpzm_stats *stats)
+// vpzm_decode_library (ranges == nullptr: whole streams) and vpzm_decode_ranges
+static int decode_call(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                       int32_t out_layout, void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity,
+                       vpzm_stream_result *results, vpzm_stats *stats)
 {
     if (!m) return VPZM_E_ARG;
     // (slots, contexts and decoder caches belong to one call at a time: a second caller waits here, it is not refused)
@@ -1209,7 +1261,7 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
         for (int d = 0; d < D; ++d) {
             // shard_range (vorbispizza_amd/sharding.py): contiguous, sizes differ by at most one
             const int32_t lo = (int32_t)((int64_t)n * d / D), hi = (int32_t)((int64_t)n * (d + 1) / D);
-            runs.emplace_back(new GroupRun{m, m->groups[(size_t)d], d, lo, hi, data, size, out_layout, pcm_out, pcm_offset,
+            runs.emplace_back(new GroupRun{m, m->groups[(size_t)d], d, lo, hi, data, size, ranges, out_layout, pcm_out, pcm_offset,
                                            pcm_capacity, results, per_device, sw, m->mixed_setups && m->opt.gpu_entropy});
         }
         for (int d = 1; d < D; ++d) threads.emplace_back([&runs, d] { runs[(size_t)d]->run_guarded(); });
@@ -1250,6 +1302,22 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
         }
     }
     return VPZM_OK;
+}
+
+int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, int32_t out_layout,
+                        void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity, vpzm_stream_result *results,
+                        vpzm_stats *stats)
+{
+    return decode_call(m, n, data, size, nullptr, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats);
+}
+
+int vpzm_decode_ranges(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                       int32_t out_layout, void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity,
+                       vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (n > 0 && !ranges) return VPZM_E_ARG;
+    static const vpzm_range none{0, 0};  // (n == 0: a ranges call all the same)
+    return decode_call(m, n, data, size, ranges ? ranges : &none, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats);
 }
 
 int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)

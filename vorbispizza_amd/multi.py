@@ -1,4 +1,4 @@
-"""ctypes view of include/vorbispizza_multi.h and include/vorbispizza_multi_mixed.h -- the in-process multi-device dispatcher of
+"""ctypes view of include/vorbispizza_multi.h, include/vorbispizza_multi_mixed.h and include/vorbispizza_multi_ranges.h -- the in-process multi-device dispatcher of
 libvorbispizza_host.so (one host process, one context group per MI355X, streams partitioned contiguously, no collective).  What a
 C# host P/Invokes; tests and bench.py use it from here."""
 import ctypes as C
@@ -9,6 +9,7 @@ from . import capi, front
 
 OK, E_ARG, E_DEVICE, E_NOMEM = 0, -1, -2, -3
 E_OPEN, E_CAPACITY, E_SYNTH, E_SETUP = -10, -11, -12, -13
+E_RANGE = -14  # (vorbispizza_multi_ranges.h)
 
 
 class Options(C.Structure):
@@ -41,6 +42,8 @@ assert RESULT_DTYPE.itemsize == C.sizeof(StreamResult)
 
 EXPORTED_SYMBOLS = ["vpzm_create", "vpzm_destroy", "vpzm_last_error", "vpzm_device_count", "vpzm_decode_library"]
 MIXED_EXPORTED_SYMBOLS = ["vpzm_set_mixed_setups", "vpzm_last_call_counts"]  # (vorbispizza_multi_mixed.h)
+RANGES_EXPORTED_SYMBOLS = ["vpzm_decode_ranges"]  # (vorbispizza_multi_ranges.h)
+RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
 
@@ -64,6 +67,9 @@ def lib():
             L.vpzm_set_mixed_setups.restype = C.c_int
             L.vpzm_last_call_counts.argtypes = [vp, C.POINTER(CallCounts)]
             L.vpzm_last_call_counts.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges"):
+            L.vpzm_decode_ranges.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges.restype = C.c_int
         _bound = True
     return L
 
@@ -137,4 +143,23 @@ class Dispatcher:
                                        C.byref(stats))
         if rc != OK:
             raise MultiError("vpzm_decode_library failed (status %d): %s" % (rc, self.last_error()))
+        return results, stats
+
+    def decode_ranges(self, datas, ranges, pcm_out, pcm_offset, pcm_capacity, s16=False):
+        """vpzm_decode_ranges: decode_library for a window of every stream.  ranges: per entry (start, count) in samples per
+        channel, count < 0 for "to the end"; entry k's samples land at pcm_out[pcm_offset[k]:], and its results' `samples` says
+        how many, `packets` how many packets were decoded for them.  Returns (results, stats) like decode_library."""
+        n = len(datas)
+        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
+        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
+        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
+        offs = np.ascontiguousarray(pcm_offset, dtype=np.int64)
+        caps = np.ascontiguousarray(pcm_capacity, dtype=np.int64)
+        assert pcm_out.dtype == (np.int16 if s16 else np.float32) and pcm_out.flags["C_CONTIGUOUS"]
+        results = np.zeros(n, dtype=RESULT_DTYPE)
+        stats = Stats()
+        rc = lib().vpzm_decode_ranges(self._h, n, ptrs, sizes, rng.ctypes.data, capi.OUT_INTERLEAVED_S16 if s16 else capi.OUT_INTERLEAVED,
+                                      pcm_out.ctypes.data, offs.ctypes.data, caps.ctypes.data, results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges failed (status %d): %s" % (rc, self.last_error()))
         return results, stats

@@ -3,6 +3,8 @@
 
     dispatcher_probe.py [--gpu-entropy | --mixed | --ab] [--setups K] [--reps N] [--s16-only] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --ranges SAMPLES [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --ranges SAMPLES --batch [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --pack-kernel
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -17,7 +19,12 @@ without vpzm_last_call_counts, taken through VPZ_LIB_DIR, prints none).
 --ranges SAMPLES: one window of SAMPLES samples per stream at a seeded random start, 16-bit PCM, into a dense [streams][SAMPLES][2] array.
 The A/B: vpzm_decode_library of the whole streams followed by slicing on the host (the slicing timed with it) against vpzm_decode_ranges,
 two dispatchers in this process taking turns, --reps times each (default 5), the pair of series run twice; the two dense arrays are
-compared.  Every line gives the median and the extremes of its series: a difference inside the extremes is no difference."""
+compared.  Every line gives the median and the extremes of its series: a difference inside the extremes is no difference.
+--ranges SAMPLES --batch: the same windows delivered as a device tensor [streams][2][SAMPLES], int16.  The A/B: vpzm_decode_ranges into
+page-locked memory (every window placed in its padded row there), torch.from_numpy(...).to(device) and the transposition to planar on the
+device, against vpzm_decode_ranges_batch; two dispatchers taking turns as above, the two tensors compared.
+--pack-kernel: vpz_pcm_pack alone for one sub-batch of 64 one-second stereo windows (44 100 samples from odd offsets of areas a block
+apart), every layout, timed with the context's event timer: median of 20 launches and the bytes it moves."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -33,7 +40,9 @@ ap.add_argument("--setup-packets", type=int, default=300)
 ap.add_argument("--reps", type=int, default=0)
 ap.add_argument("--s16-only", action="store_true")
 ap.add_argument("--ranges", type=int, default=0)
-ap.add_argument("settings", nargs="+")
+ap.add_argument("--batch", action="store_true")
+ap.add_argument("--pack-kernel", action="store_true")
+ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
 raws = [np.frombuffer(open(os.path.join(ROOT, "tests", "golden", n), "rb").read(), dtype=np.uint8) for n, _ in bench.REAL_FIXTURES]
@@ -134,8 +143,79 @@ def ranges_job(samples):
             d.close()
 
 
+def batch_job(samples):
+    import time
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n = len(datas)
+    padded = torch.zeros((n, samples, 2), dtype=torch.int16, pin_memory=True)  # (frames = SAMPLES: a row is one window, placed by its offset)
+    d_offs, d_caps = np.arange(n, dtype=np.int64) * samples * 2, np.full(n, samples, dtype=np.int64)
+    out = [None, None]
+
+    def by_ranges_and_upload(d):
+        t0 = time.perf_counter()
+        res, st = d.decode_ranges(datas, windows, padded.numpy().reshape(-1), d_offs, d_caps, s16=True)
+        out[0] = torch.from_numpy(padded.numpy()).to("cuda:0", non_blocking=True).permute(0, 2, 1).contiguous()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res, st
+
+    def by_batch(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_batch(datas, windows, 2, samples, planar=True, s16=True)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "s16 groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_ranges_and_upload(ds[0]), lambda: by_batch(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders and device arrays are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == samples).all()
+        assert torch.equal(out[0], out[1]), "the batch differs from the uploaded windows"
+        print("%s:\n    a tensor of %.1f MB, pinned %d MiB, %d streams on the device" % (
+            what, out[1].numel() * 2 / 1e6, st.pinned_mib, int(sum(st.device_gpu_entropy_streams))), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges + upload %s; decode_ranges_batch %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def pack_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, samples, area = 64, 44100, 44100 + 2 * 2048
+    rows = [(k * area * 2 + 2 * (2 * k + 1) + 1 - 1, samples, k) for k in range(n)]  # (an odd number of samples into every area)
+    for name, lay, dtype in (("planar f32", capi.OUT_PLANAR, torch.float32), ("interleaved f32", capi.OUT_INTERLEAVED, torch.float32),
+                             ("planar s16", capi.OUT_PLANAR_S16, torch.int16), ("interleaved s16", capi.OUT_INTERLEAVED_S16, torch.int16)):
+        src = (torch.rand(n * area * 2, device="cuda:0") * 2000 - 1000).to(dtype)
+        planar = lay in (capi.OUT_PLANAR, capi.OUT_PLANAR_S16)
+        dst = torch.empty((n, 2, samples) if planar else (n, samples, 2), dtype=dtype, device="cuda:0")
+        times = []
+        for _ in range(21):
+            ctx.timer_start()
+            assert capi.pcm_pack(ctx, src, rows, dst, lay) == capi.OK, ctx.last_error()
+            times.append(ctx.timer_stop())
+        want = torch.stack([src[a: a + samples * 2].view(samples, 2) for a, _, _ in rows])
+        assert torch.equal(dst, want.permute(0, 2, 1) if planar else want)
+        moved = 2 * dst.numel() * dst.element_size()  # (read once, written once)
+        ms = statistics.median(times[1:])
+        print("vpz_pcm_pack %-16s 64 windows of 44100 stereo samples: median %.1f us (min %.1f, max %.1f) for %.2f MB read + written = %.0f GB/s" % (
+            name, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, moved / 1e6, moved / ms / 1e6), flush=True)
+    ctx.close()
+
+
+if args.pack_kernel:
+    pack_kernel_job()
+    sys.exit(0)
 if args.ranges:
-    ranges_job(args.ranges)
+    (batch_job if args.batch else ranges_job)(args.ranges)
     sys.exit(0)
 
 for s16 in ((True,) if args.s16_only else (False, True)):

@@ -100,8 +100,14 @@ _DEBUG_SIGNATURES = [
 _PCM_SIGNATURES = [
     ("vpz_pcm_download", C.c_int, [_vp, _vp, _vp, C.c_uint64]),
 ]
+# include/vorbispizza_pcm_pack.h (a header of its own, like vorbispizza_pcm.h)
+_PCM_PACK_SIGNATURES = [
+    ("vpz_pcm_pack", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int64, C.c_int64, C.c_int32]),
+]
+PACK_ROW_DTYPE = np.dtype([("src", "<i8"), ("samples", "<i8"), ("row", "<i8")])  # vpz_pack_row
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
+PCM_PACK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_PACK_SIGNATURES]
 DEBUG_SYMBOLS = [s[0] for s in _DEBUG_SIGNATURES]
 
 _lib = None
@@ -130,8 +136,8 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + _PCM_SIGNATURES:
-            if (name, restype, argtypes) in _PCM_SIGNATURES and not hasattr(L, name):
+        for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + _PCM_SIGNATURES + _PCM_PACK_SIGNATURES:
+            if (name, restype, argtypes) in _PCM_SIGNATURES + _PCM_PACK_SIGNATURES and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
             fn = getattr(L, name)
             fn.restype = restype
@@ -238,6 +244,18 @@ class Context:
             out = np.empty((count, n), dtype=np.float32)
         self._check(lib().vpz_imdct_batch(self._h, n, count, _ptr(spectra), _ptr(out), MEM_HOST, mode))
         return out
+
+
+def pcm_pack(ctx, src, rows, dst, layout):
+    """vpz_pcm_pack (vorbispizza_pcm_pack.h): windows of the device array `src` (a torch tensor, interleaved [sample][channel], float32 or
+    int16) into rows of `dst`, a contiguous torch tensor [rows, channels, frames] (OUT_PLANAR / OUT_PLANAR_S16) or [rows, frames, channels]
+    (the interleaved layouts); rows: [(src, samples, row)].  Asynchronous on the context's stream; returns the status (OK or
+    E_INVALID_ARG and the like: a refusal is an answer here, not an exception)."""
+    planar = layout in (OUT_PLANAR, OUT_PLANAR_S16)
+    dst_rows, channels, frames = (dst.shape[0], dst.shape[1], dst.shape[2]) if planar else (dst.shape[0], dst.shape[2], dst.shape[1])
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_pack(ctx._h, _ptr(src), _numel(src), channels, desc.shape[0], desc.ctypes.data, _ptr(dst), dst_rows, frames, layout)
 
 
 def make_packets(count):

@@ -51,12 +51,19 @@ struct Context {
     // persistent grids of the IMDCT kernels on THIS context's device (workgroups the chip keeps resident), filled by the first
     // launch of each; per context, not per process: a host with several GPUs holds one context per device
     int resident[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // vpz_pcm_pack (pcm_pack.hip): its row descriptors go up through a page-locked buffer of the context's; `pack_done` says that the
+    // last call's copy has left it
+    void *pack_host = nullptr, *pack_dev = nullptr;
+    size_t pack_cap = 0;  // descriptors both hold
+    hipEvent_t pack_done = nullptr;
+    bool pack_pending = false;
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
 int set_error(Context *ctx, int status, const char *what, hipError_t e = hipSuccess);
 int get_tables(Context *ctx, int n, BlockTables **out);
 int ensure_stage(Context *ctx, void **buf, size_t *have, size_t need);
+void free_pack_scratch(Context *ctx);  // (pcm_pack.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

@@ -28,6 +28,10 @@
 // and its download trims every member's window out of its area (device route: an asynchronous vpz_pcm_download per member, one
 // synchronise for the sub-batch).
 //
+// vpzm_decode_ranges_batch (include/vorbispizza_multi_batch.h) is a ranges call whose PCM never comes down: both routes stage it in the
+// lane's device array (the host route uploads its slot's decoded arrays and makes a device-memory synth call), and the `download` stage
+// is one vpz_pcm_pack per sub-batch, which trims every member's window into its row of the caller's device tensor and zero-fills the rest.
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
@@ -49,7 +53,9 @@
 #include "../../include/vorbispizza_multi.h"
 #include "../../include/vorbispizza_multi_mixed.h"
 #include "../../include/vorbispizza_multi_ranges.h"
+#include "../../include/vorbispizza_multi_batch.h"
 #include "../../include/vorbispizza_pcm.h"
+#include "../../include/vorbispizza_pcm_pack.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -245,13 +251,16 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     // what a device-decoded sub-batch keeps on the device: packet bytes in, residue / posts / counts between the two calls, PCM out
     SetupCache<vpz_entropy_setup> esetups{vpz_entropy_setup_destroy, {}};
     SetupCache<vpz_entropy_group> egroups{vpz_entropy_group_destroy, {}};  // mixed_setups: the groups of the merged setups, kept alike
-    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kBuffers };
-    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
+    // (kF0Amp, kF0Coeff: a batch call's host route uploads a type-0 floor's data beside residue, posts and counts)
+    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kBuffers };
+    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
     float *residue() const { return static_cast<float *>(buf[kResidue].p); }  // (float32 or int16 values; the ABI's parameter is float-typed)
     int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
     uint8_t *counts() const { return static_cast<uint8_t *>(buf[kCounts].p); }
     char *pcm() const { return static_cast<char *>(buf[kPcm].p); }
+    float *f0_amp() const { return static_cast<float *>(buf[kF0Amp].p); }
+    float *f0_coeff() const { return static_cast<float *>(buf[kF0Coeff].p); }
 };
 
 struct Slot {  // page-locked batch arrays of one sub-batch in flight (a device-decoded one holds packets, spans and payload only)
@@ -330,11 +339,20 @@ struct Job {  // one stream of the library inside its group
     int part = 0;  // mixed_setups: which part of its class's merged setup its own setup is
     int32_t status = VPZM_OK;
     bool finished = false;  // its PCM has been written (or it has its own failure status): what an aborted run leaves alone
+    bool row_packed = false;  // a batch call: a pack launch has defined its row (the others get their zeros when the run ends)
     void close()
     {
         if (h) vpzh_close(h);
         h = nullptr;
     }
+};
+
+// vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
+// `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
+struct Batch {
+    int32_t channels = 0, layout = 0;
+    int64_t frames = 0;
+    void *dst = nullptr;
 };
 
 struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
@@ -378,6 +396,9 @@ struct GroupRun {
     int threads;
     const Switches sw;
     const bool mixed;  // the dispatcher's mixed_setups as the call found it, with gpu_entropy
+    Batch batch{};     // (decode_call fills it in for a batch call)
+    bool batched() const { return batch.dst != nullptr; }
+    int64_t capacity_of(int32_t k) const { return batched() ? batch.frames : pcm_capacity[k]; }  // samples entry k may deliver
     int lane_host_threads = std::max(1, std::min(8, threads / std::max(1, (int)G.lanes.size())));  // vpz_decoder_set_host_threads of every lane's decoders: the device's threads / its contexts
     double t_wall = 0, t_decode = 0, t_synth = 0;
     int64_t device_streams = 0, device_payload = 0;  // streams entropy-decoded on the device, their packet bytes
@@ -437,7 +458,8 @@ struct GroupRun {
                 J.residue_floats = values;
                 R.packets = J.packets;
             }
-            if (J.wanted > pcm_capacity[J.k]) { J.status = VPZM_E_CAPACITY; return; }
+            if (J.wanted > capacity_of(J.k)) { J.status = VPZM_E_CAPACITY; return; }
+            if (batched() && info.channels != batch.channels) { J.status = VPZM_E_CHANNELS; return; }
             if (J.packets > 0) {
                 J.own = std::make_shared<Setup>();
                 if (!J.own->load(J.h, m->opt.gpu_entropy != 0)) J.status = VPZM_E_SETUP;
@@ -791,6 +813,33 @@ struct GroupRun {
     }
     void synth_sub(Lane &L, size_t b, Sub &sb);  // (SubCall's stages, below)
 
+    // A batch call, the run's threads joined: the rows no sub-batch's pack has defined become zeros in ONE launch of samples = 0
+    // descriptors on the group's first lane -- entries that never reached a sub-batch (open failure, range, capacity, channel count, an
+    // empty window) and whatever a failed pack or an aborted run left -- and the lanes' streams drain.  Without it (no memory for the
+    // descriptors, a failed launch) the entries concerned say so: VPZM_E_SYNTH
+    void zero_rows() noexcept
+    {
+        bool ok = true;
+        try {
+            std::vector<vpz_pack_row> rows;
+            for (const Job &J : jobs)
+                if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
+            // (a launch that reads nothing: the destination stands in for a source of no elements)
+            if (!rows.empty())
+                ok = vpz_pcm_pack(G.lanes[0].ctx, batch.dst, 0, batch.channels, (int32_t)rows.size(), rows.data(), batch.dst, (int64_t)jobs.size(),
+                                  batch.frames, batch.layout) == VPZ_OK;
+            if (!ok) m->fail(std::string("vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+        } catch (...) {
+            ok = false;
+        }
+        for (Lane &L : G.lanes) ok = vpz_context_synchronize(L.ctx) == VPZ_OK && ok;
+        for (size_t i = 0; !ok && i < jobs.size(); ++i)
+            if (!jobs[i].row_packed && jobs[i].status == VPZM_OK) {
+                jobs[i].status = VPZM_E_SYNTH;
+                results[lo + (int32_t)i].samples = 0;
+            }
+    }
+
     // run() for a thread of its own: whatever it throws before its pipeline stands (the job table's allocation) becomes the
     // statuses of the group's streams, never an exception out of the thread
     void run_guarded() noexcept
@@ -846,6 +895,7 @@ struct GroupRun {
             guarded([this] { issuer(G.lanes[0]); });
         }
         for (std::thread &t : pool) t.join();
+        if (batched()) zero_rows();
         for (Job &J : jobs) {
             J.close();
             if (aborted && J.status == VPZM_OK && !J.finished) {  // (an aborted run: no PCM, no count -- the stream has no result)
@@ -873,6 +923,8 @@ struct SubCall {
     const int C = st.info.channels, S = R.m->call_streams();  // channels; the streams a decoder is created for
     const size_t elem = R.out_layout == VPZ_OUT_INTERLEAVED_S16 ? sizeof(int16_t) : sizeof(float);  // bytes of a PCM sample
     const bool ranged = R.ranges != nullptr;  // a vpzm_decode_ranges call: staged PCM on both routes, windows trimmed in `download`
+    const bool batched = R.batched();         // ... a vpzm_decode_ranges_batch call: staged in the lane's device array on both routes, packed in `download`
+    bool inputs_on_device = false;            // the synth call reads the lane's device arrays (decode_on_device, upload_decoded) and is a VPZ_MEM_DEVICE call
     bool any = false;  // ---- repack: a member is left ...
     int64_t n_pk = 0;  // ... and the packets of those that are
     // ---- place_outputs: every member's area (offset and capacity in samples), where the areas start, the largest capacity, all the areas
@@ -938,7 +990,7 @@ struct SubCall {
     {
         const bool dev = sb.on_device || ranged;  // (the areas are the call's own, not the caller's)
         int64_t base = INT64_MAX, dev_at = 0;
-        for (size_t j = 0; j < sb.members.size(); ++j) base = std::min(base, R.pcm_offset[job(j).k]);
+        for (size_t j = 0; !dev && j < sb.members.size(); ++j) base = std::min(base, R.pcm_offset[job(j).k]);
         cap = 0;
         for (size_t j = 0; j < sb.members.size(); ++j) {
             const Job &J = job(j);
@@ -953,7 +1005,7 @@ struct SubCall {
         }
         pcm_elems = dev_at;
         out_at = dev ? nullptr : static_cast<char *>(R.pcm_out) + elem * (size_t)base;  // (the lane's array: once decode_on_device has grown it)
-        if (ranged && !sb.on_device && has_call()) {  // (host route of a ranges call: the slot's stage; without it the members fail like a slot without arrays)
+        if (ranged && !batched && !sb.on_device && has_call()) {  // (host route of a ranges call: the slot's stage; without it the members fail like a slot without arrays)
             if (sl.buf[Slot::kStage].grow(R.G.lanes[0].ctx, (size_t)pcm_elems, elem)) out_at = sl.stage();
             else R.fail_members(sb, VPZM_E_SYNTH, "vpzm_decode_ranges: the page-locked PCM stage could not be allocated");
         }
@@ -1004,7 +1056,33 @@ struct SubCall {
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the stage's own time; otherwise nothing waits here)
         t_entropy = seconds_since(t_en);
         out_at = L.pcm();
+        inputs_on_device = true;
         return true;
+    }
+
+    // A batch call's host route brings no PCM down, so its synth call is a device-memory one like the device route's: the slot's decoded
+    // arrays -- residue, posts, counts, a type-0 floor's amp and coefficients -- go up into the lane's device arrays (vpz_memcpy_h2d: the
+    // slot is free again when it returns) and the PCM areas lie in the lane's device PCM array.  Without the memory or a copy the members
+    // fail like a slot without arrays
+    void upload_decoded()
+    {
+        const bool i16 = R.use_i16(st);
+        const size_t rec = (size_t)sb.n_packets * (size_t)C;  // (the slot's arrays as they lie: a re-packed sub-batch's calls index them by packet)
+        const size_t res_bytes = (size_t)sb.res_floats * (i16 ? sizeof(int16_t) : sizeof(float)), f0 = (size_t)st.f0_stride;
+        auto up = [&](int which, const void *from, size_t bytes) {
+            return bytes == 0 || (L.buf[which].grow(L.ctx, bytes, 1) && vpz_memcpy_h2d(L.ctx, L.buf[which].p, from, (uint64_t)bytes) == VPZ_OK);
+        };
+        const auto t_up = Clock::now();
+        bool ok = up(Lane::kResidue, sl.residue_f32(), res_bytes) && up(Lane::kPosts, sl.posts(), rec * 64 * sizeof(int16_t)) &&
+                  up(Lane::kCounts, sl.counts(), rec) && L.buf[Lane::kPcm].grow(L.ctx, (size_t)pcm_elems, elem);
+        if (ok && f0 > 0) ok = up(Lane::kF0Amp, sl.f0_amp(), rec * sizeof(float)) && up(Lane::kF0Coeff, sl.f0_coeff(), rec * f0 * sizeof(float));
+        t_upload += seconds_since(t_up);
+        if (!ok) {
+            R.fail_members(sb, VPZM_E_SYNTH, "vpzm_decode_ranges_batch: the decoded arrays of a sub-batch could not be uploaded");
+            return;
+        }
+        out_at = L.pcm();
+        inputs_on_device = true;
     }
 
     // the host path after all: the slot gets the host arrays, this thread decodes the members (their containers are still open), and
@@ -1021,7 +1099,7 @@ struct SubCall {
     // residue offsets are the slot's.  A device-decoded sub-batch's call reads the lane's device arrays, laid out the same way
     int call(int64_t p0, int64_t n)
     {
-        const bool dev = sb.on_device;
+        const bool dev = inputs_on_device;
         const int16_t *posts = dev ? L.posts() : sl.posts();
         const uint8_t *counts = dev ? L.counts() : sl.counts();
         // the decoder is re-used for new streams: back to what a StreamDecoder is after ProcessHeaderPackets
@@ -1032,7 +1110,8 @@ struct SubCall {
         for (int sidx = 0; sidx < S && r == VPZ_OK; ++sidx)
             r = vpz_decoder_set_position(dec, sidx, (size_t)sidx < sb.members.size() ? job((size_t)sidx).position : 0);
         if (r == VPZ_OK && st.f0_stride > 0)
-            r = vpz_decoder_set_floor0_data(dec, sl.f0_amp() + (size_t)p0 * C, sl.f0_coeff() + (size_t)p0 * C * st.f0_stride, st.f0_stride);
+            r = vpz_decoder_set_floor0_data(dec, (dev ? L.f0_amp() : sl.f0_amp()) + (size_t)p0 * C,
+                                            (dev ? L.f0_coeff() : sl.f0_coeff()) + (size_t)p0 * C * st.f0_stride, st.f0_stride);
         if (r == VPZ_OK) r = vpz_decoder_set_residue_format(dec, R.use_i16(st) ? VPZ_RESIDUE_I16 : VPZ_RESIDUE_F32);
         if (r == VPZ_OK) r = vpz_decoder_set_stream_capacities(dec, caps.data(), S);
         if (r == VPZ_OK)
@@ -1088,14 +1167,38 @@ struct SubCall {
     // whatever the caller likes): what samples_written says and no more, a synchronising vpz_memcpy_d2h each.  A ranges call copies on
     // both routes, and member j gets min(wanted, written - roll) samples from `roll` samples into its area -- what its window's packets
     // gave after the roll, never more than it asked for; `written` becomes that count.  Its device route queues a vpz_pcm_download per
-    // member and synchronises once; its host route is a memcpy per member from the slot's stage.
+    // member and synchronises once; its host route is a memcpy per member from the slot's stage.  A batch call copies nothing down: one
+    // vpz_pcm_pack on the lane's stream, after whichever calls stand, moves every member's window from the lane's device array into its
+    // row of the group's piece and zero-fills the rest -- a member without samples (failed, or nothing left after the roll) gets a
+    // samples = 0 descriptor; a failed pack costs the sub-batch's members VPZM_E_SYNTH (GroupRun::zero_rows defines their rows).
     void download()
     {
-        const bool dev = sb.on_device && has_call();
+        const bool dev = (sb.on_device || batched) && has_call();
         if (dev && R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the call's own time)
         t_call = seconds_since(t0) - t_upload - t_entropy;
         if (!dev && !ranged) return;
         const auto t_down = Clock::now();
+        if (batched) {
+            const bool staged = has_call() && out_at == L.pcm() && out_at;  // (else: no call was made, the lane's array may not even exist)
+            std::vector<vpz_pack_row> rows;
+            for (size_t j = 0; j < sb.members.size(); ++j) {
+                const Job &J = job(j);
+                const bool ok = live(j) && member_rc[j] == VPZ_OK && staged;
+                written[j] = ok ? std::max<int64_t>(0, std::min(J.wanted, written[j] - J.roll)) : 0;
+                rows.push_back(vpz_pack_row{written[j] > 0 ? offs[j] + J.roll * C : 0, written[j], (int64_t)(J.k - R.lo)});
+            }
+            // (no staged PCM: a launch that reads nothing -- the destination stands in for a source of no elements)
+            int rc = vpz_pcm_pack(L.ctx, staged ? (const void *)L.pcm() : R.batch.dst, staged ? pcm_elems : 0, C, (int32_t)rows.size(), rows.data(),
+                                  R.batch.dst, (int64_t)(R.hi - R.lo), R.batch.frames, R.batch.layout);
+            if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_pack: ") + vpz_context_last_error(L.ctx));
+            if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
+            for (size_t j = 0; j < sb.members.size(); ++j) {
+                if (rc == VPZ_OK) job(j).row_packed = true;
+                else if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
+            }
+            t_download = seconds_since(t_down);
+            return;
+        }
         for (size_t j = 0; j < sb.members.size(); ++j) {
             if (!live(j) || member_rc[j] != VPZ_OK) continue;
             const Job &J = job(j);
@@ -1122,9 +1225,10 @@ struct SubCall {
     {
         for (size_t j = 0; j < sb.members.size(); ++j) job(j).close();  // (a device-decoded sub-batch's containers were kept open for the host path after all)
         const double dt = seconds_since(t0), at_ms = seconds_since(R.t_begin) * 1e3;
-        if (R.sw.profile && sb.on_device)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu on the device done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, download %.2f ms; %lld packets, %lld payload bytes, %d member calls)\n",
-                    R.slot_index, b, at_ms, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, t_download * 1e3, (long long)n_pk, (long long)sb.payload_bytes, member_calls);
+        if (R.sw.profile && (sb.on_device || batched))  // (a batch call's host route has the device route's stages but the entropy decode: upload, synth, pack)
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, %s %.2f ms; %lld packets, %lld payload bytes, %d member calls)\n",
+                    R.slot_index, b, sb.on_device ? "on the device" : "uploaded", at_ms, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, batched ? "pack" : "download",
+                    t_download * 1e3, (long long)n_pk, (long long)sb.payload_bytes, member_calls);
         else if (R.sw.profile)
             fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets, %d member calls)\n", R.slot_index, b, at_ms, dt * 1e3,
                     (long long)n_pk, member_calls);
@@ -1159,6 +1263,7 @@ void GroupRun::synth_sub(Lane &L, size_t b, Sub &sb)
     c.t0 = Clock::now();
     c.place_outputs();
     if (sb.on_device && c.has_call() && !c.decode_on_device()) c.decode_on_host();
+    if (c.batched && !sb.on_device && c.has_call()) c.upload_decoded();
     c.call_batch();
     c.download();
     c.account();
@@ -1235,19 +1340,34 @@ void vpzm_destroy(vpzm_dispatcher *m)
 const char *vpzm_last_error(vpzm_dispatcher *m) { return m ? m->error.c_str() : "null dispatcher"; }
 int vpzm_device_count(vpzm_dispatcher *m) { return m ? (int)m->groups.size() : 0; }
 
-// vpzm_decode_library (ranges == nullptr: whole streams) and vpzm_decode_ranges
+// the partition rule, its one statement: group g of D decodes entries [lo, hi) of n -- shard_range (vorbispizza_amd/sharding.py):
+// contiguous, sizes differ by at most one
+static void partition(int32_t n, int g, int D, int32_t *lo, int32_t *hi)
+{
+    *lo = (int32_t)((int64_t)n * g / D);
+    *hi = (int32_t)((int64_t)n * (g + 1) / D);
+}
+
+// vpzm_decode_library (ranges == nullptr: whole streams), vpzm_decode_ranges and vpzm_decode_ranges_batch (batch != nullptr: its channels,
+// frames and layout; group_dst: every group's piece, and no host array -- out_layout is then what the synth calls write, interleaved)
 static int decode_call(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                        int32_t out_layout, void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity,
-                       vpzm_stream_result *results, vpzm_stats *stats)
+                       vpzm_stream_result *results, vpzm_stats *stats, const Batch *batch = nullptr, void *const *group_dst = nullptr)
 {
     if (!m) return VPZM_E_ARG;
     // (slots, contexts and decoder caches belong to one call at a time: a second caller waits here, it is not refused)
     std::lock_guard<std::mutex> one_call(m->call_mu);
     m->counts = vpzm_call_counts{};  // (of THIS call from here on, however it ends)
-    if (n < 0 || !results || (n > 0 && (!data || !size || !pcm_out || !pcm_offset || !pcm_capacity))) return VPZM_E_ARG;
+    if (n < 0 || !results || (n > 0 && (!data || !size))) return VPZM_E_ARG;
+    if (!batch && n > 0 && (!pcm_out || !pcm_offset || !pcm_capacity)) return VPZM_E_ARG;
     if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_INTERLEAVED_S16) return VPZM_E_ARG;
     for (int32_t k = 0; k < n; ++k)
-        if (!data[k] || pcm_offset[k] < 0 || pcm_capacity[k] < 0) return VPZM_E_ARG;
+        if (!data[k] || (!batch && (pcm_offset[k] < 0 || pcm_capacity[k] < 0))) return VPZM_E_ARG;
+    for (int d = 0; batch && d < (int)m->groups.size(); ++d) {  // (a group without rows needs no piece)
+        int32_t lo, hi;
+        partition(n, d, (int)m->groups.size(), &lo, &hi);
+        if (hi > lo && !group_dst[d]) return VPZM_E_ARG;
+    }
     // (the fields appended for gpu_entropy exist for a caller that sets the option; an older caller's struct ends before them)
     if (stats) memset(stats, 0, m->opt.gpu_entropy ? sizeof *stats : offsetof(vpzm_stats, device_gpu_entropy_streams));
     m->error.clear();
@@ -1259,10 +1379,14 @@ static int decode_call(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data
     std::vector<std::thread> threads;
     try {
         for (int d = 0; d < D; ++d) {
-            // shard_range (vorbispizza_amd/sharding.py): contiguous, sizes differ by at most one
-            const int32_t lo = (int32_t)((int64_t)n * d / D), hi = (int32_t)((int64_t)n * (d + 1) / D);
+            int32_t lo, hi;
+            partition(n, d, D, &lo, &hi);
             runs.emplace_back(new GroupRun{m, m->groups[(size_t)d], d, lo, hi, data, size, ranges, out_layout, pcm_out, pcm_offset,
                                            pcm_capacity, results, per_device, sw, m->mixed_setups && m->opt.gpu_entropy});
+            if (batch && hi > lo) {
+                runs.back()->batch = *batch;
+                runs.back()->batch.dst = group_dst[d];
+            }
         }
         for (int d = 1; d < D; ++d) threads.emplace_back([&runs, d] { runs[(size_t)d]->run_guarded(); });
         runs[0]->run_guarded();
@@ -1318,6 +1442,31 @@ int vpzm_decode_ranges(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data
     if (n > 0 && !ranges) return VPZM_E_ARG;
     static const vpzm_range none{0, 0};  // (n == 0: a ranges call all the same)
     return decode_call(m, n, data, size, ranges ? ranges : &none, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats);
+}
+
+int vpzm_batch_partition(vpzm_dispatcher *m, int32_t n, int32_t group, int32_t *lo, int32_t *hi)
+{
+    if (!m || !lo || !hi || n < 0 || group < 0 || group >= (int32_t)m->groups.size()) return VPZM_E_ARG;
+    partition(n, group, (int)m->groups.size(), lo, hi);
+    return VPZM_OK;
+}
+
+int vpzm_decode_ranges_batch(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                             int32_t channels, int64_t frames, int32_t out_layout, void *const *group_dst, vpzm_stream_result *results,
+                             vpzm_stats *stats)
+{
+    if (!group_dst || channels < 1 || channels > VPZ_MAX_CHANNELS || frames < 1 || (n > 0 && !ranges)) return VPZM_E_ARG;
+    if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_PLANAR && out_layout != VPZ_OUT_INTERLEAVED_S16 && out_layout != VPZ_OUT_PLANAR_S16)
+        return VPZM_E_ARG;
+    const bool s16 = out_layout == VPZ_OUT_INTERLEAVED_S16 || out_layout == VPZ_OUT_PLANAR_S16;
+    static const vpzm_range none{0, 0};
+    Batch batch;
+    batch.channels = channels;
+    batch.layout = out_layout;
+    batch.frames = frames;
+    // (the synth calls write their areas interleaved, in the batch's element type; the pack step gives the rows their layout)
+    return decode_call(m, n, data, size, ranges ? ranges : &none, s16 ? VPZ_OUT_INTERLEAVED_S16 : VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr,
+                       results, stats, &batch, group_dst);
 }
 
 int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)

@@ -1,4 +1,4 @@
-"""ctypes view of include/vorbispizza_multi.h, include/vorbispizza_multi_mixed.h and include/vorbispizza_multi_ranges.h -- the in-process multi-device dispatcher of
+"""ctypes view of include/vorbispizza_multi.h, include/vorbispizza_multi_mixed.h, include/vorbispizza_multi_ranges.h and include/vorbispizza_multi_batch.h -- the in-process multi-device dispatcher of
 libvorbispizza_host.so (one host process, one context group per MI355X, streams partitioned contiguously, no collective).  What a
 C# host P/Invokes; tests and bench.py use it from here."""
 import ctypes as C
@@ -10,6 +10,7 @@ from . import capi, front
 OK, E_ARG, E_DEVICE, E_NOMEM = 0, -1, -2, -3
 E_OPEN, E_CAPACITY, E_SYNTH, E_SETUP = -10, -11, -12, -13
 E_RANGE = -14  # (vorbispizza_multi_ranges.h)
+E_CHANNELS = -15  # (vorbispizza_multi_batch.h)
 
 
 class Options(C.Structure):
@@ -43,6 +44,7 @@ assert RESULT_DTYPE.itemsize == C.sizeof(StreamResult)
 EXPORTED_SYMBOLS = ["vpzm_create", "vpzm_destroy", "vpzm_last_error", "vpzm_device_count", "vpzm_decode_library"]
 MIXED_EXPORTED_SYMBOLS = ["vpzm_set_mixed_setups", "vpzm_last_call_counts"]  # (vorbispizza_multi_mixed.h)
 RANGES_EXPORTED_SYMBOLS = ["vpzm_decode_ranges"]  # (vorbispizza_multi_ranges.h)
+BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  # (vorbispizza_multi_batch.h)
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
@@ -70,6 +72,11 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges"):
             L.vpzm_decode_ranges.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp, vp, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_batch"):
+            L.vpzm_batch_partition.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            L.vpzm_batch_partition.restype = C.c_int
+            L.vpzm_decode_ranges_batch.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_batch.restype = C.c_int
         _bound = True
     return L
 
@@ -96,6 +103,7 @@ class Dispatcher:
             self._h = None
             raise MultiError("vpzm_create failed (status %d)" % rc)
         self.n_devices = len(device_ids)
+        self.device_ids = [int(d) for d in device_ids]
         if mixed_setups:
             self.set_mixed_setups(True)
 
@@ -163,3 +171,57 @@ class Dispatcher:
         if rc != OK:
             raise MultiError("vpzm_decode_ranges failed (status %d): %s" % (rc, self.last_error()))
         return results, stats
+
+    def batch_partition(self, n, group):
+        """vpzm_batch_partition: the entries [lo, hi) of an n-entry call that group `group` decodes"""
+        lo, hi = C.c_int32(), C.c_int32()
+        rc = lib().vpzm_batch_partition(self._h, n, group, C.byref(lo), C.byref(hi))
+        if rc != OK:
+            raise MultiError("vpzm_batch_partition failed (status %d)" % rc)
+        return lo.value, hi.value
+
+    def decode_ranges_batch(self, datas, ranges, channels, frames, planar=True, s16=False, out=None):
+        """vpzm_decode_ranges_batch: decode_ranges delivered as a zero-padded batch in device memory.  Entry k's window becomes row k:
+        [channels, frames] (planar) or [frames, channels], float32 or int16 (s16), its samples first, zeros behind them.
+        out: a list of torch tensors, one per group, on that group's device, contiguous, of shape [hi - lo, channels, frames] (or
+        [hi - lo, frames, channels]) for the group's entries [lo, hi) (batch_partition) -- anything else raises before the library is
+        called.  Without `out` the method allocates: when all groups share a device, one tensor whose consecutive pieces the groups get.
+        Returns (parts, whole_or_None, results, stats)."""
+        import torch
+        n = len(datas)
+        ids = self.device_ids  # (a group's HIP device id is its torch device index)
+        dtype = torch.int16 if s16 else torch.float32
+        cuts = [self.batch_partition(n, g) for g in range(self.n_devices)]
+        shape = (lambda rows: (rows, channels, frames)) if planar else (lambda rows: (rows, frames, channels))
+        if channels < 1 or frames < 1:
+            raise ValueError("decode_ranges_batch: channels and frames must be at least 1")
+        whole = None
+        if out is None:
+            if len(set(ids)) == 1:
+                whole = torch.empty(shape(n), dtype=dtype, device="cuda:%d" % ids[0])
+                out = [whole[lo:hi] for lo, hi in cuts]
+            else:
+                out = [torch.empty(shape(hi - lo), dtype=dtype, device="cuda:%d" % d) for (lo, hi), d in zip(cuts, ids)]
+        if len(out) != self.n_devices:
+            raise ValueError("decode_ranges_batch: out needs one tensor per group (%d), got %d" % (self.n_devices, len(out)))
+        for g, (t, (lo, hi), d) in enumerate(zip(out, cuts, ids)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != d:
+                raise ValueError("decode_ranges_batch: out[%d] is not a tensor on the group's device cuda:%d" % (g, d))
+            if tuple(t.shape) != shape(hi - lo) or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError("decode_ranges_batch: out[%d] must be a contiguous %s tensor of shape %s" % (g, dtype, shape(hi - lo)))
+        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
+        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
+        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
+        dst = (C.c_void_p * self.n_devices)(*[t.data_ptr() if t.numel() else None for t in out])
+        layout = {(True, False): capi.OUT_PLANAR, (False, False): capi.OUT_INTERLEAVED, (True, True): capi.OUT_PLANAR_S16,
+                  (False, True): capi.OUT_INTERLEAVED_S16}[(bool(planar), bool(s16))]
+        # (the library writes on its own streams into memory torch may have just recycled: whatever torch has queued there is done first)
+        for d in sorted(set(ids)):
+            torch.cuda.current_stream(d).synchronize()
+        results = np.zeros(n, dtype=RESULT_DTYPE)
+        stats = Stats()
+        rc = lib().vpzm_decode_ranges_batch(self._h, n, ptrs, sizes, rng.ctypes.data, channels, frames, layout, dst, results.ctypes.data,
+                                            C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_batch failed (status %d): %s" % (rc, self.last_error()))
+        return out, whole, results, stats

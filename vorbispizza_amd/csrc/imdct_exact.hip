@@ -241,7 +241,7 @@ hipError_t launch_imdct_exact(int n, int ld, const float *spectra, float *out, i
 {
     if (count <= 0) return hipSuccess;
     const size_t lds = sizeof(float) * (size_t)(n + n / 2);
-    int64_t cap = (int64_t)num_cu * 4;
+    int64_t cap = (int64_t)num_cu * 4;  // (tests/test_imdct_rounds_gpu.py `capacity` restates this: its batches run several rounds)
     int grid = (int)(count < cap ? count : cap);
     hipLaunchKernelGGL(imdct_exact_kernel, dim3(grid), dim3(kExactThreads), lds, stream, n, ld,
                        spectra, out, (long)count, A, B, C, bitrev, src_off, dst_off);

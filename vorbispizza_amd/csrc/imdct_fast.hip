@@ -290,6 +290,8 @@ __global__ __launch_bounds__(kThreads8192) void imdct8192_kernel(const float *__
 // Persistent grid: exactly as many workgroups as the chip keeps resident (CUs x measured
 // occupancy), so that every workgroup gets the same share of the batch and there is no partial
 // last round of workgroups.
+// (tests/test_imdct_rounds_gpu.py sizes its batches by this rule -- at most 2 workgroups per CU, and the blocks a workgroup takes
+// per step in each kernel above -- so that waves take a third block and a ragged last one: a change here goes with `capacity` there)
 template <typename K>
 static int resident_groups(K kernel, int num_cu, int threads = kThreads)
 {

@@ -5,6 +5,8 @@
     dispatcher_probe.py --ranges SAMPLES [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --ranges SAMPLES --batch [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --pack-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE [--mono] [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --resample-kernel
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -24,7 +26,12 @@ compared.  Every line gives the median and the extremes of its series: a differe
 page-locked memory (every window placed in its padded row there), torch.from_numpy(...).to(device) and the transposition to planar on the
 device, against vpzm_decode_ranges_batch; two dispatchers taking turns as above, the two tensors compared.
 --pack-kernel: vpz_pcm_pack alone for one sub-batch of 64 one-second stereo windows (44 100 samples from odd offsets of areas a block
-apart), every layout, timed with the context's event timer: median of 20 launches and the bytes it moves."""
+apart), every layout, timed with the context's event timer: median of 20 launches and the bytes it moves.
+--ranges SAMPLES --batch --resample RATE: the same windows as a float32 device tensor at RATE Hz ([streams][2][J], or [streams][1][J] with
+--mono).  The A/B: what a loader does without the call -- vpzm_decode_ranges_batch at the source rate, then torch conv1d with the same
+coefficient table (vpz_resample_filter) at stride = down, a reshape and the channels' mean on the device -- against
+vpzm_decode_ranges_resampled; two dispatchers taking turns as above, the largest difference of the two tensors printed.
+--resample-kernel: vpz_pcm_resample alone for the same 64 windows, 44 100 -> 16 000 Hz, every layout and the mono mix."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -42,6 +49,9 @@ ap.add_argument("--s16-only", action="store_true")
 ap.add_argument("--ranges", type=int, default=0)
 ap.add_argument("--batch", action="store_true")
 ap.add_argument("--pack-kernel", action="store_true")
+ap.add_argument("--resample", type=int, default=0)
+ap.add_argument("--mono", action="store_true")
+ap.add_argument("--resample-kernel", action="store_true")
 ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -211,8 +221,106 @@ def pack_kernel_job():
     ctx.close()
 
 
+def conv_table(up, down):
+    """vpz_resample_filter's table as ONE conv1d weight [up][1][W] for stride = down: phase p's taps start floor(p * down / up) + first_tap[p]
+    samples from the frame's first source sample; -> (weight on the device, the padding in front)"""
+    from vorbispizza_amd import capi
+    taps, first, coeffs = capi.resample_filter(up, down)
+    off = np.arange(up, dtype=np.int64) * down // up + first
+    lo, width = int(off.min()), int((off + taps).max() - off.min())
+    weight = np.zeros((up, 1, width), dtype=np.float32)
+    for p in range(up):
+        weight[p, 0, off[p] - lo: off[p] - lo + taps] = coeffs[p]
+    return torch.from_numpy(weight).to("cuda:0"), -lo
+
+
+def resample_job(samples, rate):
+    import math, time
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    state = {}
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, whole, res, st = d.decode_ranges_batch(datas, windows, 2, samples, planar=True, s16=False)
+        if "weight" not in state:  # (every stream of the set has one rate: one ratio, one table, built once like the library's)
+            fs = int(res["sample_rate"][0])
+            assert (res["sample_rate"] == fs).all()
+            g = math.gcd(fs, rate)
+            state["up"], state["down"] = rate // g, fs // g
+            state["weight"], state["front"] = conv_table(state["up"], state["down"])
+        up, down, w = state["up"], state["down"], state["weight"]
+        J = -(-samples * up // down)
+        x = torch.nn.functional.pad(whole.view(n * 2, 1, samples), (state["front"], w.shape[2] + down))
+        y = torch.nn.functional.conv1d(x, w, stride=down).transpose(1, 2).reshape(n, 2, -1)[:, :, :J]
+        out[0] = y.mean(dim=1, keepdim=True) if args.mono else y.contiguous()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res, st
+
+    def by_resampled(d):
+        t0 = time.perf_counter()
+        J = -(-samples * state["up"] // state["down"])
+        _, out[1], res, st = d.decode_ranges_batch(datas, windows, 1 if args.mono else 2, J, planar=True, s16=False, sample_rate=rate, mono=args.mono)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "f32 groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz%s" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate, ", mono" if args.mono else "")
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_resampled(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all()
+        assert out[0].shape == out[1].shape
+        print("%s:\n    ratio %d / %d, a tensor of %.1f MB, largest difference of the two tensors %.3g (largest sample %.3g), %d streams on the device" % (
+            what, state["up"], state["down"], out[1].numel() * 4 / 1e6, float((out[0] - out[1]).abs().max()), float(out[1].abs().max()),
+            int(sum(st.device_gpu_entropy_streams))), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_batch + torch conv1d %s; decode_ranges_resampled %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def resample_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, samples, area, up, down = 64, 44100, 44100 + 2 * 2048, 160, 441
+    J = -(-samples * up // down)
+    rows = [(k * area * 2 + 2 * (2 * k + 1), samples, k) for k in range(n)]
+    src = (torch.rand(n * area, 2, device="cuda:0") * 2 - 1)
+    for name, lay, dtype, mono in (("planar f32", capi.OUT_PLANAR, torch.float32, False), ("interleaved f32", capi.OUT_INTERLEAVED, torch.float32, False),
+                                   ("planar s16", capi.OUT_PLANAR_S16, torch.int16, False), ("interleaved s16", capi.OUT_INTERLEAVED_S16, torch.int16, False),
+                                   ("mono f32", capi.OUT_PLANAR, torch.float32, True), ("mono s16", capi.OUT_PLANAR_S16, torch.int16, True)):
+        co = 1 if mono else 2
+        planar = lay in (capi.OUT_PLANAR, capi.OUT_PLANAR_S16)
+        dst = torch.empty((n, co, J) if planar else (n, J, co), dtype=dtype, device="cuda:0")
+        times = []
+        for _ in range(21):
+            ctx.timer_start()
+            assert capi.pcm_resample(ctx, src, rows, dst, lay, up, down, mono) == capi.OK, ctx.last_error()
+            times.append(ctx.timer_stop())
+        moved = n * samples * 2 * 4 + dst.numel() * dst.element_size()  # (the windows read once, the rows written once)
+        ms = statistics.median(times[1:])
+        print("vpz_pcm_resample %-16s 64 windows of 44100 stereo samples to 16000 Hz: median %.1f us (min %.1f, max %.1f) for %.2f MB read + written = %.0f GB/s" % (
+            name, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, moved / 1e6, moved / ms / 1e6), flush=True)
+    ctx.close()
+
+
 if args.pack_kernel:
     pack_kernel_job()
+    sys.exit(0)
+if args.resample_kernel:
+    resample_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample:
+    resample_job(args.ranges, args.resample)
     sys.exit(0)
 if args.ranges:
     (batch_job if args.batch else ranges_job)(args.ranges)

@@ -28,6 +28,7 @@ SOURCES = {
     "synth_plan.hip": ["-ffp-contract=off"],   # the host plan of a synth call: pass 1 and the run cutting, integers only
     "entropy.hip": ["-ffp-contract=off"],  # the residue sums: plain adds in the CPU front end's order
     "pcm_pack.hip": [],  # vpz_pcm_pack: windows of a device PCM array as a padded batch (a copy: no arithmetic)
+    "pcm_resample.hip": [],  # vpz_pcm_resample: the same delivery at one sample rate (float32 multiply-adds, fused: the tolerance covers them)
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-constant-logical-operand", "-fno-strict-aliasing"]
@@ -52,6 +53,7 @@ def _deps(src):
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_entropy_group.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_pack.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_resample.h"))
     return deps
 
 
@@ -71,7 +73,8 @@ def build_host(force=False, verbose=False):
                    os.path.join(inc, "vorbispizza_entropy.h"), os.path.join(inc, "vorbispizza_entropy_group.h"),
                    os.path.join(inc, "vorbispizza_multi_mixed.h"), os.path.join(inc, "vorbispizza_multi_ranges.h"),
                    os.path.join(inc, "vorbispizza_pcm.h"), os.path.join(inc, "vorbispizza_pcm_pack.h"),
-                   os.path.join(inc, "vorbispizza_multi_batch.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi_batch.h"), os.path.join(inc, "vorbispizza_pcm_resample.h"),
+                   os.path.join(inc, "vorbispizza_multi_resample.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

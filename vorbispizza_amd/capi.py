@@ -105,9 +105,17 @@ _PCM_PACK_SIGNATURES = [
     ("vpz_pcm_pack", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, C.c_int64, C.c_int64, C.c_int32]),
 ]
 PACK_ROW_DTYPE = np.dtype([("src", "<i8"), ("samples", "<i8"), ("row", "<i8")])  # vpz_pack_row
+# include/vorbispizza_pcm_resample.h (a header of its own again)
+_PCM_RESAMPLE_SIGNATURES = [
+    ("vpz_resample_filter", C.c_int, [C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int64]),
+    ("vpz_pcm_resample", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int64, C.c_int32,
+                                   C.c_int64, C.c_int32]),
+]
+RESAMPLE_MAX_UP, RESAMPLE_MAX_DOWN_PER_UP = 1024, 32
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
 PCM_PACK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_PACK_SIGNATURES]
+PCM_RESAMPLE_EXPORTED_SYMBOLS = [s[0] for s in _PCM_RESAMPLE_SIGNATURES]
 DEBUG_SYMBOLS = [s[0] for s in _DEBUG_SIGNATURES]
 
 _lib = None
@@ -136,8 +144,9 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + _PCM_SIGNATURES + _PCM_PACK_SIGNATURES:
-            if (name, restype, argtypes) in _PCM_SIGNATURES + _PCM_PACK_SIGNATURES and not hasattr(L, name):
+        later = _PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES
+        for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
+            if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
             fn = getattr(L, name)
             fn.restype = restype
@@ -256,6 +265,34 @@ def pcm_pack(ctx, src, rows, dst, layout):
     desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
     _sync_producer(src, dst)
     return lib().vpz_pcm_pack(ctx._h, _ptr(src), _numel(src), channels, desc.shape[0], desc.ctypes.data, _ptr(dst), dst_rows, frames, layout)
+
+
+def pcm_resample(ctx, src, rows, dst, layout, up, down, downmix=False):
+    """vpz_pcm_resample (vorbispizza_pcm_resample.h): windows of the device array `src` (a float32 torch tensor, interleaved
+    [sample][channel] with `src.shape[-1]` channels) resampled by up / down, mixed down to mono with `downmix`, into rows of `dst` -- a
+    contiguous torch tensor [rows, out_channels, frames] (planar layouts) or [rows, frames, out_channels], float32 or int16; rows:
+    [(src, samples, row)].  Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
+    planar = layout in (OUT_PLANAR, OUT_PLANAR_S16)
+    dst_rows, out_channels, frames = (dst.shape[0], dst.shape[1], dst.shape[2]) if planar else (dst.shape[0], dst.shape[2], dst.shape[1])
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_resample(ctx._h, _ptr(src), _numel(src), int(src.shape[-1]), up, down, int(bool(downmix)), desc.shape[0], desc.ctypes.data,
+                                  _ptr(dst), dst_rows, out_channels, frames, layout)
+
+
+def resample_filter(up, down):
+    """vpz_resample_filter: (taps, first_tap[up] int32, coeffs[up, taps] float32) of a ratio in lowest terms; needs no device.  A refused
+    ratio raises ValueError."""
+    taps = C.c_int32(0)
+    first = np.zeros(max(int(up), 1), dtype=np.int32)
+    rc = lib().vpz_resample_filter(up, down, C.byref(taps), first.ctypes.data, None, 0)
+    if rc != OK:
+        raise ValueError("vpz_resample_filter refuses the ratio %d / %d (status %d)" % (up, down, rc))
+    coeffs = np.zeros((int(up), taps.value), dtype=np.float32)
+    rc = lib().vpz_resample_filter(up, down, C.byref(taps), first.ctypes.data, coeffs.ctypes.data, coeffs.size)
+    if rc != OK:
+        raise ValueError("vpz_resample_filter failed (status %d)" % rc)
+    return taps.value, first, coeffs
 
 
 def make_packets(count):

@@ -79,6 +79,9 @@ __global__ __launch_bounds__(kPackBlock) void pcm_pack_kernel(const T *__restric
     }
 }
 
+}  // namespace
+
+// (the two below serve vpz_pcm_resample too: vpz_internal.hpp declares them)
 // `bytes` bytes from `p` lie inside one allocation of device memory on the context's device
 bool device_range(Context *ctx, const void *p, uint64_t bytes)
 {
@@ -121,8 +124,6 @@ int pack_room(Context *ctx, size_t n)
     ctx->pack_cap = cap;
     return VPZ_OK;
 }
-
-}  // namespace
 
 void free_pack_scratch(Context *ctx)
 {

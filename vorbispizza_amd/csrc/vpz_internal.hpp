@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/vorbispizza_synth.h"
@@ -57,6 +58,13 @@ struct Context {
     size_t pack_cap = 0;  // descriptors both hold
     hipEvent_t pack_done = nullptr;
     bool pack_pending = false;
+    // vpz_pcm_resample (pcm_resample.hip): the device copy of every ratio's coefficient table, built on first use, keyed by (up, down)
+    struct ResampleTable {
+        float *d_coeff = nullptr;  // [taps][up]: a wave's lanes are consecutive phases
+        int32_t *d_first = nullptr;  // [up]
+        int taps = 0, first_min = 0;
+    };
+    std::map<std::pair<int, int>, ResampleTable> resample_tables;
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
@@ -64,6 +72,9 @@ int set_error(Context *ctx, int status, const char *what, hipError_t e = hipSucc
 int get_tables(Context *ctx, int n, BlockTables **out);
 int ensure_stage(Context *ctx, void **buf, size_t *have, size_t need);
 void free_pack_scratch(Context *ctx);  // (pcm_pack.hip; vpz_context_destroy calls it)
+bool device_range(Context *ctx, const void *p, uint64_t bytes);  // (pcm_pack.hip) inside one allocation of device memory on the context's device
+int pack_room(Context *ctx, size_t n);  // (pcm_pack.hip) room for n vpz_pack_row in pack_host / pack_dev; the previous copy has left the buffer
+void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

@@ -32,6 +32,9 @@
 // lane's device array (the host route uploads its slot's decoded arrays and makes a device-memory synth call), and the `download` stage
 // is one vpz_pcm_pack per sub-batch, which trims every member's window into its row of the caller's device tensor and zero-fills the rest.
 //
+// vpzm_decode_ranges_resampled (include/vorbispizza_multi_resample.h) is that call with vpz_pcm_resample as its last stage: open_one works out
+// every entry's ratio, the synth calls write float32, and `download` makes one launch per ratio among the sub-batch's members.
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
@@ -56,6 +59,8 @@
 #include "../../include/vorbispizza_multi_batch.h"
 #include "../../include/vorbispizza_pcm.h"
 #include "../../include/vorbispizza_pcm_pack.h"
+#include "../../include/vorbispizza_pcm_resample.h"
+#include "../../include/vorbispizza_multi_resample.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -337,6 +342,7 @@ struct Job {  // one stream of the library inside its group
     int64_t total_samples = 0;
     int64_t payload_bytes = 0, plan_failures = 0;  // gpu_entropy: what its plan needs in the payload area; packets its plan gave up
     int part = 0;  // mixed_setups: which part of its class's merged setup its own setup is
+    int32_t up = 1, down = 1;  // a resampled call: the batch's rate / the stream's, in lowest terms
     int32_t status = VPZM_OK;
     bool finished = false;  // its PCM has been written (or it has its own failure status): what an aborted run leaves alone
     bool row_packed = false;  // a batch call: a pack launch has defined its row (the others get their zeros when the run ends)
@@ -353,7 +359,12 @@ struct Batch {
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
     void *dst = nullptr;
+    int32_t rate = 0, downmix = 0;  // vpzm_decode_ranges_resampled: every row at `rate` (0: at the stream's own), mixed down to mono
+    bool resampled() const { return rate > 0; }
 };
+
+// ceil(samples * up / down): the output samples of a resampled window (the definition's J)
+int64_t resampled_length(int64_t samples, int32_t up, int32_t down) { return (samples * up + down - 1) / down; }
 
 struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
     std::shared_ptr<Setup> st;           // (its own reference: `setups` grows under the group's mutex while sub-batches are worked on outside it)
@@ -458,8 +469,19 @@ struct GroupRun {
                 J.residue_floats = values;
                 R.packets = J.packets;
             }
-            if (J.wanted > capacity_of(J.k)) { J.status = VPZM_E_CAPACITY; return; }
-            if (batched() && info.channels != batch.channels) { J.status = VPZM_E_CHANNELS; return; }
+            if (batch.resampled()) {  // (the ratio first: the row's capacity is in output samples)
+                if (!batch.downmix && info.channels != batch.channels) { J.status = VPZM_E_CHANNELS; return; }
+                int64_t a = info.sample_rate, b = batch.rate;
+                while (b) { const int64_t t = a % b; a = b; b = t; }
+                const int64_t up = a > 0 ? batch.rate / a : 0, down = a > 0 ? info.sample_rate / a : 0;
+                if (up < 1 || down < 1 || up > VPZ_RESAMPLE_MAX_UP || down > VPZ_RESAMPLE_MAX_DOWN_PER_UP * up) { J.status = VPZM_E_RATE; return; }
+                J.up = (int32_t)up;
+                J.down = (int32_t)down;
+                if (J.wanted > INT64_MAX / 2048 || resampled_length(J.wanted, J.up, J.down) > batch.frames) { J.status = VPZM_E_CAPACITY; return; }
+            } else {
+                if (J.wanted > capacity_of(J.k)) { J.status = VPZM_E_CAPACITY; return; }
+                if (batched() && info.channels != batch.channels) { J.status = VPZM_E_CHANNELS; return; }
+            }
             if (J.packets > 0) {
                 J.own = std::make_shared<Setup>();
                 if (!J.own->load(J.h, m->opt.gpu_entropy != 0)) J.status = VPZM_E_SETUP;
@@ -938,6 +960,7 @@ struct SubCall {
     Clock::time_point t0 = Clock::now();
     double t_upload = 0, t_entropy = 0, t_call = 0, t_download = 0;
     int member_calls = 0;  // synth calls made for single members after the batch call failed (the profile line says how many)
+    int resample_launches = 0;  // a resampled call: vpz_pcm_resample launches of this sub-batch, one per ratio among its members
 
     Job &job(size_t j) const { return R.jobs[(size_t)sb.members[j]]; }
     bool live(size_t j) const { return job(j).status == VPZM_OK; }
@@ -1187,10 +1210,41 @@ struct SubCall {
                 written[j] = ok ? std::max<int64_t>(0, std::min(J.wanted, written[j] - J.roll)) : 0;
                 rows.push_back(vpz_pack_row{written[j] > 0 ? offs[j] + J.roll * C : 0, written[j], (int64_t)(J.k - R.lo)});
             }
-            // (no staged PCM: a launch that reads nothing -- the destination stands in for a source of no elements)
-            int rc = vpz_pcm_pack(L.ctx, staged ? (const void *)L.pcm() : R.batch.dst, staged ? pcm_elems : 0, C, (int32_t)rows.size(), rows.data(),
-                                  R.batch.dst, (int64_t)(R.hi - R.lo), R.batch.frames, R.batch.layout);
-            if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_pack: ") + vpz_context_last_error(L.ctx));
+            int rc = VPZ_OK;
+            if (staged && R.batch.resampled()) {
+                // a resampled call: the members grouped by ratio (a sub-batch has one channel count), one vpz_pcm_resample launch per
+                // group on the lane's stream -- one launch where the members share a rate, more where streams of one setup differ in rate.
+                // A member without samples needs no ratio of its own: its zero row rides in the first group (alone, at 1:1, when no
+                // member has samples)
+                std::vector<char> taken(rows.size(), 0);
+                std::vector<vpz_pack_row> group;
+                for (size_t left = rows.size(); left > 0 && rc == VPZ_OK;) {
+                    size_t a = rows.size();
+                    for (size_t j = 0; j < rows.size() && a == rows.size(); ++j)
+                        if (!taken[j] && rows[j].samples > 0) a = j;
+                    const int32_t up = a < rows.size() ? job(a).up : 1, down = a < rows.size() ? job(a).down : 1;
+                    group.clear();
+                    for (size_t j = 0; j < rows.size(); ++j)
+                        if (!taken[j] && (rows[j].samples == 0 || (job(j).up == up && job(j).down == down))) {
+                            taken[j] = 1;
+                            group.push_back(rows[j]);
+                        }
+                    left -= group.size();
+                    rc = vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, R.batch.downmix, (int32_t)group.size(), group.data(), R.batch.dst,
+                                          (int64_t)(R.hi - R.lo), R.batch.channels, R.batch.frames, R.batch.layout);
+                    ++resample_launches;
+                }
+                for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
+                if (rc != VPZ_OK) {
+                    R.m->fail(std::string("vpz_pcm_resample: ") + vpz_context_last_error(L.ctx));
+                    (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
+                }
+            } else {
+                // (no staged PCM: a launch that reads nothing -- the destination stands in for a source of no elements)
+                rc = vpz_pcm_pack(L.ctx, staged ? (const void *)L.pcm() : R.batch.dst, staged ? pcm_elems : 0, R.batch.channels, (int32_t)rows.size(),
+                                  rows.data(), R.batch.dst, (int64_t)(R.hi - R.lo), R.batch.frames, R.batch.layout);
+                if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_pack: ") + vpz_context_last_error(L.ctx));
+            }
             if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
             for (size_t j = 0; j < sb.members.size(); ++j) {
                 if (rc == VPZ_OK) job(j).row_packed = true;
@@ -1229,7 +1283,10 @@ struct SubCall {
             fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s done at %.2f ms (upload %.2f ms, entropy %.2f ms, synth %.2f ms, %s %.2f ms; %lld packets, %lld payload bytes, %d member calls)\n",
                     R.slot_index, b, sb.on_device ? "on the device" : "uploaded", at_ms, t_upload * 1e3, t_entropy * 1e3, t_call * 1e3, batched ? "pack" : "download",
                     t_download * 1e3, (long long)n_pk, (long long)sb.payload_bytes, member_calls);
-        else if (R.sw.profile)
+        if (R.sw.profile && resample_launches > 0)
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu resampled in %d launches (one per ratio among its %zu members)\n", R.slot_index, b, resample_launches,
+                    sb.members.size());
+        if (R.sw.profile && !(sb.on_device || batched))
             fprintf(stderr, "[vpzm] group %d: sub-batch %zu synthesised at %.2f ms (call %.2f ms, %lld packets, %d member calls)\n", R.slot_index, b, at_ms, dt * 1e3,
                     (long long)n_pk, member_calls);
         std::lock_guard<std::mutex> lk(R.mu);
@@ -1467,6 +1524,25 @@ int vpzm_decode_ranges_batch(vpzm_dispatcher *m, int32_t n, const uint8_t *const
     // (the synth calls write their areas interleaved, in the batch's element type; the pack step gives the rows their layout)
     return decode_call(m, n, data, size, ranges ? ranges : &none, s16 ? VPZ_OUT_INTERLEAVED_S16 : VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr,
                        results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_resampled(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                                 int32_t sample_rate, int32_t channels, int32_t downmix, int64_t frames, int32_t out_layout, void *const *group_dst,
+                                 vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!group_dst || channels < 1 || channels > VPZ_MAX_CHANNELS || frames < 1 || (n > 0 && !ranges)) return VPZM_E_ARG;
+    if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
+    if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_PLANAR && out_layout != VPZ_OUT_INTERLEAVED_S16 && out_layout != VPZ_OUT_PLANAR_S16)
+        return VPZM_E_ARG;
+    static const vpzm_range none{0, 0};
+    Batch batch;
+    batch.channels = channels;
+    batch.layout = out_layout;
+    batch.frames = frames;
+    batch.rate = sample_rate;
+    batch.downmix = downmix;
+    // (the synth calls write float32, interleaved, whatever the batch's element type: the resample step converts once, at the end)
+    return decode_call(m, n, data, size, ranges ? ranges : &none, VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)

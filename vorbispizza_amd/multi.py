@@ -1,4 +1,5 @@
-"""ctypes view of include/vorbispizza_multi.h, include/vorbispizza_multi_mixed.h, include/vorbispizza_multi_ranges.h and include/vorbispizza_multi_batch.h -- the in-process multi-device dispatcher of
+"""ctypes view of include/vorbispizza_multi.h, include/vorbispizza_multi_mixed.h, include/vorbispizza_multi_ranges.h, include/vorbispizza_multi_batch.h and
+include/vorbispizza_multi_resample.h -- the in-process multi-device dispatcher of
 libvorbispizza_host.so (one host process, one context group per MI355X, streams partitioned contiguously, no collective).  What a
 C# host P/Invokes; tests and bench.py use it from here."""
 import ctypes as C
@@ -11,6 +12,7 @@ OK, E_ARG, E_DEVICE, E_NOMEM = 0, -1, -2, -3
 E_OPEN, E_CAPACITY, E_SYNTH, E_SETUP = -10, -11, -12, -13
 E_RANGE = -14  # (vorbispizza_multi_ranges.h)
 E_CHANNELS = -15  # (vorbispizza_multi_batch.h)
+E_RATE = -16  # (vorbispizza_multi_resample.h)
 
 
 class Options(C.Structure):
@@ -45,6 +47,7 @@ EXPORTED_SYMBOLS = ["vpzm_create", "vpzm_destroy", "vpzm_last_error", "vpzm_devi
 MIXED_EXPORTED_SYMBOLS = ["vpzm_set_mixed_setups", "vpzm_last_call_counts"]  # (vorbispizza_multi_mixed.h)
 RANGES_EXPORTED_SYMBOLS = ["vpzm_decode_ranges"]  # (vorbispizza_multi_ranges.h)
 BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  # (vorbispizza_multi_batch.h)
+RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
@@ -77,6 +80,10 @@ def lib():
             L.vpzm_batch_partition.restype = C.c_int
             L.vpzm_decode_ranges_batch.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int64, C.c_int32, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_batch.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_resampled"):
+            L.vpzm_decode_ranges_resampled.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, vp, vp,
+                                                       C.POINTER(Stats)]
+            L.vpzm_decode_ranges_resampled.restype = C.c_int
         _bound = True
     return L
 
@@ -180,12 +187,16 @@ class Dispatcher:
             raise MultiError("vpzm_batch_partition failed (status %d)" % rc)
         return lo.value, hi.value
 
-    def decode_ranges_batch(self, datas, ranges, channels, frames, planar=True, s16=False, out=None):
+    def decode_ranges_batch(self, datas, ranges, channels, frames, planar=True, s16=False, out=None, sample_rate=None, mono=False):
         """vpzm_decode_ranges_batch: decode_ranges delivered as a zero-padded batch in device memory.  Entry k's window becomes row k:
         [channels, frames] (planar) or [frames, channels], float32 or int16 (s16), its samples first, zeros behind them.
         out: a list of torch tensors, one per group, on that group's device, contiguous, of shape [hi - lo, channels, frames] (or
         [hi - lo, frames, channels]) for the group's entries [lo, hi) (batch_partition) -- anything else raises before the library is
         called.  Without `out` the method allocates: when all groups share a device, one tensor whose consecutive pieces the groups get.
+        sample_rate / mono (vpzm_decode_ranges_resampled; the defaults are the call above, the same library function as ever): every
+        window is delivered at `sample_rate` -- the ranges stay in source samples, a row holds ceil(samples * up / down) output samples and
+        results["samples"] counts those --, and with mono=True the rows have one channel (channels must be 1), the mean of the stream's.
+        mono needs a `sample_rate`: the library's resampled call has one rate.
         Returns (parts, whole_or_None, results, stats)."""
         import torch
         n = len(datas)
@@ -195,6 +206,8 @@ class Dispatcher:
         shape = (lambda rows: (rows, channels, frames)) if planar else (lambda rows: (rows, frames, channels))
         if channels < 1 or frames < 1:
             raise ValueError("decode_ranges_batch: channels and frames must be at least 1")
+        if mono and (sample_rate is None or channels != 1):
+            raise ValueError("decode_ranges_batch: mono needs a sample_rate (a resampled call has one rate) and channels == 1")
         whole = None
         if out is None:
             if len(set(ids)) == 1:
@@ -220,8 +233,14 @@ class Dispatcher:
             torch.cuda.current_stream(d).synchronize()
         results = np.zeros(n, dtype=RESULT_DTYPE)
         stats = Stats()
-        rc = lib().vpzm_decode_ranges_batch(self._h, n, ptrs, sizes, rng.ctypes.data, channels, frames, layout, dst, results.ctypes.data,
-                                            C.byref(stats))
+        if sample_rate is None:
+            rc = lib().vpzm_decode_ranges_batch(self._h, n, ptrs, sizes, rng.ctypes.data, channels, frames, layout, dst, results.ctypes.data,
+                                                C.byref(stats))
+            name = "vpzm_decode_ranges_batch"
+        else:
+            rc = lib().vpzm_decode_ranges_resampled(self._h, n, ptrs, sizes, rng.ctypes.data, int(sample_rate), channels, int(bool(mono)), frames,
+                                                    layout, dst, results.ctypes.data, C.byref(stats))
+            name = "vpzm_decode_ranges_resampled"
         if rc != OK:
-            raise MultiError("vpzm_decode_ranges_batch failed (status %d): %s" % (rc, self.last_error()))
+            raise MultiError("%s failed (status %d): %s" % (name, rc, self.last_error()))
         return out, whole, results, stats

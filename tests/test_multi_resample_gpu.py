@@ -1,7 +1,8 @@
 """vpzm_decode_ranges_resampled (include/vorbispizza_multi_resample.h, host/vorbis_multi.cpp): the padded device batch at one sample rate.
 
 Streams and windows are those of tests/test_multi_ranges_gpu.py (stereo at 44 100 Hz, six channels at 48 000, mono at 8 000 and 44 100,
-floor-0 stereo at 16 000, which a 16 000 Hz batch copies).  The truth of a row is tests/test_resample_cpu.py's float64 restatement applied to
+floor-0 stereo at 16 000, which a 16 000 Hz batch copies), the writer's five- and ten-channel streams (more channels than the kernel stages
+side by side) and copies of the stereo stream re-rated so that the ratio lies at a limit: (1, 32), (128, 125), (1024, 1023).  The truth of a row is tests/test_resample_cpu.py's float64 restatement applied to
 the slice of the stream-by-stream whole decode, held to the derived bound (T + C + 3) * 2^-24 * B[j]; it is never the call under test.
 What is compared between two calls of the dispatcher -- layouts, routes, partitions, cuts, failure paths -- is compared as raw bits, and
 the int16 layouts are the project's conversion of the float32 output of the same call's float32 twin, bit for bit."""
@@ -19,7 +20,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from test_multi_batch_gpu import as_bits, batch_call, entries_of  # noqa: E402
 from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, all_entries, golden, streams  # noqa: E402
-from test_resample_cpu import bound, ratio_of, resample_truth, to_s16  # noqa: E402
+from test_resample_cpu import bound, launch_plan, ratio_of, ratio_ok, resample_truth, to_s16  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -47,16 +48,29 @@ def ratio(s, rate):
 _rerated = {}
 
 
-def rerated(rate):
+def rerated(rate, packets=12):
     """stereo_coupled_res2 at 12 packets with another rate in its identification header: the same setup header, so it shares sub-batches
     with its 44 100 Hz twin, at another ratio"""
     import synthetic_streams as ss
-    if rate not in _rerated:
+    if (rate, packets) not in _rerated:
         st, rng = ss.stereo_coupled_res2()
         st.rate = rate
-        _rerated[rate] = Stream(bytes(st.build(rng, 12)[0]), True)
-        assert _rerated[rate].f.sample_rate == rate and _rerated[rate].channels == 2
-    return _rerated[rate]
+        _rerated[(rate, packets)] = Stream(bytes(st.build(rng, packets)[0]), True)
+        assert _rerated[(rate, packets)].f.sample_rate == rate and _rerated[(rate, packets)].channels == 2
+    return _rerated[(rate, packets)]
+
+
+_many = {}
+
+
+def many_channels(name):
+    """the writer's five_channels / ten_channels stream (48 000 Hz) at ten packets"""
+    import synthetic_streams as ss
+    if name not in _many:
+        st, rng = getattr(ss, name)()
+        _many[name] = Stream(bytes(st.build(rng, 10)[0]), True)
+        assert _many[name].f.sample_rate == 48000 and _many[name].channels == {"five_channels": 5, "ten_channels": 10}[name]
+    return _many[name]
 
 
 _rows = {}
@@ -327,3 +341,62 @@ def test_the_four_calls_in_turn_on_one_dispatcher(ctx):
                 step(d)
         finally:
             d.close()
+
+
+@pytest.mark.parametrize("mono", [False, True], ids=["unmixed", "mono"])
+@pytest.mark.parametrize("route", ["host", "device"])
+def test_five_and_ten_channels_take_several_passes_of_the_kernel(ctx, route, mono):
+    """48 000 -> 16 000 Hz is (1, 3): five channels in one pass, ten in two (8 + 2) -- more channels than the kernel stages side by side"""
+    five, ten = many_channels("five_channels"), many_channels("ten_channels")
+    assert launch_plan(1, 3, 5, False)["passes"] == [5] and launch_plan(1, 3, 10, False)["passes"] == [8, 2]
+    if mono:  # one call over both streams, their windows in turn
+        sets = [(1, [e for pair in zip(*[[(s, a, n) for a, n in s.windows()] for s in (five, ten)]) for e in pair])]
+    else:
+        sets = [(s.channels, [(s, a, n) for a, n in s.windows()]) for s in (five, ten)]
+    for channels, entries in sets:
+        assert len(entries) > 20
+        frames = most_outputs(entries, RATE) + 3
+        got, results = four_layouts(entries, RATE, channels, frames, mono, **OPTIONS[route])
+        worst = check_against_truth(ctx, got, results, entries, RATE, mono)
+        print("%s, %s channels%s: largest error / bound %.3f" % (route, "5 and 10" if mono else channels, " mixed down" if mono else "", worst))
+
+
+# (source rate, target rate) -> the ratio: the steepest one, a neighbour with many phases, and up = 1024 exactly (no source rate gives it
+# against 16 000 Hz)
+LIMIT_RATES = {(512000, RATE): (1, 32), (15625, RATE): (128, 125), (1023, 1024): (1024, 1023)}
+
+
+@pytest.mark.parametrize("fs,ft", list(LIMIT_RATES))
+@pytest.mark.parametrize("route", ["host", "device"])
+def test_rates_at_the_limits_of_the_ratio_are_accepted(ctx, route, fs, ft):
+    s = rerated(fs, 10)
+    assert ratio(s, ft) == LIMIT_RATES[(fs, ft)] and ratio_ok(*ratio(s, ft))
+    entries = [(s, a, n) for a, n in s.windows()]
+    frames = most_outputs(entries, ft) + 3
+    got, results = four_layouts(entries, ft, 2, frames, **OPTIONS[route])
+    worst = check_against_truth(ctx, got, results, entries, ft, False)
+    mono, results = resampled_call(entries, ft, 1, frames, True, False, True, **OPTIONS[route])[:2]
+    worst_mono = check_against_truth(ctx, mono.cpu().numpy(), results, entries, ft, True)
+    print("%s, %d -> %d Hz, ratio %r: largest error / bound %.3f, mixed down %.3f" % (route, fs, ft, ratio(s, ft), worst, worst_mono))
+
+
+@pytest.mark.parametrize("gpu_entropy", [False, True])
+def test_the_nearest_ratios_beyond_the_limits_are_refused_with_a_zero_row(ctx, gpu_entropy):
+    """down = 32 * up + 1 and up = 1025, each beside an accepted neighbour in the same call"""
+    from vorbispizza_amd import multi
+    for ft, fs_good, fs_bad, refused in ((RATE, 512000, 528000, (1, 33)), (1025, 15625, 1023, (1025, 1023))):
+        good, bad = rerated(fs_good, 10), rerated(fs_bad, 10)
+        assert ratio_ok(*ratio(good, ft)) and ratio(bad, ft) == refused and not ratio_ok(*refused)
+        entries = [e for a, b in zip(good.windows()[:8], bad.windows()[:8]) for e in ((good, *a), (bad, *b))]
+        ok = np.arange(0, len(entries), 2)
+        frames = most_outputs(entries[::2], ft) + 1
+        for planar, s16 in ((True, False), (False, True)):
+            got, results, _ = resampled_call(entries, ft, 2, frames, planar, s16, gpu_entropy=gpu_entropy, streams_per_call=4)
+            assert (results["status"][ok] == 0).all() and (results["status"][ok + 1] == multi.E_RATE).all(), results["status"]
+            assert (results["samples"][ok + 1] == 0).all() and (results["sample_rate"][ok + 1] == fs_bad).all()
+            img = got.cpu().numpy() if planar else got.cpu().numpy().transpose(0, 2, 1)
+            assert not img[ok + 1].any()
+            if not s16:
+                check_against_truth(ctx, img[ok], results[ok], entries[::2], ft, False)
+            else:
+                assert img[ok].any()

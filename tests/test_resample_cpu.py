@@ -8,10 +8,15 @@ export lists and the refused ratios against the headers.
 
 The tolerance of the GPU tests, `bound`, is derived, not measured: coefficients rounded once to float32 plus a float32 multiply-accumulate
 over T taps, plus C - 1 adds and a scale where C channels are mixed down, give |y - truth| <= (T + C + 3) * 2^-24 * B[j] with
-B[j] = sum |x * h| (divided by C for a downmix); C counts as 1 where nothing is mixed."""
+B[j] = sum |x * h| (divided by C for a downmix); C counts as 1 where nothing is mixed.
+
+The kernel's launch plan is restated here too (`launch_plan`, its constants read out of csrc/pcm_resample.hip), together with the case list
+of tests/test_pcm_resample_limits_gpu.py, `LIMIT_CASES`: a test without a GPU holds the list to the plan's branches, and a sweep over
+ratios up to the limits holds the two facts the kernel's staging counts on."""
 import ctypes as C
 import math
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -117,6 +122,49 @@ def to_s16(y):
     """the project's one conversion of a float32 sample: (int)(x * 32768f) clamped"""
     v = np.asarray(y, dtype=np.float32) * np.float32(32768.0)
     return np.clip(np.trunc(v.astype(np.float64)), -32768, 32767).astype(np.int16)
+
+
+def live_taps(up, down):
+    """live[up]: the live taps of every phase; table entries behind them are the zero padding of a short phase"""
+    taps, first, _ = filter_table(up, down)
+    if up == down:
+        return np.ones(1, dtype=np.int64)
+    live = [sum(tap_live((int(first[p]) + k) * up - p * down % up, up, down) for k in range(taps)) for p in range(up)]
+    return np.asarray(live, dtype=np.int64)
+
+
+# (up, down, source channels, downmix): tests/test_pcm_resample_limits_gpu.py runs every one; test_the_limit_cases_take_every_branch_of_the_plan
+# holds the list to the plan.  (1, 6) with seven channels is the list's one case of five channels to a pass; (5, 48) with seven mixed
+# down is there for the non-finite tests, which rerun it.
+LIMIT_CASES = [(1, 32, 1, False), (1, 32, 2, False), (1, 32, 6, False), (1, 32, 6, True),
+               (31, 991, 2, False), (31, 991, 3, False), (31, 991, 2, True),
+               (1024, 32767, 2, False), (1024, 32767, 2, True),
+               (1, 12, 5, False), (5, 48, 5, False), (5, 48, 7, False), (5, 48, 7, True), (1, 8, 6, False), (1, 6, 7, False),
+               (160, 441, 9, False), (160, 441, 10, False), (160, 441, 17, False), (160, 441, 255, False), (160, 441, 255, True),
+               (1024, 1023, 2, False), (1024, 1023, 8, False), (1023, 1024, 2, False), (1023, 1024, 8, False),
+               (1024, 1, 2, False), (1, 1, 10, False), (1, 1, 255, True)]
+
+
+def kernel_constants():
+    """kRsBlock, kRsLds, kRsMaxPass, kRsMaxTaps as csrc/pcm_resample.hip states them"""
+    text = open(os.path.join(ROOT, "vorbispizza_amd", "csrc", "pcm_resample.hip")).read()
+    out = {}
+    for name in ("kRsBlock", "kRsLds", "kRsMaxPass", "kRsMaxTaps"):
+        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
+        assert len(found) == 1, name
+        out[name] = int(found[0])
+    return out
+
+
+def launch_plan(up, down, channels, downmix, k=None):
+    """vpz_pcm_resample's launch plan, restated: the floats between two staged channels, the channels of every pass, the dynamic LDS"""
+    k = k or kernel_constants()
+    taps, first, _ = filter_table(up, down)
+    out_channels = 1 if downmix else channels
+    span_cap = (k["kRsBlock"] - 1) * down // up + 2 + taps
+    per_pass = max(1, min(out_channels, k["kRsMaxPass"], k["kRsLds"] // span_cap))
+    passes = [min(per_pass, out_channels - c0) for c0 in range(0, out_channels, per_pass)]
+    return dict(taps=taps, first=first, span_cap=span_cap, per_pass=per_pass, passes=passes, lds_bytes=4 * per_pass * (span_cap + k["kRsBlock"]))
 
 
 def strided_convolution_form(x, orig, new):
@@ -307,3 +355,60 @@ def test_the_resample_kernels_use_no_scratch_and_say_what_they_take():
         print(k)
         # (the LDS is dynamic, sized per ratio by the launch: at most 42 KiB, 8 KiB at 160 / 441 stereo; no static part)
         assert k.get("scratch", 0) == 0 and k["vgprs"] <= 128 and k["lds"] == 0, k
+
+
+def passes_text(passes):
+    """[8, 8, 8, 7] -> '3 x 8 + 7'"""
+    head = [n for n in passes if n == passes[0]]
+    parts = ["%d x %d" % (len(head), head[0]) if len(head) > 3 else " + ".join(str(n) for n in head)] + [str(n) for n in passes[len(head):]]
+    return " + ".join(parts)
+
+
+def test_the_limit_cases_take_every_branch_of_the_plan():
+    """the case list of tests/test_pcm_resample_limits_gpu.py against the plan: a changed constant in pcm_resample.hip fails HERE, and the
+    list is what to look at then"""
+    k = kernel_constants()
+    assert k == {"kRsBlock": 256, "kRsLds": 8704, "kRsMaxPass": 8, "kRsMaxTaps": 388}, k
+    plans = [(case, launch_plan(*case, k=k)) for case in LIMIT_CASES]
+    for (up, down, channels, downmix), pl in plans:
+        print("(%d, %d) %d channels%s: taps %d span_cap %d per_pass %d passes %s LDS %d bytes" % (
+            up, down, channels, " mixed down" if downmix else "", pl["taps"], pl["span_cap"], pl["per_pass"],
+            passes_text(pl["passes"]), pl["lds_bytes"]))
+        assert pl["taps"] <= k["kRsMaxTaps"] and pl["span_cap"] <= k["kRsLds"] and pl["lds_bytes"] <= 43008  # (42 KiB, DESIGN.md section 6)
+    assert {pl["per_pass"] for _, pl in plans} >= {1, 2, 3, 4, 5, 8}
+    assert any(len(pl["passes"]) > 2 for _, pl in plans)
+    assert any(len(pl["passes"]) > 1 and pl["passes"][-1] < pl["passes"][0] for _, pl in plans)
+    assert any(len(pl["passes"]) > 1 and pl["passes"][-1] == pl["passes"][0] for _, pl in plans)  # (... and one whose last pass is full)
+    assert any(len(pl["passes"]) == 1 and pl["passes"][0] == k["kRsMaxPass"] for _, pl in plans)
+    assert any(pl["taps"] == k["kRsMaxTaps"] for _, pl in plans)
+    assert any(pl["span_cap"] > 0.98 * k["kRsLds"] for _, pl in plans)
+    assert any(case[0] == 1024 for case, _ in plans)
+    assert any(pl["first"].max() != pl["first"].min() and pl["per_pass"] == 1 and not case[3] and case[2] > 1 for case, pl in plans)
+    assert max(case[2] for case, _ in plans) == 255  # (VPZ_MAX_CHANNELS)
+
+
+def sweep_ratios():
+    """for every `up` of the sweep: the steepest coprime down <= 32 * up, down = 1, down = up + 1 and down = up - 1"""
+    out = []
+    for up in list(range(1, 65)) + [127, 128, 255, 256, 257, 511, 512, 1023, 1024]:
+        steepest = next(d for d in range(32 * up, 0, -1) if math.gcd(up, d) == 1)
+        for down in (steepest, 1, up + 1, up - 1):
+            if down >= 1 and ratio_ok(up, down) and (up, down) not in out:
+                out.append((up, down))
+    return out
+
+
+def test_what_the_staging_counts_on_holds_up_to_the_limits():
+    """a phase's first tap is first_min or one more, no filter is longer than kRsMaxTaps, and one channel's span of a tile fits kRsLds"""
+    k = kernel_constants()
+    ratios = sweep_ratios()
+    assert len(ratios) > 250 and (1024, 32767) in ratios and (1, 32) in ratios and (1024, 1) in ratios and (1024, 1023) in ratios
+    most = 0
+    for up, down in ratios:
+        taps, first, _ = filter_table(up, down)
+        assert first.max() - first.min() <= 1, (up, down)
+        assert taps <= k["kRsMaxTaps"] == 388, (up, down, taps)
+        assert (k["kRsBlock"] - 1) * down // up + 2 + taps <= k["kRsLds"] == 8704, (up, down)
+        most = max(most, taps)
+    print("%d ratios, the largest tap count %d" % (len(ratios), most))
+    assert most == 388

@@ -283,6 +283,9 @@ extern "C" int vpz_pcm_resample(vpz_context *c, const void *src_dev, int64_t src
     // first_min or one more, and `taps` samples follow
     a.span_cap = (int32_t)((int64_t)(vpz::kRsBlock - 1) * down / up + 2 + tb->taps);
     // (<= kRsLds inside the ratio's limits: the static_assert above)
+    // tests/test_pcm_resample_limits_gpu.py runs every value per_pass takes (1, 2, 3, 4, 5, 8), last passes narrower than the others, 255
+    // channels and the ratios at which span_cap comes within 2 % of kRsLds; tests/test_resample_cpu.py restates this plan and holds the
+    // tests' case list to it, so a change of a constant above fails there first
     a.per_pass = std::max(1, std::min(std::min<int32_t>(out_channels, vpz::kRsMaxPass), vpz::kRsLds / a.span_cap));
     const int64_t blocks = (frames + vpz::kRsBlock - 1) / vpz::kRsBlock;
     if (blocks > 0x7fffffff) return refuse("vpz_pcm_resample: a row too long for one launch");

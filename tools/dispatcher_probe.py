@@ -7,6 +7,8 @@
     dispatcher_probe.py --pack-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE [--mono] [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --resample-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --logmel [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --logmel-kernel
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -31,7 +33,13 @@ apart), every layout, timed with the context's event timer: median of 20 launche
 --mono).  The A/B: what a loader does without the call -- vpzm_decode_ranges_batch at the source rate, then torch conv1d with the same
 coefficient table (vpz_resample_filter) at stride = down, a reshape and the channels' mean on the device -- against
 vpzm_decode_ranges_resampled; two dispatchers taking turns as above, the largest difference of the two tensors printed.
---resample-kernel: vpz_pcm_resample alone for the same 64 windows, 44 100 -> 16 000 Hz, every layout and the mono mix."""
+--resample-kernel: vpz_pcm_resample alone for the same 64 windows, 44 100 -> 16 000 Hz, every layout and the mono mix.
+--ranges SAMPLES --batch --resample RATE --logmel: the same windows as log-mel features of the Whisper spec (n_fft 400, hop 160, 80 Slaney
+bands, floor 1e-10), a float32 device tensor [streams][80][T].  The A/B: what a loader does without the call -- decode_ranges_batch at
+RATE Hz, mono, then on the device torch.stft (center, reflect, periodic Hann), abs() ** 2, a matmul with the same filterbank
+(vpz_mel_filterbank as a dense matrix), clamp and log10 -- against decode_ranges_logmel; two dispatchers taking turns as above, the
+largest difference of the two tensors printed.  With VPZM_PROFILE=1 the library prints the log-mel launch's own time per sub-batch.
+--logmel-kernel: vpz_pcm_logmel alone, the Whisper spec, 64 windows of one second and of thirty, both layouts, the context's event timer."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -52,6 +60,8 @@ ap.add_argument("--pack-kernel", action="store_true")
 ap.add_argument("--resample", type=int, default=0)
 ap.add_argument("--mono", action="store_true")
 ap.add_argument("--resample-kernel", action="store_true")
+ap.add_argument("--logmel", action="store_true")
+ap.add_argument("--logmel-kernel", action="store_true")
 ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -313,6 +323,95 @@ def resample_kernel_job():
     ctx.close()
 
 
+def dense_filterbank(spec):
+    """vpz_mel_filterbank as a dense [n_mels][n_fft / 2 + 1] float32 matrix on the device"""
+    from vorbispizza_amd import capi
+    first, count, weights = capi.mel_filterbank(spec)
+    W, at = np.zeros((spec.n_mels, spec.n_fft // 2 + 1), dtype=np.float32), 0
+    for b in range(spec.n_mels):
+        W[b, first[b]: first[b] + count[b]] = weights[at: at + count[b]]
+        at += count[b]
+    return torch.from_numpy(W).to("cuda:0")
+
+
+def logmel_job(samples, rate):
+    import math, time
+    from vorbispizza_amd import capi
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    spec = capi.LogMelSpec.make(sample_rate=rate)
+    W, window = dense_filterbank(spec), torch.hann_window(spec.n_fft, periodic=True, device="cuda:0")
+    fs = 44100  # (both fixtures)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, whole, res, st = d.decode_ranges_batch(datas, windows, 1, J, planar=True, s16=False, sample_rate=rate, mono=True)
+        S = torch.stft(whole.view(n, J), spec.n_fft, hop_length=spec.hop, window=window, center=True, pad_mode="reflect", return_complex=True)
+        out[0] = torch.log10(torch.clamp(torch.matmul(W, S.abs() ** 2), min=spec.floor))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res, st
+
+    def by_logmel(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_logmel(datas, windows, J, sample_rate=rate)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, log-mel 400/160/80" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_logmel(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB (the complex spectrogram it replaces: %.1f MB), largest difference of the two tensors %.3g (log10 units)" % (
+            what, J, out[1].numel() * 4 / 1e6, n * (spec.n_fft // 2 + 1) * out[1].shape[2] * 8 / 1e6, float((out[0] - out[1]).abs().max())), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_batch(mono) + torch stft/power/matmul/log %s; decode_ranges_logmel %s" % (run, describe(walls[0]), describe(walls[1])),
+                  flush=True)
+        for d in ds:
+            d.close()
+
+
+def logmel_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n = 64
+    for samples in (16000, 480000):
+        src = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+        rows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+        for name, bands_first in (("bands first", True), ("frames first", False)):
+            spec = capi.LogMelSpec.make(bands_first=bands_first)
+            T = spec.n_frames(samples)
+            dst = torch.empty((n, 80, T) if bands_first else (n, T, 80), dtype=torch.float32, device="cuda:0")
+            times = []
+            for _ in range(11):
+                ctx.timer_start()
+                assert capi.pcm_logmel(ctx, src, rows, dst, spec, samples) == capi.OK, ctx.last_error()
+                times.append(ctx.timer_stop())
+            ms = statistics.median(times[1:])
+            flop = 2.0 * n * T * 400 * 402
+            print("vpz_pcm_logmel %-12s 64 windows of %6d samples (T = %4d): median %.1f us (min %.1f, max %.1f); %.2f GFLOP of DFT = %.1f TFLOP/s; %.1f MB out, "
+                  "%.1f MB of spectrogram not written" % (name, samples, T, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, flop / 1e9, flop / ms / 1e9,
+                                                          dst.numel() * 4 / 1e6, n * 201 * T * 8 / 1e6), flush=True)
+    ctx.close()
+
+
+if args.logmel_kernel:
+    logmel_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.logmel:
+    logmel_job(args.ranges, args.resample)
+    sys.exit(0)
 if args.pack_kernel:
     pack_kernel_job()
     sys.exit(0)

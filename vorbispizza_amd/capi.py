@@ -112,6 +112,44 @@ _PCM_RESAMPLE_SIGNATURES = [
                                    C.c_int64, C.c_int32]),
 ]
 RESAMPLE_MAX_UP, RESAMPLE_MAX_DOWN_PER_UP = 1024, 32
+
+
+class LogMelSpec(C.Structure):
+    """vpz_logmel_spec (include/vorbispizza_pcm_logmel.h).  LogMelSpec.make(...) takes the names a Python caller uses."""
+    _fields_ = [("sample_rate", C.c_double), ("f_min", C.c_double), ("f_max", C.c_double), ("floor", C.c_double),
+                ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32), ("mel_scale", C.c_int32), ("mel_norm", C.c_int32),
+                ("output", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 9)]
+
+    @classmethod
+    def make(cls, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="slaney", mel_norm="slaney", log=True,
+             floor=1e-10, bands_first=True):
+        scales, norms = {"htk": MEL_HTK, "slaney": MEL_SLANEY}, {None: MEL_NORM_NONE, "none": MEL_NORM_NONE, "slaney": MEL_NORM_SLANEY}
+        if mel_scale not in scales or mel_norm not in norms:
+            raise ValueError("LogMelSpec: mel_scale is 'htk' or 'slaney', mel_norm None or 'slaney'")
+        s = cls()
+        s.sample_rate, s.f_min, s.f_max, s.floor = float(sample_rate), float(f_min), float(sample_rate / 2.0 if f_max is None else f_max), float(floor)
+        s.n_fft, s.hop, s.n_mels = int(n_fft), int(hop), int(n_mels)
+        s.mel_scale, s.mel_norm = scales[mel_scale], norms[mel_norm]
+        s.output, s.layout = (MEL_LOG10 if log else MEL_POWER), (MEL_BANDS_FIRST if bands_first else MEL_FRAMES_FIRST)
+        return s
+
+    def n_frames(self, frames):
+        """T of a row of `frames` samples."""
+        return 1 + int(frames) // self.hop
+
+
+MEL_HTK, MEL_SLANEY = 0, 1
+MEL_NORM_NONE, MEL_NORM_SLANEY = 0, 1
+MEL_POWER, MEL_LOG10 = 0, 1
+MEL_BANDS_FIRST, MEL_FRAMES_FIRST = 0, 1
+LOGMEL_MIN_NFFT, LOGMEL_MAX_NFFT, LOGMEL_MAX_MELS = 32, 1024, 256
+# include/vorbispizza_pcm_logmel.h (a header of its own again)
+_PCM_LOGMEL_SIGNATURES = [
+    ("vpz_logmel_dft_table", C.c_int, [C.c_int32, _vp, C.c_int64]),
+    ("vpz_mel_filterbank", C.c_int, [C.POINTER(LogMelSpec), _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    ("vpz_pcm_logmel", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(LogMelSpec), C.c_int32, _vp, _vp, C.c_int64]),
+]
+PCM_LOGMEL_EXPORTED_SYMBOLS = [s[0] for s in _PCM_LOGMEL_SIGNATURES]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
 PCM_PACK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_PACK_SIGNATURES]
@@ -144,7 +182,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        later = _PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES
+        later = _PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -293,6 +331,46 @@ def resample_filter(up, down):
     if rc != OK:
         raise ValueError("vpz_resample_filter failed (status %d)" % rc)
     return taps.value, first, coeffs
+
+
+def pcm_logmel(ctx, src, rows, dst, spec, frames):
+    """vpz_pcm_logmel (vorbispizza_pcm_logmel.h): windows of the MONO float32 device array `src` (a torch tensor) as (log-)mel frames of
+    rows padded to `frames` samples, into rows of `dst` -- a contiguous float32 torch tensor [rows, n_mels, T] (MEL_BANDS_FIRST) or
+    [rows, T, n_mels], T = 1 + frames // hop; rows: [(src, samples, row)]; spec: a LogMelSpec.  Asynchronous on the context's stream;
+    returns the status (a refusal is an answer, not an exception)."""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_logmel(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                                int(dst.shape[0]))
+
+
+def logmel_dft_table(n_fft):
+    """vpz_logmel_dft_table: float32 [n_fft, 2, n_fft // 2 + 1] -- [m, 0, k] = w[m] cos, [m, 1, k] = w[m] sin; needs no device.  A refused
+    n_fft raises ValueError."""
+    rc = lib().vpz_logmel_dft_table(n_fft, None, 0)
+    if rc != OK:
+        raise ValueError("vpz_logmel_dft_table refuses n_fft %r (status %d)" % (n_fft, rc))
+    table = np.zeros((int(n_fft), 2, int(n_fft) // 2 + 1), dtype=np.float32)
+    rc = lib().vpz_logmel_dft_table(n_fft, table.ctypes.data, table.size)
+    if rc != OK:
+        raise ValueError("vpz_logmel_dft_table failed (status %d)" % rc)
+    return table
+
+
+def mel_filterbank(spec):
+    """vpz_mel_filterbank: (first_bin[n_mels] int32, n_bins[n_mels] int32, weights float32 -- band after band, each band's live bins) of a
+    LogMelSpec; needs no device.  A refused spec raises ValueError."""
+    total = C.c_int64(0)
+    rc = lib().vpz_mel_filterbank(C.byref(spec), None, None, None, 0, C.byref(total))
+    if rc != OK:
+        raise ValueError("vpz_mel_filterbank refuses the spec (status %d)" % rc)
+    first, count = np.zeros(spec.n_mels, dtype=np.int32), np.zeros(spec.n_mels, dtype=np.int32)
+    weights = np.zeros(total.value, dtype=np.float32)
+    rc = lib().vpz_mel_filterbank(C.byref(spec), first.ctypes.data, count.ctypes.data, weights.ctypes.data if total.value else None, weights.size,
+                                  C.byref(total))
+    if rc != OK:
+        raise ValueError("vpz_mel_filterbank failed (status %d)" % rc)
+    return first, count, weights
 
 
 def make_packets(count):

@@ -65,6 +65,17 @@ struct Context {
         int taps = 0, first_min = 0;
     };
     std::map<std::pair<int, int>, ResampleTable> resample_tables;
+    // vpz_pcm_logmel (pcm_logmel.hip): the device copy of every n_fft's DFT table and of every spec's mel filterbank, built on first use
+    struct LogmelDft {
+        float *d_table = nullptr;  // [n_fft][2 * cols]: cos columns, then sin columns, each padded with zeros to `cols`
+        int cols = 0;              // n_fft / 2 + 1 rounded up to the kernel's column tile
+    };
+    struct LogmelBank {
+        int32_t *d_meta = nullptr;  // [n_mels][3]: first live bin, live bins, where the band's weights start (one allocation with d_w)
+        float *d_w = nullptr;
+    };
+    std::map<int, LogmelDft> logmel_dft;
+    std::map<std::vector<double>, LogmelBank> logmel_banks;  // keyed by (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
@@ -75,6 +86,7 @@ void free_pack_scratch(Context *ctx);  // (pcm_pack.hip; vpz_context_destroy cal
 bool device_range(Context *ctx, const void *p, uint64_t bytes);  // (pcm_pack.hip) inside one allocation of device memory on the context's device
 int pack_room(Context *ctx, size_t n);  // (pcm_pack.hip) room for n vpz_pack_row in pack_host / pack_dev; the previous copy has left the buffer
 void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_destroy calls it)
+void free_logmel_tables(Context *ctx);  // (pcm_logmel.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

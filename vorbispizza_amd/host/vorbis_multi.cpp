@@ -35,6 +35,9 @@
 // vpzm_decode_ranges_resampled (include/vorbispizza_multi_resample.h) is that call with vpz_pcm_resample as its last stage: open_one works out
 // every entry's ratio, the synth calls write float32, and `download` makes one launch per ratio among the sub-batch's members.
 //
+// vpzm_decode_ranges_logmel (include/vorbispizza_multi_logmel.h) is the mono resampled call with one more stage: the resample launches write
+// into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
@@ -61,6 +64,8 @@
 #include "../../include/vorbispizza_pcm_pack.h"
 #include "../../include/vorbispizza_pcm_resample.h"
 #include "../../include/vorbispizza_multi_resample.h"
+#include "../../include/vorbispizza_pcm_logmel.h"
+#include "../../include/vorbispizza_multi_logmel.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -257,8 +262,10 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     SetupCache<vpz_entropy_setup> esetups{vpz_entropy_setup_destroy, {}};
     SetupCache<vpz_entropy_group> egroups{vpz_entropy_group_destroy, {}};  // mixed_setups: the groups of the merged setups, kept alike
     // (kF0Amp, kF0Coeff: a batch call's host route uploads a type-0 floor's data beside residue, posts and counts)
-    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kBuffers };
-    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
+    // (kMono: a log-mel call's resampled mono rows [members][frames], between the resample launches and the vpz_pcm_logmel launch that
+    // reads them; the lane owns it, it only grows, and it goes with the lane when the dispatcher is destroyed)
+    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kBuffers };
+    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
     float *residue() const { return static_cast<float *>(buf[kResidue].p); }  // (float32 or int16 values; the ABI's parameter is float-typed)
     int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
@@ -266,6 +273,7 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     char *pcm() const { return static_cast<char *>(buf[kPcm].p); }
     float *f0_amp() const { return static_cast<float *>(buf[kF0Amp].p); }
     float *f0_coeff() const { return static_cast<float *>(buf[kF0Coeff].p); }
+    float *mono() const { return static_cast<float *>(buf[kMono].p); }
 };
 
 struct Slot {  // page-locked batch arrays of one sub-batch in flight (a device-decoded one holds packets, spans and payload only)
@@ -361,6 +369,8 @@ struct Batch {
     void *dst = nullptr;
     int32_t rate = 0, downmix = 0;  // vpzm_decode_ranges_resampled: every row at `rate` (0: at the stream's own), mixed down to mono
     bool resampled() const { return rate > 0; }
+    // vpzm_decode_ranges_logmel: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed)
+    const vpz_logmel_spec *mel = nullptr;
 };
 
 // ceil(samples * up / down): the output samples of a resampled window (the definition's J)
@@ -847,10 +857,14 @@ struct GroupRun {
             for (const Job &J : jobs)
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             // (a launch that reads nothing: the destination stands in for a source of no elements)
-            if (!rows.empty())
+            // (a log-mel call: samples = 0 descriptors of its own kernel, so an undelivered row is the silence row)
+            if (!rows.empty() && batch.mel)
+                ok = vpz_pcm_logmel(G.lanes[0].ctx, batch.dst, 0, batch.frames, batch.mel, (int32_t)rows.size(), rows.data(), batch.dst,
+                                    (int64_t)jobs.size()) == VPZ_OK;
+            else if (!rows.empty())
                 ok = vpz_pcm_pack(G.lanes[0].ctx, batch.dst, 0, batch.channels, (int32_t)rows.size(), rows.data(), batch.dst, (int64_t)jobs.size(),
                                   batch.frames, batch.layout) == VPZ_OK;
-            if (!ok) m->fail(std::string("vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1216,6 +1230,21 @@ struct SubCall {
                 // group on the lane's stream -- one launch where the members share a rate, more where streams of one setup differ in rate.
                 // A member without samples needs no ratio of its own: its zero row rides in the first group (alone, at 1:1, when no
                 // member has samples)
+                // A log-mel call: the launches write mono planar float32 rows into the lane's temporary [members][frames] (member j in row
+                // j), and ONE vpz_pcm_logmel launch on the same stream -- stream-ordered: no synchronise in between -- turns row j's
+                // first J_j samples into row k - lo of the group's piece
+                const vpz_logmel_spec *mel = R.batch.mel;
+                void *rs_dst = R.batch.dst;
+                int64_t rs_rows = (int64_t)(R.hi - R.lo);
+                if (mel) {
+                    if (L.buf[Lane::kMono].grow(L.ctx, rows.size() * (size_t)R.batch.frames, sizeof(float))) {
+                        rs_dst = L.mono();
+                        rs_rows = (int64_t)rows.size();
+                    } else {
+                        R.m->fail("vpzm_decode_ranges_logmel: the resampled rows' device temporary could not be allocated");
+                        rc = VPZ_E_NOMEM;
+                    }
+                }
                 std::vector<char> taken(rows.size(), 0);
                 std::vector<vpz_pack_row> group;
                 for (size_t left = rows.size(); left > 0 && rc == VPZ_OK;) {
@@ -1228,17 +1257,33 @@ struct SubCall {
                         if (!taken[j] && (rows[j].samples == 0 || (job(j).up == up && job(j).down == down))) {
                             taken[j] = 1;
                             group.push_back(rows[j]);
+                            if (mel) group.back().row = (int64_t)j;
                         }
                     left -= group.size();
-                    rc = vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, R.batch.downmix, (int32_t)group.size(), group.data(), R.batch.dst,
-                                          (int64_t)(R.hi - R.lo), R.batch.channels, R.batch.frames, R.batch.layout);
+                    rc = vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, R.batch.downmix, (int32_t)group.size(), group.data(), rs_dst, rs_rows,
+                                          R.batch.channels, R.batch.frames, R.batch.layout);
                     ++resample_launches;
                 }
                 for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
                 if (rc != VPZ_OK) {
                     R.m->fail(std::string("vpz_pcm_resample: ") + vpz_context_last_error(L.ctx));
                     (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
+                } else if (mel) {
+                    for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * R.batch.frames, written[j], rows[j].row};
+                    if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
+                    const auto t_mel = Clock::now();
+                    rc = vpz_pcm_logmel(L.ctx, L.mono(), (int64_t)rows.size() * R.batch.frames, R.batch.frames, mel, (int32_t)rows.size(), rows.data(),
+                                        R.batch.dst, (int64_t)(R.hi - R.lo));
+                    if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_logmel: ") + vpz_context_last_error(L.ctx));
+                    if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
+                        fprintf(stderr, "[vpzm] group %d: sub-batch %zu log-mel kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b,
+                                seconds_since(t_mel) * 1e3, rows.size(), (long long)R.batch.frames);
                 }
+            } else if (R.batch.mel) {
+                // (no staged PCM: silence rows, from a launch that reads nothing -- the destination stands in for a source of no elements)
+                rc = vpz_pcm_logmel(L.ctx, R.batch.dst, 0, R.batch.frames, R.batch.mel, (int32_t)rows.size(), rows.data(), R.batch.dst,
+                                    (int64_t)(R.hi - R.lo));
+                if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_logmel: ") + vpz_context_last_error(L.ctx));
             } else {
                 // (no staged PCM: a launch that reads nothing -- the destination stands in for a source of no elements)
                 rc = vpz_pcm_pack(L.ctx, staged ? (const void *)L.pcm() : R.batch.dst, staged ? pcm_elems : 0, R.batch.channels, (int32_t)rows.size(),
@@ -1542,6 +1587,25 @@ int vpzm_decode_ranges_resampled(vpzm_dispatcher *m, int32_t n, const uint8_t *c
     batch.rate = sample_rate;
     batch.downmix = downmix;
     // (the synth calls write float32, interleaved, whatever the batch's element type: the resample step converts once, at the end)
+    return decode_call(m, n, data, size, ranges ? ranges : &none, VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_logmel(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                              const vpz_logmel_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!group_dst || !spec || frames < 1 || (n > 0 && !ranges)) return VPZM_E_ARG;
+    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
+    if (vpz_mel_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
+    if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
+    if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
+    static const vpzm_range none{0, 0};
+    Batch batch;
+    batch.channels = 1;
+    batch.layout = VPZ_OUT_PLANAR;  // (of the resampled rows in the lane's temporary: mono, float32)
+    batch.frames = frames;
+    batch.rate = (int32_t)spec->sample_rate;
+    batch.downmix = 1;
+    batch.mel = spec;
     return decode_call(m, n, data, size, ranges ? ranges : &none, VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -48,6 +48,7 @@ MIXED_EXPORTED_SYMBOLS = ["vpzm_set_mixed_setups", "vpzm_last_call_counts"]  # (
 RANGES_EXPORTED_SYMBOLS = ["vpzm_decode_ranges"]  # (vorbispizza_multi_ranges.h)
 BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  # (vorbispizza_multi_batch.h)
 RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
+LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
@@ -84,6 +85,9 @@ def lib():
             L.vpzm_decode_ranges_resampled.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, vp, vp,
                                                        C.POINTER(Stats)]
             L.vpzm_decode_ranges_resampled.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_logmel"):
+            L.vpzm_decode_ranges_logmel.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.LogMelSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_logmel.restype = C.c_int
         _bound = True
     return L
 
@@ -243,4 +247,51 @@ class Dispatcher:
             name = "vpzm_decode_ranges_resampled"
         if rc != OK:
             raise MultiError("%s failed (status %d): %s" % (name, rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_logmel(self, datas, ranges, frames, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None,
+                             mel_scale="slaney", mel_norm="slaney", log=True, floor=1e-10, bands_first=True, out=None):
+        """vpzm_decode_ranges_logmel: decode_ranges_batch(..., sample_rate=sample_rate, mono=True) with one more stage on the device --
+        entry k's window, resampled and mixed down, padded with zeros to `frames` OUTPUT samples, becomes row k of (log-)mel frames:
+        [n_mels, T] (bands_first) or [T, n_mels], float32, T = 1 + frames // hop (include/vorbispizza_pcm_logmel.h states the
+        definition; f_max None: sample_rate / 2; log False: the mel power).  results["samples"] counts the window's output samples.
+        out: as for decode_ranges_batch, one contiguous float32 tensor per group of shape [hi - lo, n_mels, T] (or [hi - lo, T, n_mels])
+        on the group's device -- anything else raises before the library is called.  Returns (parts, whole_or_None, results, stats)."""
+        import torch
+        spec = capi.LogMelSpec.make(sample_rate=sample_rate, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max, mel_scale=mel_scale,
+                                    mel_norm=mel_norm, log=log, floor=floor, bands_first=bands_first)
+        if frames < 1 or hop < 1 or n_mels < 1:
+            raise ValueError("decode_ranges_logmel: frames, hop and n_mels must be at least 1")
+        n = len(datas)
+        ids = self.device_ids
+        T = spec.n_frames(frames)
+        cuts = [self.batch_partition(n, g) for g in range(self.n_devices)]
+        shape = (lambda rows: (rows, n_mels, T)) if bands_first else (lambda rows: (rows, T, n_mels))
+        whole = None
+        if out is None:
+            if len(set(ids)) == 1:
+                whole = torch.empty(shape(n), dtype=torch.float32, device="cuda:%d" % ids[0])
+                out = [whole[lo:hi] for lo, hi in cuts]
+            else:
+                out = [torch.empty(shape(hi - lo), dtype=torch.float32, device="cuda:%d" % d) for (lo, hi), d in zip(cuts, ids)]
+        if len(out) != self.n_devices:
+            raise ValueError("decode_ranges_logmel: out needs one tensor per group (%d), got %d" % (self.n_devices, len(out)))
+        for g, (t, (lo, hi), d) in enumerate(zip(out, cuts, ids)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != d:
+                raise ValueError("decode_ranges_logmel: out[%d] is not a tensor on the group's device cuda:%d" % (g, d))
+            if tuple(t.shape) != shape(hi - lo) or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("decode_ranges_logmel: out[%d] must be a contiguous float32 tensor of shape %s" % (g, shape(hi - lo)))
+        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
+        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
+        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
+        dst = (C.c_void_p * self.n_devices)(*[t.data_ptr() if t.numel() else None for t in out])
+        # (the library writes on its own streams into memory torch may have just recycled: whatever torch has queued there is done first)
+        for d in sorted(set(ids)):
+            torch.cuda.current_stream(d).synchronize()
+        results = np.zeros(n, dtype=RESULT_DTYPE)
+        stats = Stats()
+        rc = lib().vpzm_decode_ranges_logmel(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
+                                             C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_logmel failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats

@@ -150,6 +150,61 @@ def test_a_bad_entry_costs_only_itself_and_leaves_a_zero_row(ctx, gpu_entropy):
         assert not as_bits(got)[[1, 3, 4, 5, 6, 7]].any()
 
 
+def sentinel_out(d, n, shape, dtype, value):
+    """one tensor per group of `d` for an n-entry call, filled with `value`: shape(rows) is a group's"""
+    import torch
+    cuts = [d.batch_partition(n, g) for g in range(d.n_devices)]
+    return [torch.full(shape(hi - lo), value, dtype=dtype, device="cuda:%d" % i) for (lo, hi), i in zip(cuts, d.device_ids)]
+
+
+def check_failed_delivery(monkeypatch, d, run, empty_row):
+    """VPZM_FAIL_DELIVERY (host/vorbis_multi.cpp): a sub-batch's delivery launch counts as failed without being made.  run() -> (tensor,
+    results) of one call on dispatcher `d` into sentinel-filled tensors.  Every entry that a delivery launch serves -- OK in the plain
+    call, with packets -- comes back E_SYNTH with no samples; an entry with a status of its own keeps it, and so does the empty window (OK,
+    no packets: it is in no sub-batch, GroupRun::zero_rows alone defines its row); every row is `empty_row`; the next call without the
+    switch is the plain call bit for bit."""
+    import torch
+    from vorbispizza_amd import multi
+    monkeypatch.delenv("VPZM_FAIL_DELIVERY", raising=False)
+    plain, plain_results = run()
+    monkeypatch.setenv("VPZM_FAIL_DELIVERY", "1")
+    got, results = run()
+    monkeypatch.delenv("VPZM_FAIL_DELIVERY")
+    delivered = (plain_results["status"] == 0) & (plain_results["packets"] > 0)
+    assert delivered.sum() >= 3 and (plain_results["status"] != 0).sum() >= 4 and ((plain_results["status"] == 0) & ~delivered).sum() == 1
+    assert (results["status"][delivered] == multi.E_SYNTH).all(), results["status"]
+    assert np.array_equal(results["status"][~delivered], plain_results["status"][~delivered])
+    assert (results["samples"] == 0).all()
+    assert (as_bits(got) == empty_row).all()
+    assert not (as_bits(plain) == empty_row).all()
+    assert d.last_error() != ""
+    again, again_results = run()
+    assert torch.equal(as_bits(again), as_bits(plain))
+    for field in FIELDS:
+        if field != "device_slot":
+            assert np.array_equal(again_results[field], plain_results[field]), field
+
+
+@pytest.mark.parametrize("gpu_entropy", [False, True])
+def test_a_failed_pack_costs_its_members_e_synth_and_leaves_zero_rows(ctx, monkeypatch, gpu_entropy):
+    """the entries of test_a_bad_entry_costs_only_itself_and_leaves_a_zero_row under VPZM_FAIL_DELIVERY (check_failed_delivery)"""
+    import torch
+    from vorbispizza_amd import multi
+    s, mono = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"]
+    garbage = Stream.__new__(Stream)
+    garbage.data = np.frombuffer(b"not an ogg file at all" * 10, dtype=np.uint8)
+    a, n = s.bounds[3] + 7, 3000
+    entries = [(s, a, n), (s, -1, n), (s, a, n - 1), (s, s.total + 1, n), (s, a, n + 1), (garbage, a, n), (mono, 5, 100), (s, s.total, 10), (s, a + 1, n)]
+    d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
+    try:
+        for planar, s16 in ((True, False), (False, True)):
+            dtype, shape = (torch.int16 if s16 else torch.float32), (lambda rows: (rows, 2, n) if planar else (rows, n, 2))
+            check_failed_delivery(monkeypatch, d, lambda: batch_call(entries, 2, n, planar, s16, dispatcher=d,
+                                                                     out=sentinel_out(d, len(entries), shape, dtype, 77))[:2], 0)
+    finally:
+        d.close()
+
+
 def test_the_groups_share_one_tensor_and_change_no_byte(ctx):
     import torch
     from vorbispizza_amd import multi

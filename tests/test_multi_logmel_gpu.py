@@ -154,6 +154,30 @@ def test_a_refused_entry_costs_only_itself_and_leaves_the_silence_row(ctx, gpu_e
         assert (img[[0, 4, 7]].view(np.uint32) != silence).any(axis=(1, 2)).all()
 
 
+@pytest.mark.parametrize("gpu_entropy", [False, True])
+def test_a_failed_logmel_launch_costs_its_members_e_synth_and_leaves_silence_rows(ctx, monkeypatch, gpu_entropy):
+    """the entries of test_a_refused_entry_costs_only_itself_and_leaves_the_silence_row under VPZM_FAIL_DELIVERY (check_failed_delivery
+    of test_multi_batch_gpu.py): the resample launches into the lane's temporary are made, the log-mel launch is not"""
+    import torch
+    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from vorbispizza_amd import multi
+    s, mono, odd = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"], rerated(44101)
+    garbage = Stream.__new__(Stream)
+    garbage.data = np.frombuffer(b"not an ogg file at all" * 10, dtype=np.uint8)
+    up, down = ratio(s, RATE)
+    a, n = s.bounds[3] + 7, 7 * down
+    J = out_len(n, up, down)
+    entries = [(s, a, n), (s, -1, n), (s, a, n + 1), (garbage, a, n), (mono, 5, 100), (odd, 3, 500), (s, s.total, 10), (s, a + 1, n)]
+    d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
+    try:
+        for spec in VARIANTS:
+            silence = int(silence_value(spec["floor"]).view(np.int32)) if spec["log"] else 0
+            check_failed_delivery(monkeypatch, d, lambda: logmel_call(entries, J, spec, dispatcher=d, out=sentinel_out(
+                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], silence)
+    finally:
+        d.close()
+
+
 def test_a_wrong_out_tensor_raises_and_a_wrong_spec_is_refused(ctx):
     import torch
     from vorbispizza_amd import capi, multi

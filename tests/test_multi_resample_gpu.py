@@ -85,7 +85,7 @@ def truth_row(ctx, s, a, m, rate, mono):
     return _rows[key]
 
 
-def resampled_call(entries, rate, channels, frames, planar=True, s16=False, mono=False, device_ids=(0,), dispatcher=None, **opt):
+def resampled_call(entries, rate, channels, frames, planar=True, s16=False, mono=False, device_ids=(0,), dispatcher=None, out=None, **opt):
     """-> (the batch as one tensor, results, stats)"""
     import torch
     from vorbispizza_amd import multi
@@ -94,7 +94,7 @@ def resampled_call(entries, rate, channels, frames, planar=True, s16=False, mono
     d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
     try:
         parts, whole, results, stats = d.decode_ranges_batch([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], channels, frames,
-                                                             planar=planar, s16=s16, sample_rate=rate, mono=mono)
+                                                             planar=planar, s16=s16, sample_rate=rate, mono=mono, out=out)
     finally:
         if dispatcher is None:
             d.close()
@@ -272,6 +272,31 @@ def test_a_bad_entry_costs_only_itself_and_leaves_a_zero_row(ctx, gpu_entropy):
                    dict(dst=None), dict(m=None), dict(results=None), dict(ranges=None), dict(n=-1)):
         assert L.vpzm_decode_ranges_resampled(*args(**change)) == multi.E_ARG, change
     d.close()
+
+
+@pytest.mark.parametrize("gpu_entropy", [False, True])
+def test_failed_resample_launches_cost_their_members_e_synth_and_leave_zero_rows(ctx, monkeypatch, gpu_entropy):
+    """the entries of test_a_bad_entry_costs_only_itself_and_leaves_a_zero_row under VPZM_FAIL_DELIVERY (check_failed_delivery of
+    test_multi_batch_gpu.py)"""
+    import torch
+    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from vorbispizza_amd import multi
+    s, mono, odd = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"], rerated(44101)
+    garbage = Stream.__new__(Stream)
+    garbage.data = np.frombuffer(b"not an ogg file at all" * 10, dtype=np.uint8)
+    up, down = ratio(s, RATE)
+    a, n = s.bounds[3] + 7, 7 * down
+    J = out_len(n, up, down)
+    entries = [(s, a, n), (s, -1, n), (s, a, n - 2), (s, s.total + 1, n), (s, a, n + 1), (garbage, a, n), (mono, 5, 100), (s, s.total, 10), (odd, 3, 500),
+               (s, a + 1, n)]
+    d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
+    try:
+        for planar, s16 in ((True, False), (False, True)):
+            dtype, shape = (torch.int16 if s16 else torch.float32), (lambda rows: (rows, 2, J) if planar else (rows, J, 2))
+            check_failed_delivery(monkeypatch, d, lambda: resampled_call(entries, RATE, 2, J, planar, s16, dispatcher=d,
+                                                                         out=sentinel_out(d, len(entries), shape, dtype, 77))[:2], 0)
+    finally:
+        d.close()
 
 
 def test_damaged_audio_is_the_same_on_both_routes(ctx):

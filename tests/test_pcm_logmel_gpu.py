@@ -261,6 +261,7 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx):
     spec = capi.LogMelSpec.make()
     good = dict(src_ptr=src.data_ptr(), src_elems=2000, frames=F, spec=spec, rows=[(3, 100, 1), (400, 500, 3)], dst_ptr=dst.data_ptr(), dst_rows=dst_rows)
     pinned = torch.zeros(dst_rows * n_mels * T, dtype=torch.float32, pin_memory=True)
+    host_src = torch.full((2000,), 0.5, dtype=torch.float32, pin_memory=True)
     bad = [("no context", dict(handle=False)), ("null source", dict(src_ptr=None)), ("null destination", dict(dst_ptr=None)), ("null rows", dict(null_rows=True)),
            ("null spec", dict(null_spec=True)), ("frames < n_fft / 2 + 1", dict(frames=200, rows=[(3, 100, 1)])), ("n_rows < 0", dict(n_rows=-1)),
            ("dst_rows < 0", dict(dst_rows=-1)), ("src_elems < 0", dict(src_elems=-1)), ("samples > frames", dict(rows=[(3, 501, 1)])),
@@ -270,7 +271,8 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx):
            ("destination not aligned", dict(dst_ptr=dst.data_ptr() + 2)), ("source not aligned", dict(src_ptr=src.data_ptr() + 1)),
            # (the rows named lie inside the tensors: without the range checks these two calls would succeed)
            ("destination longer than its allocation", dict(dst_rows=(1 << 40) // (n_mels * T * 4))), ("source longer than its allocation", dict(src_elems=1 << 38)),
-           ("destination is host memory", dict(dst_ptr=pinned.data_ptr())), ("frames overflow", dict(frames=1 << 61, rows=[(3, 100, 1)]))]
+           ("destination is host memory", dict(dst_ptr=pinned.data_ptr())), ("source is host memory", dict(src_ptr=host_src.data_ptr())),
+           ("frames overflow", dict(frames=1 << 61, rows=[(3, 100, 1)]))]
     bad += [("spec: " + what, dict(spec=s)) for what, s in refused_specs(capi)]
     for what, change in bad:
         assert raw_call(ctx, **dict(good, **change)) == capi.E_INVALID_ARG, what

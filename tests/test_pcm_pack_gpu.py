@@ -178,6 +178,7 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx, layout):
     elem = 2 if s16 else 4
     pinned = torch.full((dst_rows, channels, frames), 77, dtype=torch.int16 if s16 else torch.float32, pin_memory=True)
     assert pinned.is_pinned() and not pinned.is_cuda
+    host_src = torch.full((1000,), 3, dtype=torch.int16 if s16 else torch.float32, pin_memory=True)
     refused = {
         "null context": dict(handle=False),
         "null source": dict(src_ptr=None),
@@ -187,6 +188,8 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx, layout):
         "too many channels": dict(channels=capi.MAX_CHANNELS + 1),
         "no frames": dict(frames=0),
         "negative descriptor count": dict(n_rows=-1),
+        "negative row count": dict(dst_rows=-1),
+        "negative source size": dict(src_elems=-1),
         "layout 4": dict(layout=4),
         "layout -1": dict(layout=-1),
         "source starts before the array": dict(rows=[(-1, 10, 1)]),
@@ -197,10 +200,14 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx, layout):
         "row behind the last": dict(rows=[(0, 1, dst_rows)]),
         "negative row": dict(rows=[(0, 1, -1)]),
         "a row named twice": dict(rows=[(0, 1, 2), (8, 3, 0), (16, 2, 2)]),
+        "more descriptors than rows": dict(rows=[(0, 1, 0)] * (dst_rows + 1)),
         "destination off its element": dict(dst_ptr=dst.data_ptr() + 1),
+        "source off its element": dict(src_ptr=src.data_ptr() + elem // 2, src_elems=999),
         "page-locked host destination": dict(dst_ptr=pinned.data_ptr()),
+        "page-locked host source": dict(src_ptr=host_src.data_ptr()),
         # (row 1 alone is named and lies inside the tensor: without the range check the call would succeed)
         "destination longer than its allocation": dict(dst_rows=(1 << 40) // (channels * frames * elem)),
+        "source longer than its allocation": dict(src_elems=1 << 38),
     }
     for what, change in refused.items():
         assert raw_call(ctx, **{**good, **change}) == capi.E_INVALID_ARG, what

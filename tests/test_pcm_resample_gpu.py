@@ -262,6 +262,8 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx, layout):
         "too many channels": dict(channels=capi.MAX_CHANNELS + 1, out_channels=capi.MAX_CHANNELS + 1),
         "no frames": dict(frames=0),
         "negative descriptor count": dict(n_rows=-1),
+        "negative row count": dict(dst_rows=-1),
+        "negative source size": dict(src_elems=-1),
         "layout 4": dict(layout=4),
         "layout -1": dict(layout=-1),
         "up above 1024": dict(up=1025, down=1),
@@ -283,6 +285,7 @@ def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx, layout):
         "row behind the last": dict(rows=[(0, 1, dst_rows)]),
         "negative row": dict(rows=[(0, 1, -1)]),
         "a row named twice": dict(rows=[(0, 1, 2), (8, 3, 0), (16, 2, 2)]),
+        "more descriptors than rows": dict(rows=[(0, 1, 0)] * (dst_rows + 1)),
         "destination off its element": dict(dst_ptr=dst.data_ptr() + 1),
         "source off its element": dict(src_ptr=src.data_ptr() + 2, src_elems=999),
         "page-locked host destination": dict(dst_ptr=pinned.data_ptr()),

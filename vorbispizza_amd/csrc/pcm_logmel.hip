@@ -318,47 +318,19 @@ extern "C" int vpz_pcm_logmel(vpz_context *c, const void *src_dev, int64_t src_e
     if (!c) return VPZ_E_INVALID_ARG;
     vpz::Context *ctx = &c->impl;
     auto refuse = [&](const char *what) { return vpz::set_error(ctx, VPZ_E_INVALID_ARG, what); };
-    if (!src_dev || !dst_dev || !rows || !spec) return refuse("vpz_pcm_logmel: null pointer");
+    if (!spec) return refuse("vpz_pcm_logmel: null pointer");
     if (!vpz::logmel_spec_ok(*spec)) return refuse("vpz_pcm_logmel: a spec outside the limits");
     const vpz_logmel_spec &s = *spec;
     if (frames < s.n_fft / 2 + 1) return refuse("vpz_pcm_logmel: frames < n_fft / 2 + 1 (the reflection needs it)");
-    if (n_rows < 0 || dst_rows < 0 || src_elems < 0) return refuse("vpz_pcm_logmel: a negative count");
     if (frames > INT64_MAX / 8) return refuse("vpz_pcm_logmel: sizes overflow");
     const int64_t T = 1 + frames / s.hop;
-    const unsigned __int128 row_elems = (unsigned __int128)(uint64_t)T * (uint64_t)s.n_mels;
-    const unsigned __int128 dst_bytes = row_elems * (uint64_t)dst_rows * sizeof(float), src_bytes = (unsigned __int128)(uint64_t)src_elems * sizeof(float);
-    if (row_elems * sizeof(float) > (uint64_t)INT64_MAX || dst_bytes > (uint64_t)INT64_MAX || src_bytes > (uint64_t)INT64_MAX)
-        return refuse("vpz_pcm_logmel: sizes overflow");
-    if (reinterpret_cast<uintptr_t>(dst_dev) % sizeof(float) || reinterpret_cast<uintptr_t>(src_dev) % sizeof(float))
-        return refuse("vpz_pcm_logmel: a pointer is not aligned to float32");
-    if (n_rows > dst_rows) return refuse("vpz_pcm_logmel: more descriptors than rows (a row named twice)");
-    std::vector<int64_t> named;
-    try {
-        named.reserve((size_t)n_rows);
-    } catch (...) {
-        return vpz::set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_logmel: out of host memory");
-    }
-    for (int32_t r = 0; r < n_rows; ++r) {
-        const vpz_pack_row &d = rows[r];
-        if (d.src < 0 || d.src > src_elems || d.samples < 0 || d.samples > src_elems - d.src)
-            return refuse("vpz_pcm_logmel: a descriptor's source range leaves the source array");
-        if (d.samples > frames) return refuse("vpz_pcm_logmel: a descriptor's samples exceed frames");
-        if (d.row < 0 || d.row >= dst_rows) return refuse("vpz_pcm_logmel: a descriptor's row is out of range");
-        named.push_back(d.row);
-    }
-    std::sort(named.begin(), named.end());
-    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return refuse("vpz_pcm_logmel: a row is named by two descriptors");
-    VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // what keeps a caller's wrong pointer from becoming a fault: both arrays are device memory of this device, inside one allocation each
-    if (!vpz::device_range(ctx, dst_dev, (uint64_t)dst_bytes))
-        return refuse("vpz_pcm_logmel: the destination is not device memory of the context's device, or leaves its allocation");
-    if (!vpz::device_range(ctx, src_dev, (uint64_t)src_bytes))
-        return refuse("vpz_pcm_logmel: the source is not device memory of the context's device, or leaves its allocation");
-    if (n_rows == 0) return VPZ_OK;
+    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_logmel", src_dev, src_elems, sizeof(float), 1, 1, 1, frames, n_rows, rows, dst_dev, dst_rows,
+                                                       (unsigned __int128)(uint64_t)T * (uint64_t)s.n_mels, sizeof(float)});
+    if (rc != VPZ_OK || n_rows == 0) return rc;
 
     const vpz::Context::LogmelDft *tb = nullptr;
     const vpz::Context::LogmelBank *bk = nullptr;
-    int rc = vpz::dft_for(ctx, s.n_fft, &tb);
+    rc = vpz::dft_for(ctx, s.n_fft, &tb);
     if (rc == VPZ_OK) rc = vpz::bank_for(ctx, s, &bk);
     if (rc != VPZ_OK) return rc;
 
@@ -378,15 +350,10 @@ extern "C" int vpz_pcm_logmel(vpz_context *c, const void *src_dev, int64_t src_e
     const int64_t blocks = (T + a.Tt - 1) / a.Tt;
     if (blocks > 0x7fffffff) return refuse("vpz_pcm_logmel: a row too long for one launch");
 
-    rc = vpz::pack_room(ctx, (size_t)n_rows);
+    rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);
     if (rc != VPZ_OK) return rc;
-    memcpy(ctx->pack_host, rows, sizeof(vpz_pack_row) * (size_t)n_rows);
-    VPZ_HIP_TRY(ctx, hipMemcpyAsync(ctx->pack_dev, ctx->pack_host, sizeof(vpz_pack_row) * (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
-    VPZ_HIP_TRY(ctx, hipEventRecord(ctx->pack_done, ctx->stream));
-    ctx->pack_pending = true;
 
     a.src = static_cast<const float *>(src_dev);
-    a.rows = static_cast<const vpz_pack_row *>(ctx->pack_dev);
     a.dst = static_cast<float *>(dst_dev);
     a.table = tb->d_table;
     a.meta = bk->d_meta;

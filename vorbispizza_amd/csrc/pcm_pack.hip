@@ -79,9 +79,7 @@ __global__ __launch_bounds__(kPackBlock) void pcm_pack_kernel(const T *__restric
     }
 }
 
-}  // namespace
-
-// (the two below serve vpz_pcm_resample too: vpz_internal.hpp declares them)
+// ---- what the three row launches share (vpz_internal.hpp declares check_row_launch, upload_rows and layout_of) ----
 // `bytes` bytes from `p` lie inside one allocation of device memory on the context's device
 bool device_range(Context *ctx, const void *p, uint64_t bytes)
 {
@@ -125,6 +123,81 @@ int pack_room(Context *ctx, size_t n)
     return VPZ_OK;
 }
 
+// The arithmetic of a row launch's contract, on numbers and descriptors alone: what is wrong with `q`, or nullptr and the two arrays'
+// sizes in bytes.  (`*status` is what the refusal costs: VPZ_E_INVALID_ARG but for the memory of the check itself)
+const char *row_launch_flaw(const RowLaunch &q, uint64_t *dst_bytes, uint64_t *src_bytes, int *status)
+{
+    *status = VPZ_E_INVALID_ARG;
+    if (!q.src || !q.dst || !q.rows) return "null pointer";
+    if (q.frames < 1 || q.n_rows < 0 || q.dst_rows < 0 || q.src_elems < 0) return "frames < 1 or a negative count";
+    // (sizes in bytes must fit 63 bits, so that every element index a kernel forms fits an int64_t)
+    const unsigned __int128 dst = q.row_elems * (uint64_t)q.dst_rows * q.dst_elem, src = (unsigned __int128)(uint64_t)q.src_elems * q.src_elem;
+    if (q.row_elems * q.dst_elem > (uint64_t)INT64_MAX || dst > (uint64_t)INT64_MAX || src > (uint64_t)INT64_MAX) return "sizes overflow";
+    if (reinterpret_cast<uintptr_t>(q.dst) % q.dst_elem || reinterpret_cast<uintptr_t>(q.src) % q.src_elem)
+        return "a pointer is not aligned to its element type";
+    if (q.n_rows > q.dst_rows) return "more descriptors than rows (a row named twice)";
+    std::vector<int64_t> named;
+    try {
+        named.reserve((size_t)q.n_rows);
+    } catch (...) {
+        *status = VPZ_E_NOMEM;
+        return "out of host memory";
+    }
+    for (int32_t r = 0; r < q.n_rows; ++r) {
+        const vpz_pack_row &d = q.rows[r];
+        if (d.src < 0 || d.src > q.src_elems || d.samples < 0 || d.samples > (q.src_elems - d.src) / q.src_channels)
+            return "a descriptor's source range leaves the source array";
+        // ceil(samples * up / down) <= frames  <=>  samples * up <= frames * down (128 bits hold both products)
+        if ((unsigned __int128)(uint64_t)d.samples * (uint64_t)q.up > (unsigned __int128)(uint64_t)q.frames * (uint64_t)q.down)
+            return "a descriptor's output samples exceed frames";
+        if (d.row < 0 || d.row >= q.dst_rows) return "a descriptor's row is out of range";
+        named.push_back(d.row);
+    }
+    std::sort(named.begin(), named.end());
+    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return "a row is named by two descriptors";
+    *dst_bytes = (uint64_t)dst;
+    *src_bytes = (uint64_t)src;
+    return nullptr;
+}
+
+}  // namespace
+
+int check_row_launch(Context *ctx, const RowLaunch &q)
+{
+    auto refuse = [&](int status, const char *what) { return set_error(ctx, status, (std::string(q.name) + ": " + what).c_str()); };
+    uint64_t dst_bytes = 0, src_bytes = 0;
+    int status = VPZ_OK;
+    if (const char *flaw = row_launch_flaw(q, &dst_bytes, &src_bytes, &status)) return refuse(status, flaw);
+    // ---- from here on HIP is touched
+    VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // what keeps a caller's wrong pointer from becoming a fault: both arrays are device memory of this device, inside one allocation each
+    if (!device_range(ctx, q.dst, dst_bytes))
+        return refuse(VPZ_E_INVALID_ARG, "the destination is not device memory of the context's device, or leaves its allocation");
+    if (!device_range(ctx, q.src, src_bytes))
+        return refuse(VPZ_E_INVALID_ARG, "the source is not device memory of the context's device, or leaves its allocation");
+    return VPZ_OK;
+}
+
+int upload_rows(Context *ctx, int32_t n_rows, const vpz_pack_row *rows, const vpz_pack_row **d_rows)
+{
+    const size_t bytes = sizeof(vpz_pack_row) * (size_t)n_rows;
+    const int rc = pack_room(ctx, (size_t)n_rows);
+    if (rc != VPZ_OK) return rc;
+    memcpy(ctx->pack_host, rows, bytes);
+    VPZ_HIP_TRY(ctx, hipMemcpyAsync(ctx->pack_dev, ctx->pack_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    VPZ_HIP_TRY(ctx, hipEventRecord(ctx->pack_done, ctx->stream));
+    ctx->pack_pending = true;
+    *d_rows = static_cast<const vpz_pack_row *>(ctx->pack_dev);
+    return VPZ_OK;
+}
+
+bool layout_of(int32_t layout, bool *s16, bool *planar)
+{
+    *s16 = layout == VPZ_OUT_INTERLEAVED_S16 || layout == VPZ_OUT_PLANAR_S16;
+    *planar = layout == VPZ_OUT_PLANAR || layout == VPZ_OUT_PLANAR_S16;
+    return *s16 || *planar || layout == VPZ_OUT_INTERLEAVED;
+}
+
 void free_pack_scratch(Context *ctx)
 {
     if (ctx->pack_host) (void)hipHostFree(ctx->pack_host);
@@ -143,62 +216,24 @@ extern "C" int vpz_pcm_pack(vpz_context *c, const void *src_dev, int64_t src_ele
     if (!c) return VPZ_E_INVALID_ARG;
     vpz::Context *ctx = &c->impl;
     auto refuse = [&](const char *what) { return vpz::set_error(ctx, VPZ_E_INVALID_ARG, what); };
-    if (!src_dev || !dst_dev || !rows) return refuse("vpz_pcm_pack: null pointer");
     if (channels < 1 || channels > VPZ_MAX_CHANNELS) return refuse("vpz_pcm_pack: channels outside 1..VPZ_MAX_CHANNELS");
-    if (frames < 1 || n_rows < 0 || dst_rows < 0 || src_elems < 0) return refuse("vpz_pcm_pack: frames < 1 or a negative count");
-    if (dst_layout != VPZ_OUT_INTERLEAVED && dst_layout != VPZ_OUT_PLANAR && dst_layout != VPZ_OUT_INTERLEAVED_S16 &&
-        dst_layout != VPZ_OUT_PLANAR_S16)
-        return refuse("vpz_pcm_pack: bad layout");
-    const bool s16 = dst_layout == VPZ_OUT_INTERLEAVED_S16 || dst_layout == VPZ_OUT_PLANAR_S16;
-    // (one channel: planar and interleaved are the same array, and the interleaved kernel reads wide)
-    const bool planar = (dst_layout == VPZ_OUT_PLANAR || dst_layout == VPZ_OUT_PLANAR_S16) && channels > 1;
+    bool s16, planar;
+    if (!vpz::layout_of(dst_layout, &s16, &planar)) return refuse("vpz_pcm_pack: bad layout");
+    planar = planar && channels > 1;  // (one channel: planar and interleaved are the same array, and the interleaved kernel reads wide)
     const uint64_t elem = s16 ? sizeof(int16_t) : sizeof(float);
-    // (sizes in bytes must fit 63 bits, so that every element index the kernel forms fits an int64_t)
-    const unsigned __int128 row_elems = (unsigned __int128)(uint64_t)frames * (uint64_t)channels;
-    const unsigned __int128 dst_bytes = row_elems * (uint64_t)dst_rows * elem, src_bytes = (unsigned __int128)(uint64_t)src_elems * elem;
-    if (row_elems * elem > (uint64_t)INT64_MAX || dst_bytes > (uint64_t)INT64_MAX || src_bytes > (uint64_t)INT64_MAX)
-        return refuse("vpz_pcm_pack: sizes overflow");
-    if (reinterpret_cast<uintptr_t>(dst_dev) % elem || reinterpret_cast<uintptr_t>(src_dev) % elem)
-        return refuse("vpz_pcm_pack: a pointer is not aligned to its element type");
-    if (n_rows > dst_rows) return refuse("vpz_pcm_pack: more descriptors than rows (a row named twice)");
-    std::vector<int64_t> named;
-    try {
-        named.reserve((size_t)n_rows);
-    } catch (...) {
-        return vpz::set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_pack: out of host memory");
-    }
-    for (int32_t r = 0; r < n_rows; ++r) {
-        const vpz_pack_row &d = rows[r];
-        if (d.samples < 0 || d.samples > frames) return refuse("vpz_pcm_pack: a descriptor's samples outside 0..frames");
-        if (d.src < 0 || d.src > src_elems || d.samples * channels > src_elems - d.src)
-            return refuse("vpz_pcm_pack: a descriptor's source range leaves the source array");
-        if (d.row < 0 || d.row >= dst_rows) return refuse("vpz_pcm_pack: a descriptor's row is out of range");
-        named.push_back(d.row);
-    }
-    std::sort(named.begin(), named.end());
-    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return refuse("vpz_pcm_pack: a row is named by two descriptors");
-    VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // what keeps a caller's wrong pointer from becoming a fault: both arrays are device memory of this device, inside one allocation each
-    if (!vpz::device_range(ctx, dst_dev, (uint64_t)dst_bytes))
-        return refuse("vpz_pcm_pack: the destination is not device memory of the context's device, or leaves its allocation");
-    if (!vpz::device_range(ctx, src_dev, (uint64_t)src_bytes))
-        return refuse("vpz_pcm_pack: the source is not device memory of the context's device, or leaves its allocation");
-    if (n_rows == 0) return VPZ_OK;
-
-    int rc = vpz::pack_room(ctx, (size_t)n_rows);
-    if (rc != VPZ_OK) return rc;
-    memcpy(ctx->pack_host, rows, sizeof(vpz_pack_row) * (size_t)n_rows);
-    VPZ_HIP_TRY(ctx, hipMemcpyAsync(ctx->pack_dev, ctx->pack_host, sizeof(vpz_pack_row) * (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
-    VPZ_HIP_TRY(ctx, hipEventRecord(ctx->pack_done, ctx->stream));
-    ctx->pack_pending = true;
+    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_pack", src_dev, src_elems, elem, channels, 1, 1, frames, n_rows, rows, dst_dev, dst_rows,
+                                                       (unsigned __int128)(uint64_t)frames * (uint64_t)channels, elem});
+    if (rc != VPZ_OK || n_rows == 0) return rc;
 
     // one lane per tile: a run of `len` elements that starts anywhere in a 16-byte unit touches at most len / kVec + 2 tiles
     const int64_t vec = 16 / (int64_t)elem, len = planar ? frames : frames * channels, runs = planar ? channels : 1;
     const int64_t tiles_per_run = len / vec + 2;
     const int64_t blocks = (tiles_per_run * runs + vpz::kPackBlock - 1) / vpz::kPackBlock;
     if (blocks > 0x7fffffff) return refuse("vpz_pcm_pack: a row too long for one launch");
+    const vpz_pack_row *d_rows = nullptr;
+    rc = vpz::upload_rows(ctx, n_rows, rows, &d_rows);
+    if (rc != VPZ_OK) return rc;
     const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kPackMaxGridY));
-    const vpz_pack_row *d_rows = static_cast<const vpz_pack_row *>(ctx->pack_dev);
     if (s16 && planar)
         vpz::pcm_pack_kernel<uint16_t, true><<<grid, vpz::kPackBlock, 0, ctx->stream>>>(static_cast<const uint16_t *>(src_dev), d_rows, n_rows,
                                                                                        static_cast<uint16_t *>(dst_dev), frames, channels, tiles_per_run);

@@ -207,66 +207,29 @@ extern "C" int vpz_pcm_resample(vpz_context *c, const void *src_dev, int64_t src
     if (!c) return VPZ_E_INVALID_ARG;
     vpz::Context *ctx = &c->impl;
     auto refuse = [&](const char *what) { return vpz::set_error(ctx, VPZ_E_INVALID_ARG, what); };
-    if (!src_dev || !dst_dev || !rows) return refuse("vpz_pcm_resample: null pointer");
     if (channels < 1 || channels > VPZ_MAX_CHANNELS) return refuse("vpz_pcm_resample: channels outside 1..VPZ_MAX_CHANNELS");
     if (downmix != 0 && downmix != 1) return refuse("vpz_pcm_resample: downmix is 0 or 1");
     if (out_channels != (downmix ? 1 : channels)) return refuse("vpz_pcm_resample: out_channels is `channels`, or 1 with downmix");
     if (!vpz::resample_ratio_ok(up, down)) return refuse("vpz_pcm_resample: a refused ratio (lowest terms, up <= 1024, down <= 32 * up)");
-    if (frames < 1 || n_rows < 0 || dst_rows < 0 || src_elems < 0) return refuse("vpz_pcm_resample: frames < 1 or a negative count");
-    if (dst_layout != VPZ_OUT_INTERLEAVED && dst_layout != VPZ_OUT_PLANAR && dst_layout != VPZ_OUT_INTERLEAVED_S16 &&
-        dst_layout != VPZ_OUT_PLANAR_S16)
-        return refuse("vpz_pcm_resample: bad layout");
-    const bool s16 = dst_layout == VPZ_OUT_INTERLEAVED_S16 || dst_layout == VPZ_OUT_PLANAR_S16;
-    const bool planar = dst_layout == VPZ_OUT_PLANAR || dst_layout == VPZ_OUT_PLANAR_S16;
-    const uint64_t elem = s16 ? sizeof(int16_t) : sizeof(float);
-    // (sizes in bytes must fit 63 bits, and so must a sample index times `up` or `down`: every index the kernel forms fits an int64_t)
-    const unsigned __int128 row_elems = (unsigned __int128)(uint64_t)frames * (uint64_t)out_channels;
-    const unsigned __int128 dst_bytes = row_elems * (uint64_t)dst_rows * elem, src_bytes = (unsigned __int128)(uint64_t)src_elems * sizeof(float);
-    if (row_elems * elem > (uint64_t)INT64_MAX || dst_bytes > (uint64_t)INT64_MAX || src_bytes > (uint64_t)INT64_MAX ||
-        (unsigned __int128)(uint64_t)frames * (uint64_t)std::max(up, down) > (uint64_t)INT64_MAX / 4)
+    bool s16, planar;
+    if (!vpz::layout_of(dst_layout, &s16, &planar)) return refuse("vpz_pcm_resample: bad layout");
+    // (a sample index times `up` or `down` must fit 63 bits like the sizes in bytes: every index the kernel forms fits an int64_t)
+    if (frames > 0 && (unsigned __int128)(uint64_t)frames * (uint64_t)std::max(up, down) > (uint64_t)INT64_MAX / 4)
         return refuse("vpz_pcm_resample: sizes overflow");
-    if (reinterpret_cast<uintptr_t>(dst_dev) % elem || reinterpret_cast<uintptr_t>(src_dev) % sizeof(float))
-        return refuse("vpz_pcm_resample: a pointer is not aligned to its element type");
-    if (n_rows > dst_rows) return refuse("vpz_pcm_resample: more descriptors than rows (a row named twice)");
-    std::vector<int64_t> named;
-    try {
-        named.reserve((size_t)n_rows);
-    } catch (...) {
-        return vpz::set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_resample: out of host memory");
-    }
-    for (int32_t r = 0; r < n_rows; ++r) {
-        const vpz_pack_row &d = rows[r];
-        if (d.src < 0 || d.src > src_elems || d.samples < 0 || d.samples > (src_elems - d.src) / channels)
-            return refuse("vpz_pcm_resample: a descriptor's source range leaves the source array");
-        // J = ceil(samples * up / down) <= frames  <=>  samples * up <= frames * down (both products fit: samples <= 2^61, see above for frames)
-        if ((unsigned __int128)(uint64_t)d.samples * (uint64_t)up > (unsigned __int128)(uint64_t)frames * (uint64_t)down)
-            return refuse("vpz_pcm_resample: a descriptor's output samples exceed frames");
-        if (d.row < 0 || d.row >= dst_rows) return refuse("vpz_pcm_resample: a descriptor's row is out of range");
-        named.push_back(d.row);
-    }
-    std::sort(named.begin(), named.end());
-    if (std::adjacent_find(named.begin(), named.end()) != named.end()) return refuse("vpz_pcm_resample: a row is named by two descriptors");
-    VPZ_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    // what keeps a caller's wrong pointer from becoming a fault: both arrays are device memory of this device, inside one allocation each
-    if (!vpz::device_range(ctx, dst_dev, (uint64_t)dst_bytes))
-        return refuse("vpz_pcm_resample: the destination is not device memory of the context's device, or leaves its allocation");
-    if (!vpz::device_range(ctx, src_dev, (uint64_t)src_bytes))
-        return refuse("vpz_pcm_resample: the source is not device memory of the context's device, or leaves its allocation");
-    if (n_rows == 0) return VPZ_OK;
+    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_resample", src_dev, src_elems, sizeof(float), channels, up, down, frames, n_rows, rows, dst_dev,
+                                                       dst_rows, (unsigned __int128)(uint64_t)frames * (uint64_t)out_channels,
+                                                       s16 ? sizeof(int16_t) : sizeof(float)});
+    if (rc != VPZ_OK || n_rows == 0) return rc;
+    const int64_t blocks = (frames + vpz::kRsBlock - 1) / vpz::kRsBlock;
+    if (blocks > 0x7fffffff) return refuse("vpz_pcm_resample: a row too long for one launch");
 
     const vpz::Context::ResampleTable *tb = nullptr;
-    int rc = vpz::table_for(ctx, up, down, &tb);
+    rc = vpz::table_for(ctx, up, down, &tb);
     if (rc != VPZ_OK) return rc;
-    rc = vpz::pack_room(ctx, (size_t)n_rows);
-    if (rc != VPZ_OK) return rc;
-    memcpy(ctx->pack_host, rows, sizeof(vpz_pack_row) * (size_t)n_rows);
-    VPZ_HIP_TRY(ctx, hipMemcpyAsync(ctx->pack_dev, ctx->pack_host, sizeof(vpz_pack_row) * (size_t)n_rows, hipMemcpyHostToDevice, ctx->stream));
-    VPZ_HIP_TRY(ctx, hipEventRecord(ctx->pack_done, ctx->stream));
-    ctx->pack_pending = true;
-
     vpz::ResampleArgs a;
+    rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);
+    if (rc != VPZ_OK) return rc;
     a.src = static_cast<const float *>(src_dev);
-    a.rows = static_cast<const vpz_pack_row *>(ctx->pack_dev);
     a.dst = dst_dev;
     a.coeff = tb->d_coeff;
     a.first = tb->d_first;
@@ -287,8 +250,6 @@ extern "C" int vpz_pcm_resample(vpz_context *c, const void *src_dev, int64_t src
     // channels and the ratios at which span_cap comes within 2 % of kRsLds; tests/test_resample_cpu.py restates this plan and holds the
     // tests' case list to it, so a change of a constant above fails there first
     a.per_pass = std::max(1, std::min(std::min<int32_t>(out_channels, vpz::kRsMaxPass), vpz::kRsLds / a.span_cap));
-    const int64_t blocks = (frames + vpz::kRsBlock - 1) / vpz::kRsBlock;
-    if (blocks > 0x7fffffff) return refuse("vpz_pcm_resample: a row too long for one launch");
     const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kRsMaxGridY));
     const size_t lds = sizeof(float) * (size_t)a.per_pass * ((size_t)a.span_cap + vpz::kRsBlock);  // (at most 42 KiB: kRsLds + kRsMaxPass tiles)
     if (s16 && planar) vpz::pcm_resample_kernel<int16_t, true><<<grid, vpz::kRsBlock, lds, ctx->stream>>>(a);

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/vorbispizza_synth.h"
+#include "../../include/vorbispizza_pcm_pack.h"
 #include "synth_desc.hpp"
 
 namespace vpz {
@@ -52,8 +53,9 @@ struct Context {
     // persistent grids of the IMDCT kernels on THIS context's device (workgroups the chip keeps resident), filled by the first
     // launch of each; per context, not per process: a host with several GPUs holds one context per device
     int resident[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // vpz_pcm_pack (pcm_pack.hip): its row descriptors go up through a page-locked buffer of the context's; `pack_done` says that the
-    // last call's copy has left it
+    // the row launches -- vpz_pcm_pack, vpz_pcm_resample and vpz_pcm_logmel -- share it (upload_rows, pcm_pack.hip): a launch's row
+    // descriptors go up through a page-locked buffer of the context's into its device copy; `pack_done` says that the last launch's copy
+    // has left the buffer
     void *pack_host = nullptr, *pack_dev = nullptr;
     size_t pack_cap = 0;  // descriptors both hold
     hipEvent_t pack_done = nullptr;
@@ -83,8 +85,31 @@ int set_error(Context *ctx, int status, const char *what, hipError_t e = hipSucc
 int get_tables(Context *ctx, int n, BlockTables **out);
 int ensure_stage(Context *ctx, void **buf, size_t *have, size_t need);
 void free_pack_scratch(Context *ctx);  // (pcm_pack.hip; vpz_context_destroy calls it)
-bool device_range(Context *ctx, const void *p, uint64_t bytes);  // (pcm_pack.hip) inside one allocation of device memory on the context's device
-int pack_room(Context *ctx, size_t n);  // (pcm_pack.hip) room for n vpz_pack_row in pack_host / pack_dev; the previous copy has left the buffer
+// ---- what the row launches share (pcm_pack.hip): vpz_pcm_pack, vpz_pcm_resample and vpz_pcm_logmel ----
+// A row launch as the three agree on it: `rows` name windows of a source array -- `src_elems` elements of `src_elem` bytes, `src_channels`
+// interleaved -- and the row each goes to in a destination of `dst_rows` rows of `row_elems` elements of `dst_elem` bytes; a window of
+// `samples` samples becomes ceil(samples * up / down) of its row's `frames` samples (1 / 1: as many)
+struct RowLaunch {
+    const char *name;  // the entry point's, in front of every refusal's text
+    const void *src;
+    int64_t src_elems;
+    uint64_t src_elem;
+    int32_t src_channels, up, down;
+    int64_t frames;
+    int32_t n_rows;
+    const vpz_pack_row *rows;
+    void *dst;
+    int64_t dst_rows;
+    unsigned __int128 row_elems;
+    uint64_t dst_elem;
+};
+// the contract of a row launch, checked: VPZ_OK, or the refusal as the context's error (nothing is enqueued; the arithmetic comes before
+// any HIP call); n_rows == 0 passes like any other count
+int check_row_launch(Context *ctx, const RowLaunch &q);
+// the descriptors of a checked launch on their way to the device, on the context's stream: *d_rows is what the kernel reads
+int upload_rows(Context *ctx, int32_t n_rows, const vpz_pack_row *rows, const vpz_pack_row **d_rows);
+// a VPZ_OUT_* layout as (int16 elements, planar); false: none of the four
+bool layout_of(int32_t layout, bool *s16, bool *planar);
 void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_destroy calls it)
 void free_logmel_tables(Context *ctx);  // (pcm_logmel.hip; vpz_context_destroy calls it)
 

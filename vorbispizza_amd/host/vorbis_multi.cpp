@@ -30,10 +30,10 @@
 //
 // vpzm_decode_ranges_batch (include/vorbispizza_multi_batch.h) is a ranges call whose PCM never comes down: both routes stage it in the
 // lane's device array (the host route uploads its slot's decoded arrays and makes a device-memory synth call), and the `download` stage
-// is one vpz_pcm_pack per sub-batch, which trims every member's window into its row of the caller's device tensor and zero-fills the rest.
+// (deliver_batch) is one vpz_pcm_pack per sub-batch, which trims every member's window into its row of the caller's device tensor and zero-fills the rest.
 //
 // vpzm_decode_ranges_resampled (include/vorbispizza_multi_resample.h) is that call with vpz_pcm_resample as its last stage: open_one works out
-// every entry's ratio, the synth calls write float32, and `download` makes one launch per ratio among the sub-batch's members.
+// every entry's ratio, the synth calls write float32, and deliver_batch makes one launch per ratio among the sub-batch's members.
 //
 // vpzm_decode_ranges_logmel (include/vorbispizza_multi_logmel.h) is the mono resampled call with one more stage: the resample launches write
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
@@ -313,6 +313,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, or the log-mel launch of a log-mel call -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -364,17 +365,30 @@ struct Job {  // one stream of the library inside its group
 // vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
+    enum Kind { kPack, kResampled, kLogmel };  // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel
+    Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
-    void *dst = nullptr;
-    int32_t rate = 0, downmix = 0;  // vpzm_decode_ranges_resampled: every row at `rate` (0: at the stream's own), mixed down to mono
-    bool resampled() const { return rate > 0; }
-    // vpzm_decode_ranges_logmel: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed)
+    int32_t rate = 0, downmix = 0;  // kResampled, kLogmel: every row at `rate`, mixed down to mono
+    // kLogmel: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed)
     const vpz_logmel_spec *mel = nullptr;
+    void *dst = nullptr;  // (decode_call fills these two in)
+    int64_t rows = 0;     // of the group's piece: its entries
+    bool resampled() const { return kind != kPack; }
+
+    // These descriptors (samples = 0 each) get rows of no samples -- zeros, or the silence row of a log-mel call, which its own kernel
+    // writes -- from a launch that reads nothing: the destination stands in for a source of no elements
+    int empty_rows(vpz_context *ctx, const std::vector<vpz_pack_row> &d) const
+    {
+        if (mel) return vpz_pcm_logmel(ctx, dst, 0, frames, mel, (int32_t)d.size(), d.data(), dst, rows);
+        return vpz_pcm_pack(ctx, dst, 0, channels, (int32_t)d.size(), d.data(), dst, rows, frames, layout);
+    }
 };
 
 // ceil(samples * up / down): the output samples of a resampled window (the definition's J)
 int64_t resampled_length(int64_t samples, int32_t up, int32_t down) { return (samples * up + down - 1) / down; }
+// the window rule: of the `written` samples its window's packets gave, a member delivers those behind the roll, never more than it asked for
+int64_t delivered_length(int64_t wanted, int64_t written, int64_t roll) { return std::max<int64_t>(0, std::min(wanted, written - roll)); }
 
 struct Sub {  // streams of one setup that ride in one vpz_decoder_synth call
     std::shared_ptr<Setup> st;           // (its own reference: `setups` grows under the group's mutex while sub-batches are worked on outside it)
@@ -856,14 +870,7 @@ struct GroupRun {
             std::vector<vpz_pack_row> rows;
             for (const Job &J : jobs)
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
-            // (a launch that reads nothing: the destination stands in for a source of no elements)
-            // (a log-mel call: samples = 0 descriptors of its own kernel, so an undelivered row is the silence row)
-            if (!rows.empty() && batch.mel)
-                ok = vpz_pcm_logmel(G.lanes[0].ctx, batch.dst, 0, batch.frames, batch.mel, (int32_t)rows.size(), rows.data(), batch.dst,
-                                    (int64_t)jobs.size()) == VPZ_OK;
-            else if (!rows.empty())
-                ok = vpz_pcm_pack(G.lanes[0].ctx, batch.dst, 0, batch.channels, (int32_t)rows.size(), rows.data(), batch.dst, (int64_t)jobs.size(),
-                                  batch.frames, batch.layout) == VPZ_OK;
+            if (!rows.empty()) ok = batch.empty_rows(G.lanes[0].ctx, rows) == VPZ_OK;
             if (!ok) m->fail(std::string(batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
@@ -948,7 +955,8 @@ struct GroupRun {
 // vpz_decoder.hip).  Two routes: a host-decoded sub-batch's arrays lie in its slot and its PCM goes straight into the caller's array;
 // a device-decoded one's packet bytes go up, vpz_entropy_decode writes the lane's device arrays, the synth call reads those and writes
 // the lane's device PCM array, and every member's PCM comes down.  `sb.on_device` says which; decode_on_device may clear it.
-// A ranges call (`ranged`) stages the PCM on both routes; `download` brings every member's window from there to the caller's area.
+// A ranges call (`ranged`) stages the PCM on both routes; `download` brings every member's window from there to the caller's area
+// (copy_down) or into its row of the caller's device tensor (deliver_batch).
 struct SubCall {
     GroupRun &R;
     Lane &L;
@@ -960,6 +968,7 @@ struct SubCall {
     const size_t elem = R.out_layout == VPZ_OUT_INTERLEAVED_S16 ? sizeof(int16_t) : sizeof(float);  // bytes of a PCM sample
     const bool ranged = R.ranges != nullptr;  // a vpzm_decode_ranges call: staged PCM on both routes, windows trimmed in `download`
     const bool batched = R.batched();         // ... a vpzm_decode_ranges_batch call: staged in the lane's device array on both routes, packed in `download`
+    const Batch &B = R.batch;                 // ... its kind, shape and destination
     bool inputs_on_device = false;            // the synth call reads the lane's device arrays (decode_on_device, upload_decoded) and is a VPZ_MEM_DEVICE call
     bool any = false;  // ---- repack: a member is left ...
     int64_t n_pk = 0;  // ... and the packets of those that are
@@ -1199,15 +1208,8 @@ struct SubCall {
         }
     }
 
-    // Every member's PCM from where the call left it to the caller's area -- one copy per member that has samples.  A library call has
-    // something to copy on the device route only (the areas in the lane's array have a block of slack between them, the caller's areas
-    // whatever the caller likes): what samples_written says and no more, a synchronising vpz_memcpy_d2h each.  A ranges call copies on
-    // both routes, and member j gets min(wanted, written - roll) samples from `roll` samples into its area -- what its window's packets
-    // gave after the roll, never more than it asked for; `written` becomes that count.  Its device route queues a vpz_pcm_download per
-    // member and synchronises once; its host route is a memcpy per member from the slot's stage.  A batch call copies nothing down: one
-    // vpz_pcm_pack on the lane's stream, after whichever calls stand, moves every member's window from the lane's device array into its
-    // row of the group's piece and zero-fills the rest -- a member without samples (failed, or nothing left after the roll) gets a
-    // samples = 0 descriptor; a failed pack costs the sub-batch's members VPZM_E_SYNTH (GroupRun::zero_rows defines their rows).
+    // Every member's PCM from where the call left it to where the caller wants it: copy_down for a library or a ranges call,
+    // deliver_batch for a batch call
     void download()
     {
         const bool dev = (sb.on_device || batched) && has_call();
@@ -1215,93 +1217,22 @@ struct SubCall {
         t_call = seconds_since(t0) - t_upload - t_entropy;
         if (!dev && !ranged) return;
         const auto t_down = Clock::now();
-        if (batched) {
-            const bool staged = has_call() && out_at == L.pcm() && out_at;  // (else: no call was made, the lane's array may not even exist)
-            std::vector<vpz_pack_row> rows;
-            for (size_t j = 0; j < sb.members.size(); ++j) {
-                const Job &J = job(j);
-                const bool ok = live(j) && member_rc[j] == VPZ_OK && staged;
-                written[j] = ok ? std::max<int64_t>(0, std::min(J.wanted, written[j] - J.roll)) : 0;
-                rows.push_back(vpz_pack_row{written[j] > 0 ? offs[j] + J.roll * C : 0, written[j], (int64_t)(J.k - R.lo)});
-            }
-            int rc = VPZ_OK;
-            if (staged && R.batch.resampled()) {
-                // a resampled call: the members grouped by ratio (a sub-batch has one channel count), one vpz_pcm_resample launch per
-                // group on the lane's stream -- one launch where the members share a rate, more where streams of one setup differ in rate.
-                // A member without samples needs no ratio of its own: its zero row rides in the first group (alone, at 1:1, when no
-                // member has samples)
-                // A log-mel call: the launches write mono planar float32 rows into the lane's temporary [members][frames] (member j in row
-                // j), and ONE vpz_pcm_logmel launch on the same stream -- stream-ordered: no synchronise in between -- turns row j's
-                // first J_j samples into row k - lo of the group's piece
-                const vpz_logmel_spec *mel = R.batch.mel;
-                void *rs_dst = R.batch.dst;
-                int64_t rs_rows = (int64_t)(R.hi - R.lo);
-                if (mel) {
-                    if (L.buf[Lane::kMono].grow(L.ctx, rows.size() * (size_t)R.batch.frames, sizeof(float))) {
-                        rs_dst = L.mono();
-                        rs_rows = (int64_t)rows.size();
-                    } else {
-                        R.m->fail("vpzm_decode_ranges_logmel: the resampled rows' device temporary could not be allocated");
-                        rc = VPZ_E_NOMEM;
-                    }
-                }
-                std::vector<char> taken(rows.size(), 0);
-                std::vector<vpz_pack_row> group;
-                for (size_t left = rows.size(); left > 0 && rc == VPZ_OK;) {
-                    size_t a = rows.size();
-                    for (size_t j = 0; j < rows.size() && a == rows.size(); ++j)
-                        if (!taken[j] && rows[j].samples > 0) a = j;
-                    const int32_t up = a < rows.size() ? job(a).up : 1, down = a < rows.size() ? job(a).down : 1;
-                    group.clear();
-                    for (size_t j = 0; j < rows.size(); ++j)
-                        if (!taken[j] && (rows[j].samples == 0 || (job(j).up == up && job(j).down == down))) {
-                            taken[j] = 1;
-                            group.push_back(rows[j]);
-                            if (mel) group.back().row = (int64_t)j;
-                        }
-                    left -= group.size();
-                    rc = vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, R.batch.downmix, (int32_t)group.size(), group.data(), rs_dst, rs_rows,
-                                          R.batch.channels, R.batch.frames, R.batch.layout);
-                    ++resample_launches;
-                }
-                for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
-                if (rc != VPZ_OK) {
-                    R.m->fail(std::string("vpz_pcm_resample: ") + vpz_context_last_error(L.ctx));
-                    (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
-                } else if (mel) {
-                    for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * R.batch.frames, written[j], rows[j].row};
-                    if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
-                    const auto t_mel = Clock::now();
-                    rc = vpz_pcm_logmel(L.ctx, L.mono(), (int64_t)rows.size() * R.batch.frames, R.batch.frames, mel, (int32_t)rows.size(), rows.data(),
-                                        R.batch.dst, (int64_t)(R.hi - R.lo));
-                    if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_logmel: ") + vpz_context_last_error(L.ctx));
-                    if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
-                        fprintf(stderr, "[vpzm] group %d: sub-batch %zu log-mel kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b,
-                                seconds_since(t_mel) * 1e3, rows.size(), (long long)R.batch.frames);
-                }
-            } else if (R.batch.mel) {
-                // (no staged PCM: silence rows, from a launch that reads nothing -- the destination stands in for a source of no elements)
-                rc = vpz_pcm_logmel(L.ctx, R.batch.dst, 0, R.batch.frames, R.batch.mel, (int32_t)rows.size(), rows.data(), R.batch.dst,
-                                    (int64_t)(R.hi - R.lo));
-                if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_logmel: ") + vpz_context_last_error(L.ctx));
-            } else {
-                // (no staged PCM: a launch that reads nothing -- the destination stands in for a source of no elements)
-                rc = vpz_pcm_pack(L.ctx, staged ? (const void *)L.pcm() : R.batch.dst, staged ? pcm_elems : 0, R.batch.channels, (int32_t)rows.size(),
-                                  rows.data(), R.batch.dst, (int64_t)(R.hi - R.lo), R.batch.frames, R.batch.layout);
-                if (rc != VPZ_OK) R.m->fail(std::string("vpz_pcm_pack: ") + vpz_context_last_error(L.ctx));
-            }
-            if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
-            for (size_t j = 0; j < sb.members.size(); ++j) {
-                if (rc == VPZ_OK) job(j).row_packed = true;
-                else if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
-            }
-            t_download = seconds_since(t_down);
-            return;
-        }
+        if (batched) deliver_batch();
+        else copy_down(dev);
+        t_download = seconds_since(t_down);
+    }
+
+    // One copy per member that has samples.  A library call has something to copy on the device route only (the areas in the lane's
+    // array have a block of slack between them, the caller's areas whatever the caller likes): what samples_written says and no more, a
+    // synchronising vpz_memcpy_d2h each.  A ranges call copies on both routes, and member j gets its window (delivered_length) from `roll`
+    // samples into its area; `written` becomes that count.  Its device route queues a vpz_pcm_download per member and synchronises
+    // once; its host route is a memcpy per member from the slot's stage
+    void copy_down(bool dev)
+    {
         for (size_t j = 0; j < sb.members.size(); ++j) {
             if (!live(j) || member_rc[j] != VPZ_OK) continue;
             const Job &J = job(j);
-            if (ranged) written[j] = std::max<int64_t>(0, std::min(J.wanted, written[j] - J.roll));
+            if (ranged) written[j] = delivered_length(J.wanted, written[j], J.roll);
             if (written[j] <= 0) continue;
             char *to = static_cast<char *>(R.pcm_out) + elem * (size_t)R.pcm_offset[J.k];
             const size_t from = elem * (size_t)(offs[j] + J.roll * C), bytes = elem * (size_t)(written[j] * C);  // (a whole stream rolls 0)
@@ -1316,7 +1247,106 @@ struct SubCall {
         if (dev && vpz_context_synchronize(L.ctx) != VPZ_OK)
             for (size_t j = 0; j < sb.members.size(); ++j)
                 if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
-        t_download = seconds_since(t_down);
+    }
+
+    // A batch call copies nothing down: launches of its kind on the lane's stream, after whichever calls stand, move every member's
+    // window from the lane's device array into its row of the group's piece and fill the rest of the row -- a member without samples
+    // (failed, or nothing left after the roll) gets a samples = 0 descriptor, and so does every member when no call was made (`staged`:
+    // the lane's array may not even exist).  One synchronise behind them; a failed launch costs the sub-batch's members VPZM_E_SYNTH
+    // (GroupRun::zero_rows defines their rows)
+    void deliver_batch()
+    {
+        const bool staged = has_call() && out_at == L.pcm() && out_at;
+        std::vector<vpz_pack_row> rows;
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            const Job &J = job(j);
+            const bool ok = live(j) && member_rc[j] == VPZ_OK && staged;
+            written[j] = ok ? delivered_length(J.wanted, written[j], J.roll) : 0;
+            rows.push_back(vpz_pack_row{written[j] > 0 ? offs[j] + J.roll * C : 0, written[j], (int64_t)(J.k - R.lo)});
+        }
+        int rc = VPZ_OK;
+        if (!staged) {
+            rc = launched(B.mel ? "vpz_pcm_logmel" : "vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP : B.empty_rows(L.ctx, rows));
+        } else if (B.kind == Batch::kPack) {
+            rc = launched("vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP
+                                                             : vpz_pcm_pack(L.ctx, L.pcm(), pcm_elems, B.channels, (int32_t)rows.size(), rows.data(), B.dst,
+                                                                            B.rows, B.frames, B.layout));
+        } else {
+            // (a log-mel call: resampled into the lane's temporary, then ONE log-mel launch on the same stream -- stream-ordered: no
+            // synchronise in between)
+            if (B.mel) rc = mono_temporary(rows.size());
+            if (rc == VPZ_OK) rc = resample_by_ratio(rows);
+            for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
+            if (rc != VPZ_OK) (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
+            else if (B.mel) rc = logmel_rows(rows);
+        }
+        if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
+        for (size_t j = 0; j < sb.members.size(); ++j) {
+            if (rc == VPZ_OK) job(j).row_packed = true;
+            else if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
+        }
+    }
+
+    // a delivery launch's status; a failure goes into the dispatcher's error text under the step's name
+    // (tests: with VPZM_FAIL_DELIVERY the callers do not make the launch and pass a failure)
+    int launched(const char *step, int rc)
+    {
+        if (rc != VPZ_OK) R.m->fail(std::string(step) + ": " + vpz_context_last_error(L.ctx));
+        return rc;
+    }
+
+    // a log-mel call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
+    int mono_temporary(size_t members)
+    {
+        if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.frames, sizeof(float))) return VPZ_OK;
+        R.m->fail("vpzm_decode_ranges_logmel: the resampled rows' device temporary could not be allocated");
+        return VPZ_E_NOMEM;
+    }
+
+    // A resampled call: the members grouped by ratio (a sub-batch has one channel count), one vpz_pcm_resample launch per group on the
+    // lane's stream -- one launch where the members share a rate, more where streams of one setup differ in rate.  A member without
+    // samples needs no ratio of its own: its zero row rides in the first group (alone, at 1:1, when no member has samples).  Into the
+    // group's piece, or a log-mel call's temporary
+    int resample_by_ratio(const std::vector<vpz_pack_row> &rows)
+    {
+        int rc = VPZ_OK;
+        std::vector<char> taken(rows.size(), 0);
+        std::vector<vpz_pack_row> group;
+        for (size_t left = rows.size(); left > 0 && rc == VPZ_OK;) {
+            size_t a = rows.size();
+            for (size_t j = 0; j < rows.size() && a == rows.size(); ++j)
+                if (!taken[j] && rows[j].samples > 0) a = j;
+            const int32_t up = a < rows.size() ? job(a).up : 1, down = a < rows.size() ? job(a).down : 1;
+            group.clear();
+            for (size_t j = 0; j < rows.size(); ++j)
+                if (!taken[j] && (rows[j].samples == 0 || (job(j).up == up && job(j).down == down))) {
+                    taken[j] = 1;
+                    group.push_back(rows[j]);
+                    if (B.mel) group.back().row = (int64_t)j;
+                }
+            left -= group.size();
+            rc = R.sw.fail_delivery && !B.mel ? VPZ_E_HIP
+                                             : vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, B.downmix, (int32_t)group.size(), group.data(),
+                                                                B.mel ? (void *)L.mono() : B.dst, B.mel ? (int64_t)rows.size() : B.rows, B.channels, B.frames,
+                                                                B.layout);
+            ++resample_launches;
+        }
+        return launched("vpz_pcm_resample", rc);
+    }
+
+    // a log-mel call: row j's first `written[j]` samples of the temporary become row k - lo of the group's piece
+    int logmel_rows(std::vector<vpz_pack_row> &rows)
+    {
+        for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.frames, written[j], rows[j].row};
+        if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
+        const auto t_mel = Clock::now();
+        const int rc = launched("vpz_pcm_logmel", R.sw.fail_delivery ? VPZ_E_HIP
+                                                                     : vpz_pcm_logmel(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, B.frames, B.mel,
+                                                                                      (int32_t)rows.size(), rows.data(), B.dst, B.rows));
+        if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu log-mel kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b,
+                    seconds_since(t_mel) * 1e3, rows.size(), (long long)B.frames);
+        return rc;
     }
 
     // the profile line, then under the group's mutex: the members' results, the group's sums, the slot handed back
@@ -1488,6 +1518,7 @@ static int decode_call(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data
             if (batch && hi > lo) {
                 runs.back()->batch = *batch;
                 runs.back()->batch.dst = group_dst[d];
+                runs.back()->batch.rows = hi - lo;
             }
         }
         for (int d = 1; d < D; ++d) threads.emplace_back([&runs, d] { runs[(size_t)d]->run_guarded(); });
@@ -1537,13 +1568,37 @@ int vpzm_decode_library(vpzm_dispatcher *m, int32_t n, const uint8_t *const *dat
     return decode_call(m, n, data, size, nullptr, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats);
 }
 
+// a VPZ_OUT_* layout as (int16 elements, planar); false: none of the four
+static bool layout_of(int32_t layout, bool *s16, bool *planar)
+{
+    *s16 = layout == VPZ_OUT_INTERLEAVED_S16 || layout == VPZ_OUT_PLANAR_S16;
+    *planar = layout == VPZ_OUT_PLANAR || layout == VPZ_OUT_PLANAR_S16;
+    return *s16 || *planar || layout == VPZ_OUT_INTERLEAVED;
+}
+
+// What the ranges family shares.  A call without ranges is refused; one without entries is a ranges call all the same.  A batch call
+// (`batch`: kind, channels, frames, layout and what its kind adds) has a piece per group, rows of at least one frame and one of the four
+// layouts, and no host array; its synth calls write their areas interleaved -- in the batch's element type where the pack step gives the
+// rows their layout, float32 where the resample step converts once, at the end
+static int ranges_call(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges, int32_t out_layout,
+                       void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity, vpzm_stream_result *results, vpzm_stats *stats,
+                       const Batch *batch = nullptr, void *const *group_dst = nullptr)
+{
+    if (n > 0 && !ranges) return VPZM_E_ARG;
+    static const vpzm_range none{0, 0};
+    if (batch) {
+        bool s16, planar;
+        if (!group_dst || batch->frames < 1 || !layout_of(batch->layout, &s16, &planar)) return VPZM_E_ARG;
+        out_layout = s16 && batch->kind == Batch::kPack ? VPZ_OUT_INTERLEAVED_S16 : VPZ_OUT_INTERLEAVED;
+    }
+    return decode_call(m, n, data, size, ranges ? ranges : &none, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats, batch, group_dst);
+}
+
 int vpzm_decode_ranges(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                        int32_t out_layout, void *pcm_out, const int64_t *pcm_offset, const int64_t *pcm_capacity,
                        vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (n > 0 && !ranges) return VPZM_E_ARG;
-    static const vpzm_range none{0, 0};  // (n == 0: a ranges call all the same)
-    return decode_call(m, n, data, size, ranges ? ranges : &none, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats);
+    return ranges_call(m, n, data, size, ranges, out_layout, pcm_out, pcm_offset, pcm_capacity, results, stats);
 }
 
 int vpzm_batch_partition(vpzm_dispatcher *m, int32_t n, int32_t group, int32_t *lo, int32_t *hi)
@@ -1557,56 +1612,32 @@ int vpzm_decode_ranges_batch(vpzm_dispatcher *m, int32_t n, const uint8_t *const
                              int32_t channels, int64_t frames, int32_t out_layout, void *const *group_dst, vpzm_stream_result *results,
                              vpzm_stats *stats)
 {
-    if (!group_dst || channels < 1 || channels > VPZ_MAX_CHANNELS || frames < 1 || (n > 0 && !ranges)) return VPZM_E_ARG;
-    if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_PLANAR && out_layout != VPZ_OUT_INTERLEAVED_S16 && out_layout != VPZ_OUT_PLANAR_S16)
-        return VPZM_E_ARG;
-    const bool s16 = out_layout == VPZ_OUT_INTERLEAVED_S16 || out_layout == VPZ_OUT_PLANAR_S16;
-    static const vpzm_range none{0, 0};
-    Batch batch;
-    batch.channels = channels;
-    batch.layout = out_layout;
-    batch.frames = frames;
-    // (the synth calls write their areas interleaved, in the batch's element type; the pack step gives the rows their layout)
-    return decode_call(m, n, data, size, ranges ? ranges : &none, s16 ? VPZ_OUT_INTERLEAVED_S16 : VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr,
-                       results, stats, &batch, group_dst);
+    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
+    const Batch batch{Batch::kPack, channels, out_layout, frames};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_decode_ranges_resampled(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                                  int32_t sample_rate, int32_t channels, int32_t downmix, int64_t frames, int32_t out_layout, void *const *group_dst,
                                  vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (!group_dst || channels < 1 || channels > VPZ_MAX_CHANNELS || frames < 1 || (n > 0 && !ranges)) return VPZM_E_ARG;
+    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
     if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
-    if (out_layout != VPZ_OUT_INTERLEAVED && out_layout != VPZ_OUT_PLANAR && out_layout != VPZ_OUT_INTERLEAVED_S16 && out_layout != VPZ_OUT_PLANAR_S16)
-        return VPZM_E_ARG;
-    static const vpzm_range none{0, 0};
-    Batch batch;
-    batch.channels = channels;
-    batch.layout = out_layout;
-    batch.frames = frames;
-    batch.rate = sample_rate;
-    batch.downmix = downmix;
-    // (the synth calls write float32, interleaved, whatever the batch's element type: the resample step converts once, at the end)
-    return decode_call(m, n, data, size, ranges ? ranges : &none, VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+    const Batch batch{Batch::kResampled, channels, out_layout, frames, sample_rate, downmix};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_decode_ranges_logmel(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                               const vpz_logmel_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (!group_dst || !spec || frames < 1 || (n > 0 && !ranges)) return VPZM_E_ARG;
+    if (!spec) return VPZM_E_ARG;
     // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
     if (vpz_mel_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
     if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
     if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
-    static const vpzm_range none{0, 0};
-    Batch batch;
-    batch.channels = 1;
-    batch.layout = VPZ_OUT_PLANAR;  // (of the resampled rows in the lane's temporary: mono, float32)
-    batch.frames = frames;
-    batch.rate = (int32_t)spec->sample_rate;
-    batch.downmix = 1;
-    batch.mel = spec;
-    return decode_call(m, n, data, size, ranges ? ranges : &none, VPZ_OUT_INTERLEAVED, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
+    const Batch batch{Batch::kLogmel, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)

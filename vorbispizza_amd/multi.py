@@ -145,18 +145,59 @@ class Dispatcher:
     def last_error(self):
         return lib().vpzm_last_error(self._h).decode()
 
+    # ---- what the decode methods share
+    @staticmethod
+    def _inputs(datas, ranges=None):
+        """-> (n, the containers' pointers, their sizes, the ranges as a contiguous [n, 2] int64 array or None)"""
+        n = len(datas)
+        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
+        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
+        rng = None if ranges is None else np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
+        return n, ptrs, sizes, rng
+
+    @staticmethod
+    def _outputs(n):
+        """-> (fresh results, fresh stats)"""
+        return np.zeros(n, dtype=RESULT_DTYPE), Stats()
+
+    def _group_tensors(self, method, n, shape, dtype, out):
+        """The per-group output tensors of a batch call of n entries: shape(rows) is a group's, for its entries [lo, hi) of
+        batch_partition.  Without `out` they are allocated -- when all groups share a device, as consecutive pieces of one tensor --, a
+        caller's are checked (anything wrong raises ValueError under the method's name).  -> (out, whole_or_None, the library's pointer array)"""
+        import torch
+        ids = self.device_ids  # (a group's HIP device id is its torch device index)
+        cuts = [self.batch_partition(n, g) for g in range(self.n_devices)]
+        whole = None
+        if out is None:
+            if len(set(ids)) == 1:
+                whole = torch.empty(shape(n), dtype=dtype, device="cuda:%d" % ids[0])
+                out = [whole[lo:hi] for lo, hi in cuts]
+            else:
+                out = [torch.empty(shape(hi - lo), dtype=dtype, device="cuda:%d" % d) for (lo, hi), d in zip(cuts, ids)]
+        if len(out) != self.n_devices:
+            raise ValueError("%s: out needs one tensor per group (%d), got %d" % (method, self.n_devices, len(out)))
+        for g, (t, (lo, hi), d) in enumerate(zip(out, cuts, ids)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != d:
+                raise ValueError("%s: out[%d] is not a tensor on the group's device cuda:%d" % (method, g, d))
+            if tuple(t.shape) != shape(hi - lo) or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError("%s: out[%d] must be a contiguous %s tensor of shape %s" % (method, g, dtype, shape(hi - lo)))
+        return out, whole, (C.c_void_p * self.n_devices)(*[t.data_ptr() if t.numel() else None for t in out])
+
+    def _drain_torch(self):
+        """the library writes on its own streams into memory torch may have just recycled: whatever torch has queued there is done first"""
+        import torch
+        for d in sorted(set(self.device_ids)):
+            torch.cuda.current_stream(d).synchronize()
+
     def decode_library(self, datas, pcm_out, pcm_offset, pcm_capacity, s16=False):
         """datas: list of numpy uint8 arrays (containers); pcm_out: numpy float32 / int16 array (or a torch pinned tensor's
         .numpy()); pcm_offset / pcm_capacity: per stream, elements / samples per channel.  Returns (results, stats):
         a numpy record array (RESULT_DTYPE) and the Stats struct."""
-        n = len(datas)
-        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
-        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
+        n, ptrs, sizes, _ = self._inputs(datas)
         offs = np.ascontiguousarray(pcm_offset, dtype=np.int64)
         caps = np.ascontiguousarray(pcm_capacity, dtype=np.int64)
         assert pcm_out.dtype == (np.int16 if s16 else np.float32) and pcm_out.flags["C_CONTIGUOUS"]
-        results = np.zeros(n, dtype=RESULT_DTYPE)
-        stats = Stats()
+        results, stats = self._outputs(n)
         rc = lib().vpzm_decode_library(self._h, n, ptrs, sizes, capi.OUT_INTERLEAVED_S16 if s16 else capi.OUT_INTERLEAVED,
                                        pcm_out.ctypes.data, offs.ctypes.data, caps.ctypes.data, results.ctypes.data,
                                        C.byref(stats))
@@ -168,15 +209,11 @@ class Dispatcher:
         """vpzm_decode_ranges: decode_library for a window of every stream.  ranges: per entry (start, count) in samples per
         channel, count < 0 for "to the end"; entry k's samples land at pcm_out[pcm_offset[k]:], and its results' `samples` says
         how many, `packets` how many packets were decoded for them.  Returns (results, stats) like decode_library."""
-        n = len(datas)
-        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
-        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
-        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         offs = np.ascontiguousarray(pcm_offset, dtype=np.int64)
         caps = np.ascontiguousarray(pcm_capacity, dtype=np.int64)
         assert pcm_out.dtype == (np.int16 if s16 else np.float32) and pcm_out.flags["C_CONTIGUOUS"]
-        results = np.zeros(n, dtype=RESULT_DTYPE)
-        stats = Stats()
+        results, stats = self._outputs(n)
         rc = lib().vpzm_decode_ranges(self._h, n, ptrs, sizes, rng.ctypes.data, capi.OUT_INTERLEAVED_S16 if s16 else capi.OUT_INTERLEAVED,
                                       pcm_out.ctypes.data, offs.ctypes.data, caps.ctypes.data, results.ctypes.data, C.byref(stats))
         if rc != OK:
@@ -203,40 +240,17 @@ class Dispatcher:
         mono needs a `sample_rate`: the library's resampled call has one rate.
         Returns (parts, whole_or_None, results, stats)."""
         import torch
-        n = len(datas)
-        ids = self.device_ids  # (a group's HIP device id is its torch device index)
-        dtype = torch.int16 if s16 else torch.float32
-        cuts = [self.batch_partition(n, g) for g in range(self.n_devices)]
-        shape = (lambda rows: (rows, channels, frames)) if planar else (lambda rows: (rows, frames, channels))
         if channels < 1 or frames < 1:
             raise ValueError("decode_ranges_batch: channels and frames must be at least 1")
         if mono and (sample_rate is None or channels != 1):
             raise ValueError("decode_ranges_batch: mono needs a sample_rate (a resampled call has one rate) and channels == 1")
-        whole = None
-        if out is None:
-            if len(set(ids)) == 1:
-                whole = torch.empty(shape(n), dtype=dtype, device="cuda:%d" % ids[0])
-                out = [whole[lo:hi] for lo, hi in cuts]
-            else:
-                out = [torch.empty(shape(hi - lo), dtype=dtype, device="cuda:%d" % d) for (lo, hi), d in zip(cuts, ids)]
-        if len(out) != self.n_devices:
-            raise ValueError("decode_ranges_batch: out needs one tensor per group (%d), got %d" % (self.n_devices, len(out)))
-        for g, (t, (lo, hi), d) in enumerate(zip(out, cuts, ids)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != d:
-                raise ValueError("decode_ranges_batch: out[%d] is not a tensor on the group's device cuda:%d" % (g, d))
-            if tuple(t.shape) != shape(hi - lo) or t.dtype != dtype or not t.is_contiguous():
-                raise ValueError("decode_ranges_batch: out[%d] must be a contiguous %s tensor of shape %s" % (g, dtype, shape(hi - lo)))
-        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
-        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
-        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
-        dst = (C.c_void_p * self.n_devices)(*[t.data_ptr() if t.numel() else None for t in out])
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        shape = (lambda rows: (rows, channels, frames)) if planar else (lambda rows: (rows, frames, channels))
+        out, whole, dst = self._group_tensors("decode_ranges_batch", n, shape, torch.int16 if s16 else torch.float32, out)
         layout = {(True, False): capi.OUT_PLANAR, (False, False): capi.OUT_INTERLEAVED, (True, True): capi.OUT_PLANAR_S16,
                   (False, True): capi.OUT_INTERLEAVED_S16}[(bool(planar), bool(s16))]
-        # (the library writes on its own streams into memory torch may have just recycled: whatever torch has queued there is done first)
-        for d in sorted(set(ids)):
-            torch.cuda.current_stream(d).synchronize()
-        results = np.zeros(n, dtype=RESULT_DTYPE)
-        stats = Stats()
+        self._drain_torch()
+        results, stats = self._outputs(n)
         if sample_rate is None:
             rc = lib().vpzm_decode_ranges_batch(self._h, n, ptrs, sizes, rng.ctypes.data, channels, frames, layout, dst, results.ctypes.data,
                                                 C.byref(stats))
@@ -262,34 +276,12 @@ class Dispatcher:
                                     mel_norm=mel_norm, log=log, floor=floor, bands_first=bands_first)
         if frames < 1 or hop < 1 or n_mels < 1:
             raise ValueError("decode_ranges_logmel: frames, hop and n_mels must be at least 1")
-        n = len(datas)
-        ids = self.device_ids
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T = spec.n_frames(frames)
-        cuts = [self.batch_partition(n, g) for g in range(self.n_devices)]
         shape = (lambda rows: (rows, n_mels, T)) if bands_first else (lambda rows: (rows, T, n_mels))
-        whole = None
-        if out is None:
-            if len(set(ids)) == 1:
-                whole = torch.empty(shape(n), dtype=torch.float32, device="cuda:%d" % ids[0])
-                out = [whole[lo:hi] for lo, hi in cuts]
-            else:
-                out = [torch.empty(shape(hi - lo), dtype=torch.float32, device="cuda:%d" % d) for (lo, hi), d in zip(cuts, ids)]
-        if len(out) != self.n_devices:
-            raise ValueError("decode_ranges_logmel: out needs one tensor per group (%d), got %d" % (self.n_devices, len(out)))
-        for g, (t, (lo, hi), d) in enumerate(zip(out, cuts, ids)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != d:
-                raise ValueError("decode_ranges_logmel: out[%d] is not a tensor on the group's device cuda:%d" % (g, d))
-            if tuple(t.shape) != shape(hi - lo) or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("decode_ranges_logmel: out[%d] must be a contiguous float32 tensor of shape %s" % (g, shape(hi - lo)))
-        ptrs = (C.c_void_p * n)(*[d.ctypes.data for d in datas])
-        sizes = (C.c_uint64 * n)(*[d.size for d in datas])
-        rng = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(n, 2))
-        dst = (C.c_void_p * self.n_devices)(*[t.data_ptr() if t.numel() else None for t in out])
-        # (the library writes on its own streams into memory torch may have just recycled: whatever torch has queued there is done first)
-        for d in sorted(set(ids)):
-            torch.cuda.current_stream(d).synchronize()
-        results = np.zeros(n, dtype=RESULT_DTYPE)
-        stats = Stats()
+        out, whole, dst = self._group_tensors("decode_ranges_logmel", n, shape, torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
         rc = lib().vpzm_decode_ranges_logmel(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
                                              C.byref(stats))
         if rc != OK:

@@ -10,10 +10,15 @@ live bins, k ascending):
     d_re[k] = (n_fft + 2) u sum_m |x w cos|        d_im likewise with sin
     e_P[k]  = 2 |re| d_re + 2 |im| d_im + d_re^2 + d_im^2 + 3 u P
     e_M[b]  = sum_k W[b][k] e_P[k] + (B + 2) u M[b]        B: the largest live-bin count of a band
-all evaluated in float64 on the same input."""
+all evaluated in float64 on the same input.
+
+THE LAUNCH PLAN of vpz_pcm_logmel is restated here as well (lds_plan, tile_plan), with the case lists of
+tests/test_pcm_logmel_limits_gpu.py, LIMIT_*: a test without a GPU holds the lists to the plan -- a changed constant in pcm_logmel.hip
+fails here, not as a quietly weaker GPU test -- and a sweep over every n_fft and hop holds the plan's index arithmetic."""
 import ctypes as C
 import math
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -135,6 +140,65 @@ def check_power(got, M, e_M):
     assert (err <= e_M).all(), float((err[e_M > 0] / e_M[e_M > 0]).max())
     assert (got[e_M == 0].view(np.uint32) == 0).all()
     return float((err[e_M > 0] / e_M[e_M > 0]).max()) if (e_M > 0).any() else 0.0
+
+
+# ---- the launch plan, restated, and the case list of tests/test_pcm_logmel_limits_gpu.py
+def logmel_kernel_constants():
+    """kLmLdsFloats, kLmAhead, kLmCols, kLmMaxGridY as csrc/pcm_logmel.hip states them"""
+    text = open(os.path.join(ROOT, "vorbispizza_amd", "csrc", "pcm_logmel.hip")).read()
+    out = {}
+    for name in ("kLmLdsFloats", "kLmAhead", "kLmCols", "kLmMaxGridY"):
+        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
+        assert len(found) == 1, name
+        out[name] = int(found[0])
+    return out
+
+
+def lds_plan(n_fft, hop, Tt):
+    """(span_cap, pstride) of a tile of Tt frames: the floats of the skewed span, the floats between two rows of the power tile"""
+    count = (Tt - 1) * hop + n_fft
+    return count + (count // hop if hop % 2 == 0 else 0) + 1, (n_fft // 2 + 1) | 1
+
+
+def tile_plan(n_fft, hop, T, n_rows, num_cu, k=None):
+    """vpz_pcm_logmel's tile choice, restated: (frames of a tile, LDS floats the launch asks for); (0, None) where no tile fits.  64
+    frames where the row has more than 32, the launch gives every CU two workgroups at that size and the LDS holds them, else 32, else 16"""
+    k = k or logmel_kernel_constants()
+    few = ((T + 63) // 64) * n_rows < 2 * num_cu
+    for Tt in (64, 32, 16):
+        span_cap, pstride = lds_plan(n_fft, hop, Tt)
+        if (Tt == 64 and (T <= 32 or few)) or span_cap + Tt * pstride > k["kLmLdsFloats"]:
+            continue
+        return Tt, span_cap + Tt * pstride
+    return 0, None
+
+
+def crowd_rows(num_cu):
+    """the rows of a launch that takes 64-frame tiles where a row has two of them: one more than gives every CU two workgroups"""
+    return -(-2 * num_cu // 2) + 1
+
+
+def limit_frames(hop, T):
+    """F with 1 + F // hop = T and a remainder (an odd F where hop allows)"""
+    return hop * (T - 1) + min(hop - 1, 5)
+
+
+# tests/test_pcm_logmel_limits_gpu.py runs every case; test_the_limit_cases_take_the_tiles_they_are_meant_to holds the lists to the plan.
+# (n_fft, hop, T, n_mels, the tile a SMALL launch -- five rows -- takes); F = limit_frames(hop, T).  T is never a multiple of 32.
+LIMIT_TAIL = [(34, 5, 71, 6, 32), (36, 6, 71, 6, 32), (38, 38, 41, 6, 32), (1022, 1022, 19, 40, 16)]   # pairs % 4 = 1, 2, 3, 3
+LIMIT_LDS = [(1024, 112, 71, 40, 32), (1024, 113, 71, 40, 32), (1024, 757, 41, 40, 32), (1024, 758, 41, 40, 16)]
+LIMIT_GROUPS = [(62, 15, 71, 10, 32), (62, 16, 71, 10, 32), (126, 31, 71, 20, 32), (126, 32, 71, 20, 32), (254, 63, 71, 32, 32), (254, 64, 71, 32, 32),
+                (256, 65, 71, 32, 32), (256, 64, 71, 32, 32)]
+# ((1024, 2) with F = 600 exactly)
+LIMIT_HOPS = [(32, 2, 71, 6, 32), (1024, 2, 301, 40, 32), (64, 4, 71, 10, 32), (32, 32, 41, 6, 32), (64, 63, 41, 10, 32), (32, 31, 41, 6, 32)]
+# launches of crowd_rows(CUs) rows with T = 104: 64-frame tiles, the last one of 40 frames; (n_fft, hop, n_mels)
+LIMIT_CROWDS = [(1024, 110, 40), (1024, 111, 40), (1022, 110, 40), (38, 4, 6), (256, 64, 32)]
+CROWD_T = 104
+
+
+def limit_F(case):
+    n_fft, hop, T = case[:3]
+    return 600 if (n_fft, hop) == (1024, 2) else limit_frames(hop, T)
 
 
 def spec_of(bank, **kw):
@@ -307,7 +371,6 @@ def test_the_logmel_binding_matches_its_header(tmp_path, capi):
     assert C.sizeof(capi.LogMelSpec) == 4 * 8 + 7 * 4 + 9 * 4
     text = cs.strip_cs_comments(open(os.path.join(cs.CS, "GpuPcmLogMel.cs")).read())
     consts = {}
-    import re
     for m in re.finditer(r"public\s+const\s+int\s+([^;]+);", text):
         for part in m.group(1).split(","):
             k, v = part.split("=")
@@ -402,3 +465,68 @@ def test_the_bound_discriminates():
     cos[n_fft // 2] *= np.float32(1.05)
     sin[n_fft // 2] *= np.float32(1.05)
     assert (np.abs(proxy(cos, sin) - M) > e_M).mean() > 0.5
+
+
+# ---- the launch plan
+def test_the_limit_cases_take_the_tiles_they_are_meant_to():
+    """tests/test_pcm_logmel_limits_gpu.py's lists against the restated plan at 256 CUs: the tile of every case, the LDS requests next
+    to the budget, every length of the k loop's tail"""
+    k, cu = logmel_kernel_constants(), 256
+    assert (k["kLmLdsFloats"], k["kLmAhead"], k["kLmCols"], k["kLmMaxGridY"]) == (40960, 4, 32, 2048)
+    for case in LIMIT_TAIL + LIMIT_LDS + LIMIT_GROUPS + LIMIT_HOPS:
+        n_fft, hop, T, n_mels, tile = case
+        F = limit_F(case)
+        assert T == 1 + F // hop and T % 32 != 0 and F >= n_fft // 2 + 1, case
+        assert tile_plan(n_fft, hop, T, 5, cu, k)[0] == tile, case
+    n = crowd_rows(cu)
+    assert n == 257 and CROWD_T % 64 == 40  # (the last 64-frame tile holds 40 frames: the second row tile is partly live)
+    for n_fft, hop, n_mels in LIMIT_CROWDS:
+        assert tile_plan(n_fft, hop, CROWD_T, n, cu, k)[0] == 64, (n_fft, hop)
+        assert tile_plan(n_fft, hop, CROWD_T, n - 1, cu, k)[0] == 64 and tile_plan(n_fft, hop, CROWD_T, n - 2, cu, k)[0] == 32  # (the threshold)
+        assert tile_plan(n_fft, hop, CROWD_T, cu // 2, cu, k)[0] == 32, (n_fft, hop)
+    # the boundaries of the LDS at n_fft 1024: 64 frames up to hop 111, 32 up to 757
+    want = {110: (64, 40859), 111: (64, 40850), 112: (32, None), 113: (32, None), 757: (32, 40908), 758: (16, None)}
+    for hop, (tile, floats) in want.items():
+        got = tile_plan(1024, hop, CROWD_T, n, cu, k)
+        assert got[0] == tile and (floats is None or got[1] == floats), (hop, got)
+        assert got[1] <= k["kLmLdsFloats"]
+    for hop in range(1, 1025):
+        assert tile_plan(1024, hop, CROWD_T, n, cu, k)[0] == (64 if hop <= 111 else 32 if hop <= 757 else 16), hop
+    assert {(hop, tile) for n_fft, hop, T, n_mels, tile in LIMIT_LDS} == {(112, 32), (113, 32), (757, 32), (758, 16)}
+    assert {hop for n_fft, hop, n_mels in LIMIT_CROWDS if n_fft == 1024} == {110, 111}
+    requests = [tile_plan(n_fft, hop, CROWD_T, n, cu, k)[1] for n_fft, hop, n_mels in LIMIT_CROWDS]
+    requests += [tile_plan(c[0], c[1], c[2], 5, cu, k)[1] for c in LIMIT_LDS]
+    assert sum(r > 40800 for r in requests) >= 4 and max(requests) == 40908  # (1024 and 1022 at hop 110, 1024 at 111 and at 757)
+    # the k loop's tail: n_fft / 2 steps in blocks of kLmAhead
+    assert {(c[0] // 2) % k["kLmAhead"] for c in LIMIT_TAIL} == {1, 2, 3}
+    assert {(n_fft // 2) % k["kLmAhead"] for n_fft, hop, n_mels in LIMIT_CROWDS} >= {3}  # (the tail in the two-row-tile kernel as well)
+    # bin groups of 32: one exactly (cols == nb), a whole number, one per wave, one more than the waves, and 17
+    groups = {n_fft: -(-(n_fft // 2 + 1) // k["kLmCols"]) for n_fft in (62, 126, 254, 256, 1024)}
+    assert groups == {62: 1, 126: 2, 254: 4, 256: 5, 1024: 17} and {c[0] for c in LIMIT_GROUPS} == {62, 126, 254, 256}
+    assert (62 // 2 + 1) % k["kLmCols"] == 0 and lds_plan(62, 15, 32)[1] == 33
+    assert all({c[1] % 2 for c in LIMIT_GROUPS if c[0] == n_fft} == {0, 1} for n_fft in (62, 126, 254, 256))  # (hop odd and even)
+
+
+def test_a_tile_fits_and_no_index_leaves_the_span_at_any_spec():
+    """every even n_fft in 32..1024 with every hop in 1..n_fft: 16 frames always fit (VPZ_E_UNSUPPORTED cannot be reached inside the
+    limits), and at each tile size the largest skewed index written by the staging and the largest read by a frame lie inside span_cap"""
+    k = logmel_kernel_constants()
+    largest = 0
+    for n_fft in range(32, 1025, 2):
+        hop = np.arange(1, n_fft + 1, dtype=np.int64)
+        skew = (hop % 2 == 0).astype(np.int64)
+        for Tt in (64, 32, 16):
+            count = (Tt - 1) * hop + n_fft
+            span_cap = count + skew * (count // hop) + 1
+            pstride = (n_fft // 2 + 1) | 1
+            assert (count - 1 + skew * ((count - 1) // hop) < span_cap).all()
+            assert ((Tt - 1) * (hop + skew) + (n_fft - 1) + skew * ((n_fft - 1) // hop) < span_cap).all()
+            if Tt == 16:
+                assert (span_cap + Tt * pstride <= k["kLmLdsFloats"]).all(), n_fft
+                largest = max(largest, int((span_cap + Tt * pstride).max()))
+        for h in (1, 2, n_fft - 1, n_fft):  # (the vector form above is the scalar restatement)
+            for Tt in (64, 32, 16):
+                c = (Tt - 1) * h + n_fft
+                assert lds_plan(n_fft, h, Tt) == (c + (c // h if h % 2 == 0 else 0) + 1, (n_fft // 2 + 1) | 1)
+            assert tile_plan(n_fft, h, 1000, 1000, 256, k)[0] in (64, 32, 16)
+    assert largest == 24609  # (n_fft = hop = 1024)

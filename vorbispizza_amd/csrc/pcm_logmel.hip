@@ -338,6 +338,8 @@ extern "C" int vpz_pcm_logmel(vpz_context *c, const void *src_dev, int64_t src_e
     // the tile: 64 frames where the row has more than 32 and the LDS holds them -- every tile reads the whole table from L2 (643 KB at
     // n_fft 400), so the larger tile halves that traffic --, else 32, else 16 (n_fft 1024 at a hop near it: the span alone is 128 KiB at 32)
     // -- a launch too small to give every CU two workgroups at 64 takes 32 (a result does not depend on the tile: the same bits)
+    // tests/test_logmel_cpu.py restates lds_plan and this choice (tile_plan); tests/test_pcm_logmel_limits_gpu.py runs every tile next to
+    // the LDS budget (n_fft 1024: 64 frames up to hop 111, 32 up to 757) and the leftover k-steps of an n_fft that is no multiple of 8
     a.Tt = 0;
     const bool few = ((T + 63) / 64) * (int64_t)n_rows < 2 * (int64_t)ctx->num_cu;
     for (int Tt : {64, 32, 16}) {

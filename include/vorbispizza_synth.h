@@ -248,7 +248,9 @@ int vpz_decoder_last_packet_status(vpz_decoder *dec, int32_t *out, int64_t capac
 
 /* Floor 0 data of the NEXT vpz_decoder_synth call (Floor0.Data after Unpack, Floor0.cs:113-162), for the
  * channel records whose floor is type 0: amp[rec] = Data.Amp (0 => ExecuteChannel false; the caller also
- * sets post_counts[rec] = Amp != 0), coeff[rec*coeff_stride + j] = Data.Coeff[j], j < order.  Pointers
+ * sets post_counts[rec] = Amp != 0), coeff[rec*coeff_stride + j] = Data.Coeff[j], j < order.  A
+ * coeff_stride smaller than the largest order among the decoder's type-0 floors is refused with
+ * VPZ_E_INVALID_ARG (a record's row could not hold its coefficients); the pending data stay as they were.  Pointers
  * live in `mem_space` like the other inputs of that call and are consumed by it.  Where the reference
  * indexes its w map out of range (bark_map_size > blocksize/2, Floor0.cs:99-109,185-190 -- it throws) the
  * value 2*cos(pi*k/bark_map_size) is computed instead. */

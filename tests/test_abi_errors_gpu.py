@@ -145,6 +145,45 @@ def test_floor0_needs_its_data_and_mapping_index_is_checked(ctx):
     dec.close()
 
 
+def test_floor0_coefficient_rows_shorter_than_an_order_are_refused(ctx):
+    """coeff[rec * coeff_stride + j], j < order: a stride below the largest order among the decoder's type-0 floors cannot hold a
+    record's coefficients (the kernels would read the next record's, and beyond the array on the last one).  Refused where it is
+    set -- no synth call follows, nothing runs on the device --, and what was pending stays pending."""
+    from vorbispizza_amd import Decoder, capi
+    order = 12
+    f0s = [{"order": 8, "rate": 44100, "bark_map_size": 64, "amp_bits": 6, "amp_ofs": 40},
+           {"order": order, "rate": 44100, "bark_map_size": 64, "amp_bits": 6, "amp_ofs": 40}]
+    maps = [{"coupling": [], "channel_floor": [0, 1]}]
+    dec = Decoder(ctx, 2, 256, 2048, floors=f0s, mappings=maps)
+    pk, res = _batch()
+    pk["flags"] &= ~np.uint8(capi.PKT_NO_FLOOR)
+    n = len(pk) * 2
+    posts = np.zeros((n, 64), dtype=np.int16)
+    counts = np.ones(n, dtype=np.uint8)
+    amp = np.full(n, 30.0, dtype=np.float32)
+    rng = np.random.default_rng(12)
+
+    def coeff(stride):
+        return np.sort(rng.uniform(0.05, 3.0, (n, stride)), axis=1).astype(np.float32)
+
+    out = np.zeros(2 * 8192, dtype=np.float32)
+    for stride in (order - 1, 8, 1):
+        assert _status(lambda: dec.set_floor0_data(amp, coeff(stride))) == capi.E_INVALID_ARG
+        assert "coeff_stride %d" % stride in ctx.last_error() and "order %d" % order in ctx.last_error()
+    # nothing was pending, and nothing is: the synth call still asks for the data
+    st = _status(lambda: dec.synth_raw(pk, res, posts, counts, out, None, 8192, capi.OUT_PLANAR, 8192, capi.MEM_HOST))
+    assert st == capi.E_INVALID_ARG and "type-0 floors need" in ctx.last_error()
+    # a row of exactly the order is enough; a refused call after it leaves the accepted data in place
+    good = coeff(order)
+    for rec in range(n):  # (an amplitude that keeps the curve at or below 0 dB)
+        amp[rec] = helpers.floor0_safe_amp(good[rec, :f0s[rec % 2]["order"]], 64, 40.0) * 0.9
+    dec.set_floor0_data(amp, good)
+    assert _status(lambda: dec.set_floor0_data(amp, coeff(order - 1))) == capi.E_INVALID_ARG
+    w = dec.synth_raw(pk, res, posts, counts, out, None, 8192, capi.OUT_PLANAR, 8192, capi.MEM_HOST)
+    assert int(w[0]) == 5 * 1024 and np.isfinite(out).all() and np.abs(out).max() > 0
+    dec.close()
+
+
 def test_imdct_batch_argument_checks(ctx):
     from vorbispizza_amd import SynthError, capi
     x = np.zeros((4, 500), dtype=np.float32)

@@ -429,7 +429,11 @@ floor0_safe_amp = helpers.floor0_safe_amp
 @pytest.mark.parametrize("size0,size1,order,bark", [(2048, 2048, 8, 256), (256, 2048, 9, 64), (512, 1024, 16, 128)])
 def test_floor0_matches_oracle(ctx, oracle, size0, size1, order, bark):
     """Type-0 (LSP) floor, Floor0.cs:164-225: channel 0 uses a floor 0, channel 1 a floor 1, coupled.
-    cosf / sqrtf / expf are the device library's, so the bar is relative (1e-5 of the signal)."""
+    The kernels evaluate cos and exp as floor0_math.hpp's series in double, rounded once to float32 (test_floor0_math_cpu.py:
+    what a correctly rounded cosf / expf gives), and divide and take the root in correctly rounded float32; the oracle calls
+    the host's cosf / expf, which differ from that by an ulp here and there, and the LSP product amplifies an ulp next to a
+    root.  So the bar is relative: 1e-5 of the signal's peak.  The orders, bark maps and record counts beyond these three
+    shapes: test_floor0_limits_gpu.py."""
     from vorbispizza_amd import Decoder, make_packets
     rng = np.random.default_rng(order)
     channels, frames = 2, 12

@@ -531,9 +531,9 @@ class Decoder:
 
     def set_floor0_data(self, amp, coeff):
         """amp [records], coeff [records, stride] (numpy, host memory) for the next synth call."""
-        self._f0 = (np.ascontiguousarray(amp, dtype=np.float32), np.ascontiguousarray(coeff, dtype=np.float32))
-        self.ctx._check(lib().vpz_decoder_set_floor0_data(self._h, _ptr(self._f0[0]), _ptr(self._f0[1]),
-                                                          self._f0[1].shape[1]))
+        f0 = (np.ascontiguousarray(amp, dtype=np.float32), np.ascontiguousarray(coeff, dtype=np.float32))
+        self.ctx._check(lib().vpz_decoder_set_floor0_data(self._h, _ptr(f0[0]), _ptr(f0[1]), f0[1].shape[1]))
+        self._f0 = f0  # (a refused call leaves the decoder pointing at the arrays it had: those stay alive)
 
     def last_packet_samples(self, n_packets):
         out = np.zeros(n_packets, dtype=np.int32)

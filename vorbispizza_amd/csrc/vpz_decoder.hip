@@ -1344,6 +1344,17 @@ int vpz_decoder_set_floor0_data(vpz_decoder *d, const float *amp, const float *c
     Decoder &D = d->impl;
     if ((amp == nullptr) != (coeff == nullptr) || (amp && coeff_stride < 1))
         return set_error(D.ctx, VPZ_E_INVALID_ARG, "vpz_decoder_set_floor0_data: bad arguments");
+    // (a record's coefficients are coeff[rec * coeff_stride + j], j < order: a row shorter than an order would make the kernels
+    // read the next record's coefficients, and beyond the array on the last record)
+    int max_order = 0;
+    for (size_t i = 0; i < D.floors0.size(); ++i)
+        if (D.floor_types[i] == 0) max_order = std::max(max_order, (int)D.floors0[i].order);
+    if (amp && coeff_stride < max_order) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "vpz_decoder_set_floor0_data: coeff_stride %d is smaller than the order %d of a type-0 floor",
+                 (int)coeff_stride, max_order);
+        return set_error(D.ctx, VPZ_E_INVALID_ARG, msg);
+    }
     D.f0_amp = amp;
     D.f0_coeff = coeff;
     D.f0_stride = coeff_stride;

@@ -9,6 +9,8 @@
     dispatcher_probe.py --resample-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --logmel [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --logmel-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --fbank [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --fbank-kernel
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -39,7 +41,13 @@ bands, floor 1e-10), a float32 device tensor [streams][80][T].  The A/B: what a 
 RATE Hz, mono, then on the device torch.stft (center, reflect, periodic Hann), abs() ** 2, a matmul with the same filterbank
 (vpz_mel_filterbank as a dense matrix), clamp and log10 -- against decode_ranges_logmel; two dispatchers taking turns as above, the
 largest difference of the two tensors printed.  With VPZM_PROFILE=1 the library prints the log-mel launch's own time per sub-batch.
---logmel-kernel: vpz_pcm_logmel alone, the Whisper spec, 64 windows of one second and of thirty, both layouts, the context's event timer."""
+--logmel-kernel: vpz_pcm_logmel alone, the Whisper spec, 64 windows of one second and of thirty, both layouts, the context's event timer.
+--ranges SAMPLES --batch --resample RATE --fbank: the same windows as Kaldi filterbank features (win 400, hop 160, n_fft 512, 80 bands, Povey
+window, pre-emphasis 0.97, per-frame mean removal, scale 32768, natural log), a float32 device tensor [streams][T][80].  The A/B: what a
+loader does without the call -- decode_ranges_batch at RATE Hz, mono, then on the device the eight torch ops unfold, mean, pre-emphasis,
+window, pad, rfft, power, matmul (vpz_fbank_filterbank as a dense matrix) and log -- against decode_ranges_fbank; two dispatchers taking
+turns as above, the largest difference of the two tensors printed.  With VPZM_PROFILE=1 the library prints the fbank launch's own time.
+--fbank-kernel: vpz_pcm_fbank alone, that spec, 64 windows of one second and of thirty, both layouts, the context's event timer."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -62,6 +70,8 @@ ap.add_argument("--mono", action="store_true")
 ap.add_argument("--resample-kernel", action="store_true")
 ap.add_argument("--logmel", action="store_true")
 ap.add_argument("--logmel-kernel", action="store_true")
+ap.add_argument("--fbank", action="store_true")
+ap.add_argument("--fbank-kernel", action="store_true")
 ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -406,6 +416,98 @@ def logmel_kernel_job():
     ctx.close()
 
 
+def fbank_job(samples, rate):
+    import math, time
+    from vorbispizza_amd import capi
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    spec = capi.FbankSpec.make(sample_rate=rate)
+    first, count, weights = capi.fbank_filterbank(spec)
+    Wh, at = np.zeros((spec.n_mels, spec.n_fft // 2 + 1), dtype=np.float32), 0  # (a zero column for the Nyquist bin rfft returns)
+    for b in range(spec.n_mels):
+        Wh[b, first[b]: first[b] + count[b]] = weights[at: at + count[b]]
+        at += count[b]
+    W = torch.from_numpy(Wh.T.copy()).to("cuda:0")
+    m = torch.arange(spec.win, dtype=torch.float64)
+    window = ((0.5 - 0.5 * torch.cos(2 * math.pi * m / (spec.win - 1))) ** 0.85).to(torch.float32).to("cuda:0")
+    fs = 44100  # (both fixtures)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, whole, res, st = d.decode_ranges_batch(datas, windows, 1, J, planar=True, s16=False, sample_rate=rate, mono=True)
+        y = whole.view(n, J).unfold(1, spec.win, spec.hop) * spec.scale                            # unfold (and the scale)
+        y = y - y.mean(dim=2, keepdim=True)                                                        # mean
+        z = y - spec.preemphasis * torch.cat([y[:, :, :1], y[:, :, :-1]], dim=2)                   # pre-emphasis
+        z = torch.nn.functional.pad(z * window, (0, spec.n_fft - spec.win))                        # window, pad
+        S = torch.fft.rfft(z, dim=2)                                                               # rfft
+        out[0] = torch.log(torch.clamp(torch.matmul(S.abs() ** 2, W), min=spec.floor))             # power, matmul, log
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res, st
+
+    def by_fbank(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_fbank(datas, windows, J, sample_rate=rate)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, fbank 400/160/512/80" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_fbank(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape
+        T = out[1].shape[1]
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB (the framed batch it replaces: %.1f MB, the complex spectrogram: %.1f MB), largest difference of "
+              "the two tensors %.3g (natural-log units)" % (what, J, out[1].numel() * 4 / 1e6, n * T * spec.n_fft * 4 / 1e6, n * (spec.n_fft // 2 + 1) * T * 8 / 1e6,
+                                                            float((out[0] - out[1]).abs().max())), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_batch(mono) + the eight torch ops %s; decode_ranges_fbank %s" % (run, describe(walls[0]), describe(walls[1])),
+                  flush=True)
+        for d in ds:
+            d.close()
+
+
+def fbank_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n = 64
+    for samples in (16000, 480000):
+        src = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+        rows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+        for name, frames_first in (("frames first", True), ("bands first", False)):
+            spec = capi.FbankSpec.make(frames_first=frames_first)
+            T = spec.n_frames(samples)
+            dst = torch.empty((n, T, 80) if frames_first else (n, 80, T), dtype=torch.float32, device="cuda:0")
+            times = []
+            for _ in range(11):
+                ctx.timer_start()
+                assert capi.pcm_fbank(ctx, src, rows, dst, spec, samples) == capi.OK, ctx.last_error()
+                times.append(ctx.timer_stop())
+            ms = statistics.median(times[1:])
+            flop = 2.0 * n * T * 400 * 512
+            print("vpz_pcm_fbank %-12s 64 windows of %6d samples (T = %4d): median %.1f us (min %.1f, max %.1f); %.2f GFLOP of the folded product = %.1f TFLOP/s; "
+                  "%.1f MB out, %.1f MB of framed batch and %.1f MB of spectrogram not written" % (
+                      name, samples, T, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, flop / 1e9, flop / ms / 1e9, dst.numel() * 4 / 1e6,
+                      n * T * 512 * 4 / 1e6, n * 257 * T * 8 / 1e6), flush=True)
+    ctx.close()
+
+
+if args.fbank_kernel:
+    fbank_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.fbank:
+    fbank_job(args.ranges, args.resample)
+    sys.exit(0)
 if args.logmel_kernel:
     logmel_kernel_job()
     sys.exit(0)

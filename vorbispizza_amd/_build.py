@@ -30,6 +30,7 @@ SOURCES = {
     "pcm_pack.hip": [],  # vpz_pcm_pack: windows of a device PCM array as a padded batch (a copy: no arithmetic)
     "pcm_resample.hip": [],  # vpz_pcm_resample: the same delivery at one sample rate (float32 multiply-adds, fused: the tolerance covers them)
     "pcm_logmel.hip": [],  # vpz_pcm_logmel: windows of a mono device array as (log-)mel frames (the DFT on the exact float32 MFMA)
+    "pcm_fbank.hip": [],  # vpz_pcm_fbank: the same windows as Kaldi filterbank frames (per-frame mean, the folded operator on the same MFMA)
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-constant-logical-operand", "-fno-strict-aliasing"]
@@ -56,6 +57,7 @@ def _deps(src):
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_pack.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_resample.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_logmel.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_fbank.h"))
     return deps
 
 
@@ -77,7 +79,8 @@ def build_host(force=False, verbose=False):
                    os.path.join(inc, "vorbispizza_pcm.h"), os.path.join(inc, "vorbispizza_pcm_pack.h"),
                    os.path.join(inc, "vorbispizza_multi_batch.h"), os.path.join(inc, "vorbispizza_pcm_resample.h"),
                    os.path.join(inc, "vorbispizza_multi_resample.h"), os.path.join(inc, "vorbispizza_pcm_logmel.h"),
-                   os.path.join(inc, "vorbispizza_multi_logmel.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi_logmel.h"), os.path.join(inc, "vorbispizza_pcm_fbank.h"),
+                   os.path.join(inc, "vorbispizza_multi_fbank.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

@@ -150,6 +150,49 @@ _PCM_LOGMEL_SIGNATURES = [
     ("vpz_pcm_logmel", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(LogMelSpec), C.c_int32, _vp, _vp, C.c_int64]),
 ]
 PCM_LOGMEL_EXPORTED_SYMBOLS = [s[0] for s in _PCM_LOGMEL_SIGNATURES]
+
+
+FLT_EPSILON = 2.0 ** -23  # (Kaldi's floor under the log)
+
+
+class FbankSpec(C.Structure):
+    """vpz_fbank_spec (include/vorbispizza_pcm_fbank.h).  FbankSpec.make(...) takes the names a Python caller uses; its defaults are
+    Kaldi's fbank at 16 kHz with 80 bands."""
+    _fields_ = [("sample_rate", C.c_double), ("low_freq", C.c_double), ("high_freq", C.c_double), ("preemphasis", C.c_double),
+                ("scale", C.c_double), ("floor", C.c_double), ("pad_value", C.c_double),
+                ("win", C.c_int32), ("hop", C.c_int32), ("n_fft", C.c_int32), ("n_mels", C.c_int32), ("window", C.c_int32),
+                ("remove_dc", C.c_int32), ("output", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 10)]
+
+    @classmethod
+    def make(cls, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=80, low_freq=20.0, high_freq=0.0, preemphasis=0.97, window="povey",
+             remove_dc=True, scale=32768.0, log=True, floor=FLT_EPSILON, pad_value=0.0, frames_first=True):
+        windows = {"hanning": FBANK_HANNING, "hamming": FBANK_HAMMING, "povey": FBANK_POVEY}
+        if window not in windows:
+            raise ValueError("FbankSpec: window is 'hanning', 'hamming' or 'povey'")
+        s = cls()
+        s.sample_rate, s.low_freq, s.high_freq, s.preemphasis = float(sample_rate), float(low_freq), float(high_freq), float(preemphasis)
+        s.scale, s.floor, s.pad_value = float(scale), float(floor), float(pad_value)
+        s.win, s.hop, s.n_fft, s.n_mels = int(win), int(hop), int(n_fft), int(n_mels)
+        s.window, s.remove_dc = windows[window], int(bool(remove_dc))
+        s.output, s.layout = (FBANK_LOG if log else FBANK_POWER), (FBANK_FRAMES_FIRST if frames_first else FBANK_BANDS_FIRST)
+        return s
+
+    def n_frames(self, frames):
+        """T of a row of `frames` samples (frames >= win); also T_L of a row's `frames` real samples, 0 below win."""
+        return 0 if int(frames) < self.win else 1 + (int(frames) - self.win) // self.hop
+
+
+FBANK_HANNING, FBANK_HAMMING, FBANK_POVEY = 0, 1, 2
+FBANK_POWER, FBANK_LOG = 0, 1
+FBANK_BANDS_FIRST, FBANK_FRAMES_FIRST = 0, 1
+FBANK_MIN_NFFT, FBANK_MAX_NFFT, FBANK_MAX_MELS = 32, 1024, 256
+# include/vorbispizza_pcm_fbank.h (a header of its own again)
+_PCM_FBANK_SIGNATURES = [
+    ("vpz_fbank_table", C.c_int, [C.POINTER(FbankSpec), _vp, C.c_int64]),
+    ("vpz_fbank_filterbank", C.c_int, [C.POINTER(FbankSpec), _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    ("vpz_pcm_fbank", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(FbankSpec), C.c_int32, _vp, _vp, C.c_int64]),
+]
+PCM_FBANK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_FBANK_SIGNATURES]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
 PCM_PACK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_PACK_SIGNATURES]
@@ -182,7 +225,7 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        later = _PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES
+        later = _PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -370,6 +413,46 @@ def mel_filterbank(spec):
                                   C.byref(total))
     if rc != OK:
         raise ValueError("vpz_mel_filterbank failed (status %d)" % rc)
+    return first, count, weights
+
+
+def pcm_fbank(ctx, src, rows, dst, spec, frames):
+    """vpz_pcm_fbank (vorbispizza_pcm_fbank.h): windows of the MONO float32 device array `src` (a torch tensor) as Kaldi filterbank
+    frames of rows padded to `frames` samples, into rows of `dst` -- a contiguous float32 torch tensor [rows, T, n_mels]
+    (FBANK_FRAMES_FIRST) or [rows, n_mels, T], T = 1 + (frames - win) // hop; rows: [(src, samples, row)]; spec: an FbankSpec.
+    Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_fbank(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                               int(dst.shape[0]))
+
+
+def fbank_table(spec):
+    """vpz_fbank_table: float32 [win, 2, n_fft // 2] -- [m, 0, k] the coefficient of x[m] - mu in re[k], [m, 1, k] in im[k]; needs no
+    device.  A refused spec raises ValueError."""
+    rc = lib().vpz_fbank_table(C.byref(spec), None, 0)
+    if rc != OK:
+        raise ValueError("vpz_fbank_table refuses the spec (status %d)" % rc)
+    table = np.zeros((int(spec.win), 2, int(spec.n_fft) // 2), dtype=np.float32)
+    rc = lib().vpz_fbank_table(C.byref(spec), table.ctypes.data, table.size)
+    if rc != OK:
+        raise ValueError("vpz_fbank_table failed (status %d)" % rc)
+    return table
+
+
+def fbank_filterbank(spec):
+    """vpz_fbank_filterbank: (first_bin[n_mels] int32, n_bins[n_mels] int32, weights float32 -- band after band, each band's live bins)
+    of an FbankSpec; needs no device.  A refused spec raises ValueError."""
+    total = C.c_int64(0)
+    rc = lib().vpz_fbank_filterbank(C.byref(spec), None, None, None, 0, C.byref(total))
+    if rc != OK:
+        raise ValueError("vpz_fbank_filterbank refuses the spec (status %d)" % rc)
+    first, count = np.zeros(spec.n_mels, dtype=np.int32), np.zeros(spec.n_mels, dtype=np.int32)
+    weights = np.zeros(total.value, dtype=np.float32)
+    rc = lib().vpz_fbank_filterbank(C.byref(spec), first.ctypes.data, count.ctypes.data, weights.ctypes.data if total.value else None, weights.size,
+                                    C.byref(total))
+    if rc != OK:
+        raise ValueError("vpz_fbank_filterbank failed (status %d)" % rc)
     return first, count, weights
 
 

@@ -1,0 +1,424 @@
+// vpz_pcm_fbank, vpz_fbank_table and vpz_fbank_filterbank (include/vorbispizza_pcm_fbank.h, which states the definition): windows of a
+// mono device PCM array as Kaldi filterbank feature frames, one launch, neither framed copy nor spectrogram in device memory.
+//
+// The mapping is that of pcm_logmel.hip where the two definitions agree:
+//   a TILE is Tt consecutive frames [t0, t0 + Tt) of one destination row (Tt = 64, 32 or 16, chosen by the launch); one workgroup of
+//   four waves per tile and descriptor;
+//   a row has T_L real frames, its own number: of a tile's frames the first nr = min(Tt, T_L - t0) are computed, the others hold
+//   pad_value; a tile with nr <= 0 stores without staging or computing;
+//   the SOURCE SPAN of the real frames -- samples t0 * hop up to the last sample of frame t0 + nr - 1, every one a real sample: no
+//   reflection, no zero extension -- is staged in LDS once, stored SKEWED for an even hop (sample i at i + floor(i / hop)), so that the
+//   32 frames a wave reads at once lie hop + 1 words apart and fall on 32 different banks;
+//   THE MEAN of every frame comes from the staged span before the product: four lanes per frame sum every fourth sample in ascending
+//   order, two shuffles add the partial sums as (s0 + s1) + (s2 + s3), one division by win -- the order the header states, the same at
+//   every tile size -- and the value goes through LDS to the lanes that read the frame;
+//   the folded operator of the frame is a matrix product on the exact float32 MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain):
+//   the frames are the A operand, A[t][m] = span[t * hop + m] - mu[t], subtracted on the read; the table B[m][k] is the B operand, read
+//   straight from L2 four k-steps ahead.  The k loop runs over win, not n_fft: floor(win / 2) steps of two samples; an odd win adds one step
+//   whose second sample is 0 against a zero last table row.  A wave owns 32 bins' cos and sin columns at a time;
+//   P = re^2 + im^2 goes into an LDS tile [Tt][n_fft/2, made odd] (no Nyquist column); then one lane per (frame, band) sums its band's
+//   live bins in ascending k, takes the natural log and stores, consecutive lanes along the layout's inner dimension.
+// All element indices are 64-bit.  No scratch memory.
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "vpz_internal.hpp"
+#include "fbank_tables.hpp"
+#include "../../include/vorbispizza_pcm_fbank.h"
+
+namespace vpz {
+
+namespace {
+
+constexpr int kFbBlock = 256;        // lanes of a workgroup: four waves
+constexpr int kFbCols = 32;          // bins a wave owns at a time (the MFMA's N)
+constexpr int kFbLdsFloats = 40960;  // 160 KiB: what a workgroup may use
+constexpr int kFbMaxGridY = 2048;    // descriptors side by side in the grid's y; a workgroup takes every kFbMaxGridY-th beyond that
+constexpr int kFbAhead = 4;          // k-steps (of two samples) whose table values are loaded ahead
+constexpr int kFbMeans = 64;         // floats of the tile's means in LDS (one per frame of the largest tile)
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+struct FbankArgs {
+    const float *src;
+    const vpz_pack_row *rows;
+    float *dst;
+    const float *table;   // [2 * ceil(win / 2)][2 * cols]
+    const int32_t *meta;  // [n_mels][3]
+    const float *w;
+    int64_t T;
+    int32_t n_rows, win, hop, nb, cols, n_mels, log, frames_first, remove_dc;
+    int32_t Tt, skew, pstride, span_cap;  // frames of a tile; 1: the span is skewed; floats between two rows of the power tile; floats of the span
+    float floor, log_floor, pad;
+};
+
+// RT: 32-frame row tiles of a workgroup's tile (2 at Tt = 64, 1 at Tt <= 32)
+template <int RT>
+__global__ __launch_bounds__(kFbBlock) void pcm_fbank_kernel(const FbankArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    float *span = lds, *mean = lds + a.span_cap, *pw = mean + kFbMeans;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31, h = lane >> 5;
+    const int win = a.win, hop = a.hop, nb = a.nb, n_mels = a.n_mels, Tt = a.Tt, skew = a.skew, pstride = a.pstride;
+    const int64_t T = a.T;
+    const int64_t t0 = (int64_t)blockIdx.x * Tt;
+    const int nt = (int)(T - t0 < Tt ? T - t0 : Tt);  // the tile's frames (the grid covers T)
+    const int items = nt * n_mels;
+    const int pairs = win / 2;                        // whole k-steps of two samples (an odd win has half a step more)
+    const size_t ld = 2 * (size_t)a.cols;
+    for (int r = blockIdx.y; r < a.n_rows; r += gridDim.y) {
+        const vpz_pack_row d = a.rows[r];
+        const int64_t L = d.samples;
+        const int64_t TL = L < win ? 0 : 1 + (L - win) / hop;  // the row's real frames
+        const int nr = (int)(TL - t0 < 0 ? 0 : TL - t0 < nt ? TL - t0 : nt);  // ... of this tile (the same for the whole workgroup)
+        if (nr > 0) {
+            // the last staged sample is t0 * hop + (nr - 1) * hop + win - 1 <= (TL - 1) * hop + win - 1 <= L - 1
+            const float *in = a.src + d.src + t0 * hop;
+            const int count = (nr - 1) * hop + win;
+            for (int i = t; i < count; i += kFbBlock) span[i + (skew ? i / hop : 0)] = in[i];
+            __syncthreads();
+            if (a.remove_dc) {
+                // four lanes per frame, 64 frames: lane q of a frame sums x[q], x[q + 4], ... (a frame behind the real ones repeats the last)
+                const int f = t >> 2, q = t & 3, fr = f < nr ? f : nr - 1;
+                const float *fp = span + fr * (hop + skew);
+                float s = 0.0f;
+                int g = q, rem = q;
+                if (skew) {
+                    g += q / hop;
+                    rem = q % hop;
+                }
+                for (int m = q; m < win; m += 4) {
+                    s += fp[g];
+                    g += 4;
+                    if (skew) {
+                        rem += 4;
+                        while (rem >= hop) {
+                            rem -= hop;
+                            ++g;
+                        }
+                    }
+                }
+                s += __shfl_xor(s, 1);  // s0 + s1 | s2 + s3
+                s += __shfl_xor(s, 2);  // (s0 + s1) + (s2 + s3), the same bits in all four
+                if (q == 0) mean[f] = s / (float)win;
+                __syncthreads();
+            }
+            int base[RT];
+            float mu[RT];
+            for (int rt = 0; rt < RT; ++rt) {
+                const int row = rt * 32 + col, fr = row < nr ? row : nr - 1;  // (a row behind the real frames repeats the last one: its results are not stored)
+                base[rt] = fr * (hop + skew);
+                mu[rt] = a.remove_dc ? mean[fr] : 0.0f;
+            }
+            for (int k0 = wave * kFbCols; k0 < nb; k0 += (kFbBlock / 64) * kFbCols) {
+                f32x16 re[RT], im[RT];
+                for (int rt = 0; rt < RT; ++rt)
+                    for (int i = 0; i < 16; ++i) re[rt][i] = im[rt][i] = 0.0f;
+                // this lane's sample of a k-step: m = 2 * step + h, as its place g = m + skew * floor(m / hop) in a frame
+                int g = h + (skew && h >= hop ? 1 : 0), rem = h >= hop ? h - hop : h;
+                auto step_a = [&]() {  // (an even hop is at least 2: one wrap per step at the most; an odd hop has no skew)
+                    rem += 2;
+                    const int c = rem >= hop ? 1 : 0;
+                    rem -= c ? hop : 0;
+                    g += 2 + (skew ? c : 0);
+                };
+                const float *tp = a.table + (size_t)h * ld + k0 + col;  // table row m = h, this lane's cos column
+                const int blocks = pairs / kFbAhead;
+                float cre[kFbAhead], cim[kFbAhead], nre[kFbAhead], nim[kFbAhead];
+                if (blocks > 0) {
+#pragma unroll
+                    for (int u = 0; u < kFbAhead; ++u) {
+                        const float *p = tp + (size_t)(2 * u) * ld;
+                        cre[u] = p[0];
+                        cim[u] = p[a.cols];
+                    }
+                }
+                for (int blk = 0; blk < blocks; ++blk) {
+                    const int nxt = blk + 1 < blocks ? blk + 1 : blk;  // (the last block loads itself again: no branch)
+#pragma unroll
+                    for (int u = 0; u < kFbAhead; ++u) {
+                        const float *p = tp + (size_t)(2 * (nxt * kFbAhead + u)) * ld;
+                        nre[u] = p[0];
+                        nim[u] = p[a.cols];
+                    }
+#pragma unroll
+                    for (int u = 0; u < kFbAhead; ++u) {
+#pragma unroll
+                        for (int rt = 0; rt < RT; ++rt) {
+                            const float av = span[base[rt] + g] - mu[rt];
+                            re[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cre[u], re[rt], 0, 0, 0);
+                            im[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, cim[u], im[rt], 0, 0, 0);
+                        }
+                        step_a();
+                    }
+#pragma unroll
+                    for (int u = 0; u < kFbAhead; ++u) {
+                        cre[u] = nre[u];
+                        cim[u] = nim[u];
+                    }
+                }
+                for (int pr = blocks * kFbAhead; pr < pairs; ++pr) {
+                    const float *p = tp + (size_t)(2 * pr) * ld;
+                    const float br = p[0], bi = p[a.cols];
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) {
+                        const float av = span[base[rt] + g] - mu[rt];
+                        re[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, br, re[rt], 0, 0, 0);
+                        im[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bi, im[rt], 0, 0, 0);
+                    }
+                    step_a();
+                }
+                if (win & 1) {  // the last sample alone: the step's second sample is no sample of the frame (0, against the table's zero row)
+                    const float *p = tp + (size_t)(2 * pairs) * ld;
+                    const float br = p[0], bi = p[a.cols];
+#pragma unroll
+                    for (int rt = 0; rt < RT; ++rt) {
+                        const float av = h ? 0.0f : span[base[rt] + g] - mu[rt];
+                        re[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, br, re[rt], 0, 0, 0);
+                        im[rt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bi, im[rt], 0, 0, 0);
+                    }
+                }
+                // the accumulators' map: column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+                const int k = k0 + col;
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int row = rt * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                        if (k < nb && row < Tt) pw[row * pstride + k] = re[rt][i] * re[rt][i] + im[rt][i] * im[rt][i];
+                    }
+            }
+            __syncthreads();
+        }
+        // (the next descriptor's staging writes the span, which no lane reads any more; its first barrier stands before the means and the
+        // power tile are written again)
+        for (int it = t; it < items; it += kFbBlock) {
+            int tl, b;
+            if (a.frames_first) {
+                tl = it / n_mels;
+                b = it - tl * n_mels;
+            } else {
+                b = it / nt;
+                tl = it - b * nt;
+            }
+            float v = a.pad;
+            if (tl < nr) {
+                const int first = a.meta[3 * b], cnt = a.meta[3 * b + 1];
+                const float *p = pw + tl * pstride + first, *ww = a.w + a.meta[3 * b + 2];
+                float acc = 0.0f;
+                for (int i = 0; i < cnt; ++i) acc = __builtin_fmaf(ww[i], p[i], acc);
+                v = !a.log ? acc : acc <= a.floor ? a.log_floor : logf(acc);
+            }
+            const int64_t at = a.frames_first ? (d.row * T + t0 + tl) * n_mels + b : (d.row * n_mels + b) * T + t0 + tl;
+            a.dst[at] = v;
+        }
+    }
+}
+
+int table_for(Context *ctx, const vpz_fbank_spec &s, const Context::LogmelDft **out)
+{
+    try {
+        const std::vector<double> key = {(double)s.win, (double)s.n_fft, (double)s.window, s.preemphasis, s.scale};
+        auto it = ctx->fbank_tables.find(key);
+        if (it != ctx->fbank_tables.end()) {
+            *out = &it->second;
+            return VPZ_OK;
+        }
+        Context::LogmelDft tb;
+        tb.cols = (s.n_fft / 2 + kFbCols - 1) / kFbCols * kFbCols;
+        const size_t rows = 2 * (size_t)((s.win + 1) / 2);  // (an odd win: one more row, of zeros)
+        std::vector<float> host(rows * 2 * (size_t)tb.cols, 0.0f);
+        fbank_table_fill(s, host.data(), 2 * (size_t)tb.cols, (size_t)tb.cols);
+        void *mem = nullptr;
+        VPZ_HIP_TRY(ctx, hipMalloc(&mem, host.size() * sizeof(float)));
+        // (a blocking copy, once per table and context: the table is whole before any launch that reads it is queued)
+        const hipError_t e = hipMemcpy(mem, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(mem);
+            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_fbank: table upload", e);
+        }
+        tb.d_table = static_cast<float *>(mem);
+        try {
+            *out = &ctx->fbank_tables.emplace(key, tb).first->second;
+        } catch (const std::bad_alloc &) {
+            (void)hipFree(mem);
+            throw;
+        }
+    } catch (const std::bad_alloc &) {
+        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_fbank: out of host memory");
+    }
+    return VPZ_OK;
+}
+
+int bank_for(Context *ctx, const vpz_fbank_spec &s, const Context::LogmelBank **out)
+{
+    try {
+        const std::vector<double> key = {s.sample_rate, (double)s.n_fft, (double)s.n_mels, s.low_freq, s.high_freq};
+        auto it = ctx->fbank_banks.find(key);
+        if (it != ctx->fbank_banks.end()) {
+            *out = &it->second;
+            return VPZ_OK;
+        }
+        FbankBank fb;
+        fbank_bank_build(s, fb);
+        std::vector<int32_t> meta((size_t)s.n_mels * 3);
+        int32_t at = 0;
+        for (int b = 0; b < s.n_mels; ++b) {
+            meta[(size_t)b * 3] = fb.first[(size_t)b];
+            meta[(size_t)b * 3 + 1] = fb.count[(size_t)b];
+            meta[(size_t)b * 3 + 2] = at;
+            at += fb.count[(size_t)b];
+        }
+        const size_t meta_bytes = meta.size() * sizeof(int32_t), w_bytes = fb.weights.size() * sizeof(float);
+        void *mem = nullptr;
+        VPZ_HIP_TRY(ctx, hipMalloc(&mem, meta_bytes + std::max<size_t>(w_bytes, sizeof(float))));
+        Context::LogmelBank bk;
+        bk.d_meta = static_cast<int32_t *>(mem);
+        bk.d_w = reinterpret_cast<float *>(static_cast<char *>(mem) + meta_bytes);
+        hipError_t e = hipMemcpy(bk.d_meta, meta.data(), meta_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess && w_bytes) e = hipMemcpy(bk.d_w, fb.weights.data(), w_bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(mem);
+            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_fbank: mel bank upload", e);
+        }
+        try {
+            *out = &ctx->fbank_banks.emplace(key, bk).first->second;
+        } catch (const std::bad_alloc &) {
+            (void)hipFree(mem);
+            throw;
+        }
+    } catch (const std::bad_alloc &) {
+        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_fbank: out of host memory");
+    }
+    return VPZ_OK;
+}
+
+// floats of a tile's LDS at `Tt` frames: the skewed span, then (behind the means) the power tile
+void lds_plan(const vpz_fbank_spec &s, int Tt, int *span_cap, int *pstride)
+{
+    const int count = (Tt - 1) * s.hop + s.win, skew = s.hop % 2 == 0 ? 1 : 0;
+    *span_cap = count + (skew ? count / s.hop : 0) + 1;
+    *pstride = (s.n_fft / 2) | 1;
+}
+
+}  // namespace
+
+void free_fbank_tables(Context *ctx)
+{
+    for (auto &kv : ctx->fbank_tables)
+        if (kv.second.d_table) (void)hipFree(kv.second.d_table);
+    ctx->fbank_tables.clear();
+    for (auto &kv : ctx->fbank_banks)
+        if (kv.second.d_meta) (void)hipFree(kv.second.d_meta);  // (one allocation: the weights lie behind the bands' records)
+    ctx->fbank_banks.clear();
+}
+
+}  // namespace vpz
+
+extern "C" int vpz_fbank_table(const vpz_fbank_spec *spec, float *table, int64_t capacity)
+{
+    if (!spec || capacity < 0 || !vpz::fbank_spec_ok(*spec)) return VPZ_E_INVALID_ARG;
+    if (!table) return VPZ_OK;
+    const int64_t nb = spec->n_fft / 2;
+    if (capacity < (int64_t)spec->win * 2 * nb) return VPZ_E_CAPACITY;
+    vpz::fbank_table_fill(*spec, table, (size_t)(2 * nb), (size_t)nb);
+    return VPZ_OK;
+}
+
+extern "C" int vpz_fbank_filterbank(const vpz_fbank_spec *spec, int32_t *first_bin, int32_t *n_bins, float *weights, int64_t capacity,
+                                    int64_t *total)
+{
+    if (!spec || capacity < 0 || !vpz::fbank_spec_ok(*spec)) return VPZ_E_INVALID_ARG;
+    vpz::FbankBank fb;
+    try {
+        vpz::fbank_bank_build(*spec, fb);
+    } catch (const std::bad_alloc &) {
+        return VPZ_E_NOMEM;
+    }
+    if (total) *total = (int64_t)fb.weights.size();
+    if (first_bin) memcpy(first_bin, fb.first.data(), sizeof(int32_t) * fb.first.size());
+    if (n_bins) memcpy(n_bins, fb.count.data(), sizeof(int32_t) * fb.count.size());
+    if (!weights) return VPZ_OK;
+    if ((uint64_t)capacity < fb.weights.size()) return VPZ_E_CAPACITY;
+    if (!fb.weights.empty()) memcpy(weights, fb.weights.data(), sizeof(float) * fb.weights.size());
+    return VPZ_OK;
+}
+
+extern "C" int vpz_pcm_fbank(vpz_context *c, const void *src_dev, int64_t src_elems, int64_t frames, const vpz_fbank_spec *spec, int32_t n_rows,
+                             const vpz_pack_row *rows, void *dst_dev, int64_t dst_rows)
+{
+    if (!c) return VPZ_E_INVALID_ARG;
+    vpz::Context *ctx = &c->impl;
+    auto refuse = [&](const char *what) { return vpz::set_error(ctx, VPZ_E_INVALID_ARG, what); };
+    if (!spec) return refuse("vpz_pcm_fbank: null pointer");
+    if (!vpz::fbank_spec_ok(*spec)) return refuse("vpz_pcm_fbank: a spec outside the limits");
+    const vpz_fbank_spec &s = *spec;
+    if (frames < s.win) return refuse("vpz_pcm_fbank: frames < win (a row holds no frame)");
+    if (frames > INT64_MAX / 8) return refuse("vpz_pcm_fbank: sizes overflow");
+    const int64_t T = 1 + (frames - s.win) / s.hop;
+    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_fbank", src_dev, src_elems, sizeof(float), 1, 1, 1, frames, n_rows, rows, dst_dev, dst_rows,
+                                                       (unsigned __int128)(uint64_t)T * (uint64_t)s.n_mels, sizeof(float)});
+    if (rc != VPZ_OK || n_rows == 0) return rc;
+
+    const vpz::Context::LogmelDft *tb = nullptr;
+    const vpz::Context::LogmelBank *bk = nullptr;
+    rc = vpz::table_for(ctx, s, &tb);
+    if (rc == VPZ_OK) rc = vpz::bank_for(ctx, s, &bk);
+    if (rc != VPZ_OK) return rc;
+
+    vpz::FbankArgs a;
+    // the tile: 64 frames where the row has more than 32, the launch gives every CU two workgroups at that size and the LDS holds them
+    // (every tile reads the whole table from L2, so the larger tile halves that traffic); else 32 where the row has more than 16 and the
+    // LDS holds them; else 16 (a result does not depend on the tile: the same bits).  tests/test_fbank_cpu.py restates lds_plan and this
+    // choice (tile_plan) and holds them at every spec inside the limits
+    a.Tt = 0;
+    const bool few = ((T + 63) / 64) * (int64_t)n_rows < 2 * (int64_t)ctx->num_cu;
+    for (int Tt : {64, 32, 16}) {
+        vpz::lds_plan(s, Tt, &a.span_cap, &a.pstride);
+        if ((Tt == 64 && (T <= 32 || few)) || (Tt == 32 && T <= 16) || a.span_cap + vpz::kFbMeans + Tt * a.pstride > vpz::kFbLdsFloats) continue;
+        a.Tt = Tt;
+        break;
+    }
+    if (a.Tt == 0) return vpz::set_error(ctx, VPZ_E_UNSUPPORTED, "vpz_pcm_fbank: no tile fits the LDS");  // (16 frames fit at every spec inside the limits)
+    const int64_t blocks = (T + a.Tt - 1) / a.Tt;
+    if (blocks > 0x7fffffff) return refuse("vpz_pcm_fbank: a row too long for one launch");
+
+    rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);
+    if (rc != VPZ_OK) return rc;
+
+    a.src = static_cast<const float *>(src_dev);
+    a.dst = static_cast<float *>(dst_dev);
+    a.table = tb->d_table;
+    a.meta = bk->d_meta;
+    a.w = bk->d_w;
+    a.T = T;
+    a.n_rows = n_rows;
+    a.win = s.win;
+    a.hop = s.hop;
+    a.nb = s.n_fft / 2;
+    a.cols = tb->cols;
+    a.n_mels = s.n_mels;
+    a.log = s.output == VPZ_FBANK_LOG;
+    a.frames_first = s.layout == VPZ_FBANK_FRAMES_FIRST;
+    a.remove_dc = s.remove_dc;
+    a.skew = s.hop % 2 == 0 ? 1 : 0;
+    a.floor = a.log ? (float)s.floor : 0.0f;
+    a.log_floor = a.log ? (float)log((double)a.floor) : 0.0f;
+    a.pad = (float)s.pad_value;
+    const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kFbMaxGridY));
+    const size_t lds = sizeof(float) * ((size_t)a.span_cap + (size_t)vpz::kFbMeans + (size_t)a.Tt * (size_t)a.pstride);
+    // (the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never lower it under each other)
+    const int max_lds = (int)(sizeof(float) * vpz::kFbLdsFloats);
+    if (a.Tt == 64) {
+        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_fbank_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        vpz::pcm_fbank_kernel<2><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(a);
+    } else {
+        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_fbank_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        vpz::pcm_fbank_kernel<1><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(a);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_fbank kernel launch", e);
+    return VPZ_OK;
+}

@@ -294,6 +294,7 @@ void vpz_context_destroy(vpz_context *c)
     vpz::free_pack_scratch(ctx);
     vpz::free_resample_tables(ctx);
     vpz::free_logmel_tables(ctx);
+    vpz::free_fbank_tables(ctx);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -53,7 +53,7 @@ struct Context {
     // persistent grids of the IMDCT kernels on THIS context's device (workgroups the chip keeps resident), filled by the first
     // launch of each; per context, not per process: a host with several GPUs holds one context per device
     int resident[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // the row launches -- vpz_pcm_pack, vpz_pcm_resample and vpz_pcm_logmel -- share it (upload_rows, pcm_pack.hip): a launch's row
+    // the row launches -- vpz_pcm_pack, vpz_pcm_resample, vpz_pcm_logmel and vpz_pcm_fbank -- share it (upload_rows, pcm_pack.hip): a launch's row
     // descriptors go up through a page-locked buffer of the context's into its device copy; `pack_done` says that the last launch's copy
     // has left the buffer
     void *pack_host = nullptr, *pack_dev = nullptr;
@@ -78,6 +78,10 @@ struct Context {
     };
     std::map<int, LogmelDft> logmel_dft;
     std::map<std::vector<double>, LogmelBank> logmel_banks;  // keyed by (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
+    // vpz_pcm_fbank (pcm_fbank.hip): the device copy of every folded table -- [2 * ceil(win / 2)][2 * cols], keyed by (win, n_fft, window,
+    // preemphasis, scale) -- and of every mel bank, keyed by (sample_rate, n_fft, n_mels, low_freq, high_freq); the records are log-mel's
+    std::map<std::vector<double>, LogmelDft> fbank_tables;
+    std::map<std::vector<double>, LogmelBank> fbank_banks;
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
@@ -112,6 +116,7 @@ int upload_rows(Context *ctx, int32_t n_rows, const vpz_pack_row *rows, const vp
 bool layout_of(int32_t layout, bool *s16, bool *planar);
 void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_destroy calls it)
 void free_logmel_tables(Context *ctx);  // (pcm_logmel.hip; vpz_context_destroy calls it)
+void free_fbank_tables(Context *ctx);  // (pcm_fbank.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

@@ -37,6 +37,7 @@
 //
 // vpzm_decode_ranges_logmel (include/vorbispizza_multi_logmel.h) is the mono resampled call with one more stage: the resample launches write
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
+// vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
 //
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
@@ -66,6 +67,8 @@
 #include "../../include/vorbispizza_multi_resample.h"
 #include "../../include/vorbispizza_pcm_logmel.h"
 #include "../../include/vorbispizza_multi_logmel.h"
+#include "../../include/vorbispizza_pcm_fbank.h"
+#include "../../include/vorbispizza_multi_fbank.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -313,7 +316,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, or the log-mel launch of a log-mel call -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, or the feature launch of a log-mel or fbank call -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -365,22 +368,33 @@ struct Job {  // one stream of the library inside its group
 // vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
-    enum Kind { kPack, kResampled, kLogmel };  // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel
+    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank
+    enum Kind { kPack, kResampled, kLogmel, kFbank };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
     int32_t rate = 0, downmix = 0;  // kResampled, kLogmel: every row at `rate`, mixed down to mono
     // kLogmel: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed)
     const vpz_logmel_spec *mel = nullptr;
+    // kFbank: the same with Kaldi filterbank frames of this spec (`dst` is [rows][T][n_mels] or transposed)
+    const vpz_fbank_spec *fbank = nullptr;
     void *dst = nullptr;  // (decode_call fills these two in)
     int64_t rows = 0;     // of the group's piece: its entries
     bool resampled() const { return kind != kPack; }
+    bool features() const { return kind == kLogmel || kind == kFbank; }  // a feature stage behind the resample launches, fed from the lane's temporary
+    const char *feature_step() const { return kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
+    // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `dst`
+    int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d) const
+    {
+        if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), dst, rows);
+        return vpz_pcm_logmel(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), dst, rows);
+    }
 
-    // These descriptors (samples = 0 each) get rows of no samples -- zeros, or the silence row of a log-mel call, which its own kernel
-    // writes -- from a launch that reads nothing: the destination stands in for a source of no elements
+    // These descriptors (samples = 0 each) get rows of no samples -- zeros, or the silence row of a log-mel call or the pad_value row of
+    // an fbank call, which their own kernels write -- from a launch that reads nothing: the destination stands in for a source of no elements
     int empty_rows(vpz_context *ctx, const std::vector<vpz_pack_row> &d) const
     {
-        if (mel) return vpz_pcm_logmel(ctx, dst, 0, frames, mel, (int32_t)d.size(), d.data(), dst, rows);
+        if (features()) return feature_rows(ctx, dst, 0, d);
         return vpz_pcm_pack(ctx, dst, 0, channels, (int32_t)d.size(), d.data(), dst, rows, frames, layout);
     }
 };
@@ -871,7 +885,7 @@ struct GroupRun {
             for (const Job &J : jobs)
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0].ctx, rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1266,19 +1280,19 @@ struct SubCall {
         }
         int rc = VPZ_OK;
         if (!staged) {
-            rc = launched(B.mel ? "vpz_pcm_logmel" : "vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP : B.empty_rows(L.ctx, rows));
+            rc = launched(B.features() ? B.feature_step() : "vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP : B.empty_rows(L.ctx, rows));
         } else if (B.kind == Batch::kPack) {
             rc = launched("vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP
                                                              : vpz_pcm_pack(L.ctx, L.pcm(), pcm_elems, B.channels, (int32_t)rows.size(), rows.data(), B.dst,
                                                                             B.rows, B.frames, B.layout));
         } else {
-            // (a log-mel call: resampled into the lane's temporary, then ONE log-mel launch on the same stream -- stream-ordered: no
-            // synchronise in between)
-            if (B.mel) rc = mono_temporary(rows.size());
+            // (a log-mel or fbank call: resampled into the lane's temporary, then ONE feature launch on the same stream -- stream-ordered:
+            // no synchronise in between)
+            if (B.features()) rc = mono_temporary(rows.size());
             if (rc == VPZ_OK) rc = resample_by_ratio(rows);
             for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
             if (rc != VPZ_OK) (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
-            else if (B.mel) rc = logmel_rows(rows);
+            else if (B.features()) rc = feature_rows(rows);
         }
         if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
         for (size_t j = 0; j < sb.members.size(); ++j) {
@@ -1295,18 +1309,18 @@ struct SubCall {
         return rc;
     }
 
-    // a log-mel call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
+    // a log-mel or fbank call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
     int mono_temporary(size_t members)
     {
         if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.frames, sizeof(float))) return VPZ_OK;
-        R.m->fail("vpzm_decode_ranges_logmel: the resampled rows' device temporary could not be allocated");
+        R.m->fail(std::string(B.kind == Batch::kFbank ? "vpzm_decode_ranges_fbank" : "vpzm_decode_ranges_logmel") + ": the resampled rows' device temporary could not be allocated");
         return VPZ_E_NOMEM;
     }
 
     // A resampled call: the members grouped by ratio (a sub-batch has one channel count), one vpz_pcm_resample launch per group on the
     // lane's stream -- one launch where the members share a rate, more where streams of one setup differ in rate.  A member without
     // samples needs no ratio of its own: its zero row rides in the first group (alone, at 1:1, when no member has samples).  Into the
-    // group's piece, or a log-mel call's temporary
+    // group's piece, or a feature call's temporary
     int resample_by_ratio(const std::vector<vpz_pack_row> &rows)
     {
         int rc = VPZ_OK;
@@ -1322,29 +1336,27 @@ struct SubCall {
                 if (!taken[j] && (rows[j].samples == 0 || (job(j).up == up && job(j).down == down))) {
                     taken[j] = 1;
                     group.push_back(rows[j]);
-                    if (B.mel) group.back().row = (int64_t)j;
+                    if (B.features()) group.back().row = (int64_t)j;
                 }
             left -= group.size();
-            rc = R.sw.fail_delivery && !B.mel ? VPZ_E_HIP
+            rc = R.sw.fail_delivery && !B.features() ? VPZ_E_HIP
                                              : vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, B.downmix, (int32_t)group.size(), group.data(),
-                                                                B.mel ? (void *)L.mono() : B.dst, B.mel ? (int64_t)rows.size() : B.rows, B.channels, B.frames,
+                                                                B.features() ? (void *)L.mono() : B.dst, B.features() ? (int64_t)rows.size() : B.rows, B.channels, B.frames,
                                                                 B.layout);
             ++resample_launches;
         }
         return launched("vpz_pcm_resample", rc);
     }
 
-    // a log-mel call: row j's first `written[j]` samples of the temporary become row k - lo of the group's piece
-    int logmel_rows(std::vector<vpz_pack_row> &rows)
+    // a log-mel or fbank call: row j's first `written[j]` samples of the temporary become row k - lo of the group's piece
+    int feature_rows(std::vector<vpz_pack_row> &rows)
     {
         for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.frames, written[j], rows[j].row};
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
         const auto t_mel = Clock::now();
-        const int rc = launched("vpz_pcm_logmel", R.sw.fail_delivery ? VPZ_E_HIP
-                                                                     : vpz_pcm_logmel(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, B.frames, B.mel,
-                                                                                      (int32_t)rows.size(), rows.data(), B.dst, B.rows));
+        const int rc = launched(B.feature_step(), R.sw.fail_delivery ? VPZ_E_HIP : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, rows));
         if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu log-mel kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b,
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b, B.kind == Batch::kFbank ? "fbank" : "log-mel",
                     seconds_since(t_mel) * 1e3, rows.size(), (long long)B.frames);
         return rc;
     }
@@ -1637,6 +1649,19 @@ int vpzm_decode_ranges_logmel(vpzm_dispatcher *m, int32_t n, const uint8_t *cons
     if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
     const Batch batch{Batch::kLogmel, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_fbank(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                             const vpz_fbank_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!spec) return VPZM_E_ARG;
+    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
+    if (vpz_fbank_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
+    if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
+    if (frames < spec->win) return VPZM_E_ARG;
+    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
+    const Batch batch{Batch::kFbank, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, nullptr, spec};
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -49,6 +49,7 @@ RANGES_EXPORTED_SYMBOLS = ["vpzm_decode_ranges"]  # (vorbispizza_multi_ranges.h)
 BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  # (vorbispizza_multi_batch.h)
 RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
+FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
@@ -88,6 +89,9 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges_logmel"):
             L.vpzm_decode_ranges_logmel.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.LogMelSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_logmel.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_fbank"):
+            L.vpzm_decode_ranges_fbank.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_fbank.restype = C.c_int
         _bound = True
     return L
 
@@ -286,4 +290,32 @@ class Dispatcher:
                                              C.byref(stats))
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_logmel failed (status %d): %s" % (rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_fbank(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=80, low_freq=20.0, high_freq=0.0,
+                            preemphasis=0.97, window="povey", remove_dc=True, scale=32768.0, log=True, floor=capi.FLT_EPSILON, pad_value=0.0,
+                            frames_first=True, out=None):
+        """vpzm_decode_ranges_fbank: decode_ranges_batch(..., sample_rate=sample_rate, mono=True) with one more stage on the device --
+        entry k's window, resampled and mixed down, becomes row k of Kaldi filterbank frames: [T, n_mels] (frames_first) or [n_mels, T],
+        float32, T = 1 + (frames - win) // hop (include/vorbispizza_pcm_fbank.h states the definition; the defaults are Kaldi's fbank at
+        16 kHz with 80 bands; log False: the mel power).  results["samples"] counts the window's output samples J: the row's first
+        FbankSpec.n_frames(J) frames are real, the others hold pad_value.
+        out: as for decode_ranges_batch, one contiguous float32 tensor per group of shape [hi - lo, T, n_mels] (or [hi - lo, n_mels, T])
+        on the group's device -- anything else raises before the library is called.  Returns (parts, whole_or_None, results, stats)."""
+        import torch
+        spec = capi.FbankSpec.make(sample_rate=sample_rate, win=win, hop=hop, n_fft=n_fft, n_mels=n_mels, low_freq=low_freq, high_freq=high_freq,
+                                   preemphasis=preemphasis, window=window, remove_dc=remove_dc, scale=scale, log=log, floor=floor,
+                                   pad_value=pad_value, frames_first=frames_first)
+        if win < 1 or frames < win or hop < 1 or n_mels < 1:
+            raise ValueError("decode_ranges_fbank: hop and n_mels must be at least 1, and frames at least win")
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        T = spec.n_frames(frames)
+        shape = (lambda rows: (rows, T, n_mels)) if frames_first else (lambda rows: (rows, n_mels, T))
+        out, whole, dst = self._group_tensors("decode_ranges_fbank", n, shape, torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = lib().vpzm_decode_ranges_fbank(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
+                                            C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_fbank failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats

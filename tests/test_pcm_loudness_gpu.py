@@ -1,0 +1,328 @@
+"""vpz_pcm_loudness (include/vorbispizza_pcm_loudness.h, csrc/pcm_loudness.hip) on the device.
+
+TRUTH: tests/loudness_truth.py's recurrence run one sample after the other in numpy.longdouble (64 bits of mantissa here), over every
+channel of every case at once -- computed once per module and never changed.
+BOUND (derived at loudness_truth.bound): |sums[j] - truth[j]| <= 64 * 2^-53 * (1 / (1 - r)^2 + S) * max_{i <= j} truth[i], r the
+high-pass pole radius of the rate; the inputs keep their crest factor at 4 or less.  The largest error / bound is printed.
+SHAPES: the smallest at which the kernels can go wrong -- lengths around one step, more steps than a wave has lanes (70 at 8 000 Hz), more
+than a workgroup takes (40 steps of 8 channels: 32 to a workgroup), every rate's own step, 1 / 2 / 3 / 6 / 8 channels (256 lanes are no
+multiple of 3 or 6), odd source offsets, rows out of order.  The DC case is the state-carry case: the high-pass state under an offset of
+0.5 is large, and a carry cut after one term would miss the bound at 8 000 Hz."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import loudness_truth as lt  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+LONGDOUBLE_BITS = np.finfo(np.longdouble).nmant
+needs_longdouble = pytest.mark.skipif(LONGDOUBLE_BITS < 63, reason="numpy.longdouble has %d mantissa bits on this machine: float64 would be "
+                                      "compared against itself" % LONGDOUBLE_BITS)
+SENTINEL, PEAK_SENTINEL = -7.25, -3.5
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import __graft_entry__ as ge
+    ge.build()
+    from vorbispizza_amd import Context
+    c = Context(0)
+    yield c
+    c.close()
+
+
+def noise(rng, n, channels):
+    """uniform in [-1, 1): crest factor sqrt(3)"""
+    return rng.uniform(-1.0, 1.0, size=(n, channels))
+
+
+def tone(n, fs, hz):
+    return np.sin(2.0 * np.pi * hz * np.arange(n) / fs)[:, None]
+
+
+def crest(x):
+    return float(np.abs(x).max() / np.sqrt(np.mean(np.square(x, dtype=np.float64)))) if x.size else 0.0
+
+
+class Case:
+    """rows of one launch: float32 [L, channels] each, one rate, one channel count"""
+
+    def __init__(self, name, fs, channels, rows, weights=None):
+        self.name, self.fs, self.channels, self.weights = name, fs, channels, weights
+        self.rows = [np.ascontiguousarray(r, dtype=np.float32).reshape(-1, channels) for r in rows]
+        for r in self.rows:  # (the bound's premise, channel by channel: every channel is a signal of its own)
+            assert r.shape[0] < lt.step_of(fs) or max(crest(r[:, ch]) for ch in range(channels)) <= 4.0, name
+
+    @property
+    def w(self):
+        return lt.weights_of(self.channels) if self.weights is None else np.asarray(self.weights, dtype=np.float64)
+
+
+def build_cases():
+    rng = np.random.default_rng(1770)
+    cases = []
+    S = 800
+    # lengths around a step, at 8 000 Hz, stereo
+    cases.append(Case("lengths", 8000, 2, [0.4 * noise(rng, L, 2) + 0.3 * tone(L, 8000, 440.0) for L in (0, S - 1, S, S + 1, 4 * S, 7 * S + 123)]))
+    # 70 steps: more units of one channel than a 64-lane wave; under a DC offset (the state-carry case) and as the gate case (a loud half,
+    # then 26 dB less: every block far from both gates)
+    n = 70 * S
+    dc = 0.5 + 0.1 * noise(rng, n, 1) + 0.1 * tone(n, 8000, 20.0)
+    envelope = np.where(np.arange(n) < 35 * S, 1.0, 0.05)[:, None]
+    gated = envelope * (0.3 * noise(rng, n, 1) + 0.5 * tone(n, 8000, 997.0))
+    cases.append(Case("dc_70_steps", 8000, 1, [dc, gated]))
+    # 40 steps of 8 channels take two workgroups of (a) and (c): 256 / 8 = 32 steps each
+    cases.append(Case("two_workgroups", 8000, 8, [0.5 * noise(rng, 40 * S + 5, 8)]))
+    # every rate's own step
+    for fs in (11025, 44100, 48000):
+        L = 7 * lt.step_of(fs) + 123
+        cases.append(Case("rate_%d" % fs, fs, 2, [0.3 * noise(rng, L, 2) + 0.4 * tone(L, fs, 1000.0)]))
+    L = 2 * 38400 + 5
+    cases.append(Case("rate_384000", 384000, 1, [0.3 * noise(rng, L, 1) + 0.4 * tone(L, 384000, 1000.0)]))
+    # channel counts: 6 has an LFE of weight 0 that is the loudest channel and holds the peak; 3 takes the caller's weights
+    for channels, weights in ((1, None), (2, None), (6, None), (8, None), (3, [0.5, 2.0, 0.0])):
+        rows = []
+        for L in (4 * S + 17, 2 * S):
+            x = 0.2 * noise(rng, L, channels) + 0.2 * tone(L, 8000, 300.0)
+            x[:, -1] *= 2.4
+            rows.append(x)
+        cases.append(Case("channels_%d" % channels, 8000, channels, rows, weights))
+    # a burst that goes silent in the middle of its third step, then six silent steps
+    burst = 0.6 * noise(rng, 9 * S, 1)
+    burst[2 * S + S // 2:] = 0.0
+    cases.append(Case("burst", 8000, 1, [burst]))
+    return {c.name: c for c in cases}
+
+
+_cases, _truth = {}, {}
+
+
+def cases():
+    if not _cases:
+        _cases.update(build_cases())
+    return _cases
+
+
+def truth():
+    """{(case, row): (per-channel step sums in longdouble [steps, channels], weighted [steps])}, computed once in one run over time"""
+    if not _truth:
+        signals, rates, keys = [], [], []
+        for c in cases().values():
+            for i, r in enumerate(c.rows):
+                for ch in range(c.channels):
+                    signals.append(r[:, ch])
+                    rates.append(c.fs)
+                    keys.append((c.name, i, ch))
+        sums = lt.step_sums_sequential(signals, rates, np.longdouble)
+        for c in cases().values():
+            for i, r in enumerate(c.rows):
+                per = np.stack([sums[keys.index((c.name, i, ch))] for ch in range(c.channels)], axis=1)
+                _truth[(c.name, i)] = (per, lt.weighted(per, c.w.astype(np.longdouble)))
+    return _truth
+
+
+def launch(ctx, case, order=None, gap=3, extra_rows=1, max_steps=None, first=0):
+    """one vpz_pcm_loudness launch over the case's rows: the windows lie in one source array with `gap` junk elements in front of each
+    (odd offsets), row i goes to destination row order[i] of extra_rows more rows than the case has.
+    -> (sums [rows, max_steps] float64, peak [rows] float32, as numpy)"""
+    import torch
+    from vorbispizza_amd import capi
+    n = len(case.rows)
+    order = list(range(n)) if order is None else list(order)
+    parts, desc, at = [], [], first
+    if first:
+        parts.append(np.full(first, 9.0, dtype=np.float32))
+    for i, r in enumerate(case.rows):
+        parts.append(np.full(gap, 9.0, dtype=np.float32))
+        at += gap
+        desc.append((at, r.shape[0], order[i]))
+        parts.append(r.reshape(-1))
+        at += r.size
+    parts.append(np.full(5, 9.0, dtype=np.float32))
+    src = torch.from_numpy(np.concatenate(parts)).to("cuda:0")
+    S = lt.step_of(case.fs)
+    if max_steps is None:
+        max_steps = max([1] + [r.shape[0] // S for r in case.rows]) + 2
+    dst_rows = max(order + [-1]) + 1 + extra_rows
+    sums = torch.full((dst_rows, max_steps), SENTINEL, dtype=torch.float64, device="cuda:0")
+    peak = torch.full((dst_rows,), PEAK_SENTINEL, dtype=torch.float32, device="cuda:0")
+    capi.pcm_loudness(ctx, src, case.channels, case.fs, desc, weights=case.weights, max_steps=max_steps, out=(sums, peak))
+    ctx.synchronize()
+    return sums.cpu().numpy(), peak.cpu().numpy()
+
+
+def check_case(case, sums, peak, order=None):
+    """every named row against the truth and the bound; -> the largest error / bound"""
+    S = lt.step_of(case.fs)
+    order = list(range(len(case.rows))) if order is None else list(order)
+    worst = 0.0
+    for i, r in enumerate(case.rows):
+        row, n = order[i], r.shape[0] // S
+        want = truth()[(case.name, i)][1]
+        assert len(want) == n
+        got = sums[row]
+        assert (got[n:].view(np.int64) == 0).all(), (case.name, i)  # +0.0 behind the steps, bit for bit
+        assert peak[row] == (np.abs(r).max() if r.size else 0.0), (case.name, i)
+        if n == 0:
+            continue
+        err = np.abs(got[:n].astype(np.longdouble) - want).astype(np.float64)
+        bound = lt.bound(case.fs, want.astype(np.float64))
+        assert (bound > 0).all()
+        ratio = err / bound
+        assert (ratio <= 1.0).all(), (case.name, i, float(ratio.max()))
+        worst = max(worst, float(ratio.max()))
+    named = set(order)
+    for row in range(sums.shape[0]):
+        if row not in named:  # an unnamed row is not touched
+            assert (sums[row] == SENTINEL).all() and peak[row] == PEAK_SENTINEL
+    return worst
+
+
+@needs_longdouble
+@pytest.mark.parametrize("name", ["lengths", "dc_70_steps", "two_workgroups", "rate_11025", "rate_44100", "rate_48000", "rate_384000", "channels_1",
+                                  "channels_2", "channels_6", "channels_8", "channels_3", "burst"])
+def test_step_sums_and_peak_against_the_longdouble_truth(ctx, name):
+    case = cases()[name]
+    n = len(case.rows)
+    order = [(2 * i + 1) % (n + 1) if n > 1 else 0 for i in range(n)]  # out of order, one row in between unnamed
+    if len(set(order)) != n:
+        order = list(range(n))[::-1]
+    sums, peak = launch(ctx, case, order=order)
+    worst = check_case(case, sums, peak, order)
+    print("%s: largest error / bound %.3g" % (name, worst))
+    if name == "channels_6":  # the LFE counts in the peak, not in the sums
+        assert case.w[-1] == 0.0 and all(np.abs(r[:, -1]).max() == np.abs(r).max() for r in case.rows)
+    if name == "burst":  # six silent steps behind the burst: the filter's tail, far below the burst's own steps, never negative
+        assert (sums[order[0]][:9] >= 0).all() and sums[order[0]][8] < 1e-6 * sums[order[0]][0]
+
+
+@needs_longdouble
+def test_a_carry_cut_after_one_term_would_miss_the_bound():
+    """the reason (b) is the exact sequential carry: with the step before as the only term -- s[j] = z[j-1], P dropped, a few parts in
+    1e8 of a large state -- the DC row's sums leave the bound.  On the restatement, in float64 (measured: 4.75 times the bound); the
+    device is held to the bound in test_step_sums_and_peak_against_the_longdouble_truth."""
+    case = cases()["dc_70_steps"]
+    fs, S = case.fs, lt.step_of(case.fs)
+    x = case.rows[0][:, 0].astype(np.float64)
+    c = lt.coefficients(fs)
+    n = len(x) // S
+    X = x[: n * S].reshape(n, S)
+    z = [np.zeros(n) for _ in range(4)]
+    for t in range(S):
+        lt._advance(c, X[:, t], z)
+    s = [np.concatenate([[0.0], z[k][:-1]]) for k in range(4)]
+    acc = np.zeros(n)
+    for t in range(S):
+        y = lt._advance(c, X[:, t], s)
+        acc += y * y
+    want = truth()[(case.name, 0)][1]
+    err = np.abs(acc.astype(np.longdouble) - want).astype(np.float64)
+    assert (err > lt.bound(fs, want.astype(np.float64))).any()
+    exact = lt.step_sums_chunked(x, fs)[:, 0]
+    assert (np.abs(exact.astype(np.longdouble) - want).astype(np.float64) <= 0.01 * lt.bound(fs, want.astype(np.float64))).all()
+
+
+@needs_longdouble
+def test_the_same_row_alone_and_among_others_is_the_same_bits(ctx):
+    base = cases()["channels_2"]
+    row = base.rows[0]
+    alone = Case("alone", 8000, 2, [row])
+    a_sums, a_peak = launch(ctx, alone, max_steps=9)
+    rng = np.random.default_rng(5)
+    others = [0.3 * noise(rng, int(L), 2) for L in rng.integers(0, 6 * 800, size=31)]
+    crowd = Case("crowd", 8000, 2, others[:17] + [row] + others[17:])
+    order = list(rng.permutation(32))
+    c_sums, c_peak = launch(ctx, crowd, order=order, gap=1, max_steps=9, first=1)
+    at = order[17]
+    assert a_sums[0].tobytes() == c_sums[at].tobytes() and a_peak[0].tobytes() == c_peak[at].tobytes()
+    # ... and another row length of the sums changes nothing in front
+    w_sums, _ = launch(ctx, alone, max_steps=300)
+    assert w_sums[0, :9].tobytes() == a_sums[0].tobytes() and (w_sums[0, 9:].view(np.int64) == 0).all()
+
+
+@needs_longdouble
+def test_the_integrated_value_against_the_truths(ctx):
+    """blocks of the truth all more than 0.01 LU from both gates (a condition on the input, asserted), then
+    |delta LUFS| <= 10 log10(1 + rho), rho the relative bound of the step sums"""
+    from vorbispizza_amd import capi
+    case = cases()["dc_70_steps"]
+    S = lt.step_of(case.fs)
+    sums, _ = launch(ctx, case)
+    want = truth()[(case.name, 1)][1].astype(np.float64)
+    lufs_t, kept_t, threshold, levels = lt.gate(want, S)
+    assert kept_t > 20 and (np.abs(levels + 70.0) > 0.01).all() and (np.abs(levels - threshold) > 0.01).all()
+    assert (levels <= threshold).any()  # (the quiet half is gated: the relative gate is at work)
+    lufs, kept = capi.loudness_gate(sums[1, :70], S)
+    print("integrated: %.6f LUFS on the device, %.6f in the truth, %d blocks" % (lufs, lufs_t, kept))
+    assert kept == kept_t and abs(lufs - lufs_t) <= 10.0 * np.log10(1.0 + lt.relative_bound(case.fs))
+
+
+def test_ebu_tech_3341_case_3_on_the_device(ctx):
+    import torch
+    from vorbispizza_amd import capi
+    fs = 48000
+    parts, target = lt.EBU_3341[3]
+    x = lt.sine(fs, parts)
+    src = torch.from_numpy(x.reshape(-1)).to("cuda:0")
+    sums, peak = capi.pcm_loudness(ctx, src, 2, fs, [(0, x.shape[0], 0)])
+    ctx.synchronize()
+    assert tuple(sums.shape) == (1, 800) and tuple(peak.shape) == (1,)
+    lufs, kept = capi.loudness_gate(sums[0].cpu().numpy(), lt.step_of(fs))
+    print("EBU Tech 3341 case 3 at 48 000 Hz on the device: %.4f LUFS, %d blocks" % (lufs, kept))
+    assert abs(lufs - target) <= 0.1
+    assert float(peak[0]) == float(np.abs(x).max())
+
+
+def test_every_refusal_launches_nothing(ctx):
+    import torch
+    from vorbispizza_amd import capi
+    L = capi.lib()
+    fs, ch, S = 8000, 2, 800
+    src = torch.full((5 * S * ch + 8,), 0.25, dtype=torch.float32, device="cuda:0")
+    sums = torch.full((4, 6), SENTINEL, dtype=torch.float64, device="cuda:0")
+    peak = torch.full((4,), PEAK_SENTINEL, dtype=torch.float32, device="cuda:0")
+    w = np.array([1.0, 1.0])
+    rows = np.array([(3, 5 * S, 2), (0, S - 1, 0)], dtype=np.int64)
+
+    def call(**kw):
+        a = dict(ctx=ctx._h, src=src.data_ptr(), src_elems=src.numel(), channels=ch, rate=fs, w=w, n_rows=len(rows), rows=rows, sums=sums.data_ptr(),
+                 peak=peak.data_ptr(), dst_rows=4, max_steps=6)
+        a.update(kw)
+        ww = None if a["w"] is None else np.ascontiguousarray(a["w"], dtype=np.float64)
+        rr = None if a["rows"] is None else np.ascontiguousarray(a["rows"], dtype=np.int64)
+        return L.vpz_pcm_loudness(a["ctx"], a["src"], a["src_elems"], a["channels"], a["rate"], None if ww is None else ww.ctypes.data, a["n_rows"],
+                                  None if rr is None else rr.ctypes.data, a["sums"], a["peak"], a["dst_rows"], a["max_steps"])
+
+    def row(k, **kw):
+        r = rows.copy()
+        for name, v in kw.items():
+            r[k, {"src": 0, "samples": 1, "row": 2}[name]] = v
+        return r
+
+    host = np.zeros(64, dtype=np.float64)
+    refused = [dict(ctx=None), dict(src=None), dict(sums=None), dict(peak=None), dict(w=None), dict(rows=None),
+               dict(channels=0), dict(channels=256), dict(rate=7999), dict(rate=384001), dict(max_steps=0), dict(max_steps=4), dict(n_rows=-1),
+               dict(dst_rows=-1), dict(dst_rows=2), dict(w=[1.0, -0.5]), dict(w=[np.nan, 1.0]), dict(w=[1.0, np.inf]),
+               dict(rows=row(0, src=-1)), dict(rows=row(0, src=9)), dict(rows=row(0, samples=-1)), dict(rows=row(0, samples=5 * S + 4)),
+               dict(rows=row(1, row=4)), dict(rows=row(1, row=-1)), dict(rows=row(1, row=2)),
+               dict(src=src.data_ptr() + 2), dict(sums=sums.data_ptr() + 4), dict(peak=peak.data_ptr() + 2),
+               dict(src_elems=src.numel() + (1 << 30)), dict(dst_rows=1 << 20, rows=rows), dict(src=host.ctypes.data, src_elems=64),
+               dict(sums=host.ctypes.data), dict(peak=host.ctypes.data)]
+    for change in refused:
+        assert call(**change) == capi.E_INVALID_ARG, change
+    ctx.synchronize()
+    assert (sums == SENTINEL).all() and (peak == PEAK_SENTINEL).all()
+    # ... and the call itself is good: five steps in row 2, none in row 0, rows 1 and 3 untouched
+    assert call() == capi.OK
+    ctx.synchronize()
+    got, pk = sums.cpu().numpy(), peak.cpu().numpy()
+    assert got[2, 0] > 0 and (got[2, :5] >= 0).all() and got[2, 5] == 0 and (got[0] == 0).all() and (got[[1, 3]] == SENTINEL).all()
+    assert list(pk) == [0.25, PEAK_SENTINEL, 0.25, PEAK_SENTINEL]
+    assert call(n_rows=0) == capi.OK  # (no descriptors: nothing to do, nothing refused)

@@ -11,6 +11,8 @@
     dispatcher_probe.py --logmel-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --fbank [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --fbank-kernel
+    dispatcher_probe.py --loudness [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --loudness-kernel
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -47,7 +49,12 @@ window, pre-emphasis 0.97, per-frame mean removal, scale 32768, natural log), a 
 loader does without the call -- decode_ranges_batch at RATE Hz, mono, then on the device the eight torch ops unfold, mean, pre-emphasis,
 window, pad, rfft, power, matmul (vpz_fbank_filterbank as a dense matrix) and log -- against decode_ranges_fbank; two dispatchers taking
 turns as above, the largest difference of the two tensors printed.  With VPZM_PROFILE=1 the library prints the fbank launch's own time.
---fbank-kernel: vpz_pcm_fbank alone, that spec, 64 windows of one second and of thirty, both layouts, the context's event timer."""
+--fbank-kernel: vpz_pcm_fbank alone, that spec, 64 windows of one second and of thirty, both layouts, the context's event timer.
+--loudness: the whole streams measured for programme loudness (BS.1770).  The A/B: what a scanner has to do first without the call --
+vpzm_decode_library of the whole streams into float32 page-locked memory, to which its host scan (two IIR filters and a gated mean over
+all of it) could only add -- against measure_loudness, which brings no PCM down; two dispatchers taking turns as above.  The records of
+the first two streams are printed.  With VPZM_PROFILE=1 the library prints the loudness launches' own time per sub-batch.
+--loudness-kernel: vpz_pcm_loudness alone, 64 stereo rows of one second and of 200 seconds at 44 100 Hz, the context's event timer."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -72,6 +79,8 @@ ap.add_argument("--logmel", action="store_true")
 ap.add_argument("--logmel-kernel", action="store_true")
 ap.add_argument("--fbank", action="store_true")
 ap.add_argument("--fbank-kernel", action="store_true")
+ap.add_argument("--loudness", action="store_true")
+ap.add_argument("--loudness-kernel", action="store_true")
 ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -502,6 +511,78 @@ def fbank_kernel_job():
     ctx.close()
 
 
+def loudness_job():
+    import time
+    n = len(datas)
+    pcm = torch.empty(int((caps * 2).sum()), dtype=torch.float32, pin_memory=True).numpy()
+    rec = [None]
+
+    def by_library(d):
+        t0 = time.perf_counter()
+        res, st = d.decode_library(datas, pcm, offs, caps, s16=False)
+        return time.perf_counter() - t0, res, st
+
+    def by_loudness(d):
+        t0 = time.perf_counter()
+        res, integrated, peak, steps, kept, st = d.measure_loudness(datas)
+        rec[0] = (integrated, peak, steps, kept)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d whole streams" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_library(ds[0]), lambda: by_loudness(ds[1])]
+        samples = []
+        for leg in legs:  # (one pass each that does not count: slots, decoders and device arrays are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all()
+            samples.append(res["samples"].copy())
+        assert np.array_equal(samples[0], samples[1]), "the samples measured are not the samples decoded"
+        integrated, peak, steps, kept = rec[0]
+        assert np.isfinite(integrated).all() and (integrated[2:] == integrated[pick[2:]]).all() and (peak[2:] == peak[pick[2:]]).all()
+        print("%s:\n    %.1f MB of float32 PCM stay on the device, %.1f kB of step sums and peaks come down; the two fixtures: %.2f LUFS (peak %.4f, %d steps, "
+              "%d blocks kept) and %.2f LUFS (peak %.4f, %d steps, %d blocks kept)" % (
+                  what, int(samples[1].sum()) * 2 * 4 / 1e6, (int(steps.sum()) * 8 + n * 4) / 1e3, integrated[0], peak[0], steps[0], kept[0], integrated[1],
+                  peak[1], steps[1], kept[1]), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_library into float32 host memory %s; measure_loudness %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def loudness_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, fs = 64, 44100
+    for samples in (44100, 200 * 44100):
+        src = (torch.rand(n * (samples + 3) * 2, device="cuda:0") * 2 - 1)
+        rows = [((k * (samples + 3) + 1) * 2, samples, k) for k in range(n)]
+        steps = samples // capi.loudness_step(fs)
+        out = (torch.empty((n, steps), dtype=torch.float64, device="cuda:0"), torch.empty((n,), dtype=torch.float32, device="cuda:0"))
+        times = []
+        for _ in range(11):
+            ctx.timer_start()
+            capi.pcm_loudness(ctx, src, 2, fs, rows, max_steps=steps, out=out)
+            times.append(ctx.timer_stop())
+        ms = statistics.median(times[1:])
+        read = 2.0 * n * samples * 2 * 4  # (the two passes read every sample once each)
+        print("vpz_pcm_loudness 64 stereo rows of %8d samples (%4d steps): median %.1f us (min %.1f, max %.1f); %.1f MB read twice = %.0f GB/s; %.1f kB out" % (
+            samples, steps, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, read / 2e6, read / ms / 1e6, (out[0].numel() * 8 + n * 4) / 1e3), flush=True)
+    ctx.close()
+
+
+if args.loudness_kernel:
+    loudness_kernel_job()
+    sys.exit(0)
+if args.loudness:
+    loudness_job()
+    sys.exit(0)
 if args.fbank_kernel:
     fbank_kernel_job()
     sys.exit(0)

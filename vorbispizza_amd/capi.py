@@ -193,6 +193,15 @@ _PCM_FBANK_SIGNATURES = [
     ("vpz_pcm_fbank", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(FbankSpec), C.c_int32, _vp, _vp, C.c_int64]),
 ]
 PCM_FBANK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_FBANK_SIGNATURES]
+LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
+# include/vorbispizza_pcm_loudness.h (a header of its own again)
+_PCM_LOUDNESS_SIGNATURES = [
+    ("vpz_loudness_filter", C.c_int, [C.c_int32, _vp]),
+    ("vpz_loudness_weights", C.c_int, [C.c_int32, _vp]),
+    ("vpz_pcm_loudness", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp, C.c_int64, C.c_int64]),
+    ("vpz_loudness_gate", C.c_int, [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+]
+PCM_LOUDNESS_EXPORTED_SYMBOLS = [s[0] for s in _PCM_LOUDNESS_SIGNATURES]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
 PCM_PACK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_PACK_SIGNATURES]
@@ -225,7 +234,8 @@ def lib():
             except ImportError:
                 pass
         L = C.CDLL(LIB_PATH)
-        later = _PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
+        later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
+                 + _PCM_LOUDNESS_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -454,6 +464,68 @@ def fbank_filterbank(spec):
     if rc != OK:
         raise ValueError("vpz_fbank_filterbank failed (status %d)" % rc)
     return first, count, weights
+
+
+def loudness_filter(sample_rate):
+    """vpz_loudness_filter: the K-weighting filter of a whole sample rate as float64 [2, 5] -- b0 b1 b2 a1 a2 of the shelf, then of the
+    high-pass (include/vorbispizza_pcm_loudness.h states them); needs no device.  A refused rate raises ValueError."""
+    coeffs = np.zeros((2, 5), dtype=np.float64)
+    rc = lib().vpz_loudness_filter(int(sample_rate), coeffs.ctypes.data)
+    if rc != OK:
+        raise ValueError("vpz_loudness_filter refuses the rate (status %d)" % rc)
+    return coeffs
+
+
+def loudness_step(sample_rate):
+    """the 100 ms step of the header in samples: S = (fs + 5) / 10 in integers"""
+    return (int(sample_rate) + 5) // 10
+
+
+def loudness_weights(channels):
+    """vpz_loudness_weights: BS.1770-4's channel weights in Vorbis channel order, float64 [channels]; needs no device."""
+    w = np.zeros(max(int(channels), 0), dtype=np.float64)
+    rc = lib().vpz_loudness_weights(int(channels), w.ctypes.data if w.size else None)
+    if rc != OK:
+        raise ValueError("vpz_loudness_weights refuses the channel count (status %d)" % rc)
+    return w
+
+
+def loudness_gate(sums, step_len):
+    """vpz_loudness_gate: (integrated LUFS, blocks kept) of the step sums of steps of `step_len` samples -- (-inf, 0) with fewer than
+    four steps or nothing kept; needs no device."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+    lufs, kept = C.c_double(0.0), C.c_int64(0)
+    rc = lib().vpz_loudness_gate(sums.ctypes.data if sums.size else None, sums.size, int(step_len), C.byref(lufs), C.byref(kept))
+    if rc != OK:
+        raise ValueError("vpz_loudness_gate refuses its arguments (status %d)" % rc)
+    return lufs.value, kept.value
+
+
+def pcm_loudness(ctx, src, channels, sample_rate, rows, weights=None, max_steps=None, out=None):
+    """vpz_pcm_loudness (vorbispizza_pcm_loudness.h): windows of the interleaved float32 device array `src` (a torch tensor) as
+    K-weighted step sums and sample peaks.  rows: [(src, samples, row)]; weights: per channel, loudness_weights(channels) by default;
+    max_steps: the row length of the sums, by default the rows' largest count of whole steps (at least 1).
+    -> (sums, peak): float64 [dst_rows, max_steps] and float32 [dst_rows] device tensors, dst_rows one more than the largest row named;
+    out: a caller's (sums, peak) instead, whose unnamed rows stay as they are.  Asynchronous on the context's stream
+    (ctx.synchronize()).  A refusal raises SynthError with nothing launched."""
+    import torch
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    w = np.ascontiguousarray(loudness_weights(channels) if weights is None else weights, dtype=np.float64)
+    if w.shape != (int(channels),):
+        raise ValueError("pcm_loudness: one weight per channel")
+    if max_steps is None:
+        max_steps = max([1] + [int(s) // loudness_step(sample_rate) for s in desc[:, 1]])
+    if out is None:
+        dst_rows = int(desc[:, 2].max()) + 1 if desc.shape[0] else 0
+        out = (torch.zeros((dst_rows, int(max_steps)), dtype=torch.float64, device=src.device),
+               torch.zeros((dst_rows,), dtype=torch.float32, device=src.device))
+    sums, peak = out
+    _sync_producer(src, sums, peak)
+    rc = lib().vpz_pcm_loudness(ctx._h, _ptr(src), _numel(src), int(channels), int(sample_rate), w.ctypes.data, desc.shape[0], desc.ctypes.data,
+                                _ptr(sums), _ptr(peak), int(peak.shape[0]), int(max_steps))
+    if rc != OK:
+        raise SynthError(rc, ctx.last_error() if hasattr(ctx, "last_error") else "vpz_pcm_loudness")
+    return sums, peak
 
 
 def make_packets(count):

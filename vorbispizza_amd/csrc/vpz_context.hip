@@ -295,6 +295,7 @@ void vpz_context_destroy(vpz_context *c)
     vpz::free_resample_tables(ctx);
     vpz::free_logmel_tables(ctx);
     vpz::free_fbank_tables(ctx);
+    vpz::free_loudness_scratch(ctx);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -82,6 +82,14 @@ struct Context {
     // preemphasis, scale) -- and of every mel bank, keyed by (sample_rate, n_fft, n_mels, low_freq, high_freq); the records are log-mel's
     std::map<std::vector<double>, LogmelDft> fbank_tables;
     std::map<std::vector<double>, LogmelBank> fbank_banks;
+    // vpz_pcm_loudness (pcm_loudness.hip): the constants of every rate -- the two biquads and the 4x4 transition of one step of silence,
+    // built on the host on first use (kernel arguments: no device copy) -- and the launch's scratch memory, grown on demand
+    struct LoudnessRate {
+        double coeffs[10], P[16];
+    };
+    std::map<int, LoudnessRate> loudness_rates;
+    void *loud_scratch = nullptr;
+    size_t loud_scratch_bytes = 0;
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
@@ -117,6 +125,7 @@ bool layout_of(int32_t layout, bool *s16, bool *planar);
 void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_destroy calls it)
 void free_logmel_tables(Context *ctx);  // (pcm_logmel.hip; vpz_context_destroy calls it)
 void free_fbank_tables(Context *ctx);  // (pcm_fbank.hip; vpz_context_destroy calls it)
+void free_loudness_scratch(Context *ctx);  // (pcm_loudness.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

@@ -39,11 +39,16 @@
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
 // vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
 //
+// vpzm_measure_loudness (include/vorbispizza_multi_loudness.h) is a batch call whose delivery measures instead of moving: one
+// vpz_pcm_loudness launch per sample rate among a sub-batch's members, into a temporary of the lane's; the step sums and peaks come down
+// in one small copy, and vpz_loudness_gate runs per member on the issuing thread.  Its "piece" is the group's part of the caller's records.
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstddef>
 #include <cstdio>
@@ -69,6 +74,8 @@
 #include "../../include/vorbispizza_multi_logmel.h"
 #include "../../include/vorbispizza_pcm_fbank.h"
 #include "../../include/vorbispizza_multi_fbank.h"
+#include "../../include/vorbispizza_pcm_loudness.h"
+#include "../../include/vorbispizza_multi_loudness.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -267,8 +274,10 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     // (kF0Amp, kF0Coeff: a batch call's host route uploads a type-0 floor's data beside residue, posts and counts)
     // (kMono: a log-mel call's resampled mono rows [members][frames], between the resample launches and the vpz_pcm_logmel launch that
     // reads them; the lane owns it, it only grows, and it goes with the lane when the dispatcher is destroyed)
-    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kBuffers };
-    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
+    // (kLoud: a loudness call's step sums [members][max_steps] float64 and, behind them, peaks [members] float32, between the
+    // vpz_pcm_loudness launches and the one copy that brings them down; owned like kMono)
+    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kLoud, kBuffers };
+    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
     float *residue() const { return static_cast<float *>(buf[kResidue].p); }  // (float32 or int16 values; the ABI's parameter is float-typed)
     int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
@@ -316,7 +325,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, or the feature launch of a log-mel or fbank call -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel or fbank call, or a loudness call's -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -368,8 +377,9 @@ struct Job {  // one stream of the library inside its group
 // vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
-    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank
-    enum Kind { kPack, kResampled, kLogmel, kFbank };
+    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or, into its
+    // record, vpz_pcm_loudness and the gate
+    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
@@ -378,9 +388,13 @@ struct Batch {
     const vpz_logmel_spec *mel = nullptr;
     // kFbank: the same with Kaldi filterbank frames of this spec (`dst` is [rows][T][n_mels] or transposed)
     const vpz_fbank_spec *fbank = nullptr;
+    // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
+    // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run
     void *dst = nullptr;  // (decode_call fills these two in)
     int64_t rows = 0;     // of the group's piece: its entries
-    bool resampled() const { return kind != kPack; }
+    bool resampled() const { return kind == kResampled || features(); }
+    bool measured() const { return kind == kLoudness; }
+    vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
     bool features() const { return kind == kLogmel || kind == kFbank; }  // a feature stage behind the resample launches, fed from the lane's temporary
     const char *feature_step() const { return kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `dst`
@@ -518,7 +532,8 @@ struct GroupRun {
                 if (J.wanted > INT64_MAX / 2048 || resampled_length(J.wanted, J.up, J.down) > batch.frames) { J.status = VPZM_E_CAPACITY; return; }
             } else {
                 if (J.wanted > capacity_of(J.k)) { J.status = VPZM_E_CAPACITY; return; }
-                if (batched() && info.channels != batch.channels) { J.status = VPZM_E_CHANNELS; return; }
+                if (batched() && !batch.measured() && info.channels != batch.channels) { J.status = VPZM_E_CHANNELS; return; }
+                if (batch.measured() && (info.sample_rate < VPZ_LOUDNESS_MIN_RATE || info.sample_rate > VPZ_LOUDNESS_MAX_RATE)) { J.status = VPZM_E_RATE; return; }
             }
             if (J.packets > 0) {
                 J.own = std::make_shared<Setup>();
@@ -884,6 +899,7 @@ struct GroupRun {
             std::vector<vpz_pack_row> rows;
             for (const Job &J : jobs)
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
+            if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0].ctx, rows) == VPZ_OK;
             if (!ok) m->fail(std::string(batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
@@ -1279,7 +1295,9 @@ struct SubCall {
             rows.push_back(vpz_pack_row{written[j] > 0 ? offs[j] + J.roll * C : 0, written[j], (int64_t)(J.k - R.lo)});
         }
         int rc = VPZ_OK;
-        if (!staged) {
+        if (B.measured()) {
+            rc = measure_rows(rows, staged);
+        } else if (!staged) {
             rc = launched(B.features() ? B.feature_step() : "vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP : B.empty_rows(L.ctx, rows));
         } else if (B.kind == Batch::kPack) {
             rc = launched("vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP
@@ -1307,6 +1325,74 @@ struct SubCall {
     {
         if (rc != VPZ_OK) R.m->fail(std::string(step) + ": " + vpz_context_last_error(L.ctx));
         return rc;
+    }
+
+    // A loudness call: the members that have samples grouped by sample rate (a sub-batch has one channel count), one vpz_pcm_loudness
+    // launch per rate on the lane's stream into the lane's temporary -- member j in row j, `max_steps` the sub-batch's largest --, one
+    // copy of the temporary down and one synchronise, then the gate per member on this thread.  A member without samples keeps the empty
+    // record and needs no launch.  A record is written once everything has succeeded: a failed sub-batch's stay empty
+    int measure_rows(std::vector<vpz_pack_row> &rows, bool staged)
+    {
+        const size_t M = rows.size();
+        std::vector<int32_t> rate(M, 0), step(M, 1);
+        int64_t max_steps = 1;
+        bool any_samples = false;
+        for (size_t j = 0; j < M; ++j) {
+            rate[j] = R.results[job(j).k].sample_rate;
+            step[j] = (rate[j] + 5) / 10;  // (the header's S)
+            if (rows[j].samples <= 0) continue;
+            any_samples = true;
+            max_steps = std::max(max_steps, rows[j].samples / step[j]);
+            rows[j].row = (int64_t)j;
+        }
+        if (R.sw.fail_delivery) return launched("vpz_pcm_loudness", VPZ_E_HIP);
+        if (!staged || !any_samples) return VPZ_OK;
+        const size_t sums_bytes = M * (size_t)max_steps * sizeof(double), bytes = sums_bytes + M * sizeof(float);
+        if (!L.buf[Lane::kLoud].grow(L.ctx, bytes, 1)) {
+            R.m->fail("vpzm_measure_loudness: the step sums' device temporary could not be allocated");
+            return VPZ_E_NOMEM;
+        }
+        double *sums_dev = static_cast<double *>(L.buf[Lane::kLoud].p);
+        float *peak_dev = reinterpret_cast<float *>(static_cast<char *>(L.buf[Lane::kLoud].p) + sums_bytes);
+        std::vector<double> w((size_t)C);
+        (void)vpz_loudness_weights(C, w.data());
+        if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launches' own time)
+        const auto t_loud = Clock::now();
+        int rc = VPZ_OK, launches = 0;
+        std::vector<char> taken(M, 0);
+        std::vector<vpz_pack_row> group;
+        for (size_t i = 0; i < M && rc == VPZ_OK; ++i) {
+            if (taken[i] || rows[i].samples <= 0) continue;
+            group.clear();
+            for (size_t j = i; j < M; ++j)
+                if (!taken[j] && rows[j].samples > 0 && rate[j] == rate[i]) {
+                    taken[j] = 1;
+                    group.push_back(rows[j]);
+                }
+            rc = launched("vpz_pcm_loudness", vpz_pcm_loudness(L.ctx, L.pcm(), pcm_elems, C, rate[i], w.data(), (int32_t)group.size(), group.data(), sums_dev,
+                                                               peak_dev, (int64_t)M, max_steps));
+            ++launches;
+        }
+        if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu loudness kernels %.3f ms (%d launches, %zu rows, %lld steps at most)\n", R.slot_index, b,
+                    seconds_since(t_loud) * 1e3, launches, M, (long long)max_steps);
+        std::vector<char> down(bytes);
+        if (rc == VPZ_OK) rc = launched("vpz_pcm_download", vpz_pcm_download(L.ctx, down.data(), L.buf[Lane::kLoud].p, (uint64_t)bytes));
+        rc = vpz_context_synchronize(L.ctx) == VPZ_OK ? rc : rc == VPZ_OK ? VPZ_E_HIP : rc;  // (the copy has landed; the launches before a failed one have left the lane's array)
+        if (rc != VPZ_OK) return rc;
+        for (size_t j = 0; j < M; ++j) {
+            if (rows[j].samples <= 0) continue;
+            const int64_t steps = rows[j].samples / step[j];
+            float peak_j = 0.0f;
+            vpzm_loudness rec{-HUGE_VAL, 0.0, steps, 0};
+            std::vector<double> sums((size_t)steps);
+            if (steps > 0) memcpy(sums.data(), down.data() + j * (size_t)max_steps * sizeof(double), (size_t)steps * sizeof(double));
+            memcpy(&peak_j, down.data() + sums_bytes + j * sizeof(float), sizeof peak_j);
+            rec.peak = (double)peak_j;
+            (void)vpz_loudness_gate(sums.data(), steps, step[j], &rec.integrated, &rec.blocks_kept);
+            B.record((int64_t)(job(j).k - R.lo)) = rec;
+        }
+        return VPZ_OK;
     }
 
     // a log-mel or fbank call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
@@ -1663,6 +1749,30 @@ int vpzm_decode_ranges_fbank(vpzm_dispatcher *m, int32_t n, const uint8_t *const
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
     const Batch batch{Batch::kFbank, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, nullptr, spec};
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_measure_loudness(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                          vpzm_loudness *out, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!m || n < 0 || (n > 0 && !out)) return VPZM_E_ARG;
+    // (no tensor and no row length: `frames` caps nothing; the synth calls write float32, interleaved; every group's piece is its part of
+    // the caller's records, which hold the empty record from here on -- a group without entries needs none)
+    static vpzm_loudness nobody{};
+    std::vector<vpzm_range> whole;
+    std::vector<void *> pieces;
+    try {
+        if (!ranges) whole.assign((size_t)n, vpzm_range{0, -1});
+        for (int g = 0; g < (int)m->groups.size(); ++g) {
+            int32_t lo, hi;
+            partition(n, g, (int)m->groups.size(), &lo, &hi);
+            pieces.push_back(hi > lo ? (void *)(out + lo) : (void *)&nobody);
+        }
+    } catch (const std::bad_alloc &) {
+        return VPZM_E_NOMEM;
+    }
+    for (int32_t k = 0; k < n; ++k) out[k] = vpzm_loudness{-HUGE_VAL, 0.0, 0, 0};
+    const Batch batch{Batch::kLoudness, 0, VPZ_OUT_INTERLEAVED, INT64_MAX};
+    return ranges_call(m, n, data, size, ranges ? ranges : whole.data(), 0, nullptr, nullptr, nullptr, results, stats, &batch, pieces.data());
 }
 
 int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)

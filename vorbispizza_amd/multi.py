@@ -50,6 +50,8 @@ BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  #
 RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
+LOUDNESS_EXPORTED_SYMBOLS = ["vpzm_measure_loudness"]  # (vorbispizza_multi_loudness.h)
+LOUDNESS_DTYPE = np.dtype([("integrated", "<f8"), ("peak", "<f8"), ("steps", "<i8"), ("blocks_kept", "<i8")])  # vpzm_loudness
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
@@ -92,6 +94,9 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges_fbank"):
             L.vpzm_decode_ranges_fbank.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_fbank.restype = C.c_int
+        if hasattr(L, "vpzm_measure_loudness"):
+            L.vpzm_measure_loudness.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+            L.vpzm_measure_loudness.restype = C.c_int
         _bound = True
     return L
 
@@ -319,3 +324,19 @@ class Dispatcher:
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_fbank failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats
+
+    def measure_loudness(self, datas, ranges=None):
+        """vpzm_measure_loudness: every entry's window (ranges None: the whole stream) measured for programme loudness on the device
+        (ITU-R BS.1770-4; include/vorbispizza_pcm_loudness.h states the definition), at the stream's own rate and channel count -- no
+        PCM comes down.  Returns (results, integrated, peak, steps, blocks_kept, stats): numpy arrays with an entry per stream --
+        float64 LUFS (-inf with fewer than four steps or nothing kept), float64 sample peak, int64 whole 100 ms steps, int64 blocks
+        behind the value; results["samples"] counts the samples measured.  An entry that delivered nothing has (-inf, 0, 0, 0)."""
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        out = np.zeros(n, dtype=LOUDNESS_DTYPE)
+        rc = lib().vpzm_measure_loudness(self._h, n, ptrs, sizes, None if rng is None else rng.ctypes.data, out.ctypes.data if n else None,
+                                         results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_measure_loudness failed (status %d): %s" % (rc, self.last_error()))
+        return (results, out["integrated"].copy(), out["peak"].copy(), out["steps"].copy(), out["blocks_kept"].copy(), stats)

@@ -42,7 +42,8 @@
  * subtracted from the sample (one float32 rounding) before the multiply-add:
  *     mu = ((s_0 + s_1) + (s_2 + s_3)) / win,   s_q = x[q] + x[q+4] + x[q+8] + ..., m ascending,
  * every addition and the division rounded to float32.  With remove_dc = 0, mu = 0 and nothing is subtracted.  A frame's bits depend on
- * its own win samples and the spec alone.
+ * its own win samples and the spec alone.  A sample that is not finite (+-Inf, NaN) makes exactly the frames that cover it not finite
+ * (Inf or NaN), in every band that has a bin; every other frame, and every other row, is the same bits as without it.
  * Limits.  n_fft even, 32 <= n_fft <= 1024 (no power of two needed); 2 <= win <= n_fft (odd lengths allowed); 1 <= hop <= win;
  * 1 <= n_mels <= 256; L <= F; preemphasis in [0, 1]; scale finite and not 0 as float32; pad_value finite as float32; reserved words zero.
  * NOT PART OF IT: dither, VTLN, use_energy / raw_energy, subtract_mean across frames, htk_compat, and magnitude instead of power.

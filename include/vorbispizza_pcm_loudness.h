@@ -20,6 +20,9 @@
  * samples behind the last whole step are filtered but not summed.
  *     sum[j] = sum_c w[c] * sum_{i in step j} y_c[i]^2,   j = 0 .. n-1,   divided by nothing.
  * Peak.  The largest |x| over all L samples of all channels, whatever their weight: the sample peak, exact, 0 for an empty window.
+ * Samples that are not finite.  A +-Inf or NaN sample makes sum[j] not finite (Inf or NaN) from the step it lies in to the window's
+ * last, also where its channel's weight is 0 (0 x NaN is NaN); the steps before it, and every other row, are the same bits as without
+ * it.  The peak is +Inf for an infinite sample; a NaN is passed over, and the peak is the largest |x| of the window's other samples.
  * Gate (vpz_loudness_gate).  Block k is steps k .. k+3, k = 0 .. n-4 (400 ms, 75 % overlap): p_k = (the sum of its four) / (4 S),
  * l_k = -0.691 + 10 log10 p_k.  The blocks with l_k > -70 pass the absolute gate; of those, the ones with l_k above
  * -0.691 + 10 log10(mean p of those) - 10 are kept; the integrated loudness is -0.691 + 10 log10(mean p of the kept), in LUFS.

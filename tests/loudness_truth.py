@@ -174,6 +174,37 @@ def relative_bound(fs):
     return 64.0 * 2.0 ** -53 * (1.0 / (1.0 - r) ** 2 + S)
 
 
+# ---- the launch plan of vpz_pcm_loudness, restated
+def kernel_constants(root):
+    """kLoudBlock, kChunk, kLoudMaxGridY as csrc/pcm_loudness.hip states them"""
+    import os
+    import re
+    text = open(os.path.join(root, "vorbispizza_amd", "csrc", "pcm_loudness.hip")).read()
+    out = {}
+    for name in ("kLoudBlock", "kChunk", "kLoudMaxGridY"):
+        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
+        assert len(found) == 1, name
+        out[name] = int(found[0])
+    return out
+
+
+def launch_plan(channels, k):
+    """(G, stride, lds_bytes) of passes (a) and (c): G = kLoudBlock / channels steps to a workgroup, lane = step * channels + channel;
+    a step's chunk of kChunk * channels floats lies at a pitch of `stride` floats in LDS, the least one >= kChunk * channels that is
+    `channels` modulo 32"""
+    G = k["kLoudBlock"] // channels
+    stride = k["kChunk"] * channels
+    stride += (channels - stride) % 32
+    return G, stride, G * stride * 4
+
+
+def tiles_of(samples, fs, channels, k):
+    """(units, steps, workgroups of (a) that hold a unit, of (c) that hold a step, samples behind the last whole step) of one row"""
+    S, G = step_of(fs), launch_plan(channels, k)[0]
+    units, steps = -(-samples // S), samples // S
+    return units, steps, -(-units // G), -(-steps // G), samples - steps * S
+
+
 def sine(fs, seconds_and_dbfs, hz=1000.0, channels=2):
     """float32 [samples, channels]: a sine of `hz` whose per-channel peak level follows [(seconds, dBFS), ...], phase running through"""
     total = sum(int(round(sec * fs)) for sec, _ in seconds_and_dbfs)

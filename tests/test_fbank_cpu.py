@@ -377,3 +377,56 @@ def test_a_tile_fits_and_no_index_leaves_the_span_at_any_spec():
         [16, 32, 32, 32, 64, 32, 64]
     # and where the LDS decides: n_fft = win = 1024
     assert [ft.tile_plan(1024, hop, 1024, 104, 600, 256, k)[0] for hop in (1, 111, 112, 755, 756, 1024)] == [64, 64, 32, 32, 16, 16]
+
+
+# ---- the cases of tests/test_pcm_fbank_limits_gpu.py
+def test_every_limit_case_is_the_shape_it_is_named_for(capi):
+    """each case of fbank_cases.py against the numbers written down there: the k loop's whole blocks, leftover pairs and odd sample, the
+    skew, the bin groups and the waves' rounds, and tile and LDS floats through tile_plan"""
+    import fbank_cases as fc
+    k = ft.kernel_constants(ROOT)
+    assert [v[0] for v in fc.SMALL.values()] == [(2, 2, 32, 1), (3, 2, 32, 2), (3, 3, 32, 2), (4, 2, 32, 3), (5, 2, 34, 3), (7, 6, 36, 4), (8, 2, 32, 3),
+                                                  (9, 8, 32, 3), (33, 32, 64, 5), (33, 2, 64, 5), (63, 62, 64, 8), (64, 64, 64, 8)]
+    for name, ((win, hop, n_fft, n_mels), chain, skew, rounds) in fc.SMALL.items():
+        change, F = fc.small(name)
+        T = ft.n_frames(F, win, hop)
+        assert T == 71 and T % 16 != 0 and (F - win) % hop != 0, name
+        assert fc.chain_of(win, k) == chain and (hop % 2 == 0) == bool(skew) and fc.rounds_of(n_fft, k) == rounds, name
+        tile, floats = fc.tile_of(change, F, 5, fc.CROWD_CUS, k)
+        assert tile == 32 and floats <= k["kFbLdsFloats"], name
+        capi.FbankSpec.make(**ft.spec_of(**change))
+    assert {v[0][1] for v in fc.SMALL.values()} >= {2, 3, 6} and all((w - 1, w) in [(v[0][1], v[0][0]) for v in fc.SMALL.values()] for w in (3, 7, 9, 33, 63))
+    # a mean lane with no term at win 3; one term each at win 4; a fifth sample to lane 0 at win 5
+    assert [len(range(3, w, 4)) for w in (3, 4, 5)] == [0, 1, 1] and len(range(0, 5, 4)) == 2
+    assert [v[0][2] // 2 for v in fc.GROUPS.values()] == [32, 33, 64, 65, 128, 129]
+    for name, ((win, hop, n_fft, n_mels), rounds) in fc.GROUPS.items():
+        change, F = fc.group(name)
+        assert win in (n_fft - 1, n_fft) and fc.rounds_of(n_fft, k) == rounds and -(-(n_fft // 2) // k["kFbCols"]) == sum(rounds), name
+        assert ft.n_frames(F, win, hop) == 71 and (F - win) % hop != 0 and fc.tile_of(change, F, 5, fc.CROWD_CUS, k)[0] == 32, name
+    change, F = fc.group(fc.CROWDED_GROUP)
+    assert fc.tile_of(change, F, fc.crowd_rows(fc.CROWD_CUS), fc.CROWD_CUS, k)[0] == 64 and fc.GROUPS[fc.CROWDED_GROUP][1][0] == 2
+    # the LDS limits at n_fft 1024
+    assert list(fc.LDS_LIMITS) == [(944, 113), (1024, 111), (1024, 112), (1012, 757), (1024, 755), (1024, 756)]
+    for (win, hop), (T, tile, floats, tile_few) in fc.LDS_LIMITS.items():
+        change, F = fc.lds_limit(win, hop)
+        assert ft.n_frames(F, win, hop) == T and T % 16 != 0 and (F - win) % hop != 0
+        for cus in (64, 256, 304):
+            assert fc.tile_of(change, F, fc.crowd_rows(cus), cus, k) == (tile, floats), (win, hop, cus)
+        assert fc.tile_of(change, F, 5, fc.CROWD_CUS, k)[0] == tile_few
+        assert floats <= k["kFbLdsFloats"]
+    assert [v[2] for v in fc.LDS_LIMITS.values()].count(k["kFbLdsFloats"]) == 2  # (the budget exactly, at 64 and at 32 frames)
+    # one frame more of hop, or one sample more of win, and the tile no longer fits
+    assert ft.lds_plan(944, 113, 1024, 64)[0] + 64 + 64 * 513 == 40960 and ft.lds_plan(1012, 757, 1024, 32)[0] + 64 + 32 * 513 == 40960
+    assert ft.tile_plan(945, 113, 1024, 40, 600, 256, k)[0] == 32 and ft.tile_plan(1013, 757, 1024, 40, 600, 256, k)[0] == 16
+    # most of 256 bands have no bin at n_fft 32
+    first, count, _ = capi.fbank_filterbank(capi.FbankSpec.make(**ft.spec_of(**fc.EMPTY_BANDS)))
+    assert (count == 0).sum() > 200 and (count > 0).sum() >= 8
+    # the second round: four waves at work, one 16-frame tile a row; the long row: more than a thousand tiles
+    d = ft.spec_of(**fc.SECOND_ROUND)
+    assert fc.rounds_of(d["n_fft"], k) == (1, 1, 1, 1) and ft.tile_plan(200, 80, 256, 3, 2100, fc.CROWD_CUS, k)[0] == 16
+    for n in (2100, 4200):
+        Ls = fc.second_round_lengths(n, 397, 200, np.random.default_rng(3))
+        assert n > k["kFbMaxGridY"] and (Ls[0], Ls[2048]) == ((397, 0) if n == 2100 else (397, 199)) and (Ls == 0).any() and (Ls < 200).sum() > 100
+    change, F = fc.LONG_ROW
+    tile, _ = fc.tile_of(change, F, 1, fc.CROWD_CUS, k)
+    assert tile == 64 and -(-ft.n_frames(F, 2, 1) // tile) > 1000  # (so many tiles of one row are a crowd by themselves)

@@ -253,3 +253,123 @@ def test_both_libraries_export_the_new_symbols(capi):
     sig = inspect.signature(capi.pcm_loudness)
     assert list(sig.parameters)[:7] == ["ctx", "src", "channels", "sample_rate", "rows", "weights", "max_steps"]
     assert callable(capi.loudness_filter) and callable(capi.loudness_weights) and callable(capi.loudness_gate) and callable(multi.Dispatcher.measure_loudness)
+
+
+# ---- the launch plan of vpz_pcm_loudness, and the cases of tests/test_pcm_loudness_limits_gpu.py
+def test_the_launch_plan_at_every_channel_count():
+    """G, the LDS pitch and its bytes as csrc/pcm_loudness.hip computes them, at 1..255 channels; and the comment's bank claim: lane
+    (s, c) reads lds[s * stride + t * C + c], and the live lanes of every aligned group of 32 fall on 32 different banks at every t"""
+    k = lt.kernel_constants(ROOT)
+    assert (k["kLoudBlock"], k["kChunk"], k["kLoudMaxGridY"]) == (256, 32, 4096)
+    most = {}
+    for channels in range(1, 256):
+        G, stride, lds_bytes = lt.launch_plan(channels, k)
+        assert stride >= 32 * channels and stride - 32 * channels < 32 and stride % 32 == channels % 32 and G >= 1, channels
+        assert G == 256 // channels and lds_bytes == 4 * G * stride <= 34 * 1024, channels
+        most[channels] = lds_bytes
+        lane = np.arange(256)
+        s, c = lane // channels, lane % channels
+        for t in (0, 1, 31):
+            bank = (s * stride + t * channels + c) % 32
+            for first in range(0, 256, 32):
+                live = bank[first: first + 32][s[first: first + 32] < G]
+                assert len(set(live.tolist())) == len(live), (channels, t, first)
+    assert max(most.values()) == most[16] == 33792
+    assert lt.launch_plan(32, k)[1] == 32 * 32 and lt.launch_plan(33, k)[1] == 32 * 33 + 1  # (no padding; one float of it)
+    assert lt.launch_plan(129, k)[0] == 1 and lt.launch_plan(128, k)[0] == 2
+
+
+def test_every_limit_case_is_the_shape_it_is_named_for():
+    """Case's constructor has held every channel of every row to a crest factor of 4 (building the list is that check); here each case's
+    G, idle lanes, step modulo 32 and, row by row, units, steps, the workgroups of (a) and (c) and the tail, against the numbers
+    loudness_cases.EXPECT writes down"""
+    import loudness_cases as lc
+    k = lt.kernel_constants(ROOT)
+    cases = lc.cases()
+    assert set(lc.EXPECT) | {"grid", "grid_checked", "crowd"} == set(cases)
+    assert {"channels_%d" % c for c in lc.CHANNEL_COUNTS} <= set(lc.EXPECT) and lc.CHANNEL_COUNTS == (4, 5, 7, 9, 31, 32, 33, 64, 85, 86, 128, 129, 255)
+    for name, (G, idle, s32, rows) in lc.EXPECT.items():
+        case = cases[name]
+        assert lt.launch_plan(case.channels, k)[0] == G and 256 - G * case.channels == idle and lt.step_of(case.fs) % 32 == s32, name
+        assert [lt.tiles_of(r.shape[0], case.fs, case.channels, k) for r in case.rows] == rows, name
+        if case.weights is None and case.channels > 8:
+            assert (case.w == 1.0).all()
+    # the lengths the cases are named for
+    S = lc.S
+    assert [r.shape[0] for r in cases["edges_8"].rows] == [32 * S, 32 * S + 1, 31 * S + 799, 33 * S, 64 * S + 31]
+    assert [r.shape[0] for r in cases["edges_3"].rows] == [85 * S, 85 * S + 1, 86 * S]
+    assert lt.step_of(11025) == 1103 and lt.step_of(44100) == 4410
+    for name in ("tails_1", "tails_6"):
+        a, b = cases[name].rows[:2]
+        assert a[-1].min() == -np.abs(a).max() and (np.abs(a[:-1]) < np.abs(a).max()).all()  # negative, the last sample of the tail
+        assert np.abs(b[0]).max() == np.abs(b).max() and (np.abs(b[1:]) < np.abs(b).max()).all()  # the first sample
+    heavy = cases["channels_255_weights"]
+    assert heavy.w[lc.PEAK_CHANNEL] == 0.0 and (np.delete(heavy.w, lc.PEAK_CHANNEL) > 0).all()
+    assert all(np.abs(r[:, lc.PEAK_CHANNEL]).max() == np.abs(r).max() for r in heavy.rows)
+    # the weight table's entries that had never run: 1.41 without an LFE, and 7's own LFE place
+    assert list(cases["channels_4"].w) == [1, 1, 1.41, 1.41] and list(cases["channels_5"].w) == [1, 1, 1, 1.41, 1.41]
+    assert list(cases["channels_7"].w) == [1, 1, 1, 1.41, 1.41, 1, 0]
+    # two grid rounds: more descriptors than the grid's y holds, lengths of every kind, checked rows in the second round
+    grid, checked = cases["grid"], lc.grid_checked_rows()
+    lengths = np.array([r.shape[0] for r in grid.rows])
+    assert len(grid.rows) == lc.GRID_ROWS > k["kLoudMaxGridY"] and lengths.max() == 2 * S + 5 and lengths.min() == 0
+    assert sum(i >= k["kLoudMaxGridY"] for i in checked) > 100 and len(cases["grid_checked"].rows) == len(checked)
+    assert (lengths < S).sum() > 1000 and (lengths >= 2 * S).sum() > 10
+    assert all(r.shape[0] == 0 for r in cases["empty_rows"].rows) and all(0 < r.shape[0] < S for r in cases["short_rows"].rows)
+    # finish_blocks: one block at max_steps 256, two at 257
+    assert [-(-m // k["kLoudBlock"]) for m in (256, 257)] == [1, 2]
+
+
+def test_the_float64_restatement_meets_the_bound_with_room_on_the_limit_cases():
+    """before any device run: step_sums_chunked -- float64, the shape of the kernels -- lies within 0.01 of the bound of the longdouble
+    truth on a multi-workgroup case and on the 255-channel case, so a device result outside the bound is the device's doing"""
+    import loudness_cases as lc
+    from test_pcm_loudness_gpu import LONGDOUBLE_BITS
+    assert LONGDOUBLE_BITS >= 63, "numpy.longdouble has %d mantissa bits here: float64 would be compared against itself" % LONGDOUBLE_BITS
+    some = [lc.cases()[n] for n in ("edges_8", "channels_255_weights")]
+    truth = lc.truth_of(some)
+    for case in some:
+        for i, r in enumerate(case.rows):
+            per, want = truth[(case.name, i)]
+            got = lt.weighted(lt.step_sums_chunked(r, case.fs), case.w)
+            assert got.shape == want.shape and len(want) == r.shape[0] // lc.S
+            bound = lt.bound(case.fs, want.astype(np.float64))
+            ratio = np.abs(got.astype(np.longdouble) - want).astype(np.float64) / bound
+            print("%s row %d: float64 by steps, largest error / bound %.3g" % (case.name, i, ratio.max()))
+            assert (ratio <= 0.01).all(), (case.name, i, float(ratio.max()))
+
+
+def test_the_shift_and_scaling_identities_hold_on_the_restatements():
+    """k steps of silence in front of a row move its sums by k places and change no bit (zero state stays zero state); a power of two
+    on the samples is its square on the sums, bit for bit (every operation a float64 multiply or add, nothing near underflow)"""
+    import loudness_cases as lc
+    base = lc.cases()["shift"]
+    for k in (1, 3, 32):
+        a, b = lc.shifted(base, k).rows
+        sa, sb = lt.step_sums_chunked(a, base.fs), lt.step_sums_chunked(b, base.fs)
+        assert sb.shape[0] == sa.shape[0] + k and (sb[:k].view(np.int64) == 0).all() and sb[k:].tobytes() == sa.tobytes(), k
+        if k < 32:
+            seq = lt.step_sums_sequential([a[:, 0], b[:, 0]], [base.fs] * 2, np.float64)
+            assert (seq[1][:k].view(np.int64) == 0).all() and seq[1][k:].tobytes() == seq[0].tobytes(), k
+    base = lc.cases()["scaling"]
+    want = lt.weighted(lt.step_sums_chunked(base.rows[0], base.fs), base.w)
+    for e in (-12, 12, -60, 60):
+        row = lc.scaled(base, e).rows[0] if abs(e) == 12 else np.ldexp(base.rows[0].astype(np.float64), e)
+        got = lt.weighted(lt.step_sums_chunked(row, base.fs), base.w)
+        assert got.tobytes() == np.ldexp(want, 2 * e).tobytes(), e
+    assert (lc.scaled(base, -12).rows[0].astype(np.float64) == np.ldexp(base.rows[0].astype(np.float64), -12)).all()  # (exact in float32)
+
+
+def test_the_loudness_kernels_use_no_scratch_and_say_what_they_take():
+    import shutil
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources as kr
+    from vorbispizza_amd import _build
+    assert shutil.which(_build._hipcc()) or os.path.exists(_build._hipcc()), "the check needs hipcc: a tool, not hardware -- nothing to skip for"
+    ks = [k for k in kr.analyse(os.path.join(_build.CSRC, "pcm_loudness.hip"), _build.SOURCES["pcm_loudness.hip"]) if "loudness_" in k["name"]]
+    assert len(ks) == 4 and sum("loudness_pass" in k["name"] for k in ks) == 2  # (a) and (c), the carry, the finish
+    assert sum("loudness_carry" in k["name"] for k in ks) == 1 and sum("loudness_finish" in k["name"] for k in ks) == 1
+    for k in ks:
+        print(k)
+        assert k["scratch"] == 0 and k.get("vgpr_spill", 0) == 0 and k.get("sgpr_spill", 0) == 0, k
+        assert k["vgprs"] + k.get("agprs", 0) <= 512 and k["occupancy"] >= 1, k

@@ -136,7 +136,11 @@ typedef struct vpz_floor0_config {        /* Floor0.cs:29-35 (LSP floor, "virtua
 } vpz_floor0_config;
 
 typedef struct vpz_mapping_config {       /* Mapping.cs:11-15 */
-    int32_t coupling_steps;
+    int32_t coupling_steps;               /* 0..VPZ_MAX_COUPLING (Mapping.cs reads 8 bits + 1); magnitude != angle, both < channels.
+                                             Every count decodes.  The fused routes have table limits of their own -- 128 step pairs
+                                             over all mappings, each list padded to four, at most 255 steps in one mapping; the pair
+                                             route 128 steps over its pairs -- and a setup beyond them takes the separate coupling
+                                             pass, with the same samples */
     uint8_t coupling_magnitude[VPZ_MAX_COUPLING];
     uint8_t coupling_angle[VPZ_MAX_COUPLING];
     uint8_t channel_floor[VPZ_MAX_CHANNELS + 1]; /* _submapFloor[_mux[ch]] per channel */
@@ -158,7 +162,7 @@ typedef struct vpz_stream_config {
     int32_t block_size0, block_size1;     /* BlockSizes.Size0 / Size1 */
     int32_t floor_count;
     const vpz_floor1_config *floors;
-    int32_t mapping_count;
+    int32_t mapping_count;                /* 0..256: vpz_packet.mapping is 8 bits (a Vorbis setup header holds at most 64) */
     const vpz_mapping_config *mappings;
     int32_t clip_samples;                 /* StreamDecoder.ClipSamples (StreamDecoder.cs:993) */
     /* floor types: NULL = every floor is type 1.  Otherwise floor_types[i] in {0, 1} for each of the

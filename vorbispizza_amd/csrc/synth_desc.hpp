@@ -34,6 +34,13 @@ constexpr int kGroupMaxChannels = 8;         // channels that fit one workgroup 
 constexpr int kFloor0Marker = 255;           // active-post count of a record whose floor is type 0 and is applied by the fused kernel
 constexpr int kFloor0MaxBark = 1024;         // bark_map_size the fused route takes (the curve sits in a wave's LDS row)
 constexpr int kGroupMaxStepPairs = 128;      // coupling steps (pairs) of all mappings staged in LDS
+constexpr int kStepsPadPairs = 4;            // a mapping's list starts on a multiple of this many pairs: the kernels read four steps at once
+// A frame names its mapping's first step with kFrameStepsOffMask's bits, right below the skip field: every place in a table the
+// kernels stage has to fit them.  A decoder whose table is longer takes neither group mode nor the stereo kernel and its frames
+// carry no such bits (vpz_decoder_create: refused, not masked -- a masked offset names another mapping's steps).
+static_assert(kGroupMaxStepPairs - 1 <= (int)kFrameStepsOffMask, "a step's place in the staged table fits the frame's offset bits");
+static_assert(kFrameStepsOffShift + 8 == kFrameSkipShift && kFrameStepsOffMask == 0xFFu, "the offset bits end where the skip field begins");
+static_assert(kGroupMaxStepPairs % kStepsPadPairs == 0, "the padded lists fill the staged table exactly");
 
 struct FrameDesc {        // 32 bytes: staged per run into LDS by the wavefront that owns the run
     int64_t spec_off;     // float offset of channel 0's spectrum; channel c at + c*(blocksize/2)

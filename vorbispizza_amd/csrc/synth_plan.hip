@@ -119,7 +119,7 @@ inline uint32_t frame_flags(const Decoder &D, const vpz_packet &pk, const Packet
     if (D.group_ok || D.dual_ok) {
         const int steps = no_floor ? 0 : D.mappings[pk.mapping].coupling_steps;
         if (pk.flags & VPZ_PKT_INTERLEAVED) f |= kFrameInterleaved;
-        if (steps > 0)
+        if (steps > 0 && D.wide_steps)  // (the pair route alone -- dual_ok on its own table's limits -- puts its own bits in)
             f |= ((uint32_t)steps << kFrameStepsShift) |
                  ((uint32_t)(D.mapping_steps_off[pk.mapping] / 2) << kFrameStepsOffShift);
     }

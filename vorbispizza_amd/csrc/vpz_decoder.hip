@@ -224,7 +224,7 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
     for (size_t m = 0; m < D.mappings.size() && rc == VPZ_OK; ++m) {
         const vpz_mapping_config &mc = D.mappings[m];
         if (mc.coupling_steps < 0 || mc.coupling_steps > VPZ_MAX_COUPLING) { rc = VPZ_E_INVALID_ARG; break; }
-        while (mc.coupling_steps && steps.size() % 8) steps.push_back(0);  // (group mode reads 8 bytes of steps at once)
+        while (mc.coupling_steps && steps.size() % (2 * kStepsPadPairs)) steps.push_back(0);  // (group mode reads 8 bytes of steps at once)
         D.mapping_steps_off.push_back(mc.coupling_steps ? (int32_t)steps.size() : -1);
         for (int i = 0; i < mc.coupling_steps; ++i) {
             const int mag = mc.coupling_magnitude[i], ang = mc.coupling_angle[i];
@@ -291,6 +291,18 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
         D.f0_k = (D.f0_k + 255) & ~255;  // (rows of whole 256-value rounds: floor0_curve_kernel stores a round without asking)
         D.dual_ok = synth_dual_supported(D.channels, D.size0, D.size1) && !D.generic && (!has_floor0 || D.f0_fused) && D.max_steps <= 255 &&
                     D.n_step_pairs <= kGroupMaxStepPairs && !(no_dual && atoi(no_dual));
+        // The frames of group mode and of the stereo kernel carry their mapping's step count and first pair (frame_flags: 8 bits
+        // each, the skip field right above).  Both follow from the limits above; a table that does not fit is refused here, never
+        // masked: a masked offset names another mapping's steps, an unmasked one runs into the skip field.
+        bool steps_fit = true;
+        for (size_t m = 0; m < D.mapping_steps_off.size(); ++m)
+            if (D.mappings[m].coupling_steps > 0 &&
+                (D.mappings[m].coupling_steps > 255 || D.mapping_steps_off[m] / 2 > (int)kFrameStepsOffMask))
+                steps_fit = false;
+        D.group_ok = D.group_ok && steps_fit;
+        D.dual_ok = D.dual_ok && steps_fit;
+        // (the pair route below sets dual_ok on the limits of ITS table: such a decoder's frames get no bits of the decoder-wide one)
+        D.wide_steps = D.group_ok || D.dual_ok;
         D.f0_fused = D.f0_fused && D.dual_ok;
         D.max_steps = max_levels;  // from here on: the barriers a frame's coupling needs in group mode
         const char *nc = getenv("VPZ_NO_COMPACT");
@@ -304,7 +316,7 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
     D.mapping_uses_floor0.assign(D.mappings.size(), 0);
     for (size_t m = 0; m < D.mappings.size(); ++m) {
         const int n = D.mappings[m].coupling_steps;
-        if ((D.group_ok || D.dual_ok) && n > 0)
+        if (D.wide_steps && n > 0)
             map_bits[m] = ((uint32_t)n << kFrameStepsShift) |
                           ((uint32_t)(D.mapping_steps_off[m] / 2) << kFrameStepsOffShift);
         map_bits[m] |= ((uint32_t)D.mapping_skip[1][m] << kFrameSkipShift) | ((uint32_t)D.mapping_skip[0][m] << kMapSkipShortShift);

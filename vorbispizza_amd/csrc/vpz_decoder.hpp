@@ -106,6 +106,9 @@ struct Decoder {
     // ... and its kernel for channel PAIRS (synth_pairs.hip): 4, 6, 8, ... channels that the coupling steps of all mappings join two
     // by two -- every pair is a stereo stream to the arithmetic (VPZ_NO_PAIRS=1: off, for A/B and bit-equality tests)
     bool pairs = false;          // (implies dual_ok)
+    // group mode and the stereo kernel find a frame's steps in the decoder-wide table (count and first pair in the frame's flags);
+    // the pair route has a table of its own (d_pair_steps) and may run where the decoder-wide one is too long for those bits
+    bool wide_steps = false;
     bool pairs_always = false;   // VPZ_PAIRS=1: the pair route wherever it can run, also where group mode is as fast or faster
     uint8_t *d_pair_ch = nullptr;         // [pair][2]: the pair's channels, coupled ones first ("channel 0" of its steps), in channel order
     uint32_t *d_pair_map_bits = nullptr;  // [pair][mapping]: SynthArgs.map_bits of the pair route

@@ -13,6 +13,8 @@
     dispatcher_probe.py --fbank-kernel
     dispatcher_probe.py --loudness [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --loudness-kernel
+    dispatcher_probe.py --r128 [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --r128-kernel
 
 --gpu-entropy: the dispatchers are created with vpzm_options.gpu_entropy (eligible streams entropy-decoded on the device).
 --mixed: ... and with mixed_setups (vpzm_set_mixed_setups: streams of different setups share device-decoded sub-batches).
@@ -54,7 +56,13 @@ turns as above, the largest difference of the two tensors printed.  With VPZM_PR
 vpzm_decode_library of the whole streams into float32 page-locked memory, to which its host scan (two IIR filters and a gated mean over
 all of it) could only add -- against measure_loudness, which brings no PCM down; two dispatchers taking turns as above.  The records of
 the first two streams are printed.  With VPZM_PROFILE=1 the library prints the loudness launches' own time per sub-batch.
---loudness-kernel: vpz_pcm_loudness alone, 64 stereo rows of one second and of 200 seconds at 44 100 Hz, the context's event timer."""
+--loudness-kernel: vpz_pcm_loudness alone, 64 stereo rows of one second and of 200 seconds at 44 100 Hz, the context's event timer.
+--r128: the whole streams measured for everything an EBU R 128 scanner reports (measure_r128: the integrated loudness, the range, the
+maxima, the true peak).  Three dispatchers taking turns: decode_library into float32 page-locked memory, measure_loudness and
+measure_r128 -- the cost of the added numbers, and what a host scanner must do first.  The records of the first two streams are
+printed.  With VPZM_PROFILE=1 the library prints the loudness and the true-peak launches' own time per sub-batch.
+--r128-kernel: vpz_pcm_true_peak alone and vpz_pcm_loudness beside it, the same rows as --loudness-kernel, the context's event timer:
+the median of 5 with its extremes, GB/s against 8 TB/s and multiply-adds per second against the float32 vector peak (157.3 TFLOP/s)."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -81,6 +89,8 @@ ap.add_argument("--fbank", action="store_true")
 ap.add_argument("--fbank-kernel", action="store_true")
 ap.add_argument("--loudness", action="store_true")
 ap.add_argument("--loudness-kernel", action="store_true")
+ap.add_argument("--r128", action="store_true")
+ap.add_argument("--r128-kernel", action="store_true")
 ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -577,6 +587,98 @@ def loudness_kernel_job():
     ctx.close()
 
 
+def r128_job():
+    import time
+    n = len(datas)
+    pcm = torch.empty(int((caps * 2).sum()), dtype=torch.float32, pin_memory=True).numpy()
+    rec = [None, None]
+
+    def by_library(d):
+        t0 = time.perf_counter()
+        res, st = d.decode_library(datas, pcm, offs, caps, s16=False)
+        return time.perf_counter() - t0, res, st
+
+    def by_loudness(d):
+        t0 = time.perf_counter()
+        res, integrated, peak, steps, kept, st = d.measure_loudness(datas)
+        rec[0] = (integrated, peak, steps, kept)
+        return time.perf_counter() - t0, res, st
+
+    def by_r128(d):
+        t0 = time.perf_counter()
+        res, rec[1], st = d.measure_r128(datas)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d whole streams" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(3)]
+        legs = [lambda: by_library(ds[0]), lambda: by_loudness(ds[1]), lambda: by_r128(ds[2])]
+        samples = []
+        for leg in legs:  # (one pass each that does not count: slots, decoders and device arrays are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all()
+            samples.append(res["samples"].copy())
+        assert np.array_equal(samples[0], samples[1]) and np.array_equal(samples[0], samples[2]), "the samples measured are not the samples decoded"
+        (integrated, peak, steps, kept), r = rec
+        assert integrated.tobytes() == r["integrated"].tobytes() and peak.tobytes() == r["sample_peak"].tobytes(), "measure_r128 is not measure_loudness's bits"
+        assert np.array_equal(steps, r["steps"]) and np.array_equal(kept, r["blocks_kept"]) and (r["true_peak"] >= r["sample_peak"]).all()
+        assert r[2:].tobytes() == r[pick[2:]].tobytes()
+        print("%s:\n    %.1f MB of float32 PCM stay on the device, %.1f kB of step sums and peaks come down" % (
+            what, int(samples[2].sum()) * 2 * 4 / 1e6, (int(r["steps"].sum()) * 8 + n * 8) / 1e3), flush=True)
+        for k in (0, 1):
+            print("    fixture %d: %.2f LUFS, range %.2f LU (%.2f .. %.2f, %d blocks), momentary max %.2f, short-term max %.2f, true peak %.4f (%.2f dBTP), "
+                  "sample peak %.4f" % (k, r["integrated"][k], r["range"][k], r["range_low"][k], r["range_high"][k], r["range_blocks"][k], r["momentary_max"][k],
+                                        r["short_term_max"][k], r["true_peak"][k], 20 * np.log10(r["true_peak"][k]), r["sample_peak"][k]), flush=True)
+        for run in (1, 2):
+            walls = [[], [], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_library into float32 host memory %s; measure_loudness %s; measure_r128 %s" % (
+                run, describe(walls[0]), describe(walls[1]), describe(walls[2])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def r128_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, fs = 64, 44100
+    for samples in (44100, 200 * 44100):
+        src = (torch.rand(n * (samples + 3) * 2, device="cuda:0") * 2 - 1)
+        rows = [((k * (samples + 3) + 1) * 2, samples, k) for k in range(n)]
+        steps = samples // capi.loudness_step(fs)
+        loud = (torch.empty((n, steps), dtype=torch.float64, device="cuda:0"), torch.empty((n,), dtype=torch.float32, device="cuda:0"))
+        peaks = (torch.empty((n,), dtype=torch.float32, device="cuda:0"), torch.empty((n,), dtype=torch.float32, device="cuda:0"))
+        calls = {"vpz_pcm_true_peak": lambda: capi.pcm_true_peak(ctx, src, 2, fs, rows, out=peaks),
+                 "vpz_pcm_loudness": lambda: capi.pcm_loudness(ctx, src, 2, fs, rows, max_steps=steps, out=loud)}
+        times = {name: [] for name in calls}
+        for _ in range(6):  # (the first of each does not count; the two take turns)
+            for name, call in calls.items():
+                ctx.timer_start()
+                call()
+                times[name].append(ctx.timer_stop())
+        read = n * samples * 2 * 4.0
+        fma = n * (samples + 11) * 2 * 36.0
+        ms = statistics.median(times["vpz_pcm_true_peak"][1:])
+        print("vpz_pcm_true_peak 64 stereo rows of %8d samples: median of 5 %.1f us (min %.1f, max %.1f); %.1f MB read once = %.0f GB/s (%.1f %% of 8 TB/s); "
+              "%.2f G multiply-adds = %.2f T/s (%.1f %% of the float32 vector peak)" % (
+                  samples, ms * 1e3, min(times["vpz_pcm_true_peak"][1:]) * 1e3, max(times["vpz_pcm_true_peak"][1:]) * 1e3, read / 1e6, read / ms / 1e6,
+                  read / ms / 1e6 / 8000 * 100, fma / 1e9, fma / ms / 1e9, 2 * fma / ms / 1e9 / 157.3 * 100), flush=True)
+        ms = statistics.median(times["vpz_pcm_loudness"][1:])
+        print("vpz_pcm_loudness  64 stereo rows of %8d samples: median of 5 %.1f us (min %.1f, max %.1f); %.1f MB read twice = %.0f GB/s" % (
+            samples, ms * 1e3, min(times["vpz_pcm_loudness"][1:]) * 1e3, max(times["vpz_pcm_loudness"][1:]) * 1e3, read / 1e6, 2 * read / ms / 1e6), flush=True)
+    ctx.close()
+
+
+if args.r128_kernel:
+    r128_kernel_job()
+    sys.exit(0)
+if args.r128:
+    r128_job()
+    sys.exit(0)
 if args.loudness_kernel:
     loudness_kernel_job()
     sys.exit(0)

@@ -202,6 +202,15 @@ _PCM_LOUDNESS_SIGNATURES = [
     ("vpz_loudness_gate", C.c_int, [_vp, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
 ]
 PCM_LOUDNESS_EXPORTED_SYMBOLS = [s[0] for s in _PCM_LOUDNESS_SIGNATURES]
+TRUE_PEAK_TAPS, TRUE_PEAK_MAX_COEFFS = 12, 49
+# include/vorbispizza_pcm_r128.h (a header of its own again)
+_PCM_R128_SIGNATURES = [
+    ("vpz_true_peak_filter", C.c_int, [C.c_int32, _vp, _vp]),
+    ("vpz_pcm_true_peak", C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, C.c_int64]),
+    ("vpz_loudness_range", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp]),
+    ("vpz_loudness_maxima", C.c_int, [_vp, C.c_int64, C.c_int32, _vp, _vp]),
+]
+PCM_R128_EXPORTED_SYMBOLS = [s[0] for s in _PCM_R128_SIGNATURES]
 EXPORTED_SYMBOLS = [s[0] for s in _SIGNATURES]
 PCM_EXPORTED_SYMBOLS = [s[0] for s in _PCM_SIGNATURES]
 PCM_PACK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_PACK_SIGNATURES]
@@ -235,7 +244,7 @@ def lib():
                 pass
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
-                 + _PCM_LOUDNESS_SIGNATURES)
+                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -526,6 +535,61 @@ def pcm_loudness(ctx, src, channels, sample_rate, rows, weights=None, max_steps=
     if rc != OK:
         raise SynthError(rc, ctx.last_error() if hasattr(ctx, "last_error") else "vpz_pcm_loudness")
     return sums, peak
+
+
+def true_peak_filter(sample_rate):
+    """vpz_true_peak_filter: (F, h) -- the oversampling factor of a whole sample rate and its interpolator as float64 [12 F + 1]
+    (include/vorbispizza_pcm_r128.h states both); needs no device.  A refused rate raises ValueError."""
+    h = np.zeros(TRUE_PEAK_MAX_COEFFS, dtype=np.float64)
+    factor = C.c_int32(0)
+    rc = lib().vpz_true_peak_filter(int(sample_rate), C.addressof(factor), h.ctypes.data)
+    if rc != OK:
+        raise ValueError("vpz_true_peak_filter refuses the rate (status %d)" % rc)
+    assert not h[TRUE_PEAK_TAPS * factor.value + 1:].any()
+    return factor.value, h[: TRUE_PEAK_TAPS * factor.value + 1].copy()
+
+
+def loudness_range(sums, step_len):
+    """vpz_loudness_range: (range in LU, low LUFS, high LUFS, 3 s blocks kept) of the step sums of steps of `step_len` samples --
+    (0, -inf, -inf, 0) with fewer than thirty steps or nothing kept; needs no device."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+    rng, low, high, kept = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0), C.c_int64(0)
+    rc = lib().vpz_loudness_range(sums.ctypes.data if sums.size else None, sums.size, int(step_len), C.addressof(rng), C.addressof(low), C.addressof(high),
+                                  C.addressof(kept))
+    if rc != OK:
+        raise ValueError("vpz_loudness_range refuses its arguments (status %d)" % rc)
+    return rng.value, low.value, high.value, kept.value
+
+
+def loudness_maxima(sums, step_len):
+    """vpz_loudness_maxima: (maximum momentary, maximum short-term loudness) in LUFS of the step sums -- -inf where there is no block or
+    no finite level; needs no device."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1)
+    momentary, short_term = C.c_double(0.0), C.c_double(0.0)
+    rc = lib().vpz_loudness_maxima(sums.ctypes.data if sums.size else None, sums.size, int(step_len), C.addressof(momentary), C.addressof(short_term))
+    if rc != OK:
+        raise ValueError("vpz_loudness_maxima refuses its arguments (status %d)" % rc)
+    return momentary.value, short_term.value
+
+
+def pcm_true_peak(ctx, src, channels, sample_rate, rows, out=None):
+    """vpz_pcm_true_peak (vorbispizza_pcm_r128.h): the true peak and the sample peak of windows of the interleaved float32 device array
+    `src` (a torch tensor).  rows: [(src, samples, row)].
+    -> (true_peak, sample_peak): float32 [dst_rows] device tensors, dst_rows one more than the largest row named; out: a caller's
+    (true_peak, sample_peak) instead -- sample_peak may be None --, whose unnamed rows stay as they are.  Asynchronous on the context's
+    stream (ctx.synchronize()).  A refusal raises SynthError with nothing launched."""
+    import torch
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    if out is None:
+        dst_rows = int(desc[:, 2].max()) + 1 if desc.shape[0] else 0
+        out = (torch.zeros((dst_rows,), dtype=torch.float32, device=src.device), torch.zeros((dst_rows,), dtype=torch.float32, device=src.device))
+    true_peak, sample_peak = out
+    _sync_producer(*[t for t in (src, true_peak, sample_peak) if t is not None])
+    rc = lib().vpz_pcm_true_peak(ctx._h, _ptr(src), _numel(src), int(channels), int(sample_rate), desc.shape[0], desc.ctypes.data, _ptr(true_peak),
+                                 None if sample_peak is None else _ptr(sample_peak), int(true_peak.shape[0]))
+    if rc != OK:
+        raise SynthError(rc, ctx.last_error() if hasattr(ctx, "last_error") else "vpz_pcm_true_peak")
+    return true_peak, sample_peak
 
 
 def make_packets(count):

@@ -296,6 +296,7 @@ void vpz_context_destroy(vpz_context *c)
     vpz::free_logmel_tables(ctx);
     vpz::free_fbank_tables(ctx);
     vpz::free_loudness_scratch(ctx);
+    vpz::free_true_peak_scratch(ctx);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);

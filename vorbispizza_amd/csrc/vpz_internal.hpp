@@ -90,6 +90,9 @@ struct Context {
     std::map<int, LoudnessRate> loudness_rates;
     void *loud_scratch = nullptr;
     size_t loud_scratch_bytes = 0;
+    // vpz_pcm_true_peak (pcm_truepeak.hip): the launch's scratch memory -- one pair of maxima per tile --, grown on demand
+    void *tp_scratch = nullptr;
+    size_t tp_scratch_bytes = 0;
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
@@ -126,6 +129,7 @@ void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_dest
 void free_logmel_tables(Context *ctx);  // (pcm_logmel.hip; vpz_context_destroy calls it)
 void free_fbank_tables(Context *ctx);  // (pcm_fbank.hip; vpz_context_destroy calls it)
 void free_loudness_scratch(Context *ctx);  // (pcm_loudness.hip; vpz_context_destroy calls it)
+void free_true_peak_scratch(Context *ctx);  // (pcm_truepeak.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

@@ -42,6 +42,8 @@
 // vpzm_measure_loudness (include/vorbispizza_multi_loudness.h) is a batch call whose delivery measures instead of moving: one
 // vpz_pcm_loudness launch per sample rate among a sub-batch's members, into a temporary of the lane's; the step sums and peaks come down
 // in one small copy, and vpz_loudness_gate runs per member on the issuing thread.  Its "piece" is the group's part of the caller's records.
+// vpzm_measure_r128 (include/vorbispizza_multi_r128.h) is that call with one vpz_pcm_true_peak launch per rate beside the loudness one --
+// the true peaks ride in the same copy -- and vpz_loudness_range and vpz_loudness_maxima beside the gate.
 //
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
@@ -60,6 +62,7 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/vorbispizza_multi.h"
@@ -76,6 +79,8 @@
 #include "../../include/vorbispizza_multi_fbank.h"
 #include "../../include/vorbispizza_pcm_loudness.h"
 #include "../../include/vorbispizza_multi_loudness.h"
+#include "../../include/vorbispizza_pcm_r128.h"
+#include "../../include/vorbispizza_multi_r128.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -275,7 +280,8 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     // (kMono: a log-mel call's resampled mono rows [members][frames], between the resample launches and the vpz_pcm_logmel launch that
     // reads them; the lane owns it, it only grows, and it goes with the lane when the dispatcher is destroyed)
     // (kLoud: a loudness call's step sums [members][max_steps] float64 and, behind them, peaks [members] float32, between the
-    // vpz_pcm_loudness launches and the one copy that brings them down; owned like kMono)
+    // vpz_pcm_loudness launches and the one copy that brings them down; an R 128 call's true peaks [members] float32 lie behind the peaks;
+    // owned like kMono)
     enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kLoud, kBuffers };
     Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
@@ -378,8 +384,8 @@ struct Job {  // one stream of the library inside its group
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
     // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or, into its
-    // record, vpz_pcm_loudness and the gate
-    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness };
+    // record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
+    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128 };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
@@ -389,12 +395,13 @@ struct Batch {
     // kFbank: the same with Kaldi filterbank frames of this spec (`dst` is [rows][T][n_mels] or transposed)
     const vpz_fbank_spec *fbank = nullptr;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
-    // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run
+    // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
     int64_t rows = 0;     // of the group's piece: its entries
     bool resampled() const { return kind == kResampled || features(); }
-    bool measured() const { return kind == kLoudness; }
+    bool measured() const { return kind == kLoudness || kind == kR128; }
     vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
+    vpzm_r128 &record_r128(int64_t row) const { return static_cast<vpzm_r128 *>(dst)[row]; }
     bool features() const { return kind == kLogmel || kind == kFbank; }  // a feature stage behind the resample launches, fed from the lane's temporary
     const char *feature_step() const { return kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `dst`
@@ -1330,7 +1337,9 @@ struct SubCall {
     // A loudness call: the members that have samples grouped by sample rate (a sub-batch has one channel count), one vpz_pcm_loudness
     // launch per rate on the lane's stream into the lane's temporary -- member j in row j, `max_steps` the sub-batch's largest --, one
     // copy of the temporary down and one synchronise, then the gate per member on this thread.  A member without samples keeps the empty
-    // record and needs no launch.  A record is written once everything has succeeded: a failed sub-batch's stay empty
+    // record and needs no launch.  A record is written once everything has succeeded: a failed sub-batch's stay empty.
+    // An R 128 call makes one vpz_pcm_true_peak launch per rate behind the loudness launches, over the same descriptors; the true peaks
+    // [members] float32 lie behind the peaks in the temporary and come down in the same copy; range and maxima run beside the gate
     int measure_rows(std::vector<vpz_pack_row> &rows, bool staged)
     {
         const size_t M = rows.size();
@@ -1347,13 +1356,15 @@ struct SubCall {
         }
         if (R.sw.fail_delivery) return launched("vpz_pcm_loudness", VPZ_E_HIP);
         if (!staged || !any_samples) return VPZ_OK;
-        const size_t sums_bytes = M * (size_t)max_steps * sizeof(double), bytes = sums_bytes + M * sizeof(float);
+        const bool r128 = B.kind == Batch::kR128;
+        const size_t sums_bytes = M * (size_t)max_steps * sizeof(double), bytes = sums_bytes + (r128 ? 2 : 1) * M * sizeof(float);
         if (!L.buf[Lane::kLoud].grow(L.ctx, bytes, 1)) {
             R.m->fail("vpzm_measure_loudness: the step sums' device temporary could not be allocated");
             return VPZ_E_NOMEM;
         }
         double *sums_dev = static_cast<double *>(L.buf[Lane::kLoud].p);
         float *peak_dev = reinterpret_cast<float *>(static_cast<char *>(L.buf[Lane::kLoud].p) + sums_bytes);
+        float *true_peak_dev = peak_dev + M;  // (kR128)
         std::vector<double> w((size_t)C);
         (void)vpz_loudness_weights(C, w.data());
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launches' own time)
@@ -1361,14 +1372,18 @@ struct SubCall {
         int rc = VPZ_OK, launches = 0;
         std::vector<char> taken(M, 0);
         std::vector<vpz_pack_row> group;
-        for (size_t i = 0; i < M && rc == VPZ_OK; ++i) {
-            if (taken[i] || rows[i].samples <= 0) continue;
+        // the members of row i's rate that no launch of this round has taken
+        auto same_rate = [&](size_t i) {
             group.clear();
             for (size_t j = i; j < M; ++j)
                 if (!taken[j] && rows[j].samples > 0 && rate[j] == rate[i]) {
                     taken[j] = 1;
                     group.push_back(rows[j]);
                 }
+        };
+        for (size_t i = 0; i < M && rc == VPZ_OK; ++i) {
+            if (taken[i] || rows[i].samples <= 0) continue;
+            same_rate(i);
             rc = launched("vpz_pcm_loudness", vpz_pcm_loudness(L.ctx, L.pcm(), pcm_elems, C, rate[i], w.data(), (int32_t)group.size(), group.data(), sums_dev,
                                                                peak_dev, (int64_t)M, max_steps));
             ++launches;
@@ -1376,10 +1391,26 @@ struct SubCall {
         if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
             fprintf(stderr, "[vpzm] group %d: sub-batch %zu loudness kernels %.3f ms (%d launches, %zu rows, %lld steps at most)\n", R.slot_index, b,
                     seconds_since(t_loud) * 1e3, launches, M, (long long)max_steps);
+        if (r128) {
+            const auto t_peak = Clock::now();
+            taken.assign(M, 0);
+            launches = 0;
+            for (size_t i = 0; i < M && rc == VPZ_OK; ++i) {
+                if (taken[i] || rows[i].samples <= 0) continue;
+                same_rate(i);
+                rc = launched("vpz_pcm_true_peak", vpz_pcm_true_peak(L.ctx, L.pcm(), pcm_elems, C, rate[i], (int32_t)group.size(), group.data(), true_peak_dev,
+                                                                     nullptr, (int64_t)M));
+                ++launches;
+            }
+            if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
+                fprintf(stderr, "[vpzm] group %d: sub-batch %zu true-peak kernels %.3f ms (%d launches, %zu rows)\n", R.slot_index, b, seconds_since(t_peak) * 1e3,
+                        launches, M);
+        }
         std::vector<char> down(bytes);
         if (rc == VPZ_OK) rc = launched("vpz_pcm_download", vpz_pcm_download(L.ctx, down.data(), L.buf[Lane::kLoud].p, (uint64_t)bytes));
         rc = vpz_context_synchronize(L.ctx) == VPZ_OK ? rc : rc == VPZ_OK ? VPZ_E_HIP : rc;  // (the copy has landed; the launches before a failed one have left the lane's array)
         if (rc != VPZ_OK) return rc;
+        std::vector<std::pair<int64_t, vpzm_r128>> full_records;  // (kR128: written once every member's are there)
         for (size_t j = 0; j < M; ++j) {
             if (rows[j].samples <= 0) continue;
             const int64_t steps = rows[j].samples / step[j];
@@ -1390,8 +1421,22 @@ struct SubCall {
             memcpy(&peak_j, down.data() + sums_bytes + j * sizeof(float), sizeof peak_j);
             rec.peak = (double)peak_j;
             (void)vpz_loudness_gate(sums.data(), steps, step[j], &rec.integrated, &rec.blocks_kept);
+            if (r128) {
+                float true_peak_j = 0.0f;
+                memcpy(&true_peak_j, down.data() + sums_bytes + (M + j) * sizeof(float), sizeof true_peak_j);
+                vpzm_r128 full{rec.integrated, 0.0, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, (double)true_peak_j, rec.peak, steps, rec.blocks_kept, 0};
+                // (the range sorts in memory of its own: out of it, the sub-batch fails with no record written)
+                if (vpz_loudness_range(sums.data(), steps, step[j], &full.range, &full.range_low, &full.range_high, &full.range_blocks) != VPZ_OK) {
+                    R.m->fail("vpzm_measure_r128: vpz_loudness_range is out of host memory");
+                    return VPZ_E_NOMEM;
+                }
+                (void)vpz_loudness_maxima(sums.data(), steps, step[j], &full.momentary_max, &full.short_term_max);
+                full_records.emplace_back((int64_t)(job(j).k - R.lo), full);
+                continue;
+            }
             B.record((int64_t)(job(j).k - R.lo)) = rec;
         }
+        for (const auto &fr : full_records) B.record_r128(fr.first) = fr.second;
         return VPZ_OK;
     }
 
@@ -1772,6 +1817,29 @@ int vpzm_measure_loudness(vpzm_dispatcher *m, int32_t n, const uint8_t *const *d
     }
     for (int32_t k = 0; k < n; ++k) out[k] = vpzm_loudness{-HUGE_VAL, 0.0, 0, 0};
     const Batch batch{Batch::kLoudness, 0, VPZ_OUT_INTERLEAVED, INT64_MAX};
+    return ranges_call(m, n, data, size, ranges ? ranges : whole.data(), 0, nullptr, nullptr, nullptr, results, stats, &batch, pieces.data());
+}
+
+int vpzm_measure_r128(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges, vpzm_r128 *out,
+                      vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!m || n < 0 || (n > 0 && !out)) return VPZM_E_ARG;
+    // (vpzm_measure_loudness with records of the other type)
+    static vpzm_r128 nobody{};
+    std::vector<vpzm_range> whole;
+    std::vector<void *> pieces;
+    try {
+        if (!ranges) whole.assign((size_t)n, vpzm_range{0, -1});
+        for (int g = 0; g < (int)m->groups.size(); ++g) {
+            int32_t lo, hi;
+            partition(n, g, (int)m->groups.size(), &lo, &hi);
+            pieces.push_back(hi > lo ? (void *)(out + lo) : (void *)&nobody);
+        }
+    } catch (const std::bad_alloc &) {
+        return VPZM_E_NOMEM;
+    }
+    for (int32_t k = 0; k < n; ++k) out[k] = vpzm_r128{-HUGE_VAL, 0.0, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, 0.0, 0.0, 0, 0, 0};
+    const Batch batch{Batch::kR128, 0, VPZ_OUT_INTERLEAVED, INT64_MAX};
     return ranges_call(m, n, data, size, ranges ? ranges : whole.data(), 0, nullptr, nullptr, nullptr, results, stats, &batch, pieces.data());
 }
 

@@ -52,6 +52,10 @@ LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_lo
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
 LOUDNESS_EXPORTED_SYMBOLS = ["vpzm_measure_loudness"]  # (vorbispizza_multi_loudness.h)
 LOUDNESS_DTYPE = np.dtype([("integrated", "<f8"), ("peak", "<f8"), ("steps", "<i8"), ("blocks_kept", "<i8")])  # vpzm_loudness
+R128_EXPORTED_SYMBOLS = ["vpzm_measure_r128"]  # (vorbispizza_multi_r128.h)
+R128_DTYPE = np.dtype([("integrated", "<f8"), ("range", "<f8"), ("range_low", "<f8"), ("range_high", "<f8"), ("momentary_max", "<f8"),
+                       ("short_term_max", "<f8"), ("true_peak", "<f8"), ("sample_peak", "<f8"), ("steps", "<i8"), ("blocks_kept", "<i8"),
+                       ("range_blocks", "<i8")])  # vpzm_r128
 RANGE_DTYPE = np.dtype([("start", "<i8"), ("count", "<i8")])  # vpzm_range
 _bound = False
 
@@ -97,6 +101,9 @@ def lib():
         if hasattr(L, "vpzm_measure_loudness"):
             L.vpzm_measure_loudness.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
             L.vpzm_measure_loudness.restype = C.c_int
+        if hasattr(L, "vpzm_measure_r128"):
+            L.vpzm_measure_r128.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+            L.vpzm_measure_r128.restype = C.c_int
         _bound = True
     return L
 
@@ -340,3 +347,21 @@ class Dispatcher:
         if rc != OK:
             raise MultiError("vpzm_measure_loudness failed (status %d): %s" % (rc, self.last_error()))
         return (results, out["integrated"].copy(), out["peak"].copy(), out["steps"].copy(), out["blocks_kept"].copy(), stats)
+
+    def measure_r128(self, datas, ranges=None):
+        """vpzm_measure_r128: every entry's window (ranges None: the whole stream) measured for what an EBU R 128 scanner reports, on the
+        device (include/vorbispizza_pcm_r128.h and vorbispizza_pcm_loudness.h state the definitions), at the stream's own rate and
+        channel count -- no PCM comes down.  Returns (results, records, stats): records is a numpy array of R128_DTYPE with an entry per
+        stream -- integrated LUFS, loudness range in LU with its two percentile levels, maximum momentary and short-term loudness, true
+        peak and sample peak (float32 values), whole 100 ms steps, and the blocks behind the integrated value and the range;
+        results["samples"] counts the samples measured.  integrated, sample_peak, steps and blocks_kept are measure_loudness's bits.  An
+        entry that delivered nothing has (-inf, 0, -inf, -inf, -inf, -inf, 0, 0, 0, 0, 0)."""
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        out = np.zeros(n, dtype=R128_DTYPE)
+        rc = lib().vpzm_measure_r128(self._h, n, ptrs, sizes, None if rng is None else rng.ctypes.data, out.ctypes.data if n else None,
+                                     results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_measure_r128 failed (status %d): %s" % (rc, self.last_error()))
+        return results, out, stats

@@ -11,6 +11,8 @@
     dispatcher_probe.py --logmel-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --fbank [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --fbank-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --mfcc [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --mfcc-kernel
     dispatcher_probe.py --loudness [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --loudness-kernel
     dispatcher_probe.py --r128 [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
@@ -52,6 +54,14 @@ loader does without the call -- decode_ranges_batch at RATE Hz, mono, then on th
 window, pad, rfft, power, matmul (vpz_fbank_filterbank as a dense matrix) and log -- against decode_ranges_fbank; two dispatchers taking
 turns as above, the largest difference of the two tensors printed.  With VPZM_PROFILE=1 the library prints the fbank launch's own time.
 --fbank-kernel: vpz_pcm_fbank alone, that spec, 64 windows of one second and of thirty, both layouts, the context's event timer.
+--ranges SAMPLES --batch --resample RATE --mfcc: the same windows as Kaldi MFCC features (13 cepstra of 23 bands, lifter 22, C0 replaced by
+the raw log energy, cepstral mean subtraction), a float32 device tensor [streams][T][13].  The A/B: what a loader does without the call
+-- decode_ranges_fbank with 23 bands, a SECOND decode through decode_ranges_batch at RATE Hz, mono, for the energy, then on the device
+unfold, mean and square-sum on that PCM, a matmul with the liftered DCT (vpz_mfcc_table), the column overwrite, the mean over the frames
+and the subtraction -- against decode_ranges_mfcc; two dispatchers taking turns as above, the largest difference of the two tensors
+printed.  With VPZM_PROFILE=1 the library prints the MFCC launches' own time.
+--mfcc-kernel: vpz_pcm_mfcc alone (with and without subtract_mean) next to vpz_pcm_fbank at the same mel spec (23 bands), 64 windows of one
+second and of thirty, the context's event timer: medians of 10 with their extremes.
 --loudness: the whole streams measured for programme loudness (BS.1770).  The A/B: what a scanner has to do first without the call --
 vpzm_decode_library of the whole streams into float32 page-locked memory, to which its host scan (two IIR filters and a gated mean over
 all of it) could only add -- against measure_loudness, which brings no PCM down; two dispatchers taking turns as above.  The records of
@@ -87,6 +97,8 @@ ap.add_argument("--logmel", action="store_true")
 ap.add_argument("--logmel-kernel", action="store_true")
 ap.add_argument("--fbank", action="store_true")
 ap.add_argument("--fbank-kernel", action="store_true")
+ap.add_argument("--mfcc", action="store_true")
+ap.add_argument("--mfcc-kernel", action="store_true")
 ap.add_argument("--loudness", action="store_true")
 ap.add_argument("--loudness-kernel", action="store_true")
 ap.add_argument("--r128", action="store_true")
@@ -521,6 +533,86 @@ def fbank_kernel_job():
     ctx.close()
 
 
+def mfcc_job(samples, rate):
+    import math, time
+    from vorbispizza_amd import capi
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    spec = capi.MfccSpec.make(sample_rate=rate, subtract_mean=True)
+    fb = spec.fbank
+    Ct = torch.from_numpy(capi.mfcc_table(spec).T.copy()).to("cuda:0")  # [23][13]
+    fs = 44100  # (both fixtures)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+
+    def by_fbank_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, E, res, st = d.decode_ranges_fbank(datas, windows, J, sample_rate=rate, n_mels=fb.n_mels)
+        _, whole, res2, _ = d.decode_ranges_batch(datas, windows, 1, J, planar=True, s16=False, sample_rate=rate, mono=True)  # (the second decode)
+        y = whole.view(n, J).unfold(1, fb.win, fb.hop) * fb.scale                                  # unfold (and the scale)
+        y = y - y.mean(dim=2, keepdim=True)                                                        # mean
+        e = torch.log(torch.clamp((y * y).sum(dim=2), min=2.0 ** -23))                             # square-sum (and the log)
+        c = torch.matmul(E, Ct)                                                                    # matmul with the DCT, the lifter in it
+        c[:, :, 0] = e                                                                             # column overwrite
+        out[0] = c - c.mean(dim=1, keepdim=True)                                                   # mean over frames, subtraction
+        torch.cuda.synchronize()
+        assert (res2["status"] == 0).all()
+        return time.perf_counter() - t0, res, st
+
+    def by_mfcc(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_mfcc(datas, windows, J, sample_rate=rate, subtract_mean=True)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, mfcc 400/160/512/23/13 with the mean" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_fbank_batch_and_torch(ds[0]), lambda: by_mfcc(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB (the framed batch it replaces: %.1f MB), largest difference of the two tensors %.3g" % (
+            what, J, out[1].numel() * 4 / 1e6, n * out[1].shape[1] * fb.win * 4 / 1e6, float((out[0] - out[1]).abs().max())), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_fbank + decode_ranges_batch(mono) + the torch chain %s; decode_ranges_mfcc %s" % (
+                run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def mfcc_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n = 64
+    for samples in (16000, 480000):
+        src = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+        rows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+        fspec = capi.FbankSpec.make(n_mels=23)
+        T = fspec.n_frames(samples)
+        calls = [("vpz_pcm_fbank, 23 bands", lambda dst: capi.pcm_fbank(ctx, src, rows, dst, fspec, samples), 23)]
+        for name, mean in (("vpz_pcm_mfcc 23 / 13", False), ("vpz_pcm_mfcc 23 / 13 with the mean", True)):
+            mspec = capi.MfccSpec.make(subtract_mean=mean)
+            calls.append((name, lambda dst, mspec=mspec: capi.pcm_mfcc(ctx, src, rows, dst, mspec, samples), 13))
+        for name, call, width in calls:
+            dst = torch.empty((n, T, width), dtype=torch.float32, device="cuda:0")
+            times = []
+            for _ in range(11):
+                ctx.timer_start()
+                assert call(dst) == capi.OK, ctx.last_error()
+                times.append(ctx.timer_stop())
+            print("%-36s 64 windows of %6d samples (T = %4d): median %.1f us (min %.1f, max %.1f)" % (
+                name, samples, T, statistics.median(times[1:]) * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3), flush=True)
+    ctx.close()
+
+
 def loudness_job():
     import time
     n = len(datas)
@@ -690,6 +782,12 @@ if args.fbank_kernel:
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.fbank:
     fbank_job(args.ranges, args.resample)
+    sys.exit(0)
+if args.mfcc_kernel:
+    mfcc_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.mfcc:
+    mfcc_job(args.ranges, args.resample)
     sys.exit(0)
 if args.logmel_kernel:
     logmel_kernel_job()

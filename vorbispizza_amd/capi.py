@@ -193,6 +193,38 @@ _PCM_FBANK_SIGNATURES = [
     ("vpz_pcm_fbank", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(FbankSpec), C.c_int32, _vp, _vp, C.c_int64]),
 ]
 PCM_FBANK_EXPORTED_SYMBOLS = [s[0] for s in _PCM_FBANK_SIGNATURES]
+
+
+class MfccSpec(C.Structure):
+    """vpz_mfcc_spec (include/vorbispizza_pcm_mfcc.h).  MfccSpec.make(...) takes FbankSpec.make's names (but `log`: the mel stage's output
+    is the log) and the cepstral stage's; its defaults are Kaldi's mfcc at 16 kHz: 13 cepstra of 23 bands, lifter 22, C0 replaced by the
+    log energy."""
+    _fields_ = [("fbank", FbankSpec), ("lifter", C.c_double), ("energy_floor", C.c_double), ("n_ceps", C.c_int32), ("use_energy", C.c_int32),
+                ("htk_compat", C.c_int32), ("subtract_mean", C.c_int32), ("reserved", C.c_int32 * 12)]
+
+    @classmethod
+    def make(cls, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=23, low_freq=20.0, high_freq=0.0, preemphasis=0.97, window="povey",
+             remove_dc=True, scale=32768.0, floor=FLT_EPSILON, pad_value=0.0, frames_first=True, n_ceps=13, lifter=22.0, use_energy=True,
+             energy_floor=0.0, htk_compat=False, subtract_mean=False):
+        s = cls()
+        s.fbank = FbankSpec.make(sample_rate=sample_rate, win=win, hop=hop, n_fft=n_fft, n_mels=n_mels, low_freq=low_freq, high_freq=high_freq,
+                                 preemphasis=preemphasis, window=window, remove_dc=remove_dc, scale=scale, log=True, floor=floor,
+                                 pad_value=pad_value, frames_first=frames_first)
+        s.lifter, s.energy_floor, s.n_ceps = float(lifter), float(energy_floor), int(n_ceps)
+        s.use_energy, s.htk_compat, s.subtract_mean = int(bool(use_energy)), int(bool(htk_compat)), int(bool(subtract_mean))
+        return s
+
+    def n_frames(self, frames):
+        """FbankSpec.n_frames of the mel stage: T of a padded length, T_L of a row's real samples."""
+        return self.fbank.n_frames(frames)
+
+
+# include/vorbispizza_pcm_mfcc.h (a header of its own again)
+_PCM_MFCC_SIGNATURES = [
+    ("vpz_mfcc_table", C.c_int, [C.POINTER(MfccSpec), _vp, C.c_int64]),
+    ("vpz_pcm_mfcc", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(MfccSpec), C.c_int32, _vp, _vp, C.c_int64]),
+]
+PCM_MFCC_EXPORTED_SYMBOLS = [s[0] for s in _PCM_MFCC_SIGNATURES]
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
 # include/vorbispizza_pcm_loudness.h (a header of its own again)
 _PCM_LOUDNESS_SIGNATURES = [
@@ -244,7 +276,7 @@ def lib():
                 pass
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
-                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES)
+                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -473,6 +505,30 @@ def fbank_filterbank(spec):
     if rc != OK:
         raise ValueError("vpz_fbank_filterbank failed (status %d)" % rc)
     return first, count, weights
+
+
+def pcm_mfcc(ctx, src, rows, dst, spec, frames):
+    """vpz_pcm_mfcc (vorbispizza_pcm_mfcc.h): windows of the MONO float32 device array `src` (a torch tensor) as Kaldi MFCC frames of
+    rows padded to `frames` samples, into rows of `dst` -- a contiguous float32 torch tensor [rows, T, n_ceps] (FBANK_FRAMES_FIRST) or
+    [rows, n_ceps, T], T = 1 + (frames - win) // hop; rows: [(src, samples, row)]; spec: an MfccSpec.
+    Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_mfcc(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                              int(dst.shape[0]))
+
+
+def mfcc_table(spec):
+    """vpz_mfcc_table: float32 [n_ceps, n_mels], row j the weights of the log-mel values in a frame's j-th STORED value; needs no device.
+    A refused spec raises ValueError."""
+    rc = lib().vpz_mfcc_table(C.byref(spec), None, 0)
+    if rc != OK:
+        raise ValueError("vpz_mfcc_table refuses the spec (status %d)" % rc)
+    table = np.zeros((int(spec.n_ceps), int(spec.fbank.n_mels)), dtype=np.float32)
+    rc = lib().vpz_mfcc_table(C.byref(spec), table.ctypes.data, table.size)
+    if rc != OK:
+        raise ValueError("vpz_mfcc_table failed (status %d)" % rc)
+    return table
 
 
 def loudness_filter(sample_rate):

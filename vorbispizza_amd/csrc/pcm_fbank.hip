@@ -19,6 +19,16 @@
 //   P = re^2 + im^2 goes into an LDS tile [Tt][n_fft/2, made odd] (no Nyquist column); then one lane per (frame, band) sums its band's
 //   live bins in ascending k, takes the natural log and stores, consecutive lanes along the layout's inner dimension.
 // All element indices are 64-bit.  No scratch memory.
+//
+// vpz_pcm_mfcc and vpz_mfcc_table (include/vorbispizza_pcm_mfcc.h, which states that definition) are the same tile core with three things
+// more (fb_tile_core<RT, CEP = true>, launched as pcm_mfcc_kernel):
+//   THE ENERGY of every frame comes from the staged span behind the mean: the same four lanes square-sum fl(x - mu) over every fourth
+//   sample with one fmaf each, the same two shuffles add, and S goes to LDS beside the mean;
+//   the band-sum stage writes the log-mel values into an LDS tile [Tt][n_mels, made odd] of its own instead of storing;
+//   behind a barrier one lane per (frame, coefficient) runs the fmaf chain over the bands against the cepstral matrix (read from L2,
+//   stored [band][coefficient] so that the lanes of a frame read side by side), puts the energy in c[0]'s place and stores, consecutive
+//   lanes along the layout's inner dimension, htk_compat applied on the store index.
+// subtract_mean is a second launch on the same stream, pcm_cmn_kernel: one wave per (row, stored coefficient) over the row's real frames.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -26,7 +36,9 @@
 
 #include "vpz_internal.hpp"
 #include "fbank_tables.hpp"
+#include "mfcc_tables.hpp"
 #include "../../include/vorbispizza_pcm_fbank.h"
+#include "../../include/vorbispizza_pcm_mfcc.h"
 
 namespace vpz {
 
@@ -54,12 +66,25 @@ struct FbankArgs {
     float floor, log_floor, pad;
 };
 
-// RT: 32-frame row tiles of a workgroup's tile (2 at Tt = 64, 1 at Tt <= 32)
-template <int RT>
-__global__ __launch_bounds__(kFbBlock) void pcm_fbank_kernel(const FbankArgs a)
+// what the cepstral stage of vpz_pcm_mfcc adds to a launch (CEP): a.n_mels stays the mel stage's, a.log is 1
+struct CepArgs {
+    const float *ct;  // the cepstral matrix, [n_mels][n_ceps]: ct[b * n_ceps + i] = C[i][b]
+    int32_t n_ceps, use_energy, htk, estride;  // ...; floats between two rows of the log-mel tile
+    float sc2, log_eps, log_efloor;  // fl(scale)^2; logf(2^-23); logf(energy_floor), -Inf without one
+};
+
+struct MfccArgs {
+    FbankArgs f;
+    CepArgs c;
+};
+
+// The tile core of both launches.  RT: 32-frame row tiles of a workgroup's tile (2 at Tt = 64, 1 at Tt <= 32); CEP: the cepstral stage
+// behind the band sums (`c` is read only then).  LDS: the span, the means, [CEP: the energies,] the power tile [, CEP: the log-mel tile]
+template <int RT, bool CEP>
+__device__ __forceinline__ void fb_tile_core(const FbankArgs a, const CepArgs c)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float *span = lds, *mean = lds + a.span_cap, *pw = mean + kFbMeans;
+    float *span = lds, *mean = lds + a.span_cap, *en = mean + kFbMeans, *pw = CEP ? en + kFbMeans : en, *et = pw + a.Tt * a.pstride;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, col = lane & 31, h = lane >> 5;
     const int win = a.win, hop = a.hop, nb = a.nb, n_mels = a.n_mels, Tt = a.Tt, skew = a.skew, pstride = a.pstride;
     const int64_t T = a.T;
@@ -104,6 +129,36 @@ __global__ __launch_bounds__(kFbBlock) void pcm_fbank_kernel(const FbankArgs a)
                 s += __shfl_xor(s, 2);  // (s0 + s1) + (s2 + s3), the same bits in all four
                 if (q == 0) mean[f] = s / (float)win;
                 __syncthreads();
+            }
+            if constexpr (CEP) {
+                if (c.use_energy) {
+                    // the same four lanes per frame once more, over fl(x - mu): the A operand's own values
+                    const int f = t >> 2, q = t & 3, fr = f < nr ? f : nr - 1;
+                    const float *fp = span + fr * (hop + skew);
+                    const float m0 = a.remove_dc ? mean[fr] : 0.0f;
+                    float s = 0.0f;
+                    int g = q, rem = q;
+                    if (skew) {
+                        g += q / hop;
+                        rem = q % hop;
+                    }
+                    for (int m = q; m < win; m += 4) {
+                        const float av = fp[g] - m0;
+                        s = __builtin_fmaf(av, av, s);
+                        g += 4;
+                        if (skew) {
+                            rem += 4;
+                            while (rem >= hop) {
+                                rem -= hop;
+                                ++g;
+                            }
+                        }
+                    }
+                    s += __shfl_xor(s, 1);
+                    s += __shfl_xor(s, 2);
+                    if (q == 0) en[f] = c.sc2 * s;
+                    // (no barrier of its own: the one behind the MFMA phase stands before the energies are read)
+                }
             }
             int base[RT];
             float mu[RT];
@@ -191,9 +246,52 @@ __global__ __launch_bounds__(kFbBlock) void pcm_fbank_kernel(const FbankArgs a)
                     }
             }
             __syncthreads();
+            if constexpr (CEP) {
+                // the log-mel values of the real frames, into their tile: consecutive lanes along the bands
+                for (int it = t; it < nr * n_mels; it += kFbBlock) {
+                    const int tl = it / n_mels, b = it - tl * n_mels;
+                    const int first = a.meta[3 * b], cnt = a.meta[3 * b + 1];
+                    const float *p = pw + tl * pstride + first, *ww = a.w + a.meta[3 * b + 2];
+                    float acc = 0.0f;
+                    for (int i = 0; i < cnt; ++i) acc = __builtin_fmaf(ww[i], p[i], acc);
+                    et[tl * c.estride + b] = acc <= a.floor ? a.log_floor : logf(acc);
+                }
+                __syncthreads();
+            }
         }
         // (the next descriptor's staging writes the span, which no lane reads any more; its first barrier stands before the means and the
-        // power tile are written again)
+        // power tile are written again.  CEP: the energies and the log-mel tile have room of their own -- nothing overlays the span --, and
+        // that same first barrier stands before the energies are written again, three more before the log-mel tile is: the cepstral
+        // stage of this descriptor needs no barrier behind it)
+        if constexpr (CEP) {
+            const int n_ceps = c.n_ceps;
+            for (int it = t; it < nt * n_ceps; it += kFbBlock) {
+                int tl, i;
+                if (a.frames_first) {
+                    tl = it / n_ceps;
+                    i = it - tl * n_ceps;
+                } else {
+                    i = it / nt;
+                    tl = it - i * nt;
+                }
+                float v = a.pad;
+                if (tl < nr) {
+                    if (c.use_energy && i == 0) {
+                        const float S = en[tl];
+                        v = S <= 0x1p-23f ? c.log_eps : logf(S);
+                        v = v < c.log_efloor ? c.log_efloor : v;
+                    } else {
+                        const float *e = et + tl * c.estride, *cp = c.ct + i;
+                        v = 0.0f;
+                        for (int b = 0; b < n_mels; ++b) v = __builtin_fmaf(cp[(size_t)b * n_ceps], e[b], v);
+                    }
+                }
+                const int j = !c.htk ? i : i == 0 ? n_ceps - 1 : i - 1;  // where the frame stores c[i]
+                const int64_t at = a.frames_first ? (d.row * T + t0 + tl) * n_ceps + j : (d.row * n_ceps + j) * T + t0 + tl;
+                a.dst[at] = v;
+            }
+            continue;  // (the filterbank's own store, below, is the other launch's)
+        }
         for (int it = t; it < items; it += kFbBlock) {
             int tl, b;
             if (a.frames_first) {
@@ -214,6 +312,46 @@ __global__ __launch_bounds__(kFbBlock) void pcm_fbank_kernel(const FbankArgs a)
             const int64_t at = a.frames_first ? (d.row * T + t0 + tl) * n_mels + b : (d.row * n_mels + b) * T + t0 + tl;
             a.dst[at] = v;
         }
+    }
+}
+
+template <int RT>
+__global__ __launch_bounds__(kFbBlock) void pcm_fbank_kernel(const FbankArgs a)
+{
+    fb_tile_core<RT, false>(a, CepArgs{});
+}
+
+template <int RT>
+__global__ __launch_bounds__(kFbBlock) void pcm_mfcc_kernel(const MfccArgs a)
+{
+    fb_tile_core<RT, true>(a.f, a.c);
+}
+
+struct CmnArgs {
+    const vpz_pack_row *rows;
+    float *dst;
+    int64_t T;
+    int32_t n_rows, win, hop, n_ceps, frames_first;
+};
+
+// Cepstral mean subtraction behind pcm_mfcc_kernel: one wave per (row, stored coefficient).  Lane q sums the real frames t = q (mod 64)
+// in float64, t ascending; six xor shuffles (1, 2, 4, 8, 16, 32) combine the 64 partial sums into the same bits in every lane; the mean
+// is rounded once to float32 and subtracted from the real frames.  Pad frames are neither read nor written
+__global__ __launch_bounds__(kFbBlock) void pcm_cmn_kernel(const CmnArgs a)
+{
+    const int lane = threadIdx.x & 63, j = blockIdx.x * (kFbBlock / 64) + (threadIdx.x >> 6);
+    if (j >= a.n_ceps) return;  // (no barrier in this kernel)
+    for (int r = blockIdx.y; r < a.n_rows; r += gridDim.y) {
+        const vpz_pack_row d = a.rows[r];
+        const int64_t L = d.samples;
+        const int64_t TL = L < a.win ? 0 : 1 + (L - a.win) / a.hop;
+        float *p = a.dst + (a.frames_first ? d.row * a.T * a.n_ceps + j : (d.row * a.n_ceps + j) * a.T);
+        const int64_t stride = a.frames_first ? a.n_ceps : 1;
+        double s = 0.0;
+        for (int64_t tt = lane; tt < TL; tt += 64) s += (double)p[tt * stride];
+        for (int dd = 1; dd < 64; dd <<= 1) s += __shfl_xor(s, dd);
+        const float m = (float)(s / (double)TL);
+        for (int64_t tt = lane; tt < TL; tt += 64) p[tt * stride] = p[tt * stride] - m;
     }
 }
 
@@ -303,6 +441,50 @@ void lds_plan(const vpz_fbank_spec &s, int Tt, int *span_cap, int *pstride)
     *pstride = (s.n_fft / 2) | 1;
 }
 
+// the cepstral matrix of a spec on the device, transposed: [n_mels][n_ceps], coefficient i in column i (the kernel permutes on the store)
+int cepstra_for(Context *ctx, const vpz_mfcc_spec &s, const float **out)
+{
+    try {
+        const std::vector<double> key = {(double)s.fbank.n_mels, (double)s.n_ceps, s.lifter, (double)s.htk_compat, (double)s.use_energy};
+        auto it = ctx->mfcc_tables.find(key);
+        if (it != ctx->mfcc_tables.end()) {
+            *out = it->second;
+            return VPZ_OK;
+        }
+        const int N = s.fbank.n_mels, n_ceps = s.n_ceps;
+        std::vector<float> host((size_t)N * (size_t)n_ceps);
+        for (int b = 0; b < N; ++b)
+            for (int i = 0; i < n_ceps; ++i) host[(size_t)b * n_ceps + i] = mfcc_weight(s, i, b);
+        void *mem = nullptr;
+        VPZ_HIP_TRY(ctx, hipMalloc(&mem, host.size() * sizeof(float)));
+        // (a blocking copy, once per matrix and context: it is whole before any launch that reads it is queued)
+        const hipError_t e = hipMemcpy(mem, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(mem);
+            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_mfcc: cepstral matrix upload", e);
+        }
+        try {
+            *out = ctx->mfcc_tables.emplace(key, static_cast<float *>(mem)).first->second;
+        } catch (const std::bad_alloc &) {
+            (void)hipFree(mem);
+            throw;
+        }
+    } catch (const std::bad_alloc &) {
+        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_mfcc: out of host memory");
+    }
+    return VPZ_OK;
+}
+
+// floats of an MFCC tile's LDS at `Tt` frames: lds_plan's span and power tile, a second kFbMeans area for the energies behind the means,
+// and behind the power tile the log-mel tile, `estride` floats between two of its rows -- room of its own, nothing overlays the span.
+// tests/test_mfcc_cpu.py restates it and holds that 16 frames fit at every spec inside the limits
+int mfcc_lds_plan(const vpz_fbank_spec &s, int Tt, int *span_cap, int *pstride, int *estride)
+{
+    lds_plan(s, Tt, span_cap, pstride);
+    *estride = s.n_mels | 1;
+    return *span_cap + 2 * kFbMeans + Tt * *pstride + Tt * *estride;
+}
+
 }  // namespace
 
 void free_fbank_tables(Context *ctx)
@@ -313,6 +495,9 @@ void free_fbank_tables(Context *ctx)
     for (auto &kv : ctx->fbank_banks)
         if (kv.second.d_meta) (void)hipFree(kv.second.d_meta);  // (one allocation: the weights lie behind the bands' records)
     ctx->fbank_banks.clear();
+    for (auto &kv : ctx->mfcc_tables)
+        if (kv.second) (void)hipFree(kv.second);
+    ctx->mfcc_tables.clear();
 }
 
 }  // namespace vpz
@@ -420,5 +605,107 @@ extern "C" int vpz_pcm_fbank(vpz_context *c, const void *src_dev, int64_t src_el
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_fbank kernel launch", e);
+    return VPZ_OK;
+}
+
+extern "C" int vpz_mfcc_table(const vpz_mfcc_spec *spec, float *table, int64_t capacity)
+{
+    if (!spec || capacity < 0 || !vpz::mfcc_spec_ok(*spec)) return VPZ_E_INVALID_ARG;
+    if (!table) return VPZ_OK;
+    const int N = spec->fbank.n_mels;
+    if (capacity < (int64_t)spec->n_ceps * N) return VPZ_E_CAPACITY;
+    for (int j = 0; j < spec->n_ceps; ++j)
+        for (int b = 0; b < N; ++b) table[(size_t)j * N + b] = vpz::mfcc_weight(*spec, vpz::mfcc_stored(*spec, j), b);
+    return VPZ_OK;
+}
+
+extern "C" int vpz_pcm_mfcc(vpz_context *c, const void *src_dev, int64_t src_elems, int64_t frames, const vpz_mfcc_spec *spec, int32_t n_rows,
+                            const vpz_pack_row *rows, void *dst_dev, int64_t dst_rows)
+{
+    if (!c) return VPZ_E_INVALID_ARG;
+    vpz::Context *ctx = &c->impl;
+    auto refuse = [&](const char *what) { return vpz::set_error(ctx, VPZ_E_INVALID_ARG, what); };
+    if (!spec) return refuse("vpz_pcm_mfcc: null pointer");
+    if (!vpz::mfcc_spec_ok(*spec)) return refuse("vpz_pcm_mfcc: a spec outside the limits");
+    const vpz_fbank_spec &s = spec->fbank;
+    if (frames < s.win) return refuse("vpz_pcm_mfcc: frames < win (a row holds no frame)");
+    if (frames > INT64_MAX / 8) return refuse("vpz_pcm_mfcc: sizes overflow");
+    const int64_t T = 1 + (frames - s.win) / s.hop;
+    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_mfcc", src_dev, src_elems, sizeof(float), 1, 1, 1, frames, n_rows, rows, dst_dev, dst_rows,
+                                                       (unsigned __int128)(uint64_t)T * (uint64_t)spec->n_ceps, sizeof(float)});
+    if (rc != VPZ_OK || n_rows == 0) return rc;
+
+    const vpz::Context::LogmelDft *tb = nullptr;
+    const vpz::Context::LogmelBank *bk = nullptr;
+    vpz::MfccArgs m;
+    vpz::FbankArgs &a = m.f;
+    rc = vpz::table_for(ctx, s, &tb);
+    if (rc == VPZ_OK) rc = vpz::bank_for(ctx, s, &bk);
+    if (rc == VPZ_OK) rc = vpz::cepstra_for(ctx, *spec, &m.c.ct);
+    if (rc != VPZ_OK) return rc;
+
+    // the tile: vpz_pcm_fbank's rule over this launch's own plan (a result does not depend on the tile: the same bits)
+    a.Tt = 0;
+    int floats = 0;
+    const bool few = ((T + 63) / 64) * (int64_t)n_rows < 2 * (int64_t)ctx->num_cu;
+    for (int Tt : {64, 32, 16}) {
+        floats = vpz::mfcc_lds_plan(s, Tt, &a.span_cap, &a.pstride, &m.c.estride);
+        if ((Tt == 64 && (T <= 32 || few)) || (Tt == 32 && T <= 16) || floats > vpz::kFbLdsFloats) continue;
+        a.Tt = Tt;
+        break;
+    }
+    if (a.Tt == 0) return vpz::set_error(ctx, VPZ_E_UNSUPPORTED, "vpz_pcm_mfcc: no tile fits the LDS");  // (16 frames fit at every spec inside the limits)
+    const int64_t blocks = (T + a.Tt - 1) / a.Tt;
+    if (blocks > 0x7fffffff) return refuse("vpz_pcm_mfcc: a row too long for one launch");
+
+    rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);
+    if (rc != VPZ_OK) return rc;
+
+    a.src = static_cast<const float *>(src_dev);
+    a.dst = static_cast<float *>(dst_dev);
+    a.table = tb->d_table;
+    a.meta = bk->d_meta;
+    a.w = bk->d_w;
+    a.T = T;
+    a.n_rows = n_rows;
+    a.win = s.win;
+    a.hop = s.hop;
+    a.nb = s.n_fft / 2;
+    a.cols = tb->cols;
+    a.n_mels = s.n_mels;
+    a.log = 1;
+    a.frames_first = s.layout == VPZ_FBANK_FRAMES_FIRST;
+    a.remove_dc = s.remove_dc;
+    a.skew = s.hop % 2 == 0 ? 1 : 0;
+    a.floor = (float)s.floor;
+    a.log_floor = (float)log((double)a.floor);
+    a.pad = (float)s.pad_value;
+    m.c.n_ceps = spec->n_ceps;
+    m.c.use_energy = spec->use_energy;
+    m.c.htk = spec->htk_compat;
+    m.c.sc2 = (float)s.scale * (float)s.scale;
+    m.c.log_eps = (float)log((double)0x1p-23f);
+    m.c.log_efloor = (float)spec->energy_floor > 0.0f ? (float)log((double)(float)spec->energy_floor) : -INFINITY;
+    const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kFbMaxGridY));
+    const size_t lds = sizeof(float) * (size_t)floats;
+    // (the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never lower it under each other)
+    const int max_lds = (int)(sizeof(float) * vpz::kFbLdsFloats);
+    if (a.Tt == 64) {
+        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_mfcc_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        vpz::pcm_mfcc_kernel<2><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(m);
+    } else {
+        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_mfcc_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+        vpz::pcm_mfcc_kernel<1><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(m);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_mfcc kernel launch", e);
+    if (!spec->subtract_mean) return VPZ_OK;
+
+    // the mean over a row's real frames: behind the cepstra on the same stream, over the same descriptors
+    const vpz::CmnArgs q{a.rows, a.dst, T, n_rows, s.win, s.hop, spec->n_ceps, a.frames_first};
+    const int per = vpz::kFbBlock / 64;
+    vpz::pcm_cmn_kernel<<<dim3((unsigned)((spec->n_ceps + per - 1) / per), grid.y), vpz::kFbBlock, 0, ctx->stream>>>(q);
+    e = hipGetLastError();
+    if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_cmn kernel launch", e);
     return VPZ_OK;
 }

@@ -53,7 +53,7 @@ struct Context {
     // persistent grids of the IMDCT kernels on THIS context's device (workgroups the chip keeps resident), filled by the first
     // launch of each; per context, not per process: a host with several GPUs holds one context per device
     int resident[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // the row launches -- vpz_pcm_pack, vpz_pcm_resample, vpz_pcm_logmel and vpz_pcm_fbank -- share it (upload_rows, pcm_pack.hip): a launch's row
+    // the row launches -- vpz_pcm_pack, vpz_pcm_resample, vpz_pcm_logmel, vpz_pcm_fbank and vpz_pcm_mfcc -- share it (upload_rows, pcm_pack.hip): a launch's row
     // descriptors go up through a page-locked buffer of the context's into its device copy; `pack_done` says that the last launch's copy
     // has left the buffer
     void *pack_host = nullptr, *pack_dev = nullptr;
@@ -82,6 +82,9 @@ struct Context {
     // preemphasis, scale) -- and of every mel bank, keyed by (sample_rate, n_fft, n_mels, low_freq, high_freq); the records are log-mel's
     std::map<std::vector<double>, LogmelDft> fbank_tables;
     std::map<std::vector<double>, LogmelBank> fbank_banks;
+    // vpz_pcm_mfcc (pcm_fbank.hip): the device copy of every cepstral matrix -- [n_mels][n_ceps], keyed by (n_mels, n_ceps, lifter,
+    // htk_compat, use_energy) --, freed with the fbank tables
+    std::map<std::vector<double>, float *> mfcc_tables;
     // vpz_pcm_loudness (pcm_loudness.hip): the constants of every rate -- the two biquads and the 4x4 transition of one step of silence,
     // built on the host on first use (kernel arguments: no device copy) -- and the launch's scratch memory, grown on demand
     struct LoudnessRate {

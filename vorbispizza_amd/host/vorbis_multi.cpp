@@ -38,6 +38,7 @@
 // vpzm_decode_ranges_logmel (include/vorbispizza_multi_logmel.h) is the mono resampled call with one more stage: the resample launches write
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
 // vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
+// vpzm_decode_ranges_mfcc (include/vorbispizza_multi_mfcc.h) is the same call with vpz_pcm_mfcc as that stage: Kaldi MFCC frames.
 //
 // vpzm_measure_loudness (include/vorbispizza_multi_loudness.h) is a batch call whose delivery measures instead of moving: one
 // vpz_pcm_loudness launch per sample rate among a sub-batch's members, into a temporary of the lane's; the step sums and peaks come down
@@ -77,6 +78,8 @@
 #include "../../include/vorbispizza_multi_logmel.h"
 #include "../../include/vorbispizza_pcm_fbank.h"
 #include "../../include/vorbispizza_multi_fbank.h"
+#include "../../include/vorbispizza_pcm_mfcc.h"
+#include "../../include/vorbispizza_multi_mfcc.h"
 #include "../../include/vorbispizza_pcm_loudness.h"
 #include "../../include/vorbispizza_multi_loudness.h"
 #include "../../include/vorbispizza_pcm_r128.h"
@@ -331,7 +334,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel or fbank call, or a loudness call's -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -383,9 +386,9 @@ struct Job {  // one stream of the library inside its group
 // vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
-    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or, into its
-    // record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
-    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128 };
+    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or then
+    // vpz_pcm_mfcc; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
+    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
@@ -394,6 +397,8 @@ struct Batch {
     const vpz_logmel_spec *mel = nullptr;
     // kFbank: the same with Kaldi filterbank frames of this spec (`dst` is [rows][T][n_mels] or transposed)
     const vpz_fbank_spec *fbank = nullptr;
+    // kMfcc: the same with Kaldi MFCC frames of this spec (`dst` is [rows][T][n_ceps] or transposed)
+    const vpz_mfcc_spec *mfcc = nullptr;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
     // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
@@ -402,17 +407,20 @@ struct Batch {
     bool measured() const { return kind == kLoudness || kind == kR128; }
     vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
     vpzm_r128 &record_r128(int64_t row) const { return static_cast<vpzm_r128 *>(dst)[row]; }
-    bool features() const { return kind == kLogmel || kind == kFbank; }  // a feature stage behind the resample launches, fed from the lane's temporary
-    const char *feature_step() const { return kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
+    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc; }  // a feature stage behind the resample launches, fed from the lane's temporary
+    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
+    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : "vpzm_decode_ranges_logmel"; }
+    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : "log-mel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `dst`
     int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d) const
     {
+        if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), dst, rows);
         if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), dst, rows);
         return vpz_pcm_logmel(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), dst, rows);
     }
 
     // These descriptors (samples = 0 each) get rows of no samples -- zeros, or the silence row of a log-mel call or the pad_value row of
-    // an fbank call, which their own kernels write -- from a launch that reads nothing: the destination stands in for a source of no elements
+    // an fbank or MFCC call, which their own kernels write -- from a launch that reads nothing: the destination stands in for a source of no elements
     int empty_rows(vpz_context *ctx, const std::vector<vpz_pack_row> &d) const
     {
         if (features()) return feature_rows(ctx, dst, 0, d);
@@ -908,7 +916,7 @@ struct GroupRun {
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0].ctx, rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1311,7 +1319,7 @@ struct SubCall {
                                                              : vpz_pcm_pack(L.ctx, L.pcm(), pcm_elems, B.channels, (int32_t)rows.size(), rows.data(), B.dst,
                                                                             B.rows, B.frames, B.layout));
         } else {
-            // (a log-mel or fbank call: resampled into the lane's temporary, then ONE feature launch on the same stream -- stream-ordered:
+            // (a log-mel, fbank or MFCC call: resampled into the lane's temporary, then ONE feature launch on the same stream -- stream-ordered:
             // no synchronise in between)
             if (B.features()) rc = mono_temporary(rows.size());
             if (rc == VPZ_OK) rc = resample_by_ratio(rows);
@@ -1440,11 +1448,11 @@ struct SubCall {
         return VPZ_OK;
     }
 
-    // a log-mel or fbank call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
+    // a log-mel, fbank or MFCC call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
     int mono_temporary(size_t members)
     {
         if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.frames, sizeof(float))) return VPZ_OK;
-        R.m->fail(std::string(B.kind == Batch::kFbank ? "vpzm_decode_ranges_fbank" : "vpzm_decode_ranges_logmel") + ": the resampled rows' device temporary could not be allocated");
+        R.m->fail(std::string(B.feature_call()) + ": the resampled rows' device temporary could not be allocated");
         return VPZ_E_NOMEM;
     }
 
@@ -1479,7 +1487,7 @@ struct SubCall {
         return launched("vpz_pcm_resample", rc);
     }
 
-    // a log-mel or fbank call: row j's first `written[j]` samples of the temporary become row k - lo of the group's piece
+    // a log-mel, fbank or MFCC call: row j's first `written[j]` samples of the temporary become row k - lo of the group's piece
     int feature_rows(std::vector<vpz_pack_row> &rows)
     {
         for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.frames, written[j], rows[j].row};
@@ -1487,7 +1495,7 @@ struct SubCall {
         const auto t_mel = Clock::now();
         const int rc = launched(B.feature_step(), R.sw.fail_delivery ? VPZ_E_HIP : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, rows));
         if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b, B.kind == Batch::kFbank ? "fbank" : "log-mel",
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b, B.feature_name(),
                     seconds_since(t_mel) * 1e3, rows.size(), (long long)B.frames);
         return rc;
     }
@@ -1793,6 +1801,20 @@ int vpzm_decode_ranges_fbank(vpzm_dispatcher *m, int32_t n, const uint8_t *const
     if (frames < spec->win) return VPZM_E_ARG;
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
     const Batch batch{Batch::kFbank, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, nullptr, spec};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_mfcc(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                            const vpz_mfcc_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!spec) return VPZM_E_ARG;
+    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
+    if (vpz_mfcc_table(spec, nullptr, 0) != VPZ_OK) return VPZM_E_ARG;
+    const double rate = spec->fbank.sample_rate;
+    if (rate < 1.0 || rate > 2147483647.0 || (double)(int32_t)rate != rate) return VPZM_E_ARG;
+    if (frames < spec->fbank.win) return VPZM_E_ARG;
+    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
+    const Batch batch{Batch::kMfcc, 1, VPZ_OUT_PLANAR, frames, (int32_t)rate, 1, nullptr, nullptr, spec};
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -50,6 +50,7 @@ BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  #
 RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
+MFCC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_mfcc"]  # (vorbispizza_multi_mfcc.h)
 LOUDNESS_EXPORTED_SYMBOLS = ["vpzm_measure_loudness"]  # (vorbispizza_multi_loudness.h)
 LOUDNESS_DTYPE = np.dtype([("integrated", "<f8"), ("peak", "<f8"), ("steps", "<i8"), ("blocks_kept", "<i8")])  # vpzm_loudness
 R128_EXPORTED_SYMBOLS = ["vpzm_measure_r128"]  # (vorbispizza_multi_r128.h)
@@ -98,6 +99,9 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges_fbank"):
             L.vpzm_decode_ranges_fbank.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_fbank.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_mfcc"):
+            L.vpzm_decode_ranges_mfcc.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.MfccSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_mfcc.restype = C.c_int
         if hasattr(L, "vpzm_measure_loudness"):
             L.vpzm_measure_loudness.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
             L.vpzm_measure_loudness.restype = C.c_int
@@ -330,6 +334,36 @@ class Dispatcher:
                                             C.byref(stats))
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_fbank failed (status %d): %s" % (rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_mfcc(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=23, low_freq=20.0, high_freq=0.0,
+                           preemphasis=0.97, window="povey", remove_dc=True, scale=32768.0, floor=capi.FLT_EPSILON, pad_value=0.0,
+                           frames_first=True, n_ceps=13, lifter=22.0, use_energy=True, energy_floor=0.0, htk_compat=False,
+                           subtract_mean=False, out=None):
+        """vpzm_decode_ranges_mfcc: decode_ranges_fbank with the cepstral stage behind the log-mel values -- entry k's window, resampled
+        and mixed down, becomes row k of Kaldi MFCC frames: [T, n_ceps] (frames_first) or [n_ceps, T], float32,
+        T = 1 + (frames - win) // hop (include/vorbispizza_pcm_mfcc.h states the definition; the defaults are Kaldi's mfcc at 16 kHz:
+        13 cepstra of 23 bands, lifter 22, C0 replaced by the log energy).  results["samples"] counts the window's output samples J: the
+        row's first MfccSpec.n_frames(J) frames are real, the others hold pad_value.
+        out: as for decode_ranges_batch, one contiguous float32 tensor per group of shape [hi - lo, T, n_ceps] (or [hi - lo, n_ceps, T])
+        on the group's device -- anything else raises before the library is called.  Returns (parts, whole_or_None, results, stats)."""
+        import torch
+        spec = capi.MfccSpec.make(sample_rate=sample_rate, win=win, hop=hop, n_fft=n_fft, n_mels=n_mels, low_freq=low_freq, high_freq=high_freq,
+                                  preemphasis=preemphasis, window=window, remove_dc=remove_dc, scale=scale, floor=floor, pad_value=pad_value,
+                                  frames_first=frames_first, n_ceps=n_ceps, lifter=lifter, use_energy=use_energy, energy_floor=energy_floor,
+                                  htk_compat=htk_compat, subtract_mean=subtract_mean)
+        if win < 1 or frames < win or hop < 1 or n_ceps < 1:
+            raise ValueError("decode_ranges_mfcc: hop and n_ceps must be at least 1, and frames at least win")
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        T = spec.n_frames(frames)
+        shape = (lambda rows: (rows, T, n_ceps)) if frames_first else (lambda rows: (rows, n_ceps, T))
+        out, whole, dst = self._group_tensors("decode_ranges_mfcc", n, shape, torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = lib().vpzm_decode_ranges_mfcc(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
+                                           C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_mfcc failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats
 
     def measure_loudness(self, datas, ranges=None):

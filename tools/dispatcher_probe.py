@@ -13,6 +13,8 @@
     dispatcher_probe.py --fbank-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --mfcc [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --mfcc-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --mfcc --post [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --post-kernel
     dispatcher_probe.py --loudness [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --loudness-kernel
     dispatcher_probe.py --r128 [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
@@ -62,6 +64,16 @@ and the subtraction -- against decode_ranges_mfcc; two dispatchers taking turns 
 printed.  With VPZM_PROFILE=1 the library prints the MFCC launches' own time.
 --mfcc-kernel: vpz_pcm_mfcc alone (with and without subtract_mean) next to vpz_pcm_fbank at the same mel spec (23 bands), 64 windows of one
 second and of thirty, the context's event timer: medians of 10 with their extremes.
+--ranges SAMPLES --batch --resample RATE --mfcc --post: the same windows as Kaldi MFCC features (the defaults, no cepstral mean) with
+add-deltas | apply-cmvn-sliding --cmn-window=300 --center=true behind them (deltas of order 2, window 2, then the sliding mean over all 39
+columns), a float32 device tensor [streams][T][39].  The A/B: what a loader does without the call -- decode_ranges_mfcc, then on the
+device the mask of the pad frames, one replicate-padded conv1d per order with the convolved scales (vpz_feat_delta_scales; right for rows
+that fill T, which all of this job's do), a float64 cumsum and the window's ends per row with the edge rules, two gathers, the mean and
+the subtraction -- against decode_ranges_mfcc_post; two dispatchers taking turns as above, the largest difference of the two tensors
+printed.
+--post-kernel: vpz_feat_post alone (that spec, its two stages alone, and the other order) next to vpz_pcm_mfcc at the same shapes, 64 rows
+of one second and of thirty at 13 columns, the context's event timer: medians of 10 with their extremes, and the bytes per second
+against the source tensor's read plus the destination's write.
 --loudness: the whole streams measured for programme loudness (BS.1770).  The A/B: what a scanner has to do first without the call --
 vpzm_decode_library of the whole streams into float32 page-locked memory, to which its host scan (two IIR filters and a gated mean over
 all of it) could only add -- against measure_loudness, which brings no PCM down; two dispatchers taking turns as above.  The records of
@@ -99,6 +111,8 @@ ap.add_argument("--fbank", action="store_true")
 ap.add_argument("--fbank-kernel", action="store_true")
 ap.add_argument("--mfcc", action="store_true")
 ap.add_argument("--mfcc-kernel", action="store_true")
+ap.add_argument("--post", action="store_true")
+ap.add_argument("--post-kernel", action="store_true")
 ap.add_argument("--loudness", action="store_true")
 ap.add_argument("--loudness-kernel", action="store_true")
 ap.add_argument("--r128", action="store_true")
@@ -613,6 +627,123 @@ def mfcc_kernel_job():
     ctx.close()
 
 
+POST = dict(norm="sliding", cmn_window=300, min_window=100, center=True, delta_order=2, delta_window=2, deltas_first=True)
+
+
+def post_job(samples, rate):
+    import math, time
+    from vorbispizza_amd import capi
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    import featpost_truth as pt
+    n, out, kept = len(datas), [None, None], {}
+    spec = capi.MfccSpec.make(sample_rate=rate)
+    post = capi.FeatPostSpec.make(**POST)
+    W, w, order = post.cmn_window, post.delta_window, post.delta_order
+    kernels = [torch.from_numpy(capi.feat_delta_scales(post, i).copy()).to("cuda:0") for i in range(1, order + 1)]
+    fs = 44100  # (both fixtures)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+
+    def by_mfcc_and_torch(d):
+        t0 = time.perf_counter()
+        _, E, res, st = d.decode_ranges_mfcc(datas, windows, J, sample_rate=rate)
+        T, D = E.shape[1], E.shape[2]
+        nf = torch.from_numpy(np.array([spec.n_frames(int(x)) for x in res["samples"]], dtype=np.int64)).to("cuda:0")
+        t = torch.arange(T, device="cuda:0")
+        mask = (t[None, :] < nf[:, None])[:, :, None]                                              # mask
+        x = (E * mask).transpose(1, 2).reshape(n * D, 1, T)
+        blocks = [x]
+        for i, k in enumerate(kernels, 1):                                                         # replicate pad, conv1d: per order
+            blocks.append(torch.nn.functional.conv1d(torch.nn.functional.pad(x, (i * w, i * w), mode="replicate"), k.view(1, 1, -1)))
+        y = torch.cat([b.view(n, D, T) for b in blocks], dim=1).transpose(1, 2)                    # [n][T][39]
+        cs = torch.nn.functional.pad(torch.cumsum(y.double(), dim=1), (0, 0, 1, 0))                # cumsum (float64), a zero in front
+        a = (t - W // 2)[None, :].expand(n, T)                                                     # the window's ends per row, edge rules
+        b = a + W
+        b = torch.where(a < 0, b - a, b)
+        a = a.clamp(min=0)
+        over = (b - nf[:, None]).clamp(min=0)
+        a, b = (a - over).clamp(min=0), torch.minimum(b, nf[:, None]).clamp(min=1)
+        S1 = cs.gather(1, b[:, :, None].expand(n, T, y.shape[2])) - cs.gather(1, a[:, :, None].expand(n, T, y.shape[2]))   # two gathers
+        out[0] = ((y - S1 / (b - a).clamp(min=1)[:, :, None]) * mask).float()                      # mean, subtraction, mask
+        kept["E"], kept["y"], kept["nf"] = E, y, nf
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res, st
+
+    def by_post(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_mfcc_post(datas, windows, J, post=post, sample_rate=rate)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, mfcc 400/160/512/23/13, deltas 2 / 2, sliding mean 300 centred" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_mfcc_and_torch(ds[0]), lambda: by_post(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape
+        # leg 1 held to the truth (tests/featpost_truth.py) on a sample of its rows, as the composition is defined: its float32 deltas
+        # against the truth of the MFCC frames, its normalised values against the truth of ITS OWN float32 deltas
+        worst = [0.0, 0.0]
+        for k in sorted({0, 1, n // 3, n // 2, n - 2, n - 1}):
+            f = int(kept["nf"][k])
+            E_k, y_k, o_k = (t[k, :f].cpu().numpy() for t in (kept["E"], kept["y"], out[0]))
+            want, bound = pt.deltas(E_k, pt.spec_of(delta_order=order, delta_window=w))
+            worst[0] = max(worst[0], pt.ratio(y_k, want, bound))
+            want, bound = pt.normalise(np.ascontiguousarray(y_k), pt.spec_of(norm="sliding", cmn_window=W, min_window=post.min_window, center=True))
+            worst[1] = max(worst[1], pt.ratio(o_k, want, bound))
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB, largest difference of the two tensors %.3g (largest value %.3g); the torch chain against the "
+              "truth's bound on 6 rows: largest error / bound %.3f for its deltas, %.3f for its normalised values" % (
+                  what, J, out[1].numel() * 4 / 1e6, float((out[0] - out[1]).abs().max()), float(out[1].abs().max()), worst[0], worst[1]), flush=True)
+        assert max(worst) <= 1.0, "the torch chain leaves the truth's bound: it does not compute what the call computes"
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_mfcc + the torch chain %s; decode_ranges_mfcc_post %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def post_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, D = 64, 13
+    for samples in (16000, 480000):
+        pcm = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+        prows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+        mspec = capi.MfccSpec.make()
+        T = mspec.n_frames(samples)
+        src = torch.empty((n, T, D), dtype=torch.float32, device="cuda:0")
+        rows = [(k, T, k) for k in range(n)]
+        calls = [("vpz_pcm_mfcc 23 / 13", lambda dst: capi.pcm_mfcc(ctx, pcm, prows, dst, mspec, samples), D, None)]
+        for name, kw in (("deltas 2 / 2, then sliding mean 300", POST), ("deltas 2 / 2 alone", dict(delta_order=2)),
+                         ("sliding mean 300 alone", dict(norm="sliding", cmn_window=300, min_window=100, center=True)),
+                         ("sliding mean 300, then deltas 2 / 2", dict(POST, deltas_first=False)),
+                         ("row mean and variance, then deltas", dict(norm="row", norm_vars=True, delta_order=2))):
+            ps = capi.FeatPostSpec.make(**kw)
+            scratch = torch.empty(max(capi.feat_post_scratch(ps, n, T, D), 1), dtype=torch.float64, device="cuda:0")
+            calls.append(("vpz_feat_post " + name, lambda dst, ps=ps, scratch=scratch: capi.feat_post(ctx, src, rows, dst, ps, scratch=scratch),
+                          ps.out_columns(D), ps))
+        for name, call, width, ps in calls:
+            dst = src if ps is None else torch.empty((n, T, width), dtype=torch.float32, device="cuda:0")
+            times = []
+            for _ in range(11):
+                ctx.timer_start()
+                assert call(dst) == capi.OK, ctx.last_error()
+                times.append(ctx.timer_stop())
+            ms = statistics.median(times[1:])
+            moved = "" if ps is None else "; %.1f MB read + %.1f MB written = %.2f TB/s" % (
+                src.numel() * 4 / 1e6, dst.numel() * 4 / 1e6, (src.numel() + dst.numel()) * 4 / ms / 1e9)
+            print("%-52s 64 rows of %6d samples (T = %4d): median %.1f us (min %.1f, max %.1f)%s" % (
+                name, samples, T, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, moved), flush=True)
+    ctx.close()
+
+
 def loudness_job():
     import time
     n = len(datas)
@@ -785,6 +916,12 @@ if args.ranges and args.batch and args.resample and args.fbank:
     sys.exit(0)
 if args.mfcc_kernel:
     mfcc_kernel_job()
+    sys.exit(0)
+if args.post_kernel:
+    post_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.mfcc and args.post:
+    post_job(args.ranges, args.resample)
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.mfcc:
     mfcc_job(args.ranges, args.resample)

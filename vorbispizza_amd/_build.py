@@ -33,6 +33,7 @@ SOURCES = {
     "pcm_fbank.hip": [],  # vpz_pcm_fbank: the same windows as Kaldi filterbank frames (per-frame mean, the folded operator on the same MFMA); vpz_pcm_mfcc: the same tile core with the cepstral stage
     "pcm_loudness.hip": [],  # vpz_pcm_loudness: windows of an interleaved device array as K-weighted step sums and a peak (float64; the recurrence cut into steps, carried exactly)
     "pcm_truepeak.hip": [],  # vpz_pcm_true_peak: the same windows' true peak (a 4x / 2x polyphase interpolator in float32, fused, one order) and sample peak; range and maxima of step sums, host only
+    "pcm_featpost.hip": ["-ffp-contract=off"],  # vpz_feat_post: deltas and mean / variance normalisation of a padded batch of feature frames (every fused step is written as one)
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-constant-logical-operand", "-fno-strict-aliasing"]
@@ -63,6 +64,7 @@ def _deps(src):
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_mfcc.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_loudness.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_r128.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_featpost.h"))
     return deps
 
 
@@ -88,7 +90,8 @@ def build_host(force=False, verbose=False):
                    os.path.join(inc, "vorbispizza_multi_fbank.h"), os.path.join(inc, "vorbispizza_pcm_loudness.h"),
                    os.path.join(inc, "vorbispizza_multi_loudness.h"), os.path.join(inc, "vorbispizza_pcm_r128.h"),
                    os.path.join(inc, "vorbispizza_multi_r128.h"), os.path.join(inc, "vorbispizza_pcm_mfcc.h"),
-                   os.path.join(inc, "vorbispizza_multi_mfcc.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi_mfcc.h"), os.path.join(inc, "vorbispizza_pcm_featpost.h"),
+                   os.path.join(inc, "vorbispizza_multi_featpost.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

@@ -225,6 +225,49 @@ _PCM_MFCC_SIGNATURES = [
     ("vpz_pcm_mfcc", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(MfccSpec), C.c_int32, _vp, _vp, C.c_int64]),
 ]
 PCM_MFCC_EXPORTED_SYMBOLS = [s[0] for s in _PCM_MFCC_SIGNATURES]
+
+
+NORM_NONE, NORM_ROW, NORM_SLIDING = 0, 1, 2
+POST_NORM_FIRST, POST_DELTAS_FIRST = 0, 1
+FEAT_COLUMNS_FIRST, FEAT_FRAMES_FIRST = 0, 1
+FEAT_MAX_COLUMNS, FEAT_MAX_DELTA_ORDER, FEAT_MAX_DELTA_WINDOW, FEAT_MAX_CMN_WINDOW, FEAT_CHUNK = 256, 3, 8, 1 << 20, 64
+
+
+class FeatPostSpec(C.Structure):
+    """vpz_feat_post_spec (include/vorbispizza_pcm_featpost.h).  FeatPostSpec.make(...) takes the names a Python caller uses; the window's
+    defaults are Kaldi's apply-cmvn-sliding (600, 100), the deltas' add-deltas' window 2."""
+    _fields_ = [("var_floor", C.c_double), ("pad_value", C.c_double), ("norm", C.c_int32), ("norm_vars", C.c_int32), ("center", C.c_int32),
+                ("cmn_window", C.c_int32), ("min_window", C.c_int32), ("delta_order", C.c_int32), ("delta_window", C.c_int32),
+                ("order", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 11)]
+
+    @classmethod
+    def make(cls, norm="none", norm_vars=False, center=False, cmn_window=600, min_window=100, var_floor=1e-10, delta_order=0, delta_window=2,
+             deltas_first=False, pad_value=0.0, frames_first=True):
+        norms = {None: NORM_NONE, "none": NORM_NONE, "row": NORM_ROW, "sliding": NORM_SLIDING}
+        if norm not in norms:
+            raise ValueError("FeatPostSpec: norm is None, 'row' or 'sliding'")
+        s = cls()
+        s.var_floor, s.pad_value = float(var_floor), float(pad_value)
+        s.norm, s.norm_vars, s.center = norms[norm], int(bool(norm_vars)), int(bool(center))
+        s.cmn_window, s.min_window, s.delta_order, s.delta_window = int(cmn_window), int(min_window), int(delta_order), int(delta_window)
+        s.order = POST_DELTAS_FIRST if deltas_first else POST_NORM_FIRST
+        s.layout = FEAT_FRAMES_FIRST if frames_first else FEAT_COLUMNS_FIRST
+        return s
+
+    def out_columns(self, D):
+        """D_out of D source columns."""
+        return int(D) * (self.delta_order + 1)
+
+
+# include/vorbispizza_pcm_featpost.h (a header of its own again)
+_PCM_FEATPOST_SIGNATURES = [
+    ("vpz_feat_delta_scales", C.c_int, [C.POINTER(FeatPostSpec), C.c_int32, _vp, C.c_int64]),
+    ("vpz_feat_cmn_window", C.c_int, [C.POINTER(FeatPostSpec), C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    ("vpz_feat_post_scratch", C.c_int, [C.POINTER(FeatPostSpec), C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_int64)]),
+    ("vpz_feat_post", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(FeatPostSpec), C.c_int32, _vp, _vp, C.c_int64, _vp,
+                                C.c_int64]),
+]
+PCM_FEATPOST_EXPORTED_SYMBOLS = [s[0] for s in _PCM_FEATPOST_SIGNATURES]
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
 # include/vorbispizza_pcm_loudness.h (a header of its own again)
 _PCM_LOUDNESS_SIGNATURES = [
@@ -276,7 +319,7 @@ def lib():
                 pass
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
-                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES)
+                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -529,6 +572,71 @@ def mfcc_table(spec):
     if rc != OK:
         raise ValueError("vpz_mfcc_table failed (status %d)" % rc)
     return table
+
+
+def feat_delta_scales(spec, i):
+    """vpz_feat_delta_scales: float32 [2 i w + 1], the scales s_i of a FeatPostSpec's deltas (index j + i w); needs no device.  A refused
+    spec or order raises ValueError."""
+    rc = lib().vpz_feat_delta_scales(C.byref(spec), i, None, 0)
+    if rc != OK:
+        raise ValueError("vpz_feat_delta_scales refuses the spec or the order %r (status %d)" % (i, rc))
+    scales = np.zeros(2 * int(i) * int(spec.delta_window) + 1, dtype=np.float32)
+    rc = lib().vpz_feat_delta_scales(C.byref(spec), i, scales.ctypes.data, scales.size)
+    if rc != OK:
+        raise ValueError("vpz_feat_delta_scales failed (status %d)" % rc)
+    return scales
+
+
+def feat_cmn_window(spec, t, n):
+    """vpz_feat_cmn_window: (a, b), the frames [a, b) that frame t of a row of n real frames is normalised over; needs no device.  A refused
+    spec, t or n raises ValueError."""
+    a, b = C.c_int64(0), C.c_int64(0)
+    rc = lib().vpz_feat_cmn_window(C.byref(spec), t, n, C.byref(a), C.byref(b))
+    if rc != OK:
+        raise ValueError("vpz_feat_cmn_window refuses the spec, t = %r or n = %r (status %d)" % (t, n, rc))
+    return a.value, b.value
+
+
+def feat_post_scratch(spec, n_rows, T, D):
+    """vpz_feat_post_scratch: the float64 elements of scratch memory a call needs; needs no device.  A refusal raises ValueError."""
+    elems = C.c_int64(0)
+    rc = lib().vpz_feat_post_scratch(C.byref(spec), n_rows, T, D, C.byref(elems))
+    if rc != OK:
+        raise ValueError("vpz_feat_post_scratch refuses the spec or the sizes (status %d)" % rc)
+    return elems.value
+
+
+def feat_post(ctx, src, rows, dst, spec, scratch=None):
+    """vpz_feat_post (vorbispizza_pcm_featpost.h): deltas and mean / variance normalisation of rows of the float32 device tensor `src` --
+    contiguous, [src_rows, T, D] (FEAT_FRAMES_FIRST) or [src_rows, D, T]: MFCC, filterbank or log-mel frames alike -- into rows of `dst`,
+    [dst_rows, T, D_out] or [dst_rows, D_out, T]; rows: [(src_row, real_frames, row)]; spec: a FeatPostSpec.  scratch: a float64 device
+    tensor of feat_post_scratch(...) elements, which the caller keeps until the context's stream has passed the call; None: one is made
+    here and the call waits for the stream before it returns.  Otherwise asynchronous on the context's stream; returns the status (a
+    refusal is an answer, not an exception)."""
+    ff = spec.layout == FEAT_FRAMES_FIRST
+    if src.dim() != 3 or dst.dim() != 3:
+        raise ValueError("feat_post: src and dst have three dimensions")
+    T, D = (int(src.shape[1]), int(src.shape[2])) if ff else (int(src.shape[2]), int(src.shape[1]))
+    D_out = D * (max(int(spec.delta_order), 0) + 1)
+    want = (T, D_out) if ff else (D_out, T)
+    if tuple(dst.shape[1:]) != want:
+        raise ValueError("feat_post: dst is [rows, %d, %d], not %r" % (want + (tuple(dst.shape),)))
+    for x in (src, dst):
+        if str(x.dtype) != "torch.float32" or not x.is_contiguous():
+            raise ValueError("feat_post: src and dst are contiguous float32 tensors")
+    desc =np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    own = None
+    if scratch is None:
+        need = C.c_int64(0)
+        if lib().vpz_feat_post_scratch(C.byref(spec), desc.shape[0], T, D, C.byref(need)) == OK and need.value:
+            import torch
+            own = scratch = torch.empty(need.value, dtype=torch.float64, device=src.device)
+    _sync_producer(src, dst)
+    rc = lib().vpz_feat_post(ctx._h, _ptr(src), int(src.shape[0]), T, D, C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                             int(dst.shape[0]), _ptr(scratch), _numel(scratch))
+    if own is not None:
+        ctx.synchronize()
+    return rc
 
 
 def loudness_filter(sample_rate):

@@ -80,7 +80,10 @@ __global__ __launch_bounds__(kPackBlock) void pcm_pack_kernel(const T *__restric
 }
 
 // ---- what the three row launches share (vpz_internal.hpp declares check_row_launch, upload_rows and layout_of) ----
-// `bytes` bytes from `p` lie inside one allocation of device memory on the context's device
+}  // namespace
+
+// `bytes` bytes from `p` lie inside one allocation of device memory on the context's device (vpz_internal.hpp declares it: vpz_feat_post
+// checks its scratch memory with it)
 bool device_range(Context *ctx, const void *p, uint64_t bytes)
 {
     hipPointerAttribute_t at;
@@ -99,6 +102,8 @@ bool device_range(Context *ctx, const void *p, uint64_t bytes)
     const uintptr_t b = reinterpret_cast<uintptr_t>(base), a = reinterpret_cast<uintptr_t>(p);
     return a >= b && bytes <= size && a - b <= size - bytes;
 }
+
+namespace {
 
 // room for n descriptors in the page-locked buffer and its device copy; the previous call's copy has left the buffer
 int pack_room(Context *ctx, size_t n)

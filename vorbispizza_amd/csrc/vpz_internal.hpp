@@ -124,6 +124,8 @@ struct RowLaunch {
 // the contract of a row launch, checked: VPZ_OK, or the refusal as the context's error (nothing is enqueued; the arithmetic comes before
 // any HIP call); n_rows == 0 passes like any other count
 int check_row_launch(Context *ctx, const RowLaunch &q);
+// `bytes` bytes from `p` lie inside one allocation of device memory on the context's device (what check_row_launch asks of both arrays)
+bool device_range(Context *ctx, const void *p, uint64_t bytes);
 // the descriptors of a checked launch on their way to the device, on the context's stream: *d_rows is what the kernel reads
 int upload_rows(Context *ctx, int32_t n_rows, const vpz_pack_row *rows, const vpz_pack_row **d_rows);
 // a VPZ_OUT_* layout as (int16 elements, planar); false: none of the four

@@ -39,6 +39,8 @@
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
 // vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
 // vpzm_decode_ranges_mfcc (include/vorbispizza_multi_mfcc.h) is the same call with vpz_pcm_mfcc as that stage: Kaldi MFCC frames.
+// vpzm_decode_ranges_fbank_post / _mfcc_post (include/vorbispizza_multi_featpost.h) are those two with vpz_feat_post behind the feature
+// launch: it writes a lane temporary [members][T][D], and the post launches deliver deltas and normalisation into the group's piece.
 //
 // vpzm_measure_loudness (include/vorbispizza_multi_loudness.h) is a batch call whose delivery measures instead of moving: one
 // vpz_pcm_loudness launch per sample rate among a sub-batch's members, into a temporary of the lane's; the step sums and peaks come down
@@ -80,6 +82,8 @@
 #include "../../include/vorbispizza_multi_fbank.h"
 #include "../../include/vorbispizza_pcm_mfcc.h"
 #include "../../include/vorbispizza_multi_mfcc.h"
+#include "../../include/vorbispizza_pcm_featpost.h"
+#include "../../include/vorbispizza_multi_featpost.h"
 #include "../../include/vorbispizza_pcm_loudness.h"
 #include "../../include/vorbispizza_multi_loudness.h"
 #include "../../include/vorbispizza_pcm_r128.h"
@@ -285,8 +289,10 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     // (kLoud: a loudness call's step sums [members][max_steps] float64 and, behind them, peaks [members] float32, between the
     // vpz_pcm_loudness launches and the one copy that brings them down; an R 128 call's true peaks [members] float32 lie behind the peaks;
     // owned like kMono)
-    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kLoud, kBuffers };
-    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
+    // (kFeat: a posted fbank or MFCC call's feature frames [members][T][D] float32, between the feature launch and the vpz_feat_post
+    // launches that read them; kPostScratch: those launches' chunk sums, float64; owned like kMono)
+    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kLoud, kFeat, kPostScratch, kBuffers };
+    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
     float *residue() const { return static_cast<float *>(buf[kResidue].p); }  // (float32 or int16 values; the ABI's parameter is float-typed)
     int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
@@ -295,6 +301,7 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     float *f0_amp() const { return static_cast<float *>(buf[kF0Amp].p); }
     float *f0_coeff() const { return static_cast<float *>(buf[kF0Coeff].p); }
     float *mono() const { return static_cast<float *>(buf[kMono].p); }
+    float *feat() const { return static_cast<float *>(buf[kFeat].p); }
 };
 
 struct Slot {  // page-locked batch arrays of one sub-batch in flight (a device-decoded one holds packets, spans and payload only)
@@ -399,6 +406,8 @@ struct Batch {
     const vpz_fbank_spec *fbank = nullptr;
     // kMfcc: the same with Kaldi MFCC frames of this spec (`dst` is [rows][T][n_ceps] or transposed)
     const vpz_mfcc_spec *mfcc = nullptr;
+    // kFbank, kMfcc: vpz_feat_post of this spec behind the feature launch (`dst` is [rows][T][D_out] or transposed); null: none
+    const vpz_feat_post_spec *post = nullptr;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
     // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
@@ -411,21 +420,56 @@ struct Batch {
     const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
     const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : "vpzm_decode_ranges_logmel"; }
     const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : "log-mel"; }
-    // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `dst`
-    int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d) const
+    // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `to` (the group's piece, or a
+    // posted call's temporary), which has `to_rows` rows
+    int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d, void *to, int64_t to_rows) const
     {
-        if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), dst, rows);
-        if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), dst, rows);
-        return vpz_pcm_logmel(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), dst, rows);
+        if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), to, to_rows);
+        if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), to, to_rows);
+        return vpz_pcm_logmel(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), to, to_rows);
+    }
+    // a posted call: the mel stage's spec, a row's frames T, its real frames T_L of J samples and the feature launch's columns D
+    const vpz_fbank_spec &mel_stage() const { return kind == kMfcc ? mfcc->fbank : *fbank; }
+    int64_t feat_T() const { return 1 + (frames - mel_stage().win) / mel_stage().hop; }
+    int64_t real_frames(int64_t J) const { return J < mel_stage().win ? 0 : 1 + (J - mel_stage().win) / mel_stage().hop; }
+    int32_t feat_D() const { return kind == kMfcc ? mfcc->n_ceps : fbank->n_mels; }
+    // a posted call's vpz_feat_post launches on the lane's stream: rows of `src` ([src_rows][T][D], the lane's temporary) into their rows
+    // of `dst`; the chunk sums live in the lane's scratch array, which grows here
+    // `*own`: the text of a failure that is not the context's (its last error says nothing about it), else null.  Descriptors without
+    // real frames (pad rows) need no chunk sums: no scratch memory is sized or grown for them
+    int post_rows(Lane &L, const void *src, int64_t src_rows, const std::vector<vpz_feat_row> &d, const char **own) const
+    {
+        *own = nullptr;
+        int64_t need = 0;
+        bool any_real = false;
+        for (const vpz_feat_row &r : d) any_real = any_real || r.real_frames > 0;
+        if (any_real && vpz_feat_post_scratch(post, (int32_t)d.size(), feat_T(), feat_D(), &need) != VPZ_OK) {
+            *own = "the scratch memory's size overflows";
+            return VPZ_E_INVALID_ARG;
+        }
+        if (need > 0 && !L.buf[Lane::kPostScratch].grow(L.ctx, (size_t)need, sizeof(double))) {
+            *own = "the chunk sums' device memory could not be allocated";
+            return VPZ_E_NOMEM;
+        }
+        return vpz_feat_post(L.ctx, src, src_rows, feat_T(), feat_D(), post, (int32_t)d.size(), d.data(), dst, rows, need > 0 ? L.buf[Lane::kPostScratch].p : nullptr,
+                             need);
     }
 
     // These descriptors (samples = 0 each) get rows of no samples -- zeros, or the silence row of a log-mel call or the pad_value row of
-    // an fbank or MFCC call, which their own kernels write -- from a launch that reads nothing: the destination stands in for a source of no elements
-    int empty_rows(vpz_context *ctx, const std::vector<vpz_pack_row> &d) const
+    // an fbank or MFCC call (a posted one: the post spec's), which their own kernels write -- from a launch that reads nothing: the
+    // destination stands in for a source of no elements
+    int empty_rows(Lane &L, const std::vector<vpz_pack_row> &d) const
     {
-        if (features()) return feature_rows(ctx, dst, 0, d);
-        return vpz_pcm_pack(ctx, dst, 0, channels, (int32_t)d.size(), d.data(), dst, rows, frames, layout);
+        if (post) {
+            std::vector<vpz_feat_row> none;
+            for (const vpz_pack_row &r : d) none.push_back(vpz_feat_row{0, 0, r.row});
+            const char *own;  // (no scratch memory is asked for: none can fail)
+            return post_rows(L, dst, 0, none, &own);
+        }
+        if (features()) return feature_rows(L.ctx, dst, 0, d, dst, rows);
+        return vpz_pcm_pack(L.ctx, dst, 0, channels, (int32_t)d.size(), d.data(), dst, rows, frames, layout);
     }
+    const char *empty_step() const { return post ? "vpz_feat_post" : features() ? feature_step() : "vpz_pcm_pack"; }
 };
 
 // ceil(samples * up / down): the output samples of a resampled window (the definition's J)
@@ -915,8 +959,8 @@ struct GroupRun {
             for (const Job &J : jobs)
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
-            if (!rows.empty()) ok = batch.empty_rows(G.lanes[0].ctx, rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!rows.empty()) ok = batch.empty_rows(G.lanes[0], rows) == VPZ_OK;
+            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1313,7 +1357,7 @@ struct SubCall {
         if (B.measured()) {
             rc = measure_rows(rows, staged);
         } else if (!staged) {
-            rc = launched(B.features() ? B.feature_step() : "vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP : B.empty_rows(L.ctx, rows));
+            rc = launched(B.empty_step(), R.sw.fail_delivery ? VPZ_E_HIP : B.empty_rows(L, rows));
         } else if (B.kind == Batch::kPack) {
             rc = launched("vpz_pcm_pack", R.sw.fail_delivery ? VPZ_E_HIP
                                                              : vpz_pcm_pack(L.ctx, L.pcm(), pcm_elems, B.channels, (int32_t)rows.size(), rows.data(), B.dst,
@@ -1493,7 +1537,28 @@ struct SubCall {
         for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.frames, written[j], rows[j].row};
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
         const auto t_mel = Clock::now();
-        const int rc = launched(B.feature_step(), R.sw.fail_delivery ? VPZ_E_HIP : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, rows));
+        // (a posted call: the feature launch writes member j's frames into row j of the lane's second temporary, and vpz_feat_post's
+        // launches, stream-ordered behind it, deliver them into the group's piece with the row's real frames T_L(J))
+        std::vector<vpz_feat_row> posted;
+        if (B.post) {
+            if (!L.buf[Lane::kFeat].grow(L.ctx, rows.size() * (size_t)B.feat_T() * (size_t)B.feat_D(), sizeof(float))) {
+                R.m->fail(std::string(B.feature_call()) + ": the feature frames' device temporary could not be allocated");
+                return VPZ_E_NOMEM;
+            }
+            for (size_t j = 0; j < rows.size(); ++j) {
+                posted.push_back(vpz_feat_row{(int64_t)j, B.real_frames(written[j]), rows[j].row});
+                rows[j].row = (int64_t)j;
+            }
+        }
+        int rc = launched(B.feature_step(), R.sw.fail_delivery ? VPZ_E_HIP
+                                                                : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, rows, B.post ? (void *)L.feat() : B.dst,
+                                                                                 B.post ? (int64_t)rows.size() : B.rows));
+        if (B.post && rc == VPZ_OK) {
+            const char *own = nullptr;
+            rc = B.post_rows(L, L.feat(), (int64_t)rows.size(), posted, &own);
+            if (own) R.m->fail(std::string("vpz_feat_post: ") + own);  // (a failure in front of the call: the context's last error is an older one)
+            else rc = launched("vpz_feat_post", rc);
+        }
         if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
             fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b, B.feature_name(),
                     seconds_since(t_mel) * 1e3, rows.size(), (long long)B.frames);
@@ -1791,8 +1856,23 @@ int vpzm_decode_ranges_logmel(vpzm_dispatcher *m, int32_t n, const uint8_t *cons
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
+// a post spec fits a feature call: inside vorbispizza_pcm_featpost.h's limits (asked of the library that states them) and in the
+// feature tensor's layout (the VPZ_FEAT_* values are the VPZ_FBANK_* ones)
+static bool post_fits(const vpz_feat_post_spec *post, const vpz_fbank_spec &mel, int64_t frames, int32_t D)
+{
+    int64_t elems = 0;
+    return post->layout == mel.layout && vpz_feat_post_scratch(post, 0, 1 + (frames - mel.win) / mel.hop, D, &elems) == VPZ_OK;
+}
+
 int vpzm_decode_ranges_fbank(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                              const vpz_fbank_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    return vpzm_decode_ranges_fbank_post(m, n, data, size, ranges, spec, nullptr, frames, group_dst, results, stats);
+}
+
+int vpzm_decode_ranges_fbank_post(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                                  const vpz_fbank_spec *spec, const vpz_feat_post_spec *post, int64_t frames, void *const *group_dst,
+                                  vpzm_stream_result *results, vpzm_stats *stats)
 {
     if (!spec) return VPZM_E_ARG;
     // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
@@ -1800,12 +1880,20 @@ int vpzm_decode_ranges_fbank(vpzm_dispatcher *m, int32_t n, const uint8_t *const
     if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
     if (frames < spec->win) return VPZM_E_ARG;
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
-    const Batch batch{Batch::kFbank, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, nullptr, spec};
+    if (post && !post_fits(post, *spec, frames, spec->n_mels)) return VPZM_E_ARG;
+    const Batch batch{Batch::kFbank, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, nullptr, spec, nullptr, post};
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_decode_ranges_mfcc(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                             const vpz_mfcc_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    return vpzm_decode_ranges_mfcc_post(m, n, data, size, ranges, spec, nullptr, frames, group_dst, results, stats);
+}
+
+int vpzm_decode_ranges_mfcc_post(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                                 const vpz_mfcc_spec *spec, const vpz_feat_post_spec *post, int64_t frames, void *const *group_dst,
+                                 vpzm_stream_result *results, vpzm_stats *stats)
 {
     if (!spec) return VPZM_E_ARG;
     // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
@@ -1814,7 +1902,8 @@ int vpzm_decode_ranges_mfcc(vpzm_dispatcher *m, int32_t n, const uint8_t *const 
     if (rate < 1.0 || rate > 2147483647.0 || (double)(int32_t)rate != rate) return VPZM_E_ARG;
     if (frames < spec->fbank.win) return VPZM_E_ARG;
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
-    const Batch batch{Batch::kMfcc, 1, VPZ_OUT_PLANAR, frames, (int32_t)rate, 1, nullptr, nullptr, spec};
+    if (post && !post_fits(post, spec->fbank, frames, spec->n_ceps)) return VPZM_E_ARG;
+    const Batch batch{Batch::kMfcc, 1, VPZ_OUT_PLANAR, frames, (int32_t)rate, 1, nullptr, nullptr, spec, post};
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -51,6 +51,7 @@ RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_mul
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
 MFCC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_mfcc"]  # (vorbispizza_multi_mfcc.h)
+FEATPOST_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank_post", "vpzm_decode_ranges_mfcc_post"]  # (vorbispizza_multi_featpost.h)
 LOUDNESS_EXPORTED_SYMBOLS = ["vpzm_measure_loudness"]  # (vorbispizza_multi_loudness.h)
 LOUDNESS_DTYPE = np.dtype([("integrated", "<f8"), ("peak", "<f8"), ("steps", "<i8"), ("blocks_kept", "<i8")])  # vpzm_loudness
 R128_EXPORTED_SYMBOLS = ["vpzm_measure_r128"]  # (vorbispizza_multi_r128.h)
@@ -102,6 +103,13 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges_mfcc"):
             L.vpzm_decode_ranges_mfcc.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.MfccSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_mfcc.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_fbank_post"):
+            L.vpzm_decode_ranges_fbank_post.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.POINTER(capi.FeatPostSpec), C.c_int64, vp,
+                                                        vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_fbank_post.restype = C.c_int
+            L.vpzm_decode_ranges_mfcc_post.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.MfccSpec), C.POINTER(capi.FeatPostSpec), C.c_int64, vp,
+                                                       vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_mfcc_post.restype = C.c_int
         if hasattr(L, "vpzm_measure_loudness"):
             L.vpzm_measure_loudness.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
             L.vpzm_measure_loudness.restype = C.c_int
@@ -365,6 +373,52 @@ class Dispatcher:
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_mfcc failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats
+
+    def _decode_ranges_posted(self, name, fn, datas, ranges, frames, spec, mel, D, post, out):
+        """the posted fbank / MFCC call: spec the feature spec, mel its FbankSpec, D its columns"""
+        import torch
+        if not isinstance(post, capi.FeatPostSpec):
+            raise TypeError("%s: post is a capi.FeatPostSpec or None" % name)
+        if mel.win < 1 or frames < mel.win or mel.hop < 1 or D < 1:
+            raise ValueError("%s: hop and the feature columns must be at least 1, and frames at least win" % name)
+        if post.layout != mel.layout:
+            raise ValueError("%s: the post spec's layout (frames_first) is the feature spec's" % name)
+        if post.delta_order < 0 or post.delta_order > capi.FEAT_MAX_DELTA_ORDER:
+            raise ValueError("%s: delta_order is 0 .. %d" % (name, capi.FEAT_MAX_DELTA_ORDER))
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        T, D_out = mel.n_frames(frames), post.out_columns(D)
+        shape = (lambda rows: (rows, T, D_out)) if mel.layout == capi.FBANK_FRAMES_FIRST else (lambda rows: (rows, D_out, T))
+        out, whole, dst = self._group_tensors(name, n, shape, torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = fn(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), C.byref(post), int(frames), dst, results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_%s failed (status %d): %s" % (name, rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_fbank_post(self, datas, ranges, frames, post=None, out=None, **fbank):
+        """vpzm_decode_ranges_fbank_post: decode_ranges_fbank(datas, ranges, frames, **fbank) with Kaldi's feature post-processing behind
+        it on the device -- post: a capi.FeatPostSpec (deltas, mean / variance normalisation over the row or a sliding window;
+        include/vorbispizza_pcm_featpost.h states the definition) in the feature spec's layout.  Row k is [T, D_out] (frames_first) or
+        [D_out, T], D_out = n_mels * (delta_order + 1); its first FbankSpec.n_frames(results["samples"][k]) frames are real, the others
+        hold the POST spec's pad_value.  The result is, bit for bit, capi.feat_post over decode_ranges_fbank's tensor.  post None:
+        decode_ranges_fbank itself.  out: one contiguous float32 tensor per group, [hi - lo, T, D_out] (or [hi - lo, D_out, T]) on the
+        group's device -- anything else raises before the library is called.  Returns (parts, whole_or_None, results, stats)."""
+        if post is None:
+            return self.decode_ranges_fbank(datas, ranges, frames, out=out, **fbank)
+        spec = capi.FbankSpec.make(**fbank)
+        return self._decode_ranges_posted("decode_ranges_fbank_post", lib().vpzm_decode_ranges_fbank_post, datas, ranges, frames, spec, spec,
+                                          spec.n_mels, post, out)
+
+    def decode_ranges_mfcc_post(self, datas, ranges, frames, post=None, out=None, **mfcc):
+        """vpzm_decode_ranges_mfcc_post: decode_ranges_mfcc(datas, ranges, frames, **mfcc) with the same post-processing behind it;
+        D_out = n_ceps * (delta_order + 1).  The MFCC spec's own subtract_mean may be combined with `post`: it runs first.  post None:
+        decode_ranges_mfcc itself."""
+        if post is None:
+            return self.decode_ranges_mfcc(datas, ranges, frames, out=out, **mfcc)
+        spec = capi.MfccSpec.make(**mfcc)
+        return self._decode_ranges_posted("decode_ranges_mfcc_post", lib().vpzm_decode_ranges_mfcc_post, datas, ranges, frames, spec, spec.fbank,
+                                          spec.n_ceps, post, out)
 
     def measure_loudness(self, datas, ranges=None):
         """vpzm_measure_loudness: every entry's window (ranges None: the whole stream) measured for programme loudness on the device

@@ -92,13 +92,8 @@ struct CallScratch {
     size_t desc_cap = 0;
     hipEvent_t desc_done = nullptr;
     bool desc_pending = false;
-    void *d_cache = nullptr; size_t cache_bytes = 0;
-    void *d_dbuf = nullptr; size_t dbuf_bytes = 0;
-    // VPZ_MEM_HOST staging
-    void *d_payload = nullptr; size_t payload_bytes = 0;
-    void *d_residue = nullptr; size_t residue_bytes = 0;
-    void *d_posts = nullptr; size_t posts_bytes = 0;
-    void *d_counts = nullptr; size_t counts_bytes = 0;
+    Scratch cache, dbuf;
+    Scratch payload, residue, posts, counts;  // VPZ_MEM_HOST staging
 };
 
 }  // namespace
@@ -258,9 +253,9 @@ bool validate(vpz::EntropyImage &S, std::string &why)
     return true;
 }
 
-int grow(vpz::Context *ctx, void **buf, size_t *have, size_t need)
+int grow(vpz::Context *ctx, vpz::Scratch &b, size_t need)
 {
-    return vpz::ensure_stage(ctx, buf, have, need < 16 ? 16 : need);
+    return b.grow(ctx, need < 16 ? 16 : need, "hipMalloc(staging)");
 }
 
 int upload_image(vpz::Context *ctx, vpz::EntropyImage &I)
@@ -272,7 +267,7 @@ int upload_image(vpz::Context *ctx, vpz::EntropyImage &I)
 
 void release(vpz::CallScratch &K)
 {
-    for (void *p : {(void *)K.d_desc, (void *)K.d_index, K.d_cache, K.d_dbuf, K.d_payload, K.d_residue, K.d_posts, K.d_counts})
+    for (void *p : {(void *)K.d_desc, (void *)K.d_index, K.cache.p, K.dbuf.p, K.payload.p, K.residue.p, K.posts.p, K.counts.p})
         if (p) (void)hipFree(p);
     if (K.h_desc) (void)hipHostFree(K.h_desc);
     if (K.h_index) (void)hipHostFree(K.h_index);
@@ -371,21 +366,21 @@ int stage_in(vpz::Context *ctx, vpz::CallScratch &K, int64_t n_packets, int chan
 {
     hipStream_t st = ctx->stream;
     int rc;
-    if ((rc = grow(ctx, &K.d_cache, &K.cache_bytes, sizeof(int32_t) * (size_t)n_packets * cache_words)) != VPZ_OK) return rc;
-    if (multi_submap && (rc = grow(ctx, &K.d_dbuf, &K.dbuf_bytes, 2 * esize * (size_t)residue_values)) != VPZ_OK) return rc;
+    if ((rc = grow(ctx, K.cache, sizeof(int32_t) * (size_t)n_packets * cache_words)) != VPZ_OK) return rc;
+    if (multi_submap && (rc = grow(ctx, K.dbuf, 2 * esize * (size_t)residue_values)) != VPZ_OK) return rc;
     B = Buffers{payload, residue, posts, post_counts};
     const size_t recs = (size_t)n_packets * channels;
     if (mem_space == VPZ_MEM_HOST) {
-        if ((rc = grow(ctx, &K.d_payload, &K.payload_bytes, (size_t)payload_bytes + 8)) != VPZ_OK) return rc;
-        if ((rc = grow(ctx, &K.d_residue, &K.residue_bytes, esize * (size_t)residue_values)) != VPZ_OK) return rc;
-        if ((rc = grow(ctx, &K.d_posts, &K.posts_bytes, recs * 64 * sizeof(int16_t))) != VPZ_OK) return rc;
-        if ((rc = grow(ctx, &K.d_counts, &K.counts_bytes, recs)) != VPZ_OK) return rc;
-        VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.d_payload, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, st));
+        if ((rc = grow(ctx, K.payload, (size_t)payload_bytes + 8)) != VPZ_OK) return rc;
+        if ((rc = grow(ctx, K.residue, esize * (size_t)residue_values)) != VPZ_OK) return rc;
+        if ((rc = grow(ctx, K.posts, recs * 64 * sizeof(int16_t))) != VPZ_OK) return rc;
+        if ((rc = grow(ctx, K.counts, recs)) != VPZ_OK) return rc;
+        VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.payload.p, payload, (size_t)payload_bytes, hipMemcpyHostToDevice, st));
         // (the whole extent goes both ways: what no packet writes comes back as it was)
         if (residue && residue_values)
-            VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.d_residue, residue, esize * (size_t)residue_values, hipMemcpyHostToDevice, st));
-        B = Buffers{static_cast<const uint8_t *>(K.d_payload), K.d_residue, static_cast<int16_t *>(K.d_posts),
-                    static_cast<uint8_t *>(K.d_counts)};
+            VPZ_HIP_TRY(ctx, hipMemcpyAsync(K.residue.p, residue, esize * (size_t)residue_values, hipMemcpyHostToDevice, st));
+        B = Buffers{static_cast<const uint8_t *>(K.payload.p), K.residue.p, static_cast<int16_t *>(K.posts.p),
+                    static_cast<uint8_t *>(K.counts.p)};
     }
     VPZ_HIP_TRY(ctx, hipMemsetAsync(B.posts, 0, recs * 64 * sizeof(int16_t), st));
     return VPZ_OK;
@@ -400,9 +395,9 @@ int stage_out(vpz::Context *ctx, vpz::CallScratch &K, int64_t n_packets, int cha
     if (mem_space != VPZ_MEM_HOST) return VPZ_OK;
     const size_t recs = (size_t)n_packets * channels;
     if (residue && residue_values)
-        VPZ_HIP_TRY(ctx, hipMemcpyAsync(residue, K.d_residue, esize * (size_t)residue_values, hipMemcpyDeviceToHost, st));
-    VPZ_HIP_TRY(ctx, hipMemcpyAsync(posts, K.d_posts, recs * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, st));
-    VPZ_HIP_TRY(ctx, hipMemcpyAsync(post_counts, K.d_counts, recs, hipMemcpyDeviceToHost, st));
+        VPZ_HIP_TRY(ctx, hipMemcpyAsync(residue, K.residue.p, esize * (size_t)residue_values, hipMemcpyDeviceToHost, st));
+    VPZ_HIP_TRY(ctx, hipMemcpyAsync(posts, K.posts.p, recs * 64 * sizeof(int16_t), hipMemcpyDeviceToHost, st));
+    VPZ_HIP_TRY(ctx, hipMemcpyAsync(post_counts, K.counts.p, recs, hipMemcpyDeviceToHost, st));
     VPZ_HIP_TRY(ctx, hipStreamSynchronize(st));
     return VPZ_OK;
 }
@@ -425,7 +420,7 @@ void launch_setup(vpz_entropy_setup *S, int64_t n_packets, bool any_decoded, con
                            h.block_size0 / 2, h.block_size1 / 2, static_cast<T *>(B.residue));
     hipLaunchKernelGGL(vpz::entropy_decode_kernel<T>, dim3(grid), dim3(block), 0, st, S->img.d_image, S->call.d_desc, n_packets,
                        reinterpret_cast<const uint32_t *>(B.payload), static_cast<T *>(B.residue), B.posts, B.counts,
-                       static_cast<int32_t *>(S->call.d_cache), S->img.cache_words, static_cast<T *>(S->call.d_dbuf));
+                       static_cast<int32_t *>(S->call.cache.p), S->img.cache_words, static_cast<T *>(S->call.dbuf.p));
 }
 
 // the same two passes over a group's lane list
@@ -441,7 +436,7 @@ void launch_group(vpz_entropy_group *G, int64_t n_lanes, bool any_decoded, const
     hipLaunchKernelGGL(vpz::entropy_group_kernel<T>, dim3(grid), dim3(block), 0, st, static_cast<const vpz::ImageAddress *>(G->d_table), G->call.d_desc, G->call.d_index,
                        n_lanes,
                        reinterpret_cast<const uint32_t *>(B.payload), static_cast<T *>(B.residue), B.posts, B.counts,
-                       static_cast<int32_t *>(G->call.d_cache), G->cache_words, static_cast<T *>(G->call.d_dbuf));
+                       static_cast<int32_t *>(G->call.cache.p), G->cache_words, static_cast<T *>(G->call.dbuf.p));
 }
 
 }  // namespace

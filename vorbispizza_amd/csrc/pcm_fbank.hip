@@ -30,11 +30,14 @@
 //   lanes along the layout's inner dimension, htk_compat applied on the store index.
 // subtract_mean is a second launch on the same stream, pcm_cmn_kernel: one wave per (row, stored coefficient) over the row's real frames.
 #include <algorithm>
+#include <array>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "vpz_internal.hpp"
+#include "device_table.hpp"
 #include "fbank_tables.hpp"
 #include "mfcc_tables.hpp"
 #include "../../include/vorbispizza_pcm_fbank.h"
@@ -355,82 +358,26 @@ __global__ __launch_bounds__(kFbBlock) void pcm_cmn_kernel(const CmnArgs a)
     }
 }
 
-int table_for(Context *ctx, const vpz_fbank_spec &s, const Context::LogmelDft **out)
+int folded_for(Context *ctx, const vpz_fbank_spec &s, const Context::LogmelDft **out)
 {
-    try {
-        const std::vector<double> key = {(double)s.win, (double)s.n_fft, (double)s.window, s.preemphasis, s.scale};
-        auto it = ctx->fbank_tables.find(key);
-        if (it != ctx->fbank_tables.end()) {
-            *out = &it->second;
-            return VPZ_OK;
-        }
-        Context::LogmelDft tb;
+    const std::array<double, 5> key = {(double)s.win, (double)s.n_fft, (double)s.window, s.preemphasis, s.scale};
+    return table_for(ctx, ctx->fbank_tables, key, "vpz_pcm_fbank: out of host memory", out, [&](Context::LogmelDft &tb) {
         tb.cols = (s.n_fft / 2 + kFbCols - 1) / kFbCols * kFbCols;
         const size_t rows = 2 * (size_t)((s.win + 1) / 2);  // (an odd win: one more row, of zeros)
         std::vector<float> host(rows * 2 * (size_t)tb.cols, 0.0f);
         fbank_table_fill(s, host.data(), 2 * (size_t)tb.cols, (size_t)tb.cols);
-        void *mem = nullptr;
-        VPZ_HIP_TRY(ctx, hipMalloc(&mem, host.size() * sizeof(float)));
-        // (a blocking copy, once per table and context: the table is whole before any launch that reads it is queued)
-        const hipError_t e = hipMemcpy(mem, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(mem);
-            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_fbank: table upload", e);
-        }
-        tb.d_table = static_cast<float *>(mem);
-        try {
-            *out = &ctx->fbank_tables.emplace(key, tb).first->second;
-        } catch (const std::bad_alloc &) {
-            (void)hipFree(mem);
-            throw;
-        }
-    } catch (const std::bad_alloc &) {
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_fbank: out of host memory");
-    }
-    return VPZ_OK;
+        return upload(ctx, "vpz_pcm_fbank: table upload", tb, {{host.data(), host.size() * sizeof(float), reinterpret_cast<void **>(&tb.d_table)}});
+    });
 }
 
 int bank_for(Context *ctx, const vpz_fbank_spec &s, const Context::LogmelBank **out)
 {
-    try {
-        const std::vector<double> key = {s.sample_rate, (double)s.n_fft, (double)s.n_mels, s.low_freq, s.high_freq};
-        auto it = ctx->fbank_banks.find(key);
-        if (it != ctx->fbank_banks.end()) {
-            *out = &it->second;
-            return VPZ_OK;
-        }
+    const std::array<double, 5> key = {s.sample_rate, (double)s.n_fft, (double)s.n_mels, s.low_freq, s.high_freq};
+    return table_for(ctx, ctx->fbank_banks, key, "vpz_pcm_fbank: out of host memory", out, [&](Context::LogmelBank &bk) {
         FbankBank fb;
         fbank_bank_build(s, fb);
-        std::vector<int32_t> meta((size_t)s.n_mels * 3);
-        int32_t at = 0;
-        for (int b = 0; b < s.n_mels; ++b) {
-            meta[(size_t)b * 3] = fb.first[(size_t)b];
-            meta[(size_t)b * 3 + 1] = fb.count[(size_t)b];
-            meta[(size_t)b * 3 + 2] = at;
-            at += fb.count[(size_t)b];
-        }
-        const size_t meta_bytes = meta.size() * sizeof(int32_t), w_bytes = fb.weights.size() * sizeof(float);
-        void *mem = nullptr;
-        VPZ_HIP_TRY(ctx, hipMalloc(&mem, meta_bytes + std::max<size_t>(w_bytes, sizeof(float))));
-        Context::LogmelBank bk;
-        bk.d_meta = static_cast<int32_t *>(mem);
-        bk.d_w = reinterpret_cast<float *>(static_cast<char *>(mem) + meta_bytes);
-        hipError_t e = hipMemcpy(bk.d_meta, meta.data(), meta_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && w_bytes) e = hipMemcpy(bk.d_w, fb.weights.data(), w_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(mem);
-            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_fbank: mel bank upload", e);
-        }
-        try {
-            *out = &ctx->fbank_banks.emplace(key, bk).first->second;
-        } catch (const std::bad_alloc &) {
-            (void)hipFree(mem);
-            throw;
-        }
-    } catch (const std::bad_alloc &) {
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_fbank: out of host memory");
-    }
-    return VPZ_OK;
+        return upload_bank(ctx, "vpz_pcm_fbank: mel bank upload", fb, bk);
+    });
 }
 
 // floats of a tile's LDS at `Tt` frames: the skewed span, then (behind the means) the power tile
@@ -444,35 +391,18 @@ void lds_plan(const vpz_fbank_spec &s, int Tt, int *span_cap, int *pstride)
 // the cepstral matrix of a spec on the device, transposed: [n_mels][n_ceps], coefficient i in column i (the kernel permutes on the store)
 int cepstra_for(Context *ctx, const vpz_mfcc_spec &s, const float **out)
 {
-    try {
-        const std::vector<double> key = {(double)s.fbank.n_mels, (double)s.n_ceps, s.lifter, (double)s.htk_compat, (double)s.use_energy};
-        auto it = ctx->mfcc_tables.find(key);
-        if (it != ctx->mfcc_tables.end()) {
-            *out = it->second;
-            return VPZ_OK;
-        }
+    const std::array<double, 5> key = {(double)s.fbank.n_mels, (double)s.n_ceps, s.lifter, (double)s.htk_compat, (double)s.use_energy};
+    const DeviceTable *rec = nullptr;
+    const int rc = table_for(ctx, ctx->mfcc_tables, key, "vpz_pcm_mfcc: out of host memory", &rec, [&](DeviceTable &ct) {
         const int N = s.fbank.n_mels, n_ceps = s.n_ceps;
         std::vector<float> host((size_t)N * (size_t)n_ceps);
         for (int b = 0; b < N; ++b)
             for (int i = 0; i < n_ceps; ++i) host[(size_t)b * n_ceps + i] = mfcc_weight(s, i, b);
-        void *mem = nullptr;
-        VPZ_HIP_TRY(ctx, hipMalloc(&mem, host.size() * sizeof(float)));
-        // (a blocking copy, once per matrix and context: it is whole before any launch that reads it is queued)
-        const hipError_t e = hipMemcpy(mem, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(mem);
-            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_mfcc: cepstral matrix upload", e);
-        }
-        try {
-            *out = ctx->mfcc_tables.emplace(key, static_cast<float *>(mem)).first->second;
-        } catch (const std::bad_alloc &) {
-            (void)hipFree(mem);
-            throw;
-        }
-    } catch (const std::bad_alloc &) {
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_mfcc: out of host memory");
-    }
-    return VPZ_OK;
+        void *at = nullptr;
+        return upload(ctx, "vpz_pcm_mfcc: cepstral matrix upload", ct, {{host.data(), host.size() * sizeof(float), &at}});
+    });
+    if (rc == VPZ_OK) *out = static_cast<const float *>(rec->mem);
+    return rc;
 }
 
 // floats of an MFCC tile's LDS at `Tt` frames: lds_plan's span and power tile, a second kFbMeans area for the energies behind the means,
@@ -485,20 +415,91 @@ int mfcc_lds_plan(const vpz_fbank_spec &s, int Tt, int *span_cap, int *pstride, 
     return *span_cap + 2 * kFbMeans + Tt * *pstride + Tt * *estride;
 }
 
-}  // namespace
-
-void free_fbank_tables(Context *ctx)
+// The launch both entry points share, planned (`q.name` is the entry point's, in front of every refusal; the spec has passed its check):
+// the frames and the row launch checked, the tables fetched, the tile chosen, the descriptors on their way, `a` filled.  `floats(Tt, a)`
+// is the tile's LDS at Tt frames and sets a's span_cap and pstride; `columns` are what a frame stores.  VPZ_OK with *grid's x = 0: a
+// launch of no rows, nothing to do
+template <class Floats>
+int plan_launch(Context *ctx, const vpz_fbank_spec &s, int64_t frames, RowLaunch q, int columns, Floats floats, FbankArgs &a, dim3 *grid, size_t *lds)
 {
-    for (auto &kv : ctx->fbank_tables)
-        if (kv.second.d_table) (void)hipFree(kv.second.d_table);
-    ctx->fbank_tables.clear();
-    for (auto &kv : ctx->fbank_banks)
-        if (kv.second.d_meta) (void)hipFree(kv.second.d_meta);  // (one allocation: the weights lie behind the bands' records)
-    ctx->fbank_banks.clear();
-    for (auto &kv : ctx->mfcc_tables)
-        if (kv.second) (void)hipFree(kv.second);
-    ctx->mfcc_tables.clear();
+    char text[96];
+    auto refuse = [&](int status, const char *what) {
+        snprintf(text, sizeof text, "%s: %s", q.name, what);
+        return set_error(ctx, status, text);
+    };
+    *grid = dim3(0, 0, 0);
+    if (frames < s.win) return refuse(VPZ_E_INVALID_ARG, "frames < win (a row holds no frame)");
+    if (frames > INT64_MAX / 8) return refuse(VPZ_E_INVALID_ARG, "sizes overflow");
+    const int64_t T = 1 + (frames - s.win) / s.hop;
+    q.frames = frames;
+    q.row_elems = (unsigned __int128)(uint64_t)T * (uint64_t)columns;
+    int rc = check_row_launch(ctx, q);
+    if (rc != VPZ_OK || q.n_rows == 0) return rc;
+
+    const Context::LogmelDft *tb = nullptr;
+    const Context::LogmelBank *bk = nullptr;
+    rc = folded_for(ctx, s, &tb);
+    if (rc == VPZ_OK) rc = bank_for(ctx, s, &bk);
+    if (rc != VPZ_OK) return rc;
+
+    // the tile: 64 frames where the row has more than 32, the launch gives every CU two workgroups at that size and the LDS holds them
+    // (every tile reads the whole table from L2, so the larger tile halves that traffic); else 32 where the row has more than 16 and the
+    // LDS holds them; else 16 (a result does not depend on the tile: the same bits).  tests/test_fbank_cpu.py restates lds_plan and this
+    // choice (tile_plan), tests/mfcc_truth.py the same over mfcc_lds_plan, and hold them at every spec inside the limits
+    a.Tt = 0;
+    int room = 0;
+    const bool few = ((T + 63) / 64) * (int64_t)q.n_rows < 2 * (int64_t)ctx->num_cu;
+    for (int Tt : {64, 32, 16}) {
+        room = floats(Tt, a);
+        if ((Tt == 64 && (T <= 32 || few)) || (Tt == 32 && T <= 16) || room > kFbLdsFloats) continue;
+        a.Tt = Tt;
+        break;
+    }
+    if (a.Tt == 0) return refuse(VPZ_E_UNSUPPORTED, "no tile fits the LDS");  // (16 frames fit at every spec inside the limits)
+    const int64_t blocks = (T + a.Tt - 1) / a.Tt;
+    if (blocks > 0x7fffffff) return refuse(VPZ_E_INVALID_ARG, "a row too long for one launch");
+
+    rc = upload_rows(ctx, q.n_rows, q.rows, &a.rows);
+    if (rc != VPZ_OK) return rc;
+
+    a.src = static_cast<const float *>(q.src);
+    a.dst = static_cast<float *>(q.dst);
+    a.table = tb->d_table;
+    a.meta = bk->d_meta;
+    a.w = bk->d_w;
+    a.T = T;
+    a.n_rows = q.n_rows;
+    a.win = s.win;
+    a.hop = s.hop;
+    a.nb = s.n_fft / 2;
+    a.cols = tb->cols;
+    a.n_mels = s.n_mels;
+    a.log = s.output == VPZ_FBANK_LOG;  // (vpz_pcm_mfcc's spec has no other output)
+    a.frames_first = s.layout == VPZ_FBANK_FRAMES_FIRST;
+    a.remove_dc = s.remove_dc;
+    a.skew = s.hop % 2 == 0 ? 1 : 0;
+    a.floor = a.log ? (float)s.floor : 0.0f;
+    a.log_floor = a.log ? (float)log((double)a.floor) : 0.0f;
+    a.pad = (float)s.pad_value;
+    *grid = dim3((unsigned)blocks, (unsigned)std::min<int64_t>(q.n_rows, kFbMaxGridY));
+    *lds = sizeof(float) * (size_t)room;
+    return VPZ_OK;
 }
+
+// the tile core at the plan's tile; the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never
+// lower it under each other
+template <class Args>
+int launch_tiles(Context *ctx, void (*two)(const Args), void (*one)(const Args), const Args &args, int Tt, dim3 grid, size_t lds, const char *what)
+{
+    void (*kernel)(const Args) = Tt == 64 ? two : one;
+    VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * kFbLdsFloats)));
+    kernel<<<grid, kFbBlock, lds, ctx->stream>>>(args);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(ctx, VPZ_E_HIP, what, e);
+    return VPZ_OK;
+}
+
+}  // namespace
 
 }  // namespace vpz
 
@@ -539,73 +540,17 @@ extern "C" int vpz_pcm_fbank(vpz_context *c, const void *src_dev, int64_t src_el
     auto refuse = [&](const char *what) { return vpz::set_error(ctx, VPZ_E_INVALID_ARG, what); };
     if (!spec) return refuse("vpz_pcm_fbank: null pointer");
     if (!vpz::fbank_spec_ok(*spec)) return refuse("vpz_pcm_fbank: a spec outside the limits");
-    const vpz_fbank_spec &s = *spec;
-    if (frames < s.win) return refuse("vpz_pcm_fbank: frames < win (a row holds no frame)");
-    if (frames > INT64_MAX / 8) return refuse("vpz_pcm_fbank: sizes overflow");
-    const int64_t T = 1 + (frames - s.win) / s.hop;
-    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_fbank", src_dev, src_elems, sizeof(float), 1, 1, 1, frames, n_rows, rows, dst_dev, dst_rows,
-                                                       (unsigned __int128)(uint64_t)T * (uint64_t)s.n_mels, sizeof(float)});
-    if (rc != VPZ_OK || n_rows == 0) return rc;
-
-    const vpz::Context::LogmelDft *tb = nullptr;
-    const vpz::Context::LogmelBank *bk = nullptr;
-    rc = vpz::table_for(ctx, s, &tb);
-    if (rc == VPZ_OK) rc = vpz::bank_for(ctx, s, &bk);
-    if (rc != VPZ_OK) return rc;
-
     vpz::FbankArgs a;
-    // the tile: 64 frames where the row has more than 32, the launch gives every CU two workgroups at that size and the LDS holds them
-    // (every tile reads the whole table from L2, so the larger tile halves that traffic); else 32 where the row has more than 16 and the
-    // LDS holds them; else 16 (a result does not depend on the tile: the same bits).  tests/test_fbank_cpu.py restates lds_plan and this
-    // choice (tile_plan) and holds them at every spec inside the limits
-    a.Tt = 0;
-    const bool few = ((T + 63) / 64) * (int64_t)n_rows < 2 * (int64_t)ctx->num_cu;
-    for (int Tt : {64, 32, 16}) {
-        vpz::lds_plan(s, Tt, &a.span_cap, &a.pstride);
-        if ((Tt == 64 && (T <= 32 || few)) || (Tt == 32 && T <= 16) || a.span_cap + vpz::kFbMeans + Tt * a.pstride > vpz::kFbLdsFloats) continue;
-        a.Tt = Tt;
-        break;
-    }
-    if (a.Tt == 0) return vpz::set_error(ctx, VPZ_E_UNSUPPORTED, "vpz_pcm_fbank: no tile fits the LDS");  // (16 frames fit at every spec inside the limits)
-    const int64_t blocks = (T + a.Tt - 1) / a.Tt;
-    if (blocks > 0x7fffffff) return refuse("vpz_pcm_fbank: a row too long for one launch");
-
-    rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);
-    if (rc != VPZ_OK) return rc;
-
-    a.src = static_cast<const float *>(src_dev);
-    a.dst = static_cast<float *>(dst_dev);
-    a.table = tb->d_table;
-    a.meta = bk->d_meta;
-    a.w = bk->d_w;
-    a.T = T;
-    a.n_rows = n_rows;
-    a.win = s.win;
-    a.hop = s.hop;
-    a.nb = s.n_fft / 2;
-    a.cols = tb->cols;
-    a.n_mels = s.n_mels;
-    a.log = s.output == VPZ_FBANK_LOG;
-    a.frames_first = s.layout == VPZ_FBANK_FRAMES_FIRST;
-    a.remove_dc = s.remove_dc;
-    a.skew = s.hop % 2 == 0 ? 1 : 0;
-    a.floor = a.log ? (float)s.floor : 0.0f;
-    a.log_floor = a.log ? (float)log((double)a.floor) : 0.0f;
-    a.pad = (float)s.pad_value;
-    const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kFbMaxGridY));
-    const size_t lds = sizeof(float) * ((size_t)a.span_cap + (size_t)vpz::kFbMeans + (size_t)a.Tt * (size_t)a.pstride);
-    // (the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never lower it under each other)
-    const int max_lds = (int)(sizeof(float) * vpz::kFbLdsFloats);
-    if (a.Tt == 64) {
-        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_fbank_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        vpz::pcm_fbank_kernel<2><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(a);
-    } else {
-        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_fbank_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        vpz::pcm_fbank_kernel<1><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(a);
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_fbank kernel launch", e);
-    return VPZ_OK;
+    dim3 grid;
+    size_t lds = 0;
+    const auto floats = [&](int Tt, vpz::FbankArgs &f) {
+        vpz::lds_plan(*spec, Tt, &f.span_cap, &f.pstride);
+        return f.span_cap + vpz::kFbMeans + Tt * f.pstride;
+    };
+    const int rc = vpz::plan_launch(ctx, *spec, frames, vpz::RowLaunch{"vpz_pcm_fbank", src_dev, src_elems, sizeof(float), 1, 1, 1, 0, n_rows, rows, dst_dev, dst_rows, 0, sizeof(float)},
+                                    spec->n_mels, floats, a, &grid, &lds);
+    if (rc != VPZ_OK || grid.x == 0) return rc;
+    return vpz::launch_tiles(ctx, &vpz::pcm_fbank_kernel<2>, &vpz::pcm_fbank_kernel<1>, a, a.Tt, grid, lds, "pcm_fbank kernel launch");
 }
 
 extern "C" int vpz_mfcc_table(const vpz_mfcc_spec *spec, float *table, int64_t capacity)
@@ -628,84 +573,32 @@ extern "C" int vpz_pcm_mfcc(vpz_context *c, const void *src_dev, int64_t src_ele
     if (!spec) return refuse("vpz_pcm_mfcc: null pointer");
     if (!vpz::mfcc_spec_ok(*spec)) return refuse("vpz_pcm_mfcc: a spec outside the limits");
     const vpz_fbank_spec &s = spec->fbank;
-    if (frames < s.win) return refuse("vpz_pcm_mfcc: frames < win (a row holds no frame)");
-    if (frames > INT64_MAX / 8) return refuse("vpz_pcm_mfcc: sizes overflow");
-    const int64_t T = 1 + (frames - s.win) / s.hop;
-    int rc = vpz::check_row_launch(ctx, vpz::RowLaunch{"vpz_pcm_mfcc", src_dev, src_elems, sizeof(float), 1, 1, 1, frames, n_rows, rows, dst_dev, dst_rows,
-                                                       (unsigned __int128)(uint64_t)T * (uint64_t)spec->n_ceps, sizeof(float)});
-    if (rc != VPZ_OK || n_rows == 0) return rc;
-
-    const vpz::Context::LogmelDft *tb = nullptr;
-    const vpz::Context::LogmelBank *bk = nullptr;
     vpz::MfccArgs m;
     vpz::FbankArgs &a = m.f;
-    rc = vpz::table_for(ctx, s, &tb);
-    if (rc == VPZ_OK) rc = vpz::bank_for(ctx, s, &bk);
-    if (rc == VPZ_OK) rc = vpz::cepstra_for(ctx, *spec, &m.c.ct);
+    dim3 grid;
+    size_t lds = 0;
+    const auto floats = [&](int Tt, vpz::FbankArgs &f) { return vpz::mfcc_lds_plan(s, Tt, &f.span_cap, &f.pstride, &m.c.estride); };
+    int rc = vpz::plan_launch(ctx, s, frames, vpz::RowLaunch{"vpz_pcm_mfcc", src_dev, src_elems, sizeof(float), 1, 1, 1, 0, n_rows, rows, dst_dev, dst_rows, 0, sizeof(float)},
+                              spec->n_ceps, floats, a, &grid, &lds);
+    if (rc != VPZ_OK || grid.x == 0) return rc;
+
+    // the cepstral stage's own
+    rc = vpz::cepstra_for(ctx, *spec, &m.c.ct);
     if (rc != VPZ_OK) return rc;
-
-    // the tile: vpz_pcm_fbank's rule over this launch's own plan (a result does not depend on the tile: the same bits)
-    a.Tt = 0;
-    int floats = 0;
-    const bool few = ((T + 63) / 64) * (int64_t)n_rows < 2 * (int64_t)ctx->num_cu;
-    for (int Tt : {64, 32, 16}) {
-        floats = vpz::mfcc_lds_plan(s, Tt, &a.span_cap, &a.pstride, &m.c.estride);
-        if ((Tt == 64 && (T <= 32 || few)) || (Tt == 32 && T <= 16) || floats > vpz::kFbLdsFloats) continue;
-        a.Tt = Tt;
-        break;
-    }
-    if (a.Tt == 0) return vpz::set_error(ctx, VPZ_E_UNSUPPORTED, "vpz_pcm_mfcc: no tile fits the LDS");  // (16 frames fit at every spec inside the limits)
-    const int64_t blocks = (T + a.Tt - 1) / a.Tt;
-    if (blocks > 0x7fffffff) return refuse("vpz_pcm_mfcc: a row too long for one launch");
-
-    rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);
-    if (rc != VPZ_OK) return rc;
-
-    a.src = static_cast<const float *>(src_dev);
-    a.dst = static_cast<float *>(dst_dev);
-    a.table = tb->d_table;
-    a.meta = bk->d_meta;
-    a.w = bk->d_w;
-    a.T = T;
-    a.n_rows = n_rows;
-    a.win = s.win;
-    a.hop = s.hop;
-    a.nb = s.n_fft / 2;
-    a.cols = tb->cols;
-    a.n_mels = s.n_mels;
-    a.log = 1;
-    a.frames_first = s.layout == VPZ_FBANK_FRAMES_FIRST;
-    a.remove_dc = s.remove_dc;
-    a.skew = s.hop % 2 == 0 ? 1 : 0;
-    a.floor = (float)s.floor;
-    a.log_floor = (float)log((double)a.floor);
-    a.pad = (float)s.pad_value;
     m.c.n_ceps = spec->n_ceps;
     m.c.use_energy = spec->use_energy;
     m.c.htk = spec->htk_compat;
     m.c.sc2 = (float)s.scale * (float)s.scale;
     m.c.log_eps = (float)log((double)0x1p-23f);
     m.c.log_efloor = (float)spec->energy_floor > 0.0f ? (float)log((double)(float)spec->energy_floor) : -INFINITY;
-    const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kFbMaxGridY));
-    const size_t lds = sizeof(float) * (size_t)floats;
-    // (the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never lower it under each other)
-    const int max_lds = (int)(sizeof(float) * vpz::kFbLdsFloats);
-    if (a.Tt == 64) {
-        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_mfcc_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        vpz::pcm_mfcc_kernel<2><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(m);
-    } else {
-        VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&vpz::pcm_mfcc_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        vpz::pcm_mfcc_kernel<1><<<grid, vpz::kFbBlock, lds, ctx->stream>>>(m);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_mfcc kernel launch", e);
-    if (!spec->subtract_mean) return VPZ_OK;
+    rc = vpz::launch_tiles(ctx, &vpz::pcm_mfcc_kernel<2>, &vpz::pcm_mfcc_kernel<1>, m, a.Tt, grid, lds, "pcm_mfcc kernel launch");
+    if (rc != VPZ_OK || !spec->subtract_mean) return rc;
 
     // the mean over a row's real frames: behind the cepstra on the same stream, over the same descriptors
-    const vpz::CmnArgs q{a.rows, a.dst, T, n_rows, s.win, s.hop, spec->n_ceps, a.frames_first};
+    const vpz::CmnArgs q{a.rows, a.dst, a.T, n_rows, s.win, s.hop, spec->n_ceps, a.frames_first};
     const int per = vpz::kFbBlock / 64;
     vpz::pcm_cmn_kernel<<<dim3((unsigned)((spec->n_ceps + per - 1) / per), grid.y), vpz::kFbBlock, 0, ctx->stream>>>(q);
-    e = hipGetLastError();
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return vpz::set_error(ctx, VPZ_E_HIP, "pcm_cmn kernel launch", e);
     return VPZ_OK;
 }

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "vpz_internal.hpp"
+#include "device_table.hpp"
 #include "logmel_tables.hpp"
 #include "../../include/vorbispizza_pcm_logmel.h"
 
@@ -186,79 +187,22 @@ __global__ __launch_bounds__(kLmBlock) void pcm_logmel_kernel(const LogmelArgs a
 
 int dft_for(Context *ctx, int n_fft, const Context::LogmelDft **out)
 {
-    auto it = ctx->logmel_dft.find(n_fft);
-    if (it != ctx->logmel_dft.end()) {
-        *out = &it->second;
-        return VPZ_OK;
-    }
-    Context::LogmelDft tb;
-    tb.cols = (n_fft / 2 + 1 + kLmCols - 1) / kLmCols * kLmCols;
-    std::vector<float> host;
-    try {
-        host.assign((size_t)n_fft * 2 * (size_t)tb.cols, 0.0f);
-    } catch (const std::bad_alloc &) {
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_logmel: out of host memory");
-    }
-    logmel_dft_fill(n_fft, host.data(), 2 * (size_t)tb.cols, (size_t)tb.cols);
-    void *mem = nullptr;
-    VPZ_HIP_TRY(ctx, hipMalloc(&mem, host.size() * sizeof(float)));
-    // (a blocking copy, once per n_fft and context: the table is whole before any launch that reads it is queued)
-    const hipError_t e = hipMemcpy(mem, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(mem);
-        return set_error(ctx, VPZ_E_HIP, "vpz_pcm_logmel: DFT table upload", e);
-    }
-    tb.d_table = static_cast<float *>(mem);
-    try {
-        *out = &ctx->logmel_dft.emplace(n_fft, tb).first->second;
-    } catch (const std::bad_alloc &) {
-        (void)hipFree(mem);
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_logmel: out of host memory");
-    }
-    return VPZ_OK;
+    return table_for(ctx, ctx->logmel_dft, n_fft, "vpz_pcm_logmel: out of host memory", out, [&](Context::LogmelDft &tb) {
+        tb.cols = (n_fft / 2 + 1 + kLmCols - 1) / kLmCols * kLmCols;
+        std::vector<float> host((size_t)n_fft * 2 * (size_t)tb.cols, 0.0f);
+        logmel_dft_fill(n_fft, host.data(), 2 * (size_t)tb.cols, (size_t)tb.cols);
+        return upload(ctx, "vpz_pcm_logmel: DFT table upload", tb, {{host.data(), host.size() * sizeof(float), reinterpret_cast<void **>(&tb.d_table)}});
+    });
 }
 
 int bank_for(Context *ctx, const vpz_logmel_spec &s, const Context::LogmelBank **out)
 {
-    try {
-        const std::vector<double> key = {s.sample_rate, (double)s.n_fft, (double)s.n_mels, s.f_min, s.f_max, (double)s.mel_scale, (double)s.mel_norm};
-        auto it = ctx->logmel_banks.find(key);
-        if (it != ctx->logmel_banks.end()) {
-            *out = &it->second;
-            return VPZ_OK;
-        }
+    const std::array<double, 7> key = {s.sample_rate, (double)s.n_fft, (double)s.n_mels, s.f_min, s.f_max, (double)s.mel_scale, (double)s.mel_norm};
+    return table_for(ctx, ctx->logmel_banks, key, "vpz_pcm_logmel: out of host memory", out, [&](Context::LogmelBank &bk) {
         MelFilterbank fb;
         mel_build(s, fb);
-        std::vector<int32_t> meta((size_t)s.n_mels * 3);
-        int32_t at = 0;
-        for (int b = 0; b < s.n_mels; ++b) {
-            meta[(size_t)b * 3] = fb.first[(size_t)b];
-            meta[(size_t)b * 3 + 1] = fb.count[(size_t)b];
-            meta[(size_t)b * 3 + 2] = at;
-            at += fb.count[(size_t)b];
-        }
-        const size_t meta_bytes = meta.size() * sizeof(int32_t), w_bytes = fb.weights.size() * sizeof(float);
-        void *mem = nullptr;
-        VPZ_HIP_TRY(ctx, hipMalloc(&mem, meta_bytes + std::max<size_t>(w_bytes, sizeof(float))));
-        Context::LogmelBank bk;
-        bk.d_meta = static_cast<int32_t *>(mem);
-        bk.d_w = reinterpret_cast<float *>(static_cast<char *>(mem) + meta_bytes);
-        hipError_t e = hipMemcpy(bk.d_meta, meta.data(), meta_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && w_bytes) e = hipMemcpy(bk.d_w, fb.weights.data(), w_bytes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(mem);
-            return set_error(ctx, VPZ_E_HIP, "vpz_pcm_logmel: filterbank upload", e);
-        }
-        try {
-            *out = &ctx->logmel_banks.emplace(key, bk).first->second;
-        } catch (const std::bad_alloc &) {
-            (void)hipFree(mem);
-            throw;
-        }
-    } catch (const std::bad_alloc &) {
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_logmel: out of host memory");
-    }
-    return VPZ_OK;
+        return upload_bank(ctx, "vpz_pcm_logmel: filterbank upload", fb, bk);
+    });
 }
 
 // floats of a tile's LDS at `Tt` frames: the skewed span, then the power tile
@@ -270,16 +214,6 @@ void lds_plan(const vpz_logmel_spec &s, int Tt, int *span_cap, int *pstride)
 }
 
 }  // namespace
-
-void free_logmel_tables(Context *ctx)
-{
-    for (auto &kv : ctx->logmel_dft)
-        if (kv.second.d_table) (void)hipFree(kv.second.d_table);
-    ctx->logmel_dft.clear();
-    for (auto &kv : ctx->logmel_banks)
-        if (kv.second.d_meta) (void)hipFree(kv.second.d_meta);  // (one allocation: the weights lie behind the bands' records)
-    ctx->logmel_banks.clear();
-}
 
 }  // namespace vpz
 

@@ -241,34 +241,7 @@ int rate_for(Context *ctx, int32_t fs, const Context::LoudnessRate **out)
     return VPZ_OK;
 }
 
-// the context's scratch memory of at least `need` bytes
-int loudness_room(Context *ctx, size_t need)
-{
-    if (ctx->loud_scratch_bytes >= need) return VPZ_OK;
-    // (the kernels of the previous call may still use it: the stream drains before it goes)
-    VPZ_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->loud_scratch) VPZ_HIP_TRY(ctx, hipFree(ctx->loud_scratch));
-    ctx->loud_scratch = nullptr;
-    ctx->loud_scratch_bytes = 0;
-    const size_t want = need + need / 4;
-    const hipError_t e = hipMalloc(&ctx->loud_scratch, want);
-    if (e != hipSuccess) {
-        ctx->loud_scratch = nullptr;
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_loudness: hipMalloc(scratch)", e);
-    }
-    ctx->loud_scratch_bytes = want;
-    return VPZ_OK;
-}
-
 }  // namespace
-
-void free_loudness_scratch(Context *ctx)
-{
-    if (ctx->loud_scratch) (void)hipFree(ctx->loud_scratch);
-    ctx->loud_scratch = nullptr;
-    ctx->loud_scratch_bytes = 0;
-    ctx->loudness_rates.clear();
-}
 
 }  // namespace vpz
 
@@ -377,9 +350,9 @@ extern "C" int vpz_pcm_loudness(vpz_context *c, const void *src_dev, int64_t src
 
     // scratch: state [total][4] and energy [total] doubles, then unit_peak [total] and chan_peak [n_rows][channels] floats
     const size_t need = (size_t)total * (5 * sizeof(double) + sizeof(float)) + (size_t)n_rows * channels * sizeof(float) + 64;
-    rc = vpz::loudness_room(ctx, need);
+    rc = ctx->loud_scratch.grow(ctx, need, "vpz_pcm_loudness: hipMalloc(scratch)");
     if (rc != VPZ_OK) return rc;
-    double *state = static_cast<double *>(ctx->loud_scratch), *energy = state + 4 * total;
+    double *state = static_cast<double *>(ctx->loud_scratch.p), *energy = state + 4 * total;
     float *unit_peak = reinterpret_cast<float *>(energy + total), *chan_peak = unit_peak + total;
 
     const int G = vpz::kLoudBlock / channels;

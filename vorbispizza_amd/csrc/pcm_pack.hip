@@ -203,16 +203,6 @@ bool layout_of(int32_t layout, bool *s16, bool *planar)
     return *s16 || *planar || layout == VPZ_OUT_INTERLEAVED;
 }
 
-void free_pack_scratch(Context *ctx)
-{
-    if (ctx->pack_host) (void)hipHostFree(ctx->pack_host);
-    if (ctx->pack_dev) (void)hipFree(ctx->pack_dev);
-    if (ctx->pack_done) (void)hipEventDestroy(ctx->pack_done);
-    ctx->pack_host = ctx->pack_dev = nullptr;
-    ctx->pack_done = nullptr;
-    ctx->pack_cap = 0;
-}
-
 }  // namespace vpz
 
 extern "C" int vpz_pcm_pack(vpz_context *c, const void *src_dev, int64_t src_elems, int32_t channels, int32_t n_rows,

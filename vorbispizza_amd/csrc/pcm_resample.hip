@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "vpz_internal.hpp"
+#include "device_table.hpp"
 #include "resample_filter.hpp"
 #include "synth_common.hpp"
 #include "../../include/vorbispizza_pcm_resample.h"
@@ -129,57 +130,24 @@ __global__ __launch_bounds__(kRsBlock) void pcm_resample_kernel(const ResampleAr
     }
 }
 
-// the context's device copy of a ratio's table, built on first use
-int table_for(Context *ctx, int up, int down, const Context::ResampleTable **out)
+// the context's device copy of a ratio's table, built on first use: the coefficients by tap, the phases' first taps behind them
+int ratio_table(Context *ctx, int up, int down, const Context::ResampleTable **out)
 {
-    const auto key = std::make_pair(up, down);
-    auto it = ctx->resample_tables.find(key);
-    if (it != ctx->resample_tables.end()) {
-        *out = &it->second;
-        return VPZ_OK;
-    }
-    ResampleFilter f;
-    std::vector<float> by_tap;
-    try {
+    return table_for(ctx, ctx->resample_tables, std::make_pair(up, down), "vpz_pcm_resample: out of host memory", out, [&](Context::ResampleTable &tb) {
+        ResampleFilter f;
         if (!resample_build(up, down, f)) return set_error(ctx, VPZ_E_INVALID_ARG, "vpz_pcm_resample: a refused ratio");
-        by_tap.resize(f.coeff.size());
-    } catch (const std::bad_alloc &) {
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_resample: out of host memory");
-    }
-    for (int p = 0; p < up; ++p)
-        for (int k = 0; k < f.taps; ++k) by_tap[(size_t)k * (size_t)up + (size_t)p] = f.coeff[(size_t)p * (size_t)f.taps + (size_t)k];
-    Context::ResampleTable tb;
-    tb.taps = f.taps;
-    tb.first_min = *std::min_element(f.first.begin(), f.first.end());
-    const size_t coeff_bytes = by_tap.size() * sizeof(float), first_bytes = f.first.size() * sizeof(int32_t);
-    void *mem = nullptr;
-    VPZ_HIP_TRY(ctx, hipMalloc(&mem, coeff_bytes + first_bytes));
-    tb.d_coeff = static_cast<float *>(mem);
-    tb.d_first = reinterpret_cast<int32_t *>(static_cast<char *>(mem) + coeff_bytes);
-    // (blocking copies, once per ratio and context: the table is whole before any launch that reads it is queued)
-    hipError_t e = hipMemcpy(tb.d_coeff, by_tap.data(), coeff_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(tb.d_first, f.first.data(), first_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(mem);
-        return set_error(ctx, VPZ_E_HIP, "vpz_pcm_resample: coefficient table upload", e);
-    }
-    try {
-        *out = &ctx->resample_tables.emplace(key, tb).first->second;
-    } catch (const std::bad_alloc &) {
-        (void)hipFree(mem);
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_resample: out of host memory");
-    }
-    return VPZ_OK;
+        std::vector<float> by_tap(f.coeff.size());
+        for (int p = 0; p < up; ++p)
+            for (int k = 0; k < f.taps; ++k) by_tap[(size_t)k * (size_t)up + (size_t)p] = f.coeff[(size_t)p * (size_t)f.taps + (size_t)k];
+        tb.taps = f.taps;
+        tb.first_min = *std::min_element(f.first.begin(), f.first.end());
+        return upload(ctx, "vpz_pcm_resample: coefficient table upload", tb,
+                      {{by_tap.data(), by_tap.size() * sizeof(float), reinterpret_cast<void **>(&tb.d_coeff)},
+                       {f.first.data(), f.first.size() * sizeof(int32_t), reinterpret_cast<void **>(&tb.d_first)}});
+    });
 }
 
 }  // namespace
-
-void free_resample_tables(Context *ctx)
-{
-    for (auto &kv : ctx->resample_tables)
-        if (kv.second.d_coeff) (void)hipFree(kv.second.d_coeff);  // (one allocation: the offsets lie behind the coefficients)
-    ctx->resample_tables.clear();
-}
 
 }  // namespace vpz
 
@@ -224,7 +192,7 @@ extern "C" int vpz_pcm_resample(vpz_context *c, const void *src_dev, int64_t src
     if (blocks > 0x7fffffff) return refuse("vpz_pcm_resample: a row too long for one launch");
 
     const vpz::Context::ResampleTable *tb = nullptr;
-    rc = vpz::table_for(ctx, up, down, &tb);
+    rc = vpz::ratio_table(ctx, up, down, &tb);
     if (rc != VPZ_OK) return rc;
     vpz::ResampleArgs a;
     rc = vpz::upload_rows(ctx, n_rows, rows, &a.rows);

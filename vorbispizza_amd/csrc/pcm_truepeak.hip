@@ -161,25 +161,6 @@ TpCoeffs<F> coeffs_of()
     return c;
 }
 
-// the context's scratch memory of at least `need` bytes
-int true_peak_room(Context *ctx, size_t need)
-{
-    if (ctx->tp_scratch_bytes >= need) return VPZ_OK;
-    // (the kernels of the previous call may still use it: the stream drains before it goes)
-    VPZ_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->tp_scratch) VPZ_HIP_TRY(ctx, hipFree(ctx->tp_scratch));
-    ctx->tp_scratch = nullptr;
-    ctx->tp_scratch_bytes = 0;
-    const size_t want = need + need / 4;
-    const hipError_t e = hipMalloc(&ctx->tp_scratch, want);
-    if (e != hipSuccess) {
-        ctx->tp_scratch = nullptr;
-        return set_error(ctx, VPZ_E_NOMEM, "vpz_pcm_true_peak: hipMalloc(scratch)", e);
-    }
-    ctx->tp_scratch_bytes = want;
-    return VPZ_OK;
-}
-
 template <int F>
 void launch_tiles(Context *ctx, dim3 grid, size_t lds_bytes, const float *src, const vpz_pack_row *d_rows, const RowTiles *d_tiles, int n_rows, int C,
                   float2 *part)
@@ -197,13 +178,6 @@ double block_power(const double *sums, int64_t k, int len, int32_t step_len)
 double level_of(double p) { return -0.691 + 10.0 * log10(p); }
 
 }  // namespace
-
-void free_true_peak_scratch(Context *ctx)
-{
-    if (ctx->tp_scratch) (void)hipFree(ctx->tp_scratch);
-    ctx->tp_scratch = nullptr;
-    ctx->tp_scratch_bytes = 0;
-}
 
 }  // namespace vpz
 
@@ -313,9 +287,9 @@ extern "C" int vpz_pcm_true_peak(vpz_context *c, const void *src_dev, int64_t sr
         most_tiles = std::max(most_tiles, u.tiles);
     }
     if (most_tiles > 0x7fffffff) return refuse("vpz_pcm_true_peak: a row too long for one launch");
-    rc = vpz::true_peak_room(ctx, (size_t)total * sizeof(float2) + 64);
+    rc = ctx->tp_scratch.grow(ctx, (size_t)total * sizeof(float2) + 64, "vpz_pcm_true_peak: hipMalloc(scratch)");
     if (rc != VPZ_OK) return rc;
-    float2 *part = static_cast<float2 *>(ctx->tp_scratch);
+    float2 *part = static_cast<float2 *>(ctx->tp_scratch.p);
 
     const vpz_pack_row *d_up = nullptr;
     rc = vpz::upload_rows(ctx, (int32_t)up.size(), up.data(), &d_up);

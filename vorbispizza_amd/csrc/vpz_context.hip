@@ -22,18 +22,21 @@ int set_error(Context *ctx, int status, const char *what, hipError_t e)
     return status;
 }
 
-int ensure_stage(Context *ctx, void **buf, size_t *have, size_t need)
+int Scratch::grow(Context *ctx, size_t need, const char *what)
 {
-    if (*have >= need) return VPZ_OK;
-    if (*buf) {
-        VPZ_HIP_TRY(ctx, hipFree(*buf));
-        *buf = nullptr;
-        *have = 0;
+    if (bytes >= need) return VPZ_OK;
+    if (drain) VPZ_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    void *old = p;
+    p = nullptr;
+    bytes = 0;
+    if (old) VPZ_HIP_TRY(ctx, hipFree(old));
+    const size_t want = need + need / 4;
+    const hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) {
+        p = nullptr;
+        return set_error(ctx, VPZ_E_NOMEM, what, e);
     }
-    size_t want = need + need / 4;
-    hipError_t e = hipMalloc(buf, want);
-    if (e != hipSuccess) return set_error(ctx, VPZ_E_NOMEM, "hipMalloc(staging)", e);
-    *have = want;
+    bytes = want;
     return VPZ_OK;
 }
 
@@ -220,6 +223,37 @@ static void free_tables(BlockTables &t)
     if (t.d_slope) (void)hipFree(t.d_slope);
 }
 
+template <class Map>
+static void free_tables(Map &tables)
+{
+    for (auto &kv : tables) (void)hipFree(kv.second.mem);
+    tables.clear();
+}
+
+// What the PCM stages and the staging copies keep on a context: the row launches' descriptor buffers, every table built on first use,
+// the scratch memory.  A stage that adds a map or a Scratch to the context adds it here.  (The stream has drained; the device is current)
+static void free_pcm_state(Context *ctx)
+{
+    if (ctx->pack_host) (void)hipHostFree(ctx->pack_host);
+    if (ctx->pack_dev) (void)hipFree(ctx->pack_dev);
+    if (ctx->pack_done) (void)hipEventDestroy(ctx->pack_done);
+    ctx->pack_host = ctx->pack_dev = nullptr;
+    ctx->pack_done = nullptr;
+    ctx->pack_cap = 0;
+    free_tables(ctx->resample_tables);
+    free_tables(ctx->logmel_dft);
+    free_tables(ctx->logmel_banks);
+    free_tables(ctx->fbank_tables);
+    free_tables(ctx->fbank_banks);
+    free_tables(ctx->mfcc_tables);
+    ctx->loudness_rates.clear();
+    for (Scratch *s : {&ctx->stage_in, &ctx->stage_out, &ctx->loud_scratch, &ctx->tp_scratch}) {
+        if (s->p) (void)hipFree(s->p);
+        s->p = nullptr;
+        s->bytes = 0;
+    }
+}
+
 }  // namespace vpz
 
 using vpz::Context;
@@ -288,15 +322,7 @@ void vpz_context_destroy(vpz_context *c)
     for (auto &kv : ctx->tables) vpz::free_tables(kv.second);
     if (ctx->host_pool && ctx->host_pool_free) ctx->host_pool_free(ctx->host_pool);
     if (ctx->d_inv_db) (void)hipFree(ctx->d_inv_db);
-    if (ctx->stage_in) (void)hipFree(ctx->stage_in);
-    if (ctx->stage_out) (void)hipFree(ctx->stage_out);
-    if (ctx->stage_aux) (void)hipFree(ctx->stage_aux);
-    vpz::free_pack_scratch(ctx);
-    vpz::free_resample_tables(ctx);
-    vpz::free_logmel_tables(ctx);
-    vpz::free_fbank_tables(ctx);
-    vpz::free_loudness_scratch(ctx);
-    vpz::free_true_peak_scratch(ctx);
+    vpz::free_pcm_state(ctx);
     if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
     if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -418,11 +444,11 @@ int vpz_imdct_batch(vpz_context *c, int n, int64_t count, const float *spectra, 
     const float *d_in = spectra;
     float *d_out = out;
     if (mem_space == VPZ_MEM_HOST) {
-        if ((rc = vpz::ensure_stage(ctx, &ctx->stage_in, &ctx->stage_in_bytes, in_bytes)) != VPZ_OK) return rc;
-        if ((rc = vpz::ensure_stage(ctx, &ctx->stage_out, &ctx->stage_out_bytes, out_bytes)) != VPZ_OK) return rc;
-        VPZ_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_in, spectra, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_in = static_cast<const float *>(ctx->stage_in);
-        d_out = static_cast<float *>(ctx->stage_out);
+        if ((rc = ctx->stage_in.grow(ctx, in_bytes, "hipMalloc(staging)")) != VPZ_OK) return rc;
+        if ((rc = ctx->stage_out.grow(ctx, out_bytes, "hipMalloc(staging)")) != VPZ_OK) return rc;
+        VPZ_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage_in.p, spectra, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        d_in = static_cast<const float *>(ctx->stage_in.p);
+        d_out = static_cast<float *>(ctx->stage_out.p);
     }
 
     hipError_t e;

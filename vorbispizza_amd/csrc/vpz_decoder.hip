@@ -57,7 +57,7 @@ static hipError_t launch_widen_i16(const void *in, float *out, int64_t n, int nu
 
 static int grow(Context *ctx, DevBuf &b, size_t need)
 {
-    return ensure_stage(ctx, &b.p, &b.bytes, need ? need : 1);
+    return b.grow(ctx, need ? need : 1, "hipMalloc(staging)");
 }
 
 static int arena_begin(Context *ctx, PinnedArena &A, size_t need)

@@ -24,10 +24,7 @@ struct StreamState {
                                 // be done before the first one has read)
 };
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t bytes = 0;
-};
+using DevBuf = Scratch;  // the decoder's buffers grow by the context's rule (vpz_internal.hpp), none of them with a drain
 
 // Pinned host arena for the per-call descriptor uploads: copies out of it are truly asynchronous,
 // and the next call waits (on an event) only for the previous call's uploads before reusing it.

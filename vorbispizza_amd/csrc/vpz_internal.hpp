@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -35,6 +36,27 @@ struct BlockTables {
     std::vector<float> h_slope;
 };
 
+struct Context;
+
+// Device scratch memory that only grows: a call that finds fewer than `need` bytes frees them and allocates
+// `need` and a quarter more.  `drain`: kernels an earlier call queued may still use the memory, so the stream drains before it goes
+// (staging memory needs none: a host-memory call ends with a synchronise of its own).  On any failure the record is empty or as it
+// was, never half: a failed hipFree leaves it EMPTY -- the pointer is not to be used or freed again -- and returns VPZ_E_HIP; a failed
+// hipMalloc leaves it empty and returns VPZ_E_NOMEM under `what`; a failed drain leaves it as it was.  Freed by free_pcm_state or
+// its owner's teardown
+struct Scratch {
+    void *p = nullptr;
+    size_t bytes = 0;
+    bool drain = false;
+    int grow(Context *ctx, size_t need, const char *what);
+};
+
+// A device table built on first use and kept under its key (device_table.hpp): the record of one allocation, which only
+// free_tables frees.  The records below add what the launches read; their pointers lie inside `mem`
+struct DeviceTable {
+    void *mem = nullptr;
+};
+
 struct Context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -43,10 +65,7 @@ struct Context {
     std::string last_error;
     std::map<int, BlockTables> tables;  // keyed by block size (Mdct._setupCache analogue)
     float *d_inv_db = nullptr;          // 256-entry floor1 inverse dB table (Floor1.cs:407-473)
-    // staging buffers for VPZ_MEM_HOST calls (grown on demand, reused)
-    void *stage_in = nullptr;  size_t stage_in_bytes = 0;
-    void *stage_out = nullptr; size_t stage_out_bytes = 0;
-    void *stage_aux = nullptr; size_t stage_aux_bytes = 0;
+    Scratch stage_in, stage_out;  // vpz_imdct_batch's staging copies of a VPZ_MEM_HOST call
     // fork-join pool of the host-side state machine (host_pool.hpp), created by the first large synth batch
     void *host_pool = nullptr;
     void (*host_pool_free)(void *) = nullptr;
@@ -60,49 +79,38 @@ struct Context {
     size_t pack_cap = 0;  // descriptors both hold
     hipEvent_t pack_done = nullptr;
     bool pack_pending = false;
-    // vpz_pcm_resample (pcm_resample.hip): the device copy of every ratio's coefficient table, built on first use, keyed by (up, down)
-    struct ResampleTable {
-        float *d_coeff = nullptr;  // [taps][up]: a wave's lanes are consecutive phases
+    // the PCM stages' tables, every one built on first use and kept for the context's life (no eviction), and their scratch memory
+    struct ResampleTable : DeviceTable {
+        float *d_coeff = nullptr;    // [taps][up]: a wave's lanes are consecutive phases
         int32_t *d_first = nullptr;  // [up]
         int taps = 0, first_min = 0;
     };
-    std::map<std::pair<int, int>, ResampleTable> resample_tables;
-    // vpz_pcm_logmel (pcm_logmel.hip): the device copy of every n_fft's DFT table and of every spec's mel filterbank, built on first use
-    struct LogmelDft {
-        float *d_table = nullptr;  // [n_fft][2 * cols]: cos columns, then sin columns, each padded with zeros to `cols`
-        int cols = 0;              // n_fft / 2 + 1 rounded up to the kernel's column tile
+    struct LogmelDft : DeviceTable {
+        float *d_table = nullptr;  // log-mel: [n_fft][2 * cols], cos columns, then sin columns, each padded with zeros to `cols`; fbank: the
+                                   // folded table, [2 * ceil(win / 2)][2 * cols]
+        int cols = 0;              // the bins rounded up to the kernel's column tile
     };
-    struct LogmelBank {
-        int32_t *d_meta = nullptr;  // [n_mels][3]: first live bin, live bins, where the band's weights start (one allocation with d_w)
+    struct LogmelBank : DeviceTable {
+        int32_t *d_meta = nullptr;  // [n_mels][3]: first live bin, live bins, where the band's weights start
         float *d_w = nullptr;
     };
-    std::map<int, LogmelDft> logmel_dft;
-    std::map<std::vector<double>, LogmelBank> logmel_banks;  // keyed by (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
-    // vpz_pcm_fbank (pcm_fbank.hip): the device copy of every folded table -- [2 * ceil(win / 2)][2 * cols], keyed by (win, n_fft, window,
-    // preemphasis, scale) -- and of every mel bank, keyed by (sample_rate, n_fft, n_mels, low_freq, high_freq); the records are log-mel's
-    std::map<std::vector<double>, LogmelDft> fbank_tables;
-    std::map<std::vector<double>, LogmelBank> fbank_banks;
-    // vpz_pcm_mfcc (pcm_fbank.hip): the device copy of every cepstral matrix -- [n_mels][n_ceps], keyed by (n_mels, n_ceps, lifter,
-    // htk_compat, use_energy) --, freed with the fbank tables
-    std::map<std::vector<double>, float *> mfcc_tables;
-    // vpz_pcm_loudness (pcm_loudness.hip): the constants of every rate -- the two biquads and the 4x4 transition of one step of silence,
-    // built on the host on first use (kernel arguments: no device copy) -- and the launch's scratch memory, grown on demand
-    struct LoudnessRate {
+    struct LoudnessRate {  // the two biquads and the 4x4 transition of one step of silence: kernel arguments, no device copy
         double coeffs[10], P[16];
     };
-    std::map<int, LoudnessRate> loudness_rates;
-    void *loud_scratch = nullptr;
-    size_t loud_scratch_bytes = 0;
-    // vpz_pcm_true_peak (pcm_truepeak.hip): the launch's scratch memory -- one pair of maxima per tile --, grown on demand
-    void *tp_scratch = nullptr;
-    size_t tp_scratch_bytes = 0;
+    std::map<std::pair<int, int>, ResampleTable> resample_tables;  // (up, down)
+    std::map<int, LogmelDft> logmel_dft;                           // n_fft
+    std::map<std::array<double, 7>, LogmelBank> logmel_banks;      // (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
+    std::map<std::array<double, 5>, LogmelDft> fbank_tables;       // (win, n_fft, window, preemphasis, scale)
+    std::map<std::array<double, 5>, LogmelBank> fbank_banks;       // (sample_rate, n_fft, n_mels, low_freq, high_freq)
+    std::map<std::array<double, 5>, DeviceTable> mfcc_tables;      // (n_mels, n_ceps, lifter, htk_compat, use_energy): [n_mels][n_ceps]
+    std::map<int, LoudnessRate> loudness_rates;                    // the sample rate
+    Scratch loud_scratch{nullptr, 0, true};  // vpz_pcm_loudness: states, energies and partial sums of a launch
+    Scratch tp_scratch{nullptr, 0, true};    // vpz_pcm_true_peak: one pair of maxima per tile
 };
 enum { kResident2048 = 0, kResident256, kResident4096, kResident8192, kResident512, kResident1024 };
 
 int set_error(Context *ctx, int status, const char *what, hipError_t e = hipSuccess);
 int get_tables(Context *ctx, int n, BlockTables **out);
-int ensure_stage(Context *ctx, void **buf, size_t *have, size_t need);
-void free_pack_scratch(Context *ctx);  // (pcm_pack.hip; vpz_context_destroy calls it)
 // ---- what the row launches share (pcm_pack.hip): vpz_pcm_pack, vpz_pcm_resample and vpz_pcm_logmel ----
 // A row launch as the three agree on it: `rows` name windows of a source array -- `src_elems` elements of `src_elem` bytes, `src_channels`
 // interleaved -- and the row each goes to in a destination of `dst_rows` rows of `row_elems` elements of `dst_elem` bytes; a window of
@@ -130,11 +138,6 @@ bool device_range(Context *ctx, const void *p, uint64_t bytes);
 int upload_rows(Context *ctx, int32_t n_rows, const vpz_pack_row *rows, const vpz_pack_row **d_rows);
 // a VPZ_OUT_* layout as (int16 elements, planar); false: none of the four
 bool layout_of(int32_t layout, bool *s16, bool *planar);
-void free_resample_tables(Context *ctx);  // (pcm_resample.hip; vpz_context_destroy calls it)
-void free_logmel_tables(Context *ctx);  // (pcm_logmel.hip; vpz_context_destroy calls it)
-void free_fbank_tables(Context *ctx);  // (pcm_fbank.hip; vpz_context_destroy calls it)
-void free_loudness_scratch(Context *ctx);  // (pcm_loudness.hip; vpz_context_destroy calls it)
-void free_true_peak_scratch(Context *ctx);  // (pcm_truepeak.hip; vpz_context_destroy calls it)
 
 #define VPZ_HIP_TRY(ctx, expr)                                                   \
     do {                                                                         \

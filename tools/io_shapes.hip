@@ -20,6 +20,9 @@ typedef float f4v __attribute__((ext_vector_type(4)));
 // MODE 0 runs, 1 wg-cyclic, 2 grid-cyclic, 3 chunked: chunks of `chunk` consecutive frames, chunk c -> workgroup c mod grid,
 // inside a chunk frame f -> wave f mod W (what a kernel with an LDS hand-off of the overlap tail and one recomputed block per
 // chunk could do).  W16: 16-byte loads.  W = waves per workgroup = blockDim.x / 64
+// MODE 5: runs of `chunk` frames as MODE 0 takes them, with the stores of steady_stereo_kernel (csrc/steady_stereo.hip): 8-byte
+// non-temporal stores, 16 per frame, each wave-store one contiguous 512 B span -- register q < 4 writes samples 512 + 128 q ...
+// of a PCM row (the upper half, ascending), q >= 4 samples 128 q - 512 ... (the lower half)
 template <int MODE, bool W16, bool NTS>
 __global__ __launch_bounds__(512) void io_dual(const float *__restrict__ in, float *__restrict__ out, long frames, long ch_stride, int chunk)
 {
@@ -107,6 +110,39 @@ __global__ __launch_bounds__(512) void io_dual(const float *__restrict__ in, flo
                 for (int m = 0; m < 4; ++m) {
                     __builtin_nontemporal_store(y[2 * m], l4 + lane + 64 * m);
                     __builtin_nontemporal_store(y[2 * m + 1], r4 + lane + 64 * m);
+                }
+            }
+        }
+        return;
+    }
+    if (MODE == 5) {
+        f4v x[8];
+        for (long r = gw; r * chunk < frames; r += n_waves) {
+            const long lo = r * chunk, hi = std::min(frames, lo + chunk);
+            auto load = [&](long q) {
+                const float *p = in + q * 2048;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const f2v a = reinterpret_cast<const f2v *>(p)[lane + 64 * m];
+                    const f2v b = reinterpret_cast<const f2v *>(p)[lane + 64 * m + 512];
+                    x[m] = f4v{a.x, a.y, b.x, b.y};
+                }
+            };
+            load(lo);
+            for (long q = lo; q < hi; ++q) {
+                f4v y[8];
+#pragma unroll
+                for (int m = 0; m < 8; ++m) y[m] = x[m];
+#pragma unroll
+                for (int m = 0; m < 8; ++m) asm volatile("" ::"v"(y[m]));
+                load(q + 1 < hi ? q + 1 : q);
+                __builtin_amdgcn_sched_barrier(0);
+                float *l = out + q * 1024, *rr = out + ch_stride + q * 1024;
+#pragma unroll
+                for (int m = 0; m < 8; ++m) {
+                    const int at = m < 4 ? 512 + 2 * (lane + 64 * m) : 2 * (lane + 64 * m) - 512;
+                    __builtin_nontemporal_store(f2v{y[m].x, y[m].y}, reinterpret_cast<f2v *>(l + at));
+                    __builtin_nontemporal_store(f2v{y[m].z, y[m].w}, reinterpret_cast<f2v *>(rr + at));
                 }
             }
         }
@@ -232,7 +268,7 @@ int main()
     const double bytes = frames * 2048.0 * 8;
     printf("device: %s, %d CUs; %ld stereo frames, %.0f MiB in + %.0f MiB out per launch\n", prop.gcnArchName, cus, frames,
            frames * 8192.0 / (1 << 20), frames * 8192.0 / (1 << 20));
-    const char *names[5] = {"runs (today)", "wg-cyclic", "grid-cyclic", "chunked", "runs, phased"};
+    const char *names[6] = {"runs (today)", "wg-cyclic", "grid-cyclic", "chunked", "runs, phased", "runs, 8 B st"};
     for (int rep = 0; rep < 2; ++rep) {
         for (int per_cu : {2, 4}) {
             const int grid = cus * per_cu;
@@ -257,6 +293,12 @@ int main()
             ONE(0, false, true, 256, 40) ONE(0, false, true, 256, 48) ONE(0, false, true, 256, 63)
             ONE(4, false, true, 256, 1) ONE(4, false, true, 256, 3) ONE(4, false, true, 256, 5) ONE(4, false, true, 256, 7)
             ONE(4, false, true, 256, 11) ONE(4, false, true, 256, 13)
+        }
+        {   // steady_stereo_kernel's stores next to today's, runs of 8 frames, taken in turns (the spread of each is the probe's own)
+            const int per_cu = 2;
+            const int grid = cus * per_cu;
+            ONE(0, false, true, 256, 8) ONE(5, false, true, 256, 8) ONE(0, false, true, 256, 8) ONE(5, false, true, 256, 8)
+            ONE(0, false, true, 256, 8) ONE(5, false, true, 256, 8)
         }
         {   // one workgroup of 8 waves per CU
             const int per_cu = 1;

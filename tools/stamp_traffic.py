@@ -30,8 +30,9 @@ WORKLOADS = {
     # key: (command after the interpreter, kernel-name substrings, sources, algorithmic bytes or None = parse the log)
     "headline": (["tools/kbench.py", "--reps", "5"], ["imdct2048_kernel"],
                  ["vorbispizza_amd/csrc/imdct_fast.hip", "vorbispizza_amd/csrc/imdct_core.hpp"], 65536 * 2 * (4 * 1024 + 4 * 2048)),
-    "north_star_line": (["tools/kbench_synth.py", "--which", "olalong", "--steps", "3"], ["synth_dual_kernel<false, false, 0, false"],
-                        FUSED_SOURCES, None),
+    # (an all-steady batch: the stereo route's second kernel takes it)
+    "north_star_line": (["tools/kbench_synth.py", "--which", "olalong", "--steps", "3"], ["steady_stereo_kernel"],
+                        FUSED_SOURCES + ["vorbispizza_amd/csrc/steady_stereo.hip", "vorbispizza_amd/csrc/steady_map.hpp"], None),
     "configs2": (["tools/kbench_synth.py", "--which", "ola", "--steps", "3"], ["synth_dual_kernel<false, false, 0, false"],
                  FUSED_SOURCES, None),
     "configs4_share": (["tools/kbench_synth.py", "--which", "real", "--steps", "3"],

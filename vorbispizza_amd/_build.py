@@ -21,6 +21,7 @@ SOURCES = {
     "synth_kernels.hip": [],
     "synth_dual.hip": [],
     "synth_pairs.hip": [],   # synth_dual.hip once more, for channel pairs of streams with 4, 6, 8, ... channels
+    "steady_stereo.hip": [],  # the stereo fast path's second kernel: batches of steady long frames, overlap-added in the lanes
     "synth_big.hip": [],
     "floor0.hip": ["-ffp-contract=off"],
     "vpz_context.hip": ["-ffp-contract=off"],

@@ -232,8 +232,12 @@ __device__ __forceinline__ void imdct256_wave8(const float2 (&xa)[8], float2 *sc
 // entries for every 2048 block: tw[m] = s_tw[lane + 64 m], twAB[p] = s_twAB[64 p + lane], twBC[q] = s_twBC[8 (lane & 7) + q]; entries
 // 0 of the last two are not used): the stereo kernel keeps them across the frames of a run -- 11 KB less through the CU's LDS pipe
 // per pass.
-__device__ __forceinline__ void imdct2048_wave_x2_regs(const float2 (&xa)[8], const float2 (&xb)[8], float2 *scratch_a, float2 *scratch_b,
-                                                       const float2 (&tw)[8], const float2 (&twAB)[8], const float2 (&twBC)[8], int lane)
+// The transform up to and including the post-twiddle: lane l, register q (j = l + 64 q) gets re[q] = Re W[j] = h[2j] and
+// nim[q] = -Im W[j] = h[1023 - 2j] of each spectrum -- what steady_stereo_kernel overlap-adds where it lies (steady_map.hpp); the
+// scratch areas are free again on return.
+__device__ __forceinline__ void imdct2048_wave_x2_spectrum(const float2 (&xa)[8], const float2 (&xb)[8], float2 *scratch_a, float2 *scratch_b,
+                                                           const float2 (&tw)[8], const float2 (&twAB)[8], const float2 (&twBC)[8], int lane,
+                                                           float (&re_a)[8], float (&nim_a)[8], float (&re_b)[8], float (&nim_b)[8])
 {
     float2 za[8], zb[8];
 #pragma unroll
@@ -282,20 +286,27 @@ __device__ __forceinline__ void imdct2048_wave_x2_regs(const float2 (&xa)[8], co
         radix8_inverse(za);
         radix8_inverse(zb);
     }
-    float wa[8], wb[8];
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const float2 a = cmul(za[q], tw[q]), b = cmul(zb[q], tw[q]);
-        za[q].x = a.x;
-        wa[q] = -a.y;
-        zb[q].x = b.x;
-        wb[q] = -b.y;
+        re_a[q] = a.x;
+        nim_a[q] = -a.y;
+        re_b[q] = b.x;
+        nim_b[q] = -b.y;
     }
+}
+
+__device__ __forceinline__ void imdct2048_wave_x2_regs(const float2 (&xa)[8], const float2 (&xb)[8], float2 *scratch_a, float2 *scratch_b,
+                                                       const float2 (&tw)[8], const float2 (&twAB)[8], const float2 (&twBC)[8], int lane)
+{
+    float ra[8], wa[8], rb[8], wb[8];
+    imdct2048_wave_x2_spectrum(xa, xb, scratch_a, scratch_b, tw, twAB, twBC, lane, ra, wa, rb, wb);
+    // h[2j] = Re W[j];  h[2j+1] = -Im W[N/4-1-j], held by lane 63-lane in register 7-q
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
         const float ha = lane_mirror64(wa[7 - q], lane), hb = lane_mirror64(wb[7 - q], lane);
-        scratch_a[lane + 64 * q] = make_float2(za[q].x, ha);
-        scratch_b[lane + 64 * q] = make_float2(zb[q].x, hb);
+        scratch_a[lane + 64 * q] = make_float2(ra[q], ha);
+        scratch_b[lane + 64 * q] = make_float2(rb[q], hb);
     }
 }
 

@@ -938,6 +938,25 @@ void chain_runs(SynthPlan &P)
     }
 }
 
+// One more fact of the batch, beside the ones pass 1 gathers: every frame is the steady state of its stream, or its stream's
+// first block after a reset -- what steady_stereo_kernel walks without descriptors (steady_stereo.hip).  The packets' flags are
+// a fact of pass 1 (every packet long, long windows on both sides, already floored, planar); what is left is per stream: the
+// block in front of the call's first packet, if there is one, is a long one with a long window towards it, no window check
+// failed and no EOS trim cut the last packet.  The runs are the ones any batch of the stereo route gets.
+bool all_steady(const SynthPlan &P, const Cut &c)
+{
+    const Decoder &D = P.D;
+    if (!P.use_dual || D.pairs || !P.compact || c.batches || D.no_steady || D.channels != 2 || D.size0 != 256 || D.size1 != 2048) return false;
+    if (!P.facts.all_steady_flags || P.facts.any_floor || P.facts.any_short || P.facts.ilv_seen || !D.mismatch_packets.empty()) return false;
+    for (int s = 0; s < D.n_streams; ++s) {
+        if (D.plan.s_cnt[s] <= 0) continue;
+        const StreamState &S = D.states[s];  // (the state in front of the call: P.st is the one after it)
+        if (S.has_prev && !(S.prev_long && S.prev_end == 1024 && S.prev_stop == 2048)) return false;
+        if (D.plan.trim_out_count[s] >= 0) return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 // The stereo fast path takes a batch whose packets all have ONE input layout (its loads are unconditional: the
@@ -1032,6 +1051,7 @@ void plan_runs(SynthPlan &P)
     if (c.batches && !c.reuse) W.cut_hint_runs = (int64_t)P.n_runs;
     P.cut_R = c.R;
     chain_runs(P);
+    P.steady = all_steady(P, c);
     if (getenv("VPZ_HOST_PROFILE"))
         fprintf(stderr, "[vpz host] cut: %s, by %s, R %d, target %lld eighths, %zu runs for %lld slots, %d segments on %d threads, heavy below %lld, "
                         "hint (frames %lld, runs %lld), chained %lld, runs filled by %s on %d threads, chain sweep on %d threads\n",

@@ -17,6 +17,7 @@ struct BatchFacts {
     bool ilv_seen = false, planar_seen = false;  // layouts of the packets that become frames (the dual kernel wants one)
     bool group_align_ok = true;   // every interleaved packet starts on a 16-byte boundary (group mode loads 16 bytes)
     bool align2_ok = true;        // every packet starts on an 8-byte boundary (planar packets are read 8 bytes at a time)
+    bool all_steady_flags = true; // every packet: a long block with long windows on both sides, already floored, planar
     int64_t res_extent = 0;
     void note(const Decoder &D, const vpz_packet &pk)
     {
@@ -32,11 +33,13 @@ struct BatchFacts {
         else planar_seen = true;
         if (pk.residue_offset & 3) group_align_ok = false;  // group mode reads every packet in 16-byte pieces
         if (pk.residue_offset & 1) align2_ok = false;
+        if ((pk.flags & (7u | VPZ_PKT_NO_FLOOR | VPZ_PKT_INTERLEAVED)) != (7u | VPZ_PKT_NO_FLOOR)) all_steady_flags = false;
     }
     void merge(const BatchFacts &o)
     {
         any_floor |= o.any_floor; any_floor0 |= o.any_floor0; need_coupling |= o.need_coupling; any_short |= o.any_short;
         ilv_seen |= o.ilv_seen; planar_seen |= o.planar_seen; group_align_ok &= o.group_align_ok; align2_ok &= o.align2_ok;
+        all_steady_flags &= o.all_steady_flags;
         res_extent = std::max(res_extent, o.res_extent);
     }
 };
@@ -81,6 +84,9 @@ struct SynthPlan {
     size_t n_runs = 0, runs_cap = 0;
     bool host_failed = false;  // a share of a fork-join threw (allocation): the call returns VPZ_E_NOMEM
     int64_t n_chained = 0;
+    bool steady = false;       // one more batch fact, set with the runs: EVERY frame is the steady state of its stream (a 2048 block
+                               // after a 2048 block, long windows on both sides, already floored, planar) or a stream's first block
+                               // after a reset -- such a batch may take steady_stereo_kernel (the launch looks at the PCM's layout)
     int cut_R = 0;  // the run length (or cost target, in passes) plan_runs settled on
     int fill_threads = 1, chain_threads = 1;  // threads that wrote the run records / swept them for chaining (VPZ_HOST_PROFILE)
 

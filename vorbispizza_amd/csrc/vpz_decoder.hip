@@ -200,6 +200,7 @@ int vpz_decoder_create(vpz_context *c, const vpz_stream_config *cfg, int32_t n_s
     for (int f = 0; f < 8; ++f) D.packet_info[f] = get_packet_info(D.size0, D.size1, f & 1, f & 2, f & 4);
     if (const char *e = getenv("VPZ_NO_DIRECT_I16")) D.no_direct_i16 = atoi(e) != 0;  // A/B and bit-equality tests: always widen int16 residue first
     if (const char *e = getenv("VPZ_NO_CHAIN")) D.no_chain = atoi(e) != 0;  // A/B tests: every run recomputes its predecessor block
+    if (const char *e = getenv("VPZ_NO_STEADY")) D.no_steady = atoi(e) != 0;  // A/B tests: no batch takes steady_stereo_kernel
     if (const char *e = getenv("VPZ_DUAL_RUN")) D.dual_run = std::max(4, atoi(e));
     if (const char *e = getenv("VPZ_PLAN_SLOTS")) D.plan_slots = std::max<int64_t>(0, atoll(e));  // tests: long runs from small batches
     if (const char *e = getenv("VPZ_SYNTH_ABLATE")) D.ablate = atoi(e);
@@ -619,6 +620,7 @@ struct SynthCall {
         return base + (static_cast<const char *>(host_ptr) - A->base);
     }
     bool zero_copy = false;
+    bool steady_kernel = false;   // launch() gave the batch to steady_stereo_kernel (VPZ_HOST_PROFILE's `kernel` word)
 
     // The host threads this decoder's calls may use (vpz_decoder_set_host_threads / VPZ_HOST_THREADS; 0: the CPUs the process
     // may run on, divided by LOCAL_WORLD_SIZE, at most 16)
@@ -1112,7 +1114,18 @@ struct SynthCall {
         (void)hipMemsetAsync(d_stamps, 0, (16 + 16 * std::min<size_t>(kStampWaves, P.n_runs)) * sizeof(unsigned long long), ctx->stream);
         a.stamps = d_stamps;
 #endif
-        hipError_t e = P.use_dual ? (D.pairs ? launch_synth_pairs(a, P.facts.any_floor, P.facts.ilv_seen, ctx->stream) : launch_synth_dual(a, P.facts.any_floor, P.facts.ilv_seen, ctx->stream))
+        // An all-steady batch (SynthPlan::steady) to planar float32 PCM whose rows take 8-byte stores: steady_stereo_kernel
+        // walks the same runs.  The launch alone picks the kernel.
+        steady_kernel = false;
+        if (P.steady && !out_interleaved && !out_s16 && !spec_i16) {
+            int64_t bits = (int64_t)reinterpret_cast<uintptr_t>(d_out) / (int64_t)sizeof(float) | dev_channel_stride;
+            if (reinterpret_cast<uintptr_t>(d_out) % sizeof(float)) bits |= 1;
+            for (int s = 0; s < D.n_streams; ++s)
+                if (D.plan.s_cnt[s] > 0) bits |= offs[s];
+            steady_kernel = (bits & 1) == 0;
+        }
+        hipError_t e = steady_kernel ? launch_steady_stereo(a, ctx->stream)
+                     : P.use_dual ? (D.pairs ? launch_synth_pairs(a, P.facts.any_floor, P.facts.ilv_seen, ctx->stream) : launch_synth_dual(a, P.facts.any_floor, P.facts.ilv_seen, ctx->stream))
                                 : D.big ? launch_synth_big(a, P.facts.any_floor, ctx->stream) : launch_synth(a, P.facts.any_floor, ctx->stream);
         if (e != hipSuccess) return set_error(ctx, VPZ_E_HIP, "synth kernel launch", e);
 #if defined(VPZ_STAMPS) || defined(VPZ_WAVE_TIMES)
@@ -1263,8 +1276,9 @@ static int synth_impl(vpz_decoder *d, int64_t n_packets, const vpz_packet *packe
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         // (route: which kernel synthesises -- the tests read it to know that the route they ask for is the one that ran)
         const char *route = D.generic ? "generic" : plan.use_dual ? (D.pairs ? "pairs" : "stereo") : D.big ? "big" : plan.use_group ? "group" : "separate";
-        fprintf(stderr, "[vpz host] packets %lld: route %s, arena wait %.1f us, pass1 %.1f us (%s), runs %.1f us, uploads+launch %.1f us\n",
-                (long long)n_packets, route, us(t_begin, t_arena), us(t_arena, t_pass1), plan.was_parallel ? "parallel" : "serial",
+        // (kernel: on the stereo route, which of its two kernels the launch picked -- `steady` is steady_stereo_kernel)
+        fprintf(stderr, "[vpz host] packets %lld: route %s, kernel %s, arena wait %.1f us, pass1 %.1f us (%s), runs %.1f us, uploads+launch %.1f us\n",
+                (long long)n_packets, route, call.steady_kernel ? "steady" : "general", us(t_begin, t_arena), us(t_arena, t_pass1), plan.was_parallel ? "parallel" : "serial",
                 us(t_pass1, t_pass2), us(t_pass2, t_end));
     }
     return VPZ_OK;  // (window mismatches are per-packet conditions: vpz_decoder_last_packet_status)

@@ -142,6 +142,7 @@ struct Decoder {
     int64_t plan_slots = 0;  // VPZ_PLAN_SLOTS=n (tests): the resident slots the run cut plans for, on every route; 0: the kernels' own
     bool no_direct_i16 = false;
     bool no_chain = false;  // VPZ_NO_CHAIN=1 (A/B tests): no run of the stereo fast path takes its predecessor's tail over in LDS
+    bool no_steady = false;  // VPZ_NO_STEADY=1 (A/B and bit-equality tests): all-steady batches take synth_dual_kernel too (steady_stereo.hip)
     int ablate = 0;  // VPZ_SYNTH_ABLATE, tuning experiments only
     bool no_early_upload = false;  // VPZ_NO_EARLY_UPLOAD=1 (A/B tests): a host-memory call's H2D copies stay behind its host pass
     std::vector<int32_t> packet_samples;  // per packet of the last synth call

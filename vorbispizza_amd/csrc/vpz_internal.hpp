@@ -189,6 +189,8 @@ bool synth_dual_supported(int channels, int size0, int size1);
 hipError_t launch_synth_dual(const SynthArgs &args, bool has_floor, bool interleaved_in, hipStream_t stream);
 int synth_dual_resident_slots(bool has_floor, int num_cu);
 int synth_dual_waves();
+// steady_stereo.hip: the same plan's runs when every frame of the batch is the steady state (SynthPlan::steady), planar float32 PCM
+hipError_t launch_steady_stereo(const SynthArgs &args, hipStream_t stream);
 bool synth_pairs_supported(int channels, int size0, int size1);
 hipError_t launch_synth_pairs(const SynthArgs &args, bool has_floor, bool interleaved_in, hipStream_t stream);
 bool synth_big_supported(int size0, int size1);

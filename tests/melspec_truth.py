@@ -1,0 +1,235 @@
+"""THE TRUTH of the mel-spectrogram tests (include/vorbispizza_pcm_melspec.h states the definition), in float64 numpy, and what the tests
+of vpz_pcm_melspec share: the derived bound, a float32 restatement of the kernel's own network, the launch plan restated from
+csrc/pcm_melspec.hip's constants, and the case list of tests/test_pcm_melspec_gpu.py (tests/test_melspec_cpu.py holds the list to the plan
+and to the check's cap without a GPU).
+
+Truth: extend / frames_of and mel_weights64 are tests/test_logmel_cpu.py's; the spectrum is numpy.fft.rfft of the float64 windowed frames
+(re = Re X, im = -Im X; P does not see the sign).
+
+The bound (u = 2^-24).  For a frame with extended samples x[m] and window w[m], S = sum_m |x[m]| w[m]; the kernel's re and im lie within
+    d = K(n_fft) u S,        K = sqrt(2) (5 r4 + r2 + 2) + 7,   r4 / r2 the radix-4 / radix-2 passes of the n_fft/2-point complex transform
+(the header derives it: per pass a path's relative perturbation in the modulus is two sums and a product by a once-rounded twiddle,
+2u + 3u; the windowing 2u; the split pass mixes two values with moduli adding up to sqrt(2) at the most and adds 6u S; 1 for the second
+order).  Then
+    e_P = 2 |re| d + 2 |im| d + 2 d^2 + 3 u P
+    e_M = e_P W^T + (B + 2) u M        B: the largest live-bin count of a band
+and the values go through test_logmel_cpu's check_log / check_power as they stand."""
+import math
+import os
+import re
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from test_logmel_cpu import U, extend, frames_of, mel_weights64  # noqa: E402,F401
+
+NFFTS = (2048, 4096, 8192)
+FLOOR = 1e-10
+
+
+def passes(n_fft):
+    """(radix-4 passes, radix-2 passes) of the n_fft / 2-point complex transform"""
+    lg = (n_fft // 2).bit_length() - 1
+    return lg // 2, lg % 2
+
+
+def K(n_fft):
+    r4, r2 = passes(n_fft)
+    return math.sqrt(2.0) * (5 * r4 + r2 + 2) + 7
+
+
+def hann64(n_fft):
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft)
+
+
+def spectrum64(X, n_fft):
+    """(re, im), float64 [T, n_fft / 2 + 1], of frames X"""
+    Z = np.fft.rfft(np.asarray(X, dtype=np.float64) * hann64(n_fft), axis=-1)
+    return Z.real, -Z.imag
+
+
+def power_truth(X, n_fft):
+    """(P, e_P), float64 [T, n_fft / 2 + 1], of frames X"""
+    re_, im_ = spectrum64(X, n_fft)
+    d = (K(n_fft) * U * (np.abs(X) @ hann64(n_fft)))[:, None]
+    P = re_ * re_ + im_ * im_
+    return P, 2 * np.abs(re_) * d + 2 * np.abs(im_) * d + 2 * d * d + 3 * U * P
+
+
+def melspec_truth(x, L, F, n_fft, hop, W):
+    """(M, e_M), float64 [T, n_mels], of one row"""
+    P, e_P = power_truth(frames_of(x, L, F, n_fft, hop), n_fft)
+    B = int((W > 0).sum(axis=1).max())
+    M = P @ W.T
+    return M, e_P @ W.T + (B + 2) * U * M
+
+
+# ---- the kernel's own network, in float32 numpy (frames along the first axis)
+def tables64(n_fft):
+    """(w, t) in float64: the window and t[k] = (cos, -sin)(2 pi k / n_fft), exact on the axes"""
+    k = np.arange(n_fft)
+    a = 2.0 * np.pi * k / n_fft
+    c, s = np.cos(a), -np.sin(a)
+    c[[n_fft // 4, 3 * n_fft // 4]] = 0.0
+    s[[0, n_fft // 2]] = 0.0
+    return hann64(n_fft), np.stack([c, s], axis=1)
+
+
+def _fma(a, b, c):
+    """float32 fused multiply-add: the float32 product is exact in float64"""
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
+
+
+def _cmul(tr, ti, vr, vi):
+    """t * v as the header writes it"""
+    return _fma(vr, tr, -(vi * ti)), _fma(vr, ti, vi * tr)
+
+
+def network32(X, n_fft, w=None, t=None):
+    """(re, im), float32 [T, n_fft / 2 + 1]: the header's network step for step on float32 frames X, with the float32 tables w [n_fft]
+    and t [n_fft, 2] (the library's own by default rounding of tables64)"""
+    w64, t64 = tables64(n_fft)
+    w = w64.astype(np.float32) if w is None else w
+    t = t64.astype(np.float32) if t is None else t
+    N, H = n_fft, n_fft // 2
+    X = np.asarray(X, dtype=np.float32)
+    y = X * w[None, :]
+    zr, zi = y[:, 0::2].copy(), y[:, 1::2].copy()
+    n, s = H, 1
+    while n >= 4:
+        q4 = n // 4
+        # in[q + s (p + j n/4)] as [T, j, p, q]
+        ar, ai = zr.reshape(-1, 4, q4, s), zi.reshape(-1, 4, q4, s)
+        a_r, b_r, c_r, d_r = ar[:, 0], ar[:, 1], ar[:, 2], ar[:, 3]
+        a_i, b_i, c_i, d_i = ai[:, 0], ai[:, 1], ai[:, 2], ai[:, 3]
+        apc_r, apc_i, amc_r, amc_i = a_r + c_r, a_i + c_i, a_r - c_r, a_i - c_i
+        bpd_r, bpd_i, bmd_r, bmd_i = b_r + d_r, b_i + d_i, b_r - d_r, b_i - d_i
+        p = np.arange(q4)
+        t1, t2, t3 = t[2 * p * s][None, :, None, :], t[4 * p * s][None, :, None, :], t[6 * p * s][None, :, None, :]
+        o0r, o0i = apc_r + bpd_r, apc_i + bpd_i
+        o1r, o1i = _cmul(t1[..., 0], t1[..., 1], amc_r + bmd_i, amc_i - bmd_r)
+        o2r, o2i = _cmul(t2[..., 0], t2[..., 1], apc_r - bpd_r, apc_i - bpd_i)
+        o3r, o3i = _cmul(t3[..., 0], t3[..., 1], amc_r - bmd_i, amc_i + bmd_r)
+        # out[q + s (4p + j)] as [T, p, j, q]
+        zr = np.stack([o0r, o1r, o2r, o3r], axis=2).reshape(-1, H)
+        zi = np.stack([o0i, o1i, o2i, o3i], axis=2).reshape(-1, H)
+        n, s = n // 4, s * 4
+    if n == 2:
+        ar, ai = zr.reshape(-1, 2, s), zi.reshape(-1, 2, s)
+        zr = np.concatenate([ar[:, 0] + ar[:, 1], ar[:, 0] - ar[:, 1]], axis=1)
+        zi = np.concatenate([ai[:, 0] + ai[:, 1], ai[:, 0] - ai[:, 1]], axis=1)
+    k = np.arange(H // 2 + 1)
+    m = (H - k) % H
+    half = np.float32(0.5)
+    Er, Ei = (zr[:, k] + zr[:, m]) * half, (zi[:, k] - zi[:, m]) * half
+    Or, Oi = (zi[:, k] + zi[:, m]) * half, (zr[:, m] - zr[:, k]) * half
+    tr, ti = _cmul(t[k, 0][None, :], t[k, 1][None, :], Or, Oi)
+    re_, im_ = np.zeros((X.shape[0], H + 1), np.float32), np.zeros((X.shape[0], H + 1), np.float32)
+    re_[:, H - k], im_[:, H - k] = Er - tr, -(Ei - ti)  # conj(E - t O)
+    re_[:, k], im_[:, k] = Er + tr, Ei + ti
+    return re_, -im_
+
+
+def proxy_mel(X, n_fft, W, w=None, t=None):
+    """M, float64 [T, n_mels]: the network's power through the once-rounded bank (the band sums in float64: no worse than the kernel's)"""
+    re_, im_ = network32(X, n_fft, w, t)
+    P = _fma(re_, re_, im_ * im_)
+    return P.astype(np.float64) @ W.astype(np.float32).astype(np.float64).T
+
+
+# ---- the launch plan, restated
+def kernel_constants():
+    """the constants of csrc/pcm_melspec.hip's plan as the file states them"""
+    text = open(os.path.join(ROOT, "vorbispizza_amd", "csrc", "pcm_melspec.hip")).read()
+    out = {}
+    for name in ("kMsBlock", "kMsLdsFloats", "kMsMaxGridY", "kMsMelRoom", "kMsTileA", "kMsTileB", "kMsTileC"):
+        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
+        assert len(found) == 1, name
+        out[name] = int(found[0])
+    return out
+
+
+def lds_floats(n_fft, hop, Tt, k):
+    """the two complex arrays, the span, the mel tile"""
+    return 2 * n_fft + (Tt - 1) * hop + n_fft + Tt * k["kMsMelRoom"]
+
+
+def tile_plan(n_fft, hop, k=None):
+    """(frames of a tile, LDS floats of the launch): the largest tile that fits, from n_fft and hop alone; (0, None) where none does"""
+    k = k or kernel_constants()
+    for Tt in (k["kMsTileA"], k["kMsTileB"], k["kMsTileC"]):
+        if lds_floats(n_fft, hop, Tt, k) <= k["kMsLdsFloats"]:
+            return Tt, lds_floats(n_fft, hop, Tt, k)
+    return 0, None
+
+
+# ---- the cases of tests/test_pcm_melspec_gpu.py
+# name: (sample_rate, n_fft, hop, n_mels, f_min, f_max, mel_scale, mel_norm, F, the tile the plan takes).  f_max None: Nyquist, so that bin
+# n_fft / 2 is live.  Every case carries rows of L = F, F - 1 (the right-hand reflection starts at the one zero), F - n_fft / 4 (it reads
+# the zero tail), about a third (silent tiles behind it), 1 and 0.
+def _smallest(n_fft, hop, tile):
+    return (44100, n_fft, hop, 16, 0.0, None, "slaney", "slaney", n_fft // 2 + 1, tile)
+
+
+CASES = {
+    "smallest_2048_one_frame": _smallest(2048, 2048, 16), "smallest_2048_hop_1": _smallest(2048, 1, 16),
+    "smallest_4096_one_frame": _smallest(4096, 4096, 2), "smallest_4096_hop_1": _smallest(4096, 1, 16),
+    "smallest_8192_one_frame": _smallest(8192, 8192, 2), "smallest_8192_hop_1": _smallest(8192, 1, 16),
+    "odd_hop_2048_441": (44100, 2048, 441, 128, 0.0, None, "slaney", "slaney", 441 * 37 + 5, 16),        # T = 38: two whole tiles and one of 6
+    "disjoint_4096_4096": (48000, 4096, 4096, 128, 20.0, 20000.0, "htk", None, 4096 * 4 + 100, 2),       # T = 5
+    "librosa_2048_512_T15": (22050, 2048, 512, 128, 0.0, None, "slaney", "slaney", 512 * 14 + 5, 16),
+    "librosa_2048_512_T16": (22050, 2048, 512, 128, 0.0, None, "slaney", "slaney", 512 * 15 + 5, 16),
+    "librosa_2048_512_T17": (22050, 2048, 512, 128, 0.0, None, "slaney", "slaney", 512 * 16 + 5, 16),
+    "half_4096_2048_T7": (44100, 4096, 2048, 64, 0.0, None, "htk", "slaney", 2048 * 6 + 5, 8),
+    "half_4096_2048_T8": (44100, 4096, 2048, 64, 0.0, None, "htk", "slaney", 2048 * 7 + 5, 8),
+    "half_4096_2048_T9": (44100, 4096, 2048, 64, 0.0, None, "htk", "slaney", 2048 * 8 + 5, 8),
+    "widest_8192_8192_T2": (48000, 8192, 8192, 256, 0.0, None, "htk", "slaney", 8192 * 1 + 100, 2),       # the most LDS a launch asks for
+    "widest_8192_8192_T3": (48000, 8192, 8192, 256, 0.0, None, "htk", "slaney", 8192 * 2 + 100, 2),
+    "one_band_4096_1024": (44100, 4096, 1024, 1, 0.0, None, "slaney", "slaney", 1024 * 9 + 3, 16),
+    "empty_bands_2048_256": (44100, 2048, 1024, 256, 0.0, 2000.0, "slaney", None, 1024 * 6 + 3, 16),       # bands narrower than a bin
+}
+DST_ROWS = 9
+
+
+def case_weights(name):
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = CASES[name]
+    return mel_weights64(sr, n_fft, n_mels, f_min, sr / 2.0 if f_max is None else f_max, scale, norm)
+
+
+_INPUTS = {}
+
+
+def case_input(name):
+    """(src float32, rows [(src offset, L, destination row)]) of a case: broadband noise of amplitude 0.05 .. 0.5, never under 1e-3 in
+    magnitude, so that with the floor at 1e-10 the check's cap is a property of the input (test_melspec_cpu confirms it)"""
+    if name in _INPUTS:
+        return _INPUTS[name]
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = CASES[name]
+    rng = np.random.default_rng(sum(name.encode()) * 1000 + hop)
+    Ls = [F, F - 1, F - n_fft // 4, F // 3, 1, 0]
+    gap = F // 5
+    src = rng.standard_normal(2 * (len(Ls) - 1) * gap + F + 64) * 0.25
+    src = (np.sign(src) * np.maximum(np.abs(src), 1e-3)).astype(np.float32)
+    order = rng.permutation(DST_ROWS)[: len(Ls)]
+    # (the rows share one source array at odd offsets, and overlap in it)
+    rows = [(1 + 2 * i * gap, L, int(row)) for i, (L, row) in enumerate(zip(Ls, order))]
+    assert all(a % 2 == 1 and a + L <= src.size for a, L, _ in rows)
+    _INPUTS[name] = (src, rows)
+    return _INPUTS[name]
+
+
+_TRUTHS = {}
+
+
+def case_truth(name):
+    """[(M, e_M)] of a case's rows, computed once"""
+    if name not in _TRUTHS:
+        sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = CASES[name]
+        src, rows = case_input(name)
+        W = case_weights(name)
+        _TRUTHS[name] = [melspec_truth(src[a: a + L], L, F, n_fft, hop, W) for a, L, _ in rows]
+    return _TRUTHS[name]

@@ -9,6 +9,8 @@
     dispatcher_probe.py --resample-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --logmel [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --logmel-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --melspec [--nfft N --hop H] [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --melspec-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --fbank [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --fbank-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --mfcc [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
@@ -50,6 +52,12 @@ RATE Hz, mono, then on the device torch.stft (center, reflect, periodic Hann), a
 (vpz_mel_filterbank as a dense matrix), clamp and log10 -- against decode_ranges_logmel; two dispatchers taking turns as above, the
 largest difference of the two tensors printed.  With VPZM_PROFILE=1 the library prints the log-mel launch's own time per sub-batch.
 --logmel-kernel: vpz_pcm_logmel alone, the Whisper spec, 64 windows of one second and of thirty, both layouts, the context's event timer.
+--ranges SAMPLES --batch --resample RATE --melspec: the same windows as mel spectrograms of a music front end (n_fft 2048, hop 512 -- or
+--nfft / --hop --, 128 Slaney bands, log10) -- what a loader does without the call, decode_ranges_batch(mono) + torch.stft, power, matmul with the
+same bank (vpz_melspec_filterbank as a dense matrix), clamp and log10 -- against decode_ranges_melspec; two dispatchers taking turns as
+above.  Both legs are held to one truth: the same chain in float64 (torch, on the float32 rows the batch call delivers).
+--melspec-kernel: vpz_pcm_melspec alone, 64 windows of one second and of thirty at 44 100 Hz, at 2048 / 512 / 128 and 4096 / 1024 / 128, the
+context's event timer; the time, and the HBM bytes that must move (PCM read plus mel write) against it.
 --ranges SAMPLES --batch --resample RATE --fbank: the same windows as Kaldi filterbank features (win 400, hop 160, n_fft 512, 80 bands, Povey
 window, pre-emphasis 0.97, per-frame mean removal, scale 32768, natural log), a float32 device tensor [streams][T][80].  The A/B: what a
 loader does without the call -- decode_ranges_batch at RATE Hz, mono, then on the device the eight torch ops unfold, mean, pre-emphasis,
@@ -107,6 +115,10 @@ ap.add_argument("--mono", action="store_true")
 ap.add_argument("--resample-kernel", action="store_true")
 ap.add_argument("--logmel", action="store_true")
 ap.add_argument("--logmel-kernel", action="store_true")
+ap.add_argument("--melspec", action="store_true")
+ap.add_argument("--melspec-kernel", action="store_true")
+ap.add_argument("--nfft", type=int, default=2048)
+ap.add_argument("--hop", type=int, default=512)
 ap.add_argument("--fbank", action="store_true")
 ap.add_argument("--fbank-kernel", action="store_true")
 ap.add_argument("--mfcc", action="store_true")
@@ -458,6 +470,94 @@ def logmel_kernel_job():
             print("vpz_pcm_logmel %-12s 64 windows of %6d samples (T = %4d): median %.1f us (min %.1f, max %.1f); %.2f GFLOP of DFT = %.1f TFLOP/s; %.1f MB out, "
                   "%.1f MB of spectrogram not written" % (name, samples, T, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, flop / 1e9, flop / ms / 1e9,
                                                           dst.numel() * 4 / 1e6, n * 201 * T * 8 / 1e6), flush=True)
+    ctx.close()
+
+
+def melspec_job(samples, rate):
+    import math, time
+    from vorbispizza_amd import capi
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    spec = capi.LogMelSpec.make(sample_rate=rate, n_fft=args.nfft, hop=args.hop, n_mels=128)
+    first, count, weights = capi.melspec_filterbank(spec)
+    Wh, at = np.zeros((spec.n_mels, spec.n_fft // 2 + 1), dtype=np.float32), 0
+    for b in range(spec.n_mels):
+        Wh[b, first[b]: first[b] + count[b]] = weights[at: at + count[b]]
+        at += count[b]
+    W, window = torch.from_numpy(Wh).to("cuda:0"), torch.hann_window(spec.n_fft, periodic=True, device="cuda:0")
+    fs = 44100  # (both fixtures)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+    state = {}
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, whole, res, st = d.decode_ranges_batch(datas, windows, 1, J, planar=True, s16=False, sample_rate=rate, mono=True)
+        S = torch.stft(whole.view(n, J), spec.n_fft, hop_length=spec.hop, window=window, center=True, pad_mode="reflect", return_complex=True)
+        out[0] = torch.log10(torch.clamp(torch.matmul(W, S.abs() ** 2), min=spec.floor))
+        torch.cuda.synchronize()
+        state["rows"] = whole
+        return time.perf_counter() - t0, res, st
+
+    def by_melspec(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_melspec(datas, windows, J, sample_rate=rate, n_fft=spec.n_fft, hop=spec.hop, n_mels=spec.n_mels)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, mel %d/%d/%d" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate, spec.n_fft, spec.hop, spec.n_mels)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_melspec(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape
+        # one truth for both legs: the same chain in float64 on the rows the batch call delivered (eight rows are enough to say)
+        rows64 = state["rows"].view(n, J)[:8].double()
+        S64 = torch.stft(rows64, spec.n_fft, hop_length=spec.hop, window=torch.hann_window(spec.n_fft, periodic=True, device="cuda:0", dtype=torch.float64),
+                         center=True, pad_mode="reflect", return_complex=True)
+        truth = torch.log10(torch.clamp(torch.matmul(W.double(), S64.abs() ** 2), min=float(np.float32(spec.floor))))
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB (the complex spectrogram it replaces: %.1f MB), largest difference of the two tensors %.3g; against the "
+              "float64 chain: torch %.3g, decode_ranges_melspec %.3g (log10 units)" % (
+                  what, J, out[1].numel() * 4 / 1e6, n * (spec.n_fft // 2 + 1) * out[1].shape[2] * 8 / 1e6, float((out[0] - out[1]).abs().max()),
+                  float((out[0][:8].double() - truth).abs().max()), float((out[1][:8].double() - truth).abs().max())), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_batch(mono) + torch stft/power/matmul/log %s; decode_ranges_melspec %s" % (run, describe(walls[0]), describe(walls[1])),
+                  flush=True)
+        for d in ds:
+            d.close()
+
+
+def melspec_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, rate = 64, 44100
+    for n_fft, hop in ((2048, 512), (4096, 1024)):
+        for samples in (rate, 30 * rate):
+            src = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+            rows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+            for name, bands_first in (("bands first", True), ("frames first", False)):
+                spec = capi.LogMelSpec.make(sample_rate=rate, n_fft=n_fft, hop=hop, n_mels=128, bands_first=bands_first)
+                T = spec.n_frames(samples)
+                dst = torch.empty((n, 128, T) if bands_first else (n, T, 128), dtype=torch.float32, device="cuda:0")
+                for run in (1, 2):
+                    times = []
+                    for _ in range(6):
+                        ctx.timer_start()
+                        assert capi.pcm_melspec(ctx, src, rows, dst, spec, samples) == capi.OK, ctx.last_error()
+                        times.append(ctx.timer_stop())
+                    ms = statistics.median(times[1:])
+                    moved = n * samples * 4 + dst.numel() * 4  # (the PCM read once, the mel frames written once)
+                    print("vpz_pcm_melspec %d/%d/128 %-12s 64 windows of %7d samples (T = %4d) run %d: median of 5 %.1f us (min %.1f, max %.1f); %.1f MB must move = "
+                          "%.0f GB/s; %.1f MB of spectrogram not written" % (n_fft, hop, name, samples, T, run, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3,
+                                                                             moved / 1e6, moved / ms / 1e6, n * (n_fft // 2 + 1) * T * 8 / 1e6), flush=True)
     ctx.close()
 
 
@@ -928,6 +1028,12 @@ if args.ranges and args.batch and args.resample and args.mfcc:
     sys.exit(0)
 if args.logmel_kernel:
     logmel_kernel_job()
+    sys.exit(0)
+if args.melspec_kernel:
+    melspec_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.melspec:
+    melspec_job(args.ranges, args.resample)
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.logmel:
     logmel_job(args.ranges, args.resample)

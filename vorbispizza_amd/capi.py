@@ -150,6 +150,14 @@ _PCM_LOGMEL_SIGNATURES = [
     ("vpz_pcm_logmel", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(LogMelSpec), C.c_int32, _vp, _vp, C.c_int64]),
 ]
 PCM_LOGMEL_EXPORTED_SYMBOLS = [s[0] for s in _PCM_LOGMEL_SIGNATURES]
+MELSPEC_MIN_NFFT, MELSPEC_MAX_NFFT, MELSPEC_MAX_MELS = 2048, 8192, 256
+# include/vorbispizza_pcm_melspec.h (a header of its own again; the spec is LogMelSpec)
+_PCM_MELSPEC_SIGNATURES = [
+    ("vpz_melspec_twiddles", C.c_int, [C.c_int32, _vp, C.c_int64]),
+    ("vpz_melspec_filterbank", C.c_int, [C.POINTER(LogMelSpec), _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    ("vpz_pcm_melspec", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(LogMelSpec), C.c_int32, _vp, _vp, C.c_int64]),
+]
+PCM_MELSPEC_EXPORTED_SYMBOLS = [s[0] for s in _PCM_MELSPEC_SIGNATURES]
 
 
 FLT_EPSILON = 2.0 ** -23  # (Kaldi's floor under the log)
@@ -319,7 +327,7 @@ def lib():
                 pass
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
-                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES)
+                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES + _PCM_MELSPEC_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -497,17 +505,49 @@ def logmel_dft_table(n_fft):
 def mel_filterbank(spec):
     """vpz_mel_filterbank: (first_bin[n_mels] int32, n_bins[n_mels] int32, weights float32 -- band after band, each band's live bins) of a
     LogMelSpec; needs no device.  A refused spec raises ValueError."""
+    return _mel_filterbank_of(lib().vpz_mel_filterbank, "vpz_mel_filterbank", spec)
+
+
+def _mel_filterbank_of(fn, name, spec):
     total = C.c_int64(0)
-    rc = lib().vpz_mel_filterbank(C.byref(spec), None, None, None, 0, C.byref(total))
+    rc = fn(C.byref(spec), None, None, None, 0, C.byref(total))
     if rc != OK:
-        raise ValueError("vpz_mel_filterbank refuses the spec (status %d)" % rc)
+        raise ValueError("%s refuses the spec (status %d)" % (name, rc))
     first, count = np.zeros(spec.n_mels, dtype=np.int32), np.zeros(spec.n_mels, dtype=np.int32)
     weights = np.zeros(total.value, dtype=np.float32)
-    rc = lib().vpz_mel_filterbank(C.byref(spec), first.ctypes.data, count.ctypes.data, weights.ctypes.data if total.value else None, weights.size,
-                                  C.byref(total))
+    rc = fn(C.byref(spec), first.ctypes.data, count.ctypes.data, weights.ctypes.data if total.value else None, weights.size, C.byref(total))
     if rc != OK:
-        raise ValueError("vpz_mel_filterbank failed (status %d)" % rc)
+        raise ValueError("%s failed (status %d)" % (name, rc))
     return first, count, weights
+
+
+def pcm_melspec(ctx, src, rows, dst, spec, frames):
+    """vpz_pcm_melspec (vorbispizza_pcm_melspec.h): pcm_logmel's arguments and shapes, for a LogMelSpec with n_fft 2048, 4096 or 8192 (a
+    real FFT per frame, held to the header's bound).  Asynchronous on the context's stream; returns the status (a refusal is an answer,
+    not an exception)."""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_melspec(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                                 int(dst.shape[0]))
+
+
+def melspec_twiddles(n_fft):
+    """vpz_melspec_twiddles: (w float32 [n_fft], t float32 [n_fft, 2]) -- the periodic Hann window and t[k] = (cos, -sin)(2 pi k / n_fft),
+    two views of the one table of 3 * n_fft floats the kernel reads; needs no device.  A refused n_fft raises ValueError."""
+    rc = lib().vpz_melspec_twiddles(n_fft, None, 0)
+    if rc != OK:
+        raise ValueError("vpz_melspec_twiddles refuses n_fft %r (status %d)" % (n_fft, rc))
+    table = np.zeros(3 * int(n_fft), dtype=np.float32)
+    rc = lib().vpz_melspec_twiddles(n_fft, table.ctypes.data, table.size)
+    if rc != OK:
+        raise ValueError("vpz_melspec_twiddles failed (status %d)" % rc)
+    return table[:int(n_fft)], table[int(n_fft):].reshape(int(n_fft), 2)
+
+
+def melspec_filterbank(spec):
+    """vpz_melspec_filterbank: mel_filterbank's outputs for a LogMelSpec with n_fft 2048, 4096 or 8192; needs no device.  A refused spec
+    raises ValueError."""
+    return _mel_filterbank_of(lib().vpz_melspec_filterbank, "vpz_melspec_filterbank", spec)
 
 
 def pcm_fbank(ctx, src, rows, dst, spec, frames):

@@ -4,7 +4,9 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
+#include <new>
 #include <vector>
 
 #include "../../include/vorbispizza_pcm_logmel.h"
@@ -13,10 +15,11 @@ namespace vpz {
 
 inline bool logmel_nfft_ok(int64_t n_fft) { return n_fft >= VPZ_LOGMEL_MIN_NFFT && n_fft <= VPZ_LOGMEL_MAX_NFFT && n_fft % 2 == 0; }
 
-// every field inside the limits of the definition (`floor` only where the output mode reads it)
-inline bool logmel_spec_ok(const vpz_logmel_spec &s)
+// every field but n_fft inside the limits of the definition (`floor` only where the output mode reads it): what vpz_pcm_logmel and
+// vpz_pcm_melspec (melspec_tables.hpp), which differ in the transform sizes they take, ask alike
+inline bool mel_spec_rest_ok(const vpz_logmel_spec &s)
 {
-    if (!logmel_nfft_ok(s.n_fft) || s.hop < 1 || s.hop > s.n_fft || s.n_mels < 1 || s.n_mels > VPZ_LOGMEL_MAX_MELS) return false;
+    if (s.n_fft < 1 || s.hop < 1 || s.hop > s.n_fft || s.n_mels < 1 || s.n_mels > VPZ_LOGMEL_MAX_MELS) return false;
     if (!(s.sample_rate > 0.0) || !isfinite(s.sample_rate) || !(s.f_min >= 0.0) || !(s.f_min < s.f_max) || !(s.f_max <= s.sample_rate / 2.0))
         return false;
     if (s.mel_scale != VPZ_MEL_HTK && s.mel_scale != VPZ_MEL_SLANEY) return false;
@@ -28,6 +31,8 @@ inline bool logmel_spec_ok(const vpz_logmel_spec &s)
         if (s.reserved[i] != 0) return false;
     return true;
 }
+
+inline bool logmel_spec_ok(const vpz_logmel_spec &s) { return logmel_nfft_ok(s.n_fft) && mel_spec_rest_ok(s); }
 
 // table[m][0 .. nb) = w[m] cos, table[m][nb .. 2 nb) = w[m] sin, nb = n_fft / 2 + 1; `ld` floats between two rows (>= 2 * nb), the sin
 // columns start at column `sin_at` (>= nb): the exported table is dense (ld = 2 nb, sin_at = nb), the device copy pads both halves
@@ -105,6 +110,24 @@ inline void mel_build(const vpz_logmel_spec &s, MelFilterbank &fb)
             fb.weights.push_back((float)((w > 0.0 ? w : 0.0) * scale));
         }
     }
+}
+
+// what vpz_mel_filterbank and vpz_melspec_filterbank return for a spec each has checked against its own limits
+inline int mel_filterbank_out(const vpz_logmel_spec &spec, int32_t *first_bin, int32_t *n_bins, float *weights, int64_t capacity, int64_t *total)
+{
+    MelFilterbank fb;
+    try {
+        mel_build(spec, fb);
+    } catch (const std::bad_alloc &) {
+        return VPZ_E_NOMEM;
+    }
+    if (total) *total = (int64_t)fb.weights.size();
+    if (first_bin) memcpy(first_bin, fb.first.data(), sizeof(int32_t) * fb.first.size());
+    if (n_bins) memcpy(n_bins, fb.count.data(), sizeof(int32_t) * fb.count.size());
+    if (!weights) return VPZ_OK;
+    if ((uint64_t)capacity < fb.weights.size()) return VPZ_E_CAPACITY;
+    if (!fb.weights.empty()) memcpy(weights, fb.weights.data(), sizeof(float) * fb.weights.size());
+    return VPZ_OK;
 }
 
 }  // namespace vpz

@@ -231,19 +231,7 @@ extern "C" int vpz_mel_filterbank(const vpz_logmel_spec *spec, int32_t *first_bi
                                   int64_t *total)
 {
     if (!spec || capacity < 0 || !vpz::logmel_spec_ok(*spec)) return VPZ_E_INVALID_ARG;
-    vpz::MelFilterbank fb;
-    try {
-        vpz::mel_build(*spec, fb);
-    } catch (const std::bad_alloc &) {
-        return VPZ_E_NOMEM;
-    }
-    if (total) *total = (int64_t)fb.weights.size();
-    if (first_bin) memcpy(first_bin, fb.first.data(), sizeof(int32_t) * fb.first.size());
-    if (n_bins) memcpy(n_bins, fb.count.data(), sizeof(int32_t) * fb.count.size());
-    if (!weights) return VPZ_OK;
-    if ((uint64_t)capacity < fb.weights.size()) return VPZ_E_CAPACITY;
-    if (!fb.weights.empty()) memcpy(weights, fb.weights.data(), sizeof(float) * fb.weights.size());
-    return VPZ_OK;
+    return vpz::mel_filterbank_out(*spec, first_bin, n_bins, weights, capacity, total);
 }
 
 extern "C" int vpz_pcm_logmel(vpz_context *c, const void *src_dev, int64_t src_elems, int64_t frames, const vpz_logmel_spec *spec,

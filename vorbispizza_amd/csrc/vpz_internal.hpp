@@ -98,8 +98,8 @@ struct Context {
         double coeffs[10], P[16];
     };
     std::map<std::pair<int, int>, ResampleTable> resample_tables;  // (up, down)
-    std::map<int, LogmelDft> logmel_dft;                           // n_fft
-    std::map<std::array<double, 7>, LogmelBank> logmel_banks;      // (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
+    std::map<int, LogmelDft> logmel_dft;                           // n_fft (up to 1024: log-mel's DFT table; 2048, 4096, 8192: vpz_pcm_melspec's window and twiddles, 3 n_fft floats)
+    std::map<std::array<double, 7>, LogmelBank> logmel_banks;      // (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm): vpz_pcm_logmel's and vpz_pcm_melspec's
     std::map<std::array<double, 5>, LogmelDft> fbank_tables;       // (win, n_fft, window, preemphasis, scale)
     std::map<std::array<double, 5>, LogmelBank> fbank_banks;       // (sample_rate, n_fft, n_mels, low_freq, high_freq)
     std::map<std::array<double, 5>, DeviceTable> mfcc_tables;      // (n_mels, n_ceps, lifter, htk_compat, use_energy): [n_mels][n_ceps]

@@ -37,6 +37,8 @@
 //
 // vpzm_decode_ranges_logmel (include/vorbispizza_multi_logmel.h) is the mono resampled call with one more stage: the resample launches write
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
+// vpzm_decode_ranges_melspec (include/vorbispizza_multi_melspec.h) is that call with vpz_pcm_melspec as the feature launch: transforms of
+// 2048, 4096 and 8192 samples.
 // vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
 // vpzm_decode_ranges_mfcc (include/vorbispizza_multi_mfcc.h) is the same call with vpz_pcm_mfcc as that stage: Kaldi MFCC frames.
 // vpzm_decode_ranges_fbank_post / _mfcc_post (include/vorbispizza_multi_featpost.h) are those two with vpz_feat_post behind the feature
@@ -78,6 +80,8 @@
 #include "../../include/vorbispizza_multi_resample.h"
 #include "../../include/vorbispizza_pcm_logmel.h"
 #include "../../include/vorbispizza_multi_logmel.h"
+#include "../../include/vorbispizza_pcm_melspec.h"
+#include "../../include/vorbispizza_multi_melspec.h"
 #include "../../include/vorbispizza_pcm_fbank.h"
 #include "../../include/vorbispizza_multi_fbank.h"
 #include "../../include/vorbispizza_pcm_mfcc.h"
@@ -341,7 +345,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -394,13 +398,14 @@ struct Job {  // one stream of the library inside its group
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
     // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or then
-    // vpz_pcm_mfcc; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
-    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc };
+    // vpz_pcm_mfcc; or then vpz_pcm_melspec; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
+    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc, kMelspec };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
     int32_t rate = 0, downmix = 0;  // kResampled, kLogmel: every row at `rate`, mixed down to mono
-    // kLogmel: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed)
+    // kLogmel, kMelspec: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed);
+    // kMelspec with the transform sizes of vorbispizza_pcm_melspec.h
     const vpz_logmel_spec *mel = nullptr;
     // kFbank: the same with Kaldi filterbank frames of this spec (`dst` is [rows][T][n_mels] or transposed)
     const vpz_fbank_spec *fbank = nullptr;
@@ -416,16 +421,17 @@ struct Batch {
     bool measured() const { return kind == kLoudness || kind == kR128; }
     vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
     vpzm_r128 &record_r128(int64_t row) const { return static_cast<vpzm_r128 *>(dst)[row]; }
-    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc; }  // a feature stage behind the resample launches, fed from the lane's temporary
-    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : "vpz_pcm_logmel"; }
-    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : "vpzm_decode_ranges_logmel"; }
-    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : "log-mel"; }
+    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc || kind == kMelspec; }  // a feature stage behind the resample launches, fed from the lane's temporary
+    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : kind == kMelspec ? "vpz_pcm_melspec" : "vpz_pcm_logmel"; }
+    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : kind == kMelspec ? "vpzm_decode_ranges_melspec" : "vpzm_decode_ranges_logmel"; }
+    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : kind == kMelspec ? "mel-spectrogram" : "log-mel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `to` (the group's piece, or a
     // posted call's temporary), which has `to_rows` rows
     int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d, void *to, int64_t to_rows) const
     {
         if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), to, to_rows);
         if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), to, to_rows);
+        if (kind == kMelspec) return vpz_pcm_melspec(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), to, to_rows);
         return vpz_pcm_logmel(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), to, to_rows);
     }
     // a posted call: the mel stage's spec, a row's frames T, its real frames T_L of J samples and the feature launch's columns D
@@ -960,7 +966,7 @@ struct GroupRun {
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0], rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.kind == Batch::kMelspec ? "vpz_pcm_melspec (silence rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1853,6 +1859,19 @@ int vpzm_decode_ranges_logmel(vpzm_dispatcher *m, int32_t n, const uint8_t *cons
     if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
     const Batch batch{Batch::kLogmel, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_melspec(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                               const vpz_logmel_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!spec) return VPZM_E_ARG;
+    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
+    if (vpz_melspec_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
+    if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
+    if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
+    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
+    const Batch batch{Batch::kMelspec, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -49,6 +49,7 @@ RANGES_EXPORTED_SYMBOLS = ["vpzm_decode_ranges"]  # (vorbispizza_multi_ranges.h)
 BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  # (vorbispizza_multi_batch.h)
 RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
+MELSPEC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_melspec"]  # (vorbispizza_multi_melspec.h)
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
 MFCC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_mfcc"]  # (vorbispizza_multi_mfcc.h)
 FEATPOST_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank_post", "vpzm_decode_ranges_mfcc_post"]  # (vorbispizza_multi_featpost.h)
@@ -97,6 +98,9 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges_logmel"):
             L.vpzm_decode_ranges_logmel.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.LogMelSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_logmel.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_melspec"):
+            L.vpzm_decode_ranges_melspec.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.LogMelSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_melspec.restype = C.c_int
         if hasattr(L, "vpzm_decode_ranges_fbank"):
             L.vpzm_decode_ranges_fbank.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_fbank.restype = C.c_int
@@ -314,6 +318,28 @@ class Dispatcher:
                                              C.byref(stats))
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_logmel failed (status %d): %s" % (rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_melspec(self, datas, ranges, frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=None,
+                              mel_scale="slaney", mel_norm="slaney", log=True, floor=1e-10, bands_first=True, out=None):
+        """vpzm_decode_ranges_melspec: decode_ranges_logmel's call, shapes and results with the transforms of music front ends -- n_fft
+        2048, 4096 or 8192, one real FFT per frame on the device (include/vorbispizza_pcm_melspec.h states the definition and the error
+        bound; the defaults are librosa's mel spectrogram at 22 050 Hz).  Returns (parts, whole_or_None, results, stats)."""
+        import torch
+        spec = capi.LogMelSpec.make(sample_rate=sample_rate, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max, mel_scale=mel_scale,
+                                    mel_norm=mel_norm, log=log, floor=floor, bands_first=bands_first)
+        if frames < 1 or hop < 1 or n_mels < 1:
+            raise ValueError("decode_ranges_melspec: frames, hop and n_mels must be at least 1")
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        T = spec.n_frames(frames)
+        shape = (lambda rows: (rows, n_mels, T)) if bands_first else (lambda rows: (rows, T, n_mels))
+        out, whole, dst = self._group_tensors("decode_ranges_melspec", n, shape, torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = lib().vpzm_decode_ranges_melspec(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
+                                              C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_melspec failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats
 
     def decode_ranges_fbank(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=80, low_freq=20.0, high_freq=0.0,

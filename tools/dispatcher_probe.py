@@ -11,6 +11,8 @@
     dispatcher_probe.py --logmel-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --melspec [--nfft N --hop H] [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --melspec-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --stft [--nfft N --hop H] [--mono] [--stft-output complex|magnitude|power] [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --stft-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --fbank [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --fbank-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --mfcc [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
@@ -58,6 +60,14 @@ same bank (vpz_melspec_filterbank as a dense matrix), clamp and log10 -- against
 above.  Both legs are held to one truth: the same chain in float64 (torch, on the float32 rows the batch call delivers).
 --melspec-kernel: vpz_pcm_melspec alone, 64 windows of one second and of thirty at 44 100 Hz, at 2048 / 512 / 128 and 4096 / 1024 / 128, the
 context's event timer; the time, and the HBM bytes that must move (PCM read plus mel write) against it.
+--ranges SAMPLES --batch --resample RATE --stft: the same windows as STFT spectrograms of every channel (or, with --mono, of the mixed-down
+one) at --nfft / --hop, periodic Hann, --stft-output complex (the default), magnitude or power, in torch's order -- what a loader does
+without the call, decode_ranges_batch at RATE Hz + torch.stft with the same window (and abs() or abs() ** 2) -- against
+decode_ranges_stft; two dispatchers taking turns as above.  Both legs are held to one truth: torch.stft in float64 on the float32 rows
+the batch call delivers.
+--stft-kernel: vpz_pcm_stft alone, 64 stereo windows (128 rows) of one second and of thirty at 44 100 Hz, at 4096 / 1024 complex, 1024 / 256
+magnitude and 2048 / 512 power, both layouts, the context's event timer; the time, the bytes it stores per second, and vpz_pcm_melspec on
+the same rows at the same n_fft and hop where it takes the size.
 --ranges SAMPLES --batch --resample RATE --fbank: the same windows as Kaldi filterbank features (win 400, hop 160, n_fft 512, 80 bands, Povey
 window, pre-emphasis 0.97, per-frame mean removal, scale 32768, natural log), a float32 device tensor [streams][T][80].  The A/B: what a
 loader does without the call -- decode_ranges_batch at RATE Hz, mono, then on the device the eight torch ops unfold, mean, pre-emphasis,
@@ -117,6 +127,9 @@ ap.add_argument("--logmel", action="store_true")
 ap.add_argument("--logmel-kernel", action="store_true")
 ap.add_argument("--melspec", action="store_true")
 ap.add_argument("--melspec-kernel", action="store_true")
+ap.add_argument("--stft", action="store_true")
+ap.add_argument("--stft-kernel", action="store_true")
+ap.add_argument("--stft-output", default="complex")
 ap.add_argument("--nfft", type=int, default=2048)
 ap.add_argument("--hop", type=int, default=512)
 ap.add_argument("--fbank", action="store_true")
@@ -558,6 +571,102 @@ def melspec_kernel_job():
                     print("vpz_pcm_melspec %d/%d/128 %-12s 64 windows of %7d samples (T = %4d) run %d: median of 5 %.1f us (min %.1f, max %.1f); %.1f MB must move = "
                           "%.0f GB/s; %.1f MB of spectrogram not written" % (n_fft, hop, name, samples, T, run, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3,
                                                                              moved / 1e6, moved / ms / 1e6, n * (n_fft // 2 + 1) * T * 8 / 1e6), flush=True)
+    ctx.close()
+
+
+def stft_job(samples, rate):
+    import math, time
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    n_fft, hop, output, Cn = args.nfft, args.hop, args.stft_output, 1 if args.mono else 2
+    window = torch.hann_window(n_fft, periodic=True, device="cuda:0")
+    fs = 44100  # (both fixtures, stereo)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+    state = {}
+
+    def of(S):
+        return S if output == "complex" else S.abs() if output == "magnitude" else S.abs() ** 2
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, whole, res, st = d.decode_ranges_batch(datas, windows, Cn, J, planar=True, s16=False, sample_rate=rate, mono=args.mono)
+        S = torch.stft(whole.view(n * Cn, J), n_fft, hop_length=hop, window=window, center=True, pad_mode="reflect", return_complex=True)
+        out[0] = of(S).view(n, Cn, n_fft // 2 + 1, -1)
+        torch.cuda.synchronize()
+        state["rows"] = whole
+        return time.perf_counter() - t0, res, st
+
+    def by_stft(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_stft(datas, windows, J, sample_rate=rate, channels=Cn, mono=args.mono, n_fft=n_fft, hop=hop, output=output)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, stft %d/%d %s of %d channel%s" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate, n_fft, hop, output, Cn, "s" if Cn > 1 else "")
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_stft(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape and out[0].dtype == out[1].dtype
+        # one truth for both legs: torch.stft in float64 on the rows the batch call delivered (eight entries are enough to say)
+        rows64 = state["rows"].view(n * Cn, J)[:8 * Cn].double()
+        truth = of(torch.stft(rows64, n_fft, hop_length=hop, window=torch.hann_window(n_fft, periodic=True, device="cuda:0", dtype=torch.float64), center=True,
+                              pad_mode="reflect", return_complex=True)).view(8, Cn, n_fft // 2 + 1, -1)
+        wide = torch.complex128 if output == "complex" else torch.float64
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB, largest difference of the two tensors %.3g; against the float64 chain: torch %.3g, "
+              "decode_ranges_stft %.3g (largest |X| %.3g)" % (
+                  what, J, out[1].numel() * out[1].element_size() / 1e6, float((out[0] - out[1]).abs().max()), float((out[0][:8].to(wide) - truth).abs().max()),
+                  float((out[1][:8].to(wide) - truth).abs().max()), float(truth.abs().max())), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_batch + torch.stft %s; decode_ranges_stft %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def stft_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, rate = 128, 44100  # (64 stereo windows: a channel is a row)
+    for n_fft, hop, output in ((4096, 1024, "complex"), (1024, 256, "magnitude"), (2048, 512, "power")):
+        for samples in (rate, 30 * rate):
+            src = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+            rows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+            for name, bins_first in (("bins first", True), ("frames first", False)):
+                spec = capi.StftSpec.make(n_fft=n_fft, hop=hop, output=output, bins_first=bins_first)
+                T = spec.n_frames(samples)
+                dst = torch.empty((n,) + spec.row_shape(samples), dtype=torch.float32, device="cuda:0")
+                for run in (1, 2):
+                    times = []
+                    for _ in range(6):
+                        ctx.timer_start()
+                        assert capi.pcm_stft(ctx, src, rows, dst, spec, samples) == capi.OK, ctx.last_error()
+                        times.append(ctx.timer_stop())
+                    ms = statistics.median(times[1:])
+                    print("vpz_pcm_stft %d/%d %-9s %-12s 128 rows of %7d samples (T = %4d) run %d: median of 5 %.1f us (min %.1f, max %.1f); stores %.1f MB = %.0f GB/s"
+                          % (n_fft, hop, output, name, samples, T, run, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, dst.numel() * 4 / 1e6,
+                             dst.numel() * 4 / ms / 1e6), flush=True)
+                del dst
+            if n_fft >= 2048:  # the mel stage on the same rows: the same transforms, a 128-band tile stored in the spectrogram's place
+                mel = capi.LogMelSpec.make(sample_rate=rate, n_fft=n_fft, hop=hop, n_mels=128)
+                T = mel.n_frames(samples)
+                dst = torch.empty((n, 128, T), dtype=torch.float32, device="cuda:0")
+                times = []
+                for _ in range(6):
+                    ctx.timer_start()
+                    assert capi.pcm_melspec(ctx, src, rows, dst, mel, samples) == capi.OK, ctx.last_error()
+                    times.append(ctx.timer_stop())
+                print("vpz_pcm_melspec %d/%d/128 on the same 128 rows of %7d samples: median of 5 %.1f us (min %.1f, max %.1f)" % (
+                    n_fft, hop, samples, statistics.median(times[1:]) * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3), flush=True)
+                del dst
     ctx.close()
 
 
@@ -1034,6 +1143,12 @@ if args.melspec_kernel:
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.melspec:
     melspec_job(args.ranges, args.resample)
+    sys.exit(0)
+if args.stft_kernel:
+    stft_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.stft:
+    stft_job(args.ranges, args.resample)
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.logmel:
     logmel_job(args.ranges, args.resample)

@@ -160,6 +160,48 @@ _PCM_MELSPEC_SIGNATURES = [
 PCM_MELSPEC_EXPORTED_SYMBOLS = [s[0] for s in _PCM_MELSPEC_SIGNATURES]
 
 
+class StftSpec(C.Structure):
+    """vpz_stft_spec (include/vorbispizza_pcm_stft.h).  StftSpec.make(...) takes the names a Python caller uses."""
+    _fields_ = [("n_fft", C.c_int32), ("hop", C.c_int32), ("win_length", C.c_int32), ("window", C.c_int32), ("output", C.c_int32),
+                ("layout", C.c_int32), ("reserved", C.c_int32 * 10)]
+
+    @classmethod
+    def make(cls, n_fft=4096, hop=1024, win_length=None, window="hann", output="complex", bins_first=True):
+        windows = {"hann": STFT_HANN, "hamming": STFT_HAMMING}
+        outputs = {"complex": STFT_COMPLEX, "magnitude": STFT_MAGNITUDE, "power": STFT_POWER}
+        if window not in windows or output not in outputs:
+            raise ValueError("StftSpec: window is 'hann' or 'hamming', output 'complex', 'magnitude' or 'power'")
+        s = cls()
+        s.n_fft, s.hop, s.win_length = int(n_fft), int(hop), int(n_fft if win_length is None else win_length)
+        s.window, s.output, s.layout = windows[window], outputs[output], (STFT_BINS_FIRST if bins_first else STFT_FRAMES_FIRST)
+        return s
+
+    def n_frames(self, frames):
+        """T of a row of `frames` samples."""
+        return 1 + int(frames) // self.hop
+
+    @property
+    def n_freq(self):
+        return self.n_fft // 2 + 1
+
+    def row_shape(self, frames):
+        """a row of the destination as float32: (n_freq, T) or (T, n_freq), with a last 2 for the complex output"""
+        inner = (self.n_freq, self.n_frames(frames)) if self.layout == STFT_BINS_FIRST else (self.n_frames(frames), self.n_freq)
+        return inner + ((2,) if self.output == STFT_COMPLEX else ())
+
+
+STFT_HANN, STFT_HAMMING = 0, 1
+STFT_COMPLEX, STFT_MAGNITUDE, STFT_POWER = 0, 1, 2
+STFT_BINS_FIRST, STFT_FRAMES_FIRST = 0, 1
+STFT_MIN_NFFT, STFT_MAX_NFFT = 512, 8192
+# include/vorbispizza_pcm_stft.h (a header of its own again)
+_PCM_STFT_SIGNATURES = [
+    ("vpz_stft_table", C.c_int, [C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64]),
+    ("vpz_pcm_stft", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(StftSpec), C.c_int32, _vp, _vp, C.c_int64]),
+]
+PCM_STFT_EXPORTED_SYMBOLS = [s[0] for s in _PCM_STFT_SIGNATURES]
+
+
 FLT_EPSILON = 2.0 ** -23  # (Kaldi's floor under the log)
 
 
@@ -327,7 +369,8 @@ def lib():
                 pass
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
-                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES + _PCM_MELSPEC_SIGNATURES)
+                 + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES + _PCM_MELSPEC_SIGNATURES
+                 + _PCM_STFT_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -548,6 +591,34 @@ def melspec_filterbank(spec):
     """vpz_melspec_filterbank: mel_filterbank's outputs for a LogMelSpec with n_fft 2048, 4096 or 8192; needs no device.  A refused spec
     raises ValueError."""
     return _mel_filterbank_of(lib().vpz_melspec_filterbank, "vpz_melspec_filterbank", spec)
+
+
+def pcm_stft(ctx, src, rows, dst, spec, frames):
+    """vpz_pcm_stft (vorbispizza_pcm_stft.h): windows of the float32 device array `src` (a torch tensor; a channel of a planar array is
+    a row) as short-time Fourier spectrograms of rows padded to `frames` samples, into rows of `dst` -- a contiguous torch tensor whose
+    first dimension counts the rows: float32 [rows, n_freq, T] (bins first) or [rows, T, n_freq], with a last dimension of 2 for the
+    complex output (or the complex64 tensor torch.view_as_complex gives of it).  rows: [(src element offset, samples, destination row)].
+    Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_stft(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                              int(dst.shape[0]))
+
+
+def stft_table(n_fft, win_length=None, window="hann"):
+    """vpz_stft_table: (w float32 [n_fft], t float32 [n_fft, 2]) -- the window of win_length centred in n_fft and t[k] = (cos, -sin)(2 pi k
+    / n_fft), two views of the one table of 3 * n_fft floats the kernel reads; needs no device.  window: 'hann' / 'hamming' or the
+    VPZ_STFT_* value.  Refused arguments raise ValueError."""
+    wl = int(n_fft if win_length is None else win_length)
+    wd = {"hann": STFT_HANN, "hamming": STFT_HAMMING}.get(window, window)
+    rc = lib().vpz_stft_table(int(n_fft), wl, int(wd), None, 0)
+    if rc != OK:
+        raise ValueError("vpz_stft_table refuses n_fft %r, win_length %r, window %r (status %d)" % (n_fft, win_length, window, rc))
+    table = np.zeros(3 * int(n_fft), dtype=np.float32)
+    rc = lib().vpz_stft_table(int(n_fft), wl, int(wd), table.ctypes.data, table.size)
+    if rc != OK:
+        raise ValueError("vpz_stft_table failed (status %d)" % rc)
+    return table[:int(n_fft)], table[int(n_fft):].reshape(int(n_fft), 2)
 
 
 def pcm_fbank(ctx, src, rows, dst, spec, frames):

@@ -103,7 +103,8 @@ struct Context {
     std::map<std::array<double, 5>, LogmelDft> fbank_tables;       // (win, n_fft, window, preemphasis, scale)
     std::map<std::array<double, 5>, LogmelBank> fbank_banks;       // (sample_rate, n_fft, n_mels, low_freq, high_freq)
     std::map<std::array<double, 5>, DeviceTable> mfcc_tables;      // (n_mels, n_ceps, lifter, htk_compat, use_energy): [n_mels][n_ceps]
-    std::map<int, LoudnessRate> loudness_rates;                    // the sample rate
+    std::map<std::array<int, 3>, LogmelDft> stft_tables;           // (n_fft, win_length, window): vpz_pcm_stft's window and twiddles, 3 n_fft floats
+    std::map<int, LoudnessRate> loudness_rates;                   // the sample rate
     Scratch loud_scratch{nullptr, 0, true};  // vpz_pcm_loudness: states, energies and partial sums of a launch
     Scratch tp_scratch{nullptr, 0, true};    // vpz_pcm_true_peak: one pair of maxima per tile
 };

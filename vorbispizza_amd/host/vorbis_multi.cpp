@@ -39,6 +39,8 @@
 // into the lane's own temporary, and one vpz_pcm_logmel launch per sub-batch turns its rows into (log-)mel frames in the caller's tensor.
 // vpzm_decode_ranges_melspec (include/vorbispizza_multi_melspec.h) is that call with vpz_pcm_melspec as the feature launch: transforms of
 // 2048, 4096 and 8192 samples.
+// vpzm_decode_ranges_stft (include/vorbispizza_multi_stft.h) keeps the channels and the spectrum: the resample launches write planar rows
+// [members][C][frames] into the temporary, and vpz_pcm_stft takes every (member, channel) as a row of its own.
 // vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
 // vpzm_decode_ranges_mfcc (include/vorbispizza_multi_mfcc.h) is the same call with vpz_pcm_mfcc as that stage: Kaldi MFCC frames.
 // vpzm_decode_ranges_fbank_post / _mfcc_post (include/vorbispizza_multi_featpost.h) are those two with vpz_feat_post behind the feature
@@ -82,6 +84,8 @@
 #include "../../include/vorbispizza_multi_logmel.h"
 #include "../../include/vorbispizza_pcm_melspec.h"
 #include "../../include/vorbispizza_multi_melspec.h"
+#include "../../include/vorbispizza_pcm_stft.h"
+#include "../../include/vorbispizza_multi_stft.h"
 #include "../../include/vorbispizza_pcm_fbank.h"
 #include "../../include/vorbispizza_multi_fbank.h"
 #include "../../include/vorbispizza_pcm_mfcc.h"
@@ -289,7 +293,7 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     SetupCache<vpz_entropy_group> egroups{vpz_entropy_group_destroy, {}};  // mixed_setups: the groups of the merged setups, kept alike
     // (kF0Amp, kF0Coeff: a batch call's host route uploads a type-0 floor's data beside residue, posts and counts)
     // (kMono: a log-mel call's resampled mono rows [members][frames], between the resample launches and the vpz_pcm_logmel launch that
-    // reads them; the lane owns it, it only grows, and it goes with the lane when the dispatcher is destroyed)
+    // reads them -- an STFT call's are [members][channels][frames], every channel a row of the vpz_pcm_stft launch; the lane owns it, it only grows, and it goes with the lane when the dispatcher is destroyed)
     // (kLoud: a loudness call's step sums [members][max_steps] float64 and, behind them, peaks [members] float32, between the
     // vpz_pcm_loudness launches and the one copy that brings them down; an R 128 call's true peaks [members] float32 lie behind the peaks;
     // owned like kMono)
@@ -345,7 +349,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, STFT, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -398,8 +402,8 @@ struct Job {  // one stream of the library inside its group
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
     // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or then
-    // vpz_pcm_mfcc; or then vpz_pcm_melspec; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
-    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc, kMelspec };
+    // vpz_pcm_mfcc; or then vpz_pcm_melspec; or then vpz_pcm_stft; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
+    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc, kMelspec, kStft };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
@@ -413,6 +417,9 @@ struct Batch {
     const vpz_mfcc_spec *mfcc = nullptr;
     // kFbank, kMfcc: vpz_feat_post of this spec behind the feature launch (`dst` is [rows][T][D_out] or transposed); null: none
     const vpz_feat_post_spec *post = nullptr;
+    // kStft: a resampled call of `channels` planar channels (one with `downmix`) whose every channel is a row of spectrum frames of this
+    // spec: entry k's channel c is row (k - lo) * channels + c of `dst` ([rows][channels][n_freq][T], complex pairs included, or transposed)
+    const vpz_stft_spec *stft = nullptr;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
     // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
@@ -421,14 +428,23 @@ struct Batch {
     bool measured() const { return kind == kLoudness || kind == kR128; }
     vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
     vpzm_r128 &record_r128(int64_t row) const { return static_cast<vpzm_r128 *>(dst)[row]; }
-    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc || kind == kMelspec; }  // a feature stage behind the resample launches, fed from the lane's temporary
-    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : kind == kMelspec ? "vpz_pcm_melspec" : "vpz_pcm_logmel"; }
-    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : kind == kMelspec ? "vpzm_decode_ranges_melspec" : "vpzm_decode_ranges_logmel"; }
-    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : kind == kMelspec ? "mel-spectrogram" : "log-mel"; }
+    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc || kind == kMelspec || kind == kStft; }  // a feature stage behind the resample launches, fed from the lane's temporary
+    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : kind == kMelspec ? "vpz_pcm_melspec" : kind == kStft ? "vpz_pcm_stft" : "vpz_pcm_logmel"; }
+    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : kind == kMelspec ? "vpzm_decode_ranges_melspec" : kind == kStft ? "vpzm_decode_ranges_stft" : "vpzm_decode_ranges_logmel"; }
+    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : kind == kMelspec ? "mel-spectrogram" : kind == kStft ? "stft" : "log-mel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `to` (the group's piece, or a
-    // posted call's temporary), which has `to_rows` rows
+    // posted call's temporary), which has `to_rows` rows.  An STFT call's array is planar -- a descriptor's `src` is the window in its
+    // member's first channel, the next channel lies `frames` elements on (none is read where samples = 0) -- and a descriptor stands for
+    // its entry's `channels` rows: one descriptor of the launch per channel
     int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d, void *to, int64_t to_rows) const
     {
+        if (kind == kStft) {
+            std::vector<vpz_pack_row> each;
+            each.reserve(d.size() * (size_t)channels);
+            for (const vpz_pack_row &r : d)
+                for (int32_t c = 0; c < channels; ++c) each.push_back(vpz_pack_row{r.samples > 0 ? r.src + c * frames : 0, r.samples, r.row * channels + c});
+            return vpz_pcm_stft(ctx, src, src_elems, frames, stft, (int32_t)each.size(), each.data(), to, to_rows * channels);
+        }
         if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), to, to_rows);
         if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), to, to_rows);
         if (kind == kMelspec) return vpz_pcm_melspec(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), to, to_rows);
@@ -966,7 +982,7 @@ struct GroupRun {
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0], rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.kind == Batch::kMelspec ? "vpz_pcm_melspec (silence rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.kind == Batch::kMelspec ? "vpz_pcm_melspec (silence rows): " : batch.kind == Batch::kStft ? "vpz_pcm_stft (zero rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1498,10 +1514,11 @@ struct SubCall {
         return VPZ_OK;
     }
 
-    // a log-mel, fbank or MFCC call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j
+    // a log-mel, fbank or MFCC call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j;
+    // an STFT call's keep their channels: [members][channels][frames]
     int mono_temporary(size_t members)
     {
-        if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.frames, sizeof(float))) return VPZ_OK;
+        if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.channels * (size_t)B.frames, sizeof(float))) return VPZ_OK;
         R.m->fail(std::string(B.feature_call()) + ": the resampled rows' device temporary could not be allocated");
         return VPZ_E_NOMEM;
     }
@@ -1540,7 +1557,7 @@ struct SubCall {
     // a log-mel, fbank or MFCC call: row j's first `written[j]` samples of the temporary become row k - lo of the group's piece
     int feature_rows(std::vector<vpz_pack_row> &rows)
     {
-        for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.frames, written[j], rows[j].row};
+        for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.channels * B.frames, written[j], rows[j].row};
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
         const auto t_mel = Clock::now();
         // (a posted call: the feature launch writes member j's frames into row j of the lane's second temporary, and vpz_feat_post's
@@ -1557,7 +1574,7 @@ struct SubCall {
             }
         }
         int rc = launched(B.feature_step(), R.sw.fail_delivery ? VPZ_E_HIP
-                                                                : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.frames, rows, B.post ? (void *)L.feat() : B.dst,
+                                                                : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.channels * B.frames, rows, B.post ? (void *)L.feat() : B.dst,
                                                                                  B.post ? (int64_t)rows.size() : B.rows));
         if (B.post && rc == VPZ_OK) {
             const char *own = nullptr;
@@ -1872,6 +1889,27 @@ int vpzm_decode_ranges_melspec(vpzm_dispatcher *m, int32_t n, const uint8_t *con
     if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
     // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
     const Batch batch{Batch::kMelspec, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_stft(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                            int32_t sample_rate, int32_t channels, int32_t downmix, const vpz_stft_spec *spec, int64_t frames,
+                            void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!spec) return VPZM_E_ARG;
+    // (the table's limits are asked of the library that states them; the rest of vorbispizza_pcm_stft.h's are four ranges and the reserved words)
+    if (vpz_stft_table(spec->n_fft, spec->win_length, spec->window, nullptr, 0) != VPZ_OK) return VPZM_E_ARG;
+    if (spec->hop < 1 || spec->hop > spec->n_fft || spec->output < VPZ_STFT_COMPLEX || spec->output > VPZ_STFT_POWER) return VPZM_E_ARG;
+    if (spec->layout != VPZ_STFT_BINS_FIRST && spec->layout != VPZ_STFT_FRAMES_FIRST) return VPZM_E_ARG;
+    for (int32_t r : spec->reserved)
+        if (r != 0) return VPZM_E_ARG;
+    if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
+    // (what the resampled call refuses)
+    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
+    if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
+    // (channels and layout: of the resampled rows in the lane's temporary -- planar, float32)
+    Batch batch{Batch::kStft, channels, VPZ_OUT_PLANAR, frames, sample_rate, downmix};
+    batch.stft = spec;
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -50,6 +50,7 @@ BATCH_EXPORTED_SYMBOLS = ["vpzm_batch_partition", "vpzm_decode_ranges_batch"]  #
 RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_multi_resample.h)
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
 MELSPEC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_melspec"]  # (vorbispizza_multi_melspec.h)
+STFT_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_stft"]  # (vorbispizza_multi_stft.h)
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
 MFCC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_mfcc"]  # (vorbispizza_multi_mfcc.h)
 FEATPOST_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank_post", "vpzm_decode_ranges_mfcc_post"]  # (vorbispizza_multi_featpost.h)
@@ -101,6 +102,10 @@ def lib():
         if hasattr(L, "vpzm_decode_ranges_melspec"):
             L.vpzm_decode_ranges_melspec.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.LogMelSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_melspec.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_stft"):
+            L.vpzm_decode_ranges_stft.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(capi.StftSpec), C.c_int64,
+                                                  vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_stft.restype = C.c_int
         if hasattr(L, "vpzm_decode_ranges_fbank"):
             L.vpzm_decode_ranges_fbank.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_fbank.restype = C.c_int
@@ -340,6 +345,33 @@ class Dispatcher:
                                               C.byref(stats))
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_melspec failed (status %d): %s" % (rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_stft(self, datas, ranges, frames, sample_rate=44100, channels=2, mono=False, n_fft=4096, hop=1024, win_length=None,
+                           window="hann", output="complex", bins_first=True, out=None):
+        """vpzm_decode_ranges_stft: decode_ranges_batch(..., sample_rate=sample_rate, planar float32) with one more stage on the device
+        -- every channel of entry k's window, resampled, padded with zeros to `frames` OUTPUT samples, becomes a short-time Fourier
+        spectrogram: torch.stft(row, n_fft, hop, win_length, window, center=True, pad_mode="reflect", return_complex=True) with a
+        periodic 'hann' or 'hamming' window (include/vorbispizza_pcm_stft.h states the definition and the error bound; n_fft 512 to
+        8192; the defaults are a separation model's at 44.1 kHz).  output 'complex' gives complex64 tensors, 'magnitude' and 'power'
+        float32: [n, C, n_fft / 2 + 1, T] (bins_first, torch's order) or [n, C, T, n_fft / 2 + 1], T = 1 + frames // hop.  The channel
+        dimension is always there: C = channels, or 1 with mono=True (the mean of the stream's channels, whatever `channels` says).
+        out: as in decode_ranges_batch, tensors of that shape and element type.  Returns (parts, whole_or_None, results, stats)."""
+        import torch
+        spec = capi.StftSpec.make(n_fft=n_fft, hop=hop, win_length=win_length, window=window, output=output, bins_first=bins_first)
+        C_out = 1 if mono else int(channels)
+        if frames < 1 or hop < 1 or n_fft < 2 or C_out < 1:
+            raise ValueError("decode_ranges_stft: frames, hop and channels must be at least 1")
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        T, n_freq = spec.n_frames(frames), spec.n_freq
+        shape = (lambda rows: (rows, C_out, n_freq, T)) if bins_first else (lambda rows: (rows, C_out, T, n_freq))
+        out, whole, dst = self._group_tensors("decode_ranges_stft", n, shape, torch.complex64 if output == "complex" else torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = lib().vpzm_decode_ranges_stft(self._h, n, ptrs, sizes, rng.ctypes.data, int(sample_rate), C_out, int(bool(mono)), C.byref(spec),
+                                           int(frames), dst, results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_stft failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats
 
     def decode_ranges_fbank(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=80, low_freq=20.0, high_freq=0.0,

@@ -13,6 +13,8 @@
     dispatcher_probe.py --melspec-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --stft [--nfft N --hop H] [--mono] [--stft-output complex|magnitude|power] [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --stft-kernel
+    dispatcher_probe.py --ranges SAMPLES --batch --resample 22050 --cqt [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
+    dispatcher_probe.py --cqt-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --fbank [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
     dispatcher_probe.py --fbank-kernel
     dispatcher_probe.py --ranges SAMPLES --batch --resample RATE --mfcc [--gpu-entropy] [--reps N] groups,threads,streams_per_call,contexts,slots ...
@@ -68,6 +70,13 @@ the batch call delivers.
 --stft-kernel: vpz_pcm_stft alone, 64 stereo windows (128 rows) of one second and of thirty at 44 100 Hz, at 4096 / 1024 complex, 1024 / 256
 magnitude and 2048 / 512 power, both layouts, the context's event timer; the time, the bytes it stores per second, and vpz_pcm_melspec on
 the same rows at the same n_fft and hop where it takes the size.
+--ranges SAMPLES --batch --resample RATE --cqt: the same windows as constant-Q spectrograms of the mixed-down signal at the default music spec
+(84 bins from 32.70 Hz, 12 to the octave, hop 512, magnitude, bins first; RATE is the spec's sample rate) -- what a loader does without the
+call, decode_ranges_batch(mono) at RATE Hz, then one float32 torch.nn.functional.conv1d over the reflect-padded rows with the same kernels
+(vpz_cqt_kernel's) zero-padded to N_0 and stride hop, then the magnitude -- against decode_ranges_cqt; two dispatchers taking turns as above.
+--cqt-kernel: vpz_pcm_cqt alone, 64 mono rows of one second and of thirty at the default spec, magnitude, bins first, the context's event
+timer; the time, and the multiply-add rate over sum N_k (what the definition needs) and over the padded block lengths (what the kernel
+runs), each as a fraction of the 157 TFLOP/s float32 matrix peak.
 --ranges SAMPLES --batch --resample RATE --fbank: the same windows as Kaldi filterbank features (win 400, hop 160, n_fft 512, 80 bands, Povey
 window, pre-emphasis 0.97, per-frame mean removal, scale 32768, natural log), a float32 device tensor [streams][T][80].  The A/B: what a
 loader does without the call -- decode_ranges_batch at RATE Hz, mono, then on the device the eight torch ops unfold, mean, pre-emphasis,
@@ -130,6 +139,8 @@ ap.add_argument("--melspec-kernel", action="store_true")
 ap.add_argument("--stft", action="store_true")
 ap.add_argument("--stft-kernel", action="store_true")
 ap.add_argument("--stft-output", default="complex")
+ap.add_argument("--cqt", action="store_true")
+ap.add_argument("--cqt-kernel", action="store_true")
 ap.add_argument("--nfft", type=int, default=2048)
 ap.add_argument("--hop", type=int, default=512)
 ap.add_argument("--fbank", action="store_true")
@@ -670,6 +681,116 @@ def stft_kernel_job():
     ctx.close()
 
 
+def cqt_job(samples, rate):
+    import math, time
+    from vorbispizza_amd import capi
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, out = len(datas), [None, None]
+    spec = capi.CqtSpec.make(sample_rate=rate)
+    freqs, lengths = capi.cqt_bins(spec)
+    n0, nb, hop = int(lengths[0]), spec.n_bins, spec.hop
+    fs = 44100  # (both fixtures, stereo)
+    J = -(-samples * (rate // math.gcd(fs, rate)) // (fs // math.gcd(fs, rate)))
+    assert J >= n0 // 2 + 1, "windows shorter than the reflection of the lowest bin"
+    T = spec.n_frames(J)
+    # the dense bank a loader builds: every kernel centre-aligned in N_0, zeros elsewhere (Re rows, then Im rows)
+    dense = np.zeros((2 * nb, 1, n0), dtype=np.float32)
+    for k in range(nb):
+        hr, hi = capi.cqt_kernel(spec, k)
+        at = n0 // 2 - hr.size // 2
+        dense[k, 0, at: at + hr.size], dense[nb + k, 0, at: at + hr.size] = hr, hi
+    bank = torch.from_numpy(dense).to("cuda:0")
+    print("the dense bank: %d x %d = %d coefficients, %d of them live (%.1f %% zeros)" % (2 * nb, n0, 2 * nb * n0, 2 * int(lengths.sum()),
+                                                                                        100.0 * (1 - lengths.sum() / (nb * n0))), flush=True)
+    state = {}
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        _, whole, res, st = d.decode_ranges_batch(datas, windows, 1, J, planar=True, s16=False, sample_rate=rate, mono=True)
+        x = torch.nn.functional.pad(whole.view(n, 1, J), (n0 // 2, n0 // 2), mode="reflect")
+        x = torch.nn.functional.pad(x, (0, 1))  # (beyond the reflection x is zero: an odd N_0 reads one such sample when hop divides J)
+        y = torch.nn.functional.conv1d(x, bank, stride=hop)[:, :, :T]
+        out[0] = torch.sqrt(y[:, :nb] ** 2 + y[:, nb:] ** 2).view(n, 1, nb, T)
+        torch.cuda.synchronize()
+        state["rows"] = whole
+        return time.perf_counter() - t0, res, st
+
+    def by_cqt(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = d.decode_ranges_cqt(datas, windows, J, sample_rate=rate)
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz, cqt %d bins, hop %d, magnitude" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate, nb, hop)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_cqt(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all() and (res["samples"] == J).all()
+        assert out[0].shape == out[1].shape and out[0].dtype == out[1].dtype
+        # one truth for both legs: the same convolution in float64 on the rows the batch call delivered (four entries are enough to say)
+        x64 = torch.nn.functional.pad(torch.nn.functional.pad(state["rows"].view(n, 1, J)[:4].double(), (n0 // 2, n0 // 2), mode="reflect"), (0, 1))
+        wide = torch.from_numpy(np.stack([np.concatenate(capi_cqt_kernel64(spec, k, n0)) for k in range(nb)])).to("cuda:0")
+        y64 = torch.nn.functional.conv1d(x64, wide.view(nb, 2, n0).transpose(0, 1).reshape(2 * nb, 1, n0), stride=hop)[:, :, :T]
+        truth = torch.sqrt(y64[:, :nb] ** 2 + y64[:, nb:] ** 2).view(4, 1, nb, T)
+        print("%s:\n    rows of %d samples, a tensor of %.1f MB, largest difference of the two tensors %.3g; against the float64 chain: torch %.3g, "
+              "decode_ranges_cqt %.3g (largest |X| %.3g)" % (
+                  what, J, out[1].numel() * out[1].element_size() / 1e6, float((out[0] - out[1]).abs().max()), float((out[0][:4].double() - truth).abs().max()),
+                  float((out[1][:4].double() - truth).abs().max()), float(truth.abs().max())), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: decode_ranges_batch(mono) + conv1d + magnitude %s; decode_ranges_cqt %s" % (run, describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def capi_cqt_kernel64(spec, k, n0):
+    """bin k's float32 coefficients widened to float64 and centre-aligned in n0: (hr, hi)"""
+    from vorbispizza_amd import capi
+    hr, hi = capi.cqt_kernel(spec, k)
+    a, b = np.zeros(n0), np.zeros(n0)
+    at = n0 // 2 - hr.size // 2
+    a[at: at + hr.size], b[at: at + hr.size] = hr, hi
+    return a, b
+
+
+def cqt_kernel_job():
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n, rate = 64, 22050
+    spec = capi.CqtSpec.make()
+    freqs, lengths = capi.cqt_bins(spec)
+    live = int(lengths.sum())
+    padded = sum(32 * ((int(lengths[k0]) + 1) & ~1) for k0 in range(0, spec.n_bins, 32))
+    print("the default spec: sum N_k = %d, padded block lengths x 32 columns = %d (%.2f x), dense %d" % (live, padded, padded / live, spec.n_bins * int(lengths[0])), flush=True)
+    for samples in (rate, 30 * rate):
+        src = (torch.rand(n * (samples + 3), device="cuda:0") * 2 - 1)
+        rows = [(k * (samples + 3) + 1, samples, k) for k in range(n)]
+        T = spec.n_frames(samples)
+        dst = torch.empty((n,) + spec.row_shape(samples), dtype=torch.float32, device="cuda:0")
+        for run in (1, 2):
+            times = []
+            for _ in range(6):
+                ctx.timer_start()
+                assert capi.pcm_cqt(ctx, src, rows, dst, spec, samples) == capi.OK, ctx.last_error()
+                times.append(ctx.timer_stop())
+            ms = statistics.median(times[1:])
+            # a multiply-add is two operations; Re and Im are two sums
+            rate_live, rate_padded = 2 * 2 * n * T * live / ms / 1e9, 2 * 2 * n * T * padded / ms / 1e9
+            print("vpz_pcm_cqt 84 bins hop 512 magnitude bins first, 64 rows of %7d samples (T = %4d) run %d: median of 5 %.1f us (min %.1f, max %.1f); "
+                  "%.2f TFLOP/s over sum N_k = %.1f %% of 157, %.2f TFLOP/s over the padded blocks = %.1f %%"
+                  % (samples, T, run, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, rate_live, rate_live / 157 * 100, rate_padded, rate_padded / 157 * 100), flush=True)
+        del dst
+    ctx.close()
+
+
 def fbank_job(samples, rate):
     import math, time
     from vorbispizza_amd import capi
@@ -1149,6 +1270,12 @@ if args.stft_kernel:
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.stft:
     stft_job(args.ranges, args.resample)
+    sys.exit(0)
+if args.cqt_kernel:
+    cqt_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.cqt:
+    cqt_job(args.ranges, args.resample)
     sys.exit(0)
 if args.ranges and args.batch and args.resample and args.logmel:
     logmel_job(args.ranges, args.resample)

@@ -33,6 +33,7 @@ SOURCES = {
     "pcm_logmel.hip": [],  # vpz_pcm_logmel: windows of a mono device array as (log-)mel frames (the DFT on the exact float32 MFMA)
     "pcm_melspec.hip": ["-ffp-contract=off"],  # vpz_pcm_melspec: the same frames with transforms of 2048, 4096 and 8192: a real FFT in LDS, one transform per frame (every fused step is written as one)
     "pcm_stft.hip": ["-ffp-contract=off"],  # vpz_pcm_stft: the spectrum itself -- complex, magnitude or power -- of rows of a float32 array, transforms of 512 to 8192: the same real FFT, two or four frames side by side at the small sizes
+    "pcm_cqt.hip": ["-ffp-contract=off"],  # vpz_pcm_cqt: rows of a float32 array as constant-Q spectrograms: one kernel per bin, a framed matrix product on the exact float32 MFMA whose dead k-ranges are skipped per block of 32 bins
     "pcm_fbank.hip": [],  # vpz_pcm_fbank: the same windows as Kaldi filterbank frames (per-frame mean, the folded operator on the same MFMA); vpz_pcm_mfcc: the same tile core with the cepstral stage
     "pcm_loudness.hip": [],  # vpz_pcm_loudness: windows of an interleaved device array as K-weighted step sums and a peak (float64; the recurrence cut into steps, carried exactly)
     "pcm_truepeak.hip": [],  # vpz_pcm_true_peak: the same windows' true peak (a 4x / 2x polyphase interpolator in float32, fused, one order) and sample peak; range and maxima of step sums, host only
@@ -65,6 +66,7 @@ def _deps(src):
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_logmel.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_melspec.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_stft.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_cqt.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_fbank.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_mfcc.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_loudness.h"))
@@ -98,7 +100,8 @@ def build_host(force=False, verbose=False):
                    os.path.join(inc, "vorbispizza_multi_mfcc.h"), os.path.join(inc, "vorbispizza_pcm_featpost.h"),
                    os.path.join(inc, "vorbispizza_multi_featpost.h"), os.path.join(inc, "vorbispizza_pcm_melspec.h"),
                    os.path.join(inc, "vorbispizza_multi_melspec.h"), os.path.join(inc, "vorbispizza_pcm_stft.h"),
-                   os.path.join(inc, "vorbispizza_multi_stft.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi_stft.h"), os.path.join(inc, "vorbispizza_pcm_cqt.h"),
+                   os.path.join(inc, "vorbispizza_multi_cqt.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

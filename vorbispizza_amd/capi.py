@@ -202,6 +202,55 @@ _PCM_STFT_SIGNATURES = [
 PCM_STFT_EXPORTED_SYMBOLS = [s[0] for s in _PCM_STFT_SIGNATURES]
 
 
+class CqtSpec(C.Structure):
+    """vpz_cqt_spec (include/vorbispizza_pcm_cqt.h).  CqtSpec.make(...) takes the names a Python caller uses; its defaults are the music
+    spec: 84 bins from C1 (32.70 Hz), 12 to the octave, at 22 050 Hz with a hop of 512."""
+    _fields_ = [("sample_rate", C.c_double), ("f_min", C.c_double), ("filter_scale", C.c_double), ("gamma", C.c_double),
+                ("n_bins", C.c_int32), ("bins_per_octave", C.c_int32), ("hop", C.c_int32), ("window", C.c_int32), ("scale", C.c_int32),
+                ("pad", C.c_int32), ("output", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+    @classmethod
+    def make(cls, sample_rate=22050, f_min=32.70319566257483, n_bins=84, bins_per_octave=12, hop=512, filter_scale=1.0, gamma=0.0,
+             window="hann", scale="sqrt_length", pad="reflect", output="magnitude", bins_first=True):
+        windows = {"hann": CQT_HANN, "hamming": CQT_HAMMING}
+        scales = {"none": CQT_SCALE_NONE, "sqrt_length": CQT_SCALE_SQRT_LENGTH}
+        pads = {"reflect": CQT_PAD_REFLECT, "zero": CQT_PAD_ZERO}
+        outputs = {"complex": CQT_COMPLEX, "magnitude": CQT_MAGNITUDE, "power": CQT_POWER}
+        if window not in windows or scale not in scales or pad not in pads or output not in outputs:
+            raise ValueError("CqtSpec: window is 'hann' or 'hamming', scale 'none' or 'sqrt_length', pad 'reflect' or 'zero', output "
+                             "'complex', 'magnitude' or 'power'")
+        s = cls()
+        s.sample_rate, s.f_min, s.filter_scale, s.gamma = float(sample_rate), float(f_min), float(filter_scale), float(gamma)
+        s.n_bins, s.bins_per_octave, s.hop = int(n_bins), int(bins_per_octave), int(hop)
+        s.window, s.scale, s.pad, s.output = windows[window], scales[scale], pads[pad], outputs[output]
+        s.layout = CQT_BINS_FIRST if bins_first else CQT_FRAMES_FIRST
+        return s
+
+    def n_frames(self, frames):
+        """T of a row of `frames` samples."""
+        return 1 + int(frames) // self.hop
+
+    def row_shape(self, frames):
+        """a row of the destination as float32: (n_bins, T) or (T, n_bins), with a last 2 for the complex output"""
+        inner = (self.n_bins, self.n_frames(frames)) if self.layout == CQT_BINS_FIRST else (self.n_frames(frames), self.n_bins)
+        return inner + ((2,) if self.output == CQT_COMPLEX else ())
+
+
+CQT_HANN, CQT_HAMMING = 0, 1
+CQT_SCALE_NONE, CQT_SCALE_SQRT_LENGTH = 0, 1
+CQT_PAD_REFLECT, CQT_PAD_ZERO = 0, 1
+CQT_COMPLEX, CQT_MAGNITUDE, CQT_POWER = 0, 1, 2
+CQT_BINS_FIRST, CQT_FRAMES_FIRST = 0, 1
+CQT_MAX_BINS, CQT_MAX_BINS_PER_OCTAVE, CQT_MAX_LENGTH, CQT_MAX_HOP = 512, 96, 65536, 2048
+# include/vorbispizza_pcm_cqt.h (a header of its own again)
+_PCM_CQT_SIGNATURES = [
+    ("vpz_cqt_bins", C.c_int, [C.POINTER(CqtSpec), _vp, _vp, C.c_int32]),
+    ("vpz_cqt_kernel", C.c_int, [C.POINTER(CqtSpec), C.c_int32, _vp, C.c_int64, C.POINTER(C.c_int32)]),
+    ("vpz_pcm_cqt", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(CqtSpec), C.c_int32, _vp, _vp, C.c_int64]),
+]
+PCM_CQT_EXPORTED_SYMBOLS = [s[0] for s in _PCM_CQT_SIGNATURES]
+
+
 FLT_EPSILON = 2.0 ** -23  # (Kaldi's floor under the log)
 
 
@@ -370,7 +419,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
                  + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES + _PCM_MELSPEC_SIGNATURES
-                 + _PCM_STFT_SIGNATURES)
+                 + _PCM_STFT_SIGNATURES + _PCM_CQT_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -619,6 +668,43 @@ def stft_table(n_fft, win_length=None, window="hann"):
     if rc != OK:
         raise ValueError("vpz_stft_table failed (status %d)" % rc)
     return table[:int(n_fft)], table[int(n_fft):].reshape(int(n_fft), 2)
+
+
+def pcm_cqt(ctx, src, rows, dst, spec, frames):
+    """vpz_pcm_cqt (vorbispizza_pcm_cqt.h): windows of the float32 device array `src` (a torch tensor; a channel of a planar array is a
+    row) as constant-Q spectrograms of rows padded to `frames` samples, into rows of `dst` -- a contiguous torch tensor whose first
+    dimension counts the rows: float32 [rows, n_bins, T] (bins first) or [rows, T, n_bins], with a last dimension of 2 for the complex
+    output.  rows: [(src element offset, samples, destination row)]; spec: a CqtSpec.  Asynchronous on the context's stream; returns the
+    status (a refusal is an answer, not an exception)."""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return lib().vpz_pcm_cqt(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
+                             int(dst.shape[0]))
+
+
+def cqt_bins(spec):
+    """vpz_cqt_bins: (f_k float64 [n_bins], N_k int32 [n_bins]) of a CqtSpec; needs no device.  A spec outside the limits raises
+    ValueError."""
+    n = max(0, int(spec.n_bins))
+    freqs, lengths = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int32)
+    rc = lib().vpz_cqt_bins(C.byref(spec), freqs.ctypes.data, lengths.ctypes.data, n)
+    if rc != OK:
+        raise ValueError("vpz_cqt_bins refuses the spec (status %d)" % rc)
+    return freqs, lengths
+
+
+def cqt_kernel(spec, k):
+    """vpz_cqt_kernel: (hr_k, hi_k), float32 [N_k] each -- bin k's coefficients as the kernel multiplies them; needs no device.  A spec
+    outside the limits or a k outside the bins raises ValueError."""
+    n = C.c_int32(0)
+    rc = lib().vpz_cqt_kernel(C.byref(spec), int(k), None, 0, C.byref(n))
+    if rc != OK:
+        raise ValueError("vpz_cqt_kernel refuses the spec or bin %r (status %d)" % (k, rc))
+    table = np.zeros(2 * n.value, dtype=np.float32)
+    rc = lib().vpz_cqt_kernel(C.byref(spec), int(k), table.ctypes.data, table.size, None)
+    if rc != OK:
+        raise ValueError("vpz_cqt_kernel failed (status %d)" % rc)
+    return table[:n.value], table[n.value:]
 
 
 def pcm_fbank(ctx, src, rows, dst, spec, frames):

@@ -247,6 +247,7 @@ static void free_pcm_state(Context *ctx)
     free_tables(ctx->fbank_banks);
     free_tables(ctx->mfcc_tables);
     free_tables(ctx->stft_tables);
+    free_tables(ctx->cqt_tables);
     ctx->loudness_rates.clear();
     for (Scratch *s : {&ctx->stage_in, &ctx->stage_out, &ctx->loud_scratch, &ctx->tp_scratch}) {
         if (s->p) (void)hipFree(s->p);

@@ -90,6 +90,11 @@ struct Context {
                                    // folded table, [2 * ceil(win / 2)][2 * cols]
         int cols = 0;              // the bins rounded up to the kernel's column tile
     };
+    struct CqtTable : DeviceTable {
+        float *d_table = nullptr;  // per column block of 32 bins: [len][2][32], the Re columns, then the Im columns, of its centre-aligned kernels
+        void *d_blocks = nullptr;  // [n_blocks] records of pcm_cqt.hip: where a block's table starts, its padded length, floor(longest / 2)
+        int n_blocks = 0, n0 = 0;  // the column blocks; N_0
+    };
     struct LogmelBank : DeviceTable {
         int32_t *d_meta = nullptr;  // [n_mels][3]: first live bin, live bins, where the band's weights start
         float *d_w = nullptr;
@@ -104,6 +109,7 @@ struct Context {
     std::map<std::array<double, 5>, LogmelBank> fbank_banks;       // (sample_rate, n_fft, n_mels, low_freq, high_freq)
     std::map<std::array<double, 5>, DeviceTable> mfcc_tables;      // (n_mels, n_ceps, lifter, htk_compat, use_energy): [n_mels][n_ceps]
     std::map<std::array<int, 3>, LogmelDft> stft_tables;           // (n_fft, win_length, window): vpz_pcm_stft's window and twiddles, 3 n_fft floats
+    std::map<std::array<double, 8>, CqtTable> cqt_tables;          // (sample_rate, f_min, filter_scale, gamma, n_bins, bins_per_octave, window, scale): vpz_pcm_cqt's kernels
     std::map<int, LoudnessRate> loudness_rates;                   // the sample rate
     Scratch loud_scratch{nullptr, 0, true};  // vpz_pcm_loudness: states, energies and partial sums of a launch
     Scratch tp_scratch{nullptr, 0, true};    // vpz_pcm_true_peak: one pair of maxima per tile

@@ -41,6 +41,7 @@
 // 2048, 4096 and 8192 samples.
 // vpzm_decode_ranges_stft (include/vorbispizza_multi_stft.h) keeps the channels and the spectrum: the resample launches write planar rows
 // [members][C][frames] into the temporary, and vpz_pcm_stft takes every (member, channel) as a row of its own.
+// vpzm_decode_ranges_cqt (include/vorbispizza_multi_cqt.h) is the STFT call with vpz_pcm_cqt as its feature stage: constant-Q spectrograms.
 // vpzm_decode_ranges_fbank (include/vorbispizza_multi_fbank.h) is the same call with vpz_pcm_fbank as that stage: Kaldi filterbank frames.
 // vpzm_decode_ranges_mfcc (include/vorbispizza_multi_mfcc.h) is the same call with vpz_pcm_mfcc as that stage: Kaldi MFCC frames.
 // vpzm_decode_ranges_fbank_post / _mfcc_post (include/vorbispizza_multi_featpost.h) are those two with vpz_feat_post behind the feature
@@ -86,6 +87,8 @@
 #include "../../include/vorbispizza_multi_melspec.h"
 #include "../../include/vorbispizza_pcm_stft.h"
 #include "../../include/vorbispizza_multi_stft.h"
+#include "../../include/vorbispizza_pcm_cqt.h"
+#include "../../include/vorbispizza_multi_cqt.h"
 #include "../../include/vorbispizza_pcm_fbank.h"
 #include "../../include/vorbispizza_multi_fbank.h"
 #include "../../include/vorbispizza_pcm_mfcc.h"
@@ -349,7 +352,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, STFT, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, STFT, CQT, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -402,8 +405,8 @@ struct Job {  // one stream of the library inside its group
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
     // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or then
-    // vpz_pcm_mfcc; or then vpz_pcm_melspec; or then vpz_pcm_stft; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
-    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc, kMelspec, kStft };
+    // vpz_pcm_mfcc; or then vpz_pcm_melspec; or then vpz_pcm_stft; or then vpz_pcm_cqt; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
+    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc, kMelspec, kStft, kCqt };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
@@ -420,6 +423,8 @@ struct Batch {
     // kStft: a resampled call of `channels` planar channels (one with `downmix`) whose every channel is a row of spectrum frames of this
     // spec: entry k's channel c is row (k - lo) * channels + c of `dst` ([rows][channels][n_freq][T], complex pairs included, or transposed)
     const vpz_stft_spec *stft = nullptr;
+    // kCqt: the same with constant-Q frames of this spec ([rows][channels][n_bins][T], complex pairs included, or transposed)
+    const vpz_cqt_spec *cqt = nullptr;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
     // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
@@ -428,21 +433,22 @@ struct Batch {
     bool measured() const { return kind == kLoudness || kind == kR128; }
     vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
     vpzm_r128 &record_r128(int64_t row) const { return static_cast<vpzm_r128 *>(dst)[row]; }
-    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc || kind == kMelspec || kind == kStft; }  // a feature stage behind the resample launches, fed from the lane's temporary
-    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : kind == kMelspec ? "vpz_pcm_melspec" : kind == kStft ? "vpz_pcm_stft" : "vpz_pcm_logmel"; }
-    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : kind == kMelspec ? "vpzm_decode_ranges_melspec" : kind == kStft ? "vpzm_decode_ranges_stft" : "vpzm_decode_ranges_logmel"; }
-    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : kind == kMelspec ? "mel-spectrogram" : kind == kStft ? "stft" : "log-mel"; }
+    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc || kind == kMelspec || kind == kStft || kind == kCqt; }  // a feature stage behind the resample launches, fed from the lane's temporary
+    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : kind == kMelspec ? "vpz_pcm_melspec" : kind == kStft ? "vpz_pcm_stft" : kind == kCqt ? "vpz_pcm_cqt" : "vpz_pcm_logmel"; }
+    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : kind == kMelspec ? "vpzm_decode_ranges_melspec" : kind == kStft ? "vpzm_decode_ranges_stft" : kind == kCqt ? "vpzm_decode_ranges_cqt" : "vpzm_decode_ranges_logmel"; }
+    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : kind == kMelspec ? "mel-spectrogram" : kind == kStft ? "stft" : kind == kCqt ? "cqt" : "log-mel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `to` (the group's piece, or a
-    // posted call's temporary), which has `to_rows` rows.  An STFT call's array is planar -- a descriptor's `src` is the window in its
+    // posted call's temporary), which has `to_rows` rows.  An STFT or CQT call's array is planar -- a descriptor's `src` is the window in its
     // member's first channel, the next channel lies `frames` elements on (none is read where samples = 0) -- and a descriptor stands for
     // its entry's `channels` rows: one descriptor of the launch per channel
     int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d, void *to, int64_t to_rows) const
     {
-        if (kind == kStft) {
+        if (kind == kStft || kind == kCqt) {
             std::vector<vpz_pack_row> each;
             each.reserve(d.size() * (size_t)channels);
             for (const vpz_pack_row &r : d)
                 for (int32_t c = 0; c < channels; ++c) each.push_back(vpz_pack_row{r.samples > 0 ? r.src + c * frames : 0, r.samples, r.row * channels + c});
+            if (kind == kCqt) return vpz_pcm_cqt(ctx, src, src_elems, frames, cqt, (int32_t)each.size(), each.data(), to, to_rows * channels);
             return vpz_pcm_stft(ctx, src, src_elems, frames, stft, (int32_t)each.size(), each.data(), to, to_rows * channels);
         }
         if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), to, to_rows);
@@ -982,7 +988,7 @@ struct GroupRun {
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0], rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.kind == Batch::kMelspec ? "vpz_pcm_melspec (silence rows): " : batch.kind == Batch::kStft ? "vpz_pcm_stft (zero rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.kind == Batch::kMelspec ? "vpz_pcm_melspec (silence rows): " : batch.kind == Batch::kStft ? "vpz_pcm_stft (zero rows): " : batch.kind == Batch::kCqt ? "vpz_pcm_cqt (zero rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1515,7 +1521,7 @@ struct SubCall {
     }
 
     // a log-mel, fbank or MFCC call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j;
-    // an STFT call's keep their channels: [members][channels][frames]
+    // an STFT or CQT call's keep their channels: [members][channels][frames]
     int mono_temporary(size_t members)
     {
         if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.channels * (size_t)B.frames, sizeof(float))) return VPZ_OK;
@@ -1910,6 +1916,25 @@ int vpzm_decode_ranges_stft(vpzm_dispatcher *m, int32_t n, const uint8_t *const 
     // (channels and layout: of the resampled rows in the lane's temporary -- planar, float32)
     Batch batch{Batch::kStft, channels, VPZ_OUT_PLANAR, frames, sample_rate, downmix};
     batch.stft = spec;
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+int vpzm_decode_ranges_cqt(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                           int32_t sample_rate, int32_t channels, int32_t downmix, const vpz_cqt_spec *spec, int64_t frames,
+                           void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!spec) return VPZM_E_ARG;
+    // (the spec's limits are asked of the library that states them, and N_0 with them: the reflect mode's shortest row)
+    if (vpz_cqt_bins(spec, nullptr, nullptr, 0) != VPZ_OK) return VPZM_E_ARG;
+    int32_t n0 = 0;
+    if (vpz_cqt_kernel(spec, 0, nullptr, 0, &n0) != VPZ_OK) return VPZM_E_ARG;
+    if (frames < 1 || (spec->pad == VPZ_CQT_PAD_REFLECT && frames < n0 / 2 + 1)) return VPZM_E_ARG;
+    // (what the resampled call refuses)
+    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
+    if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
+    // (channels and layout: of the resampled rows in the lane's temporary -- planar, float32)
+    Batch batch{Batch::kCqt, channels, VPZ_OUT_PLANAR, frames, sample_rate, downmix};
+    batch.cqt = spec;
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

@@ -51,6 +51,7 @@ RESAMPLE_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_resampled"]  # (vorbispizza_mul
 LOGMEL_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_logmel"]  # (vorbispizza_multi_logmel.h)
 MELSPEC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_melspec"]  # (vorbispizza_multi_melspec.h)
 STFT_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_stft"]  # (vorbispizza_multi_stft.h)
+CQT_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_cqt"]  # (vorbispizza_multi_cqt.h)
 FBANK_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank"]  # (vorbispizza_multi_fbank.h)
 MFCC_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_mfcc"]  # (vorbispizza_multi_mfcc.h)
 FEATPOST_EXPORTED_SYMBOLS = ["vpzm_decode_ranges_fbank_post", "vpzm_decode_ranges_mfcc_post"]  # (vorbispizza_multi_featpost.h)
@@ -106,6 +107,10 @@ def lib():
             L.vpzm_decode_ranges_stft.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(capi.StftSpec), C.c_int64,
                                                   vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_stft.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_cqt"):
+            L.vpzm_decode_ranges_cqt.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(capi.CqtSpec), C.c_int64,
+                                                 vp, vp, C.POINTER(Stats)]
+            L.vpzm_decode_ranges_cqt.restype = C.c_int
         if hasattr(L, "vpzm_decode_ranges_fbank"):
             L.vpzm_decode_ranges_fbank.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.FbankSpec), C.c_int64, vp, vp, C.POINTER(Stats)]
             L.vpzm_decode_ranges_fbank.restype = C.c_int
@@ -372,6 +377,37 @@ class Dispatcher:
                                            int(frames), dst, results.ctypes.data, C.byref(stats))
         if rc != OK:
             raise MultiError("vpzm_decode_ranges_stft failed (status %d): %s" % (rc, self.last_error()))
+        return out, whole, results, stats
+
+    def decode_ranges_cqt(self, datas, ranges, frames, sample_rate=22050, channels=1, mono=True, f_min=32.70319566257483, n_bins=84,
+                          bins_per_octave=12, hop=512, filter_scale=1.0, gamma=0.0, window="hann", scale="sqrt_length", pad="reflect",
+                          output="magnitude", bins_first=True, out=None):
+        """vpzm_decode_ranges_cqt: decode_ranges_stft with the constant-Q transform as its stage -- every channel of entry k's window,
+        resampled to `sample_rate`, padded with zeros to `frames` OUTPUT samples, becomes a constant-Q spectrogram: n_bins bins at
+        f_min * 2^(k / bins_per_octave), each with its own periodic 'hann' or 'hamming' window of N_k = ceil(Q sample_rate / (f_k +
+        gamma / alpha)) samples centred on sample t * hop (include/vorbispizza_pcm_cqt.h states the definition and the error bound;
+        the defaults are 84 bins from C1 at 22.05 kHz).  scale 'sqrt_length' reads white noise flat across the bins, 'none' a unit cosine
+        as 0.5; pad 'reflect' centres as the other stages do, 'zero' takes clips shorter than the lowest bin's window.  output 'complex'
+        gives complex64 tensors, 'magnitude' and 'power' float32: [n, C, n_bins, T] (bins_first) or [n, C, T, n_bins], T = 1 + frames //
+        hop.  The channel dimension is always there: C = channels, or 1 with mono=True (the mean of the stream's channels, whatever
+        `channels` says).  out: as in decode_ranges_batch, tensors of that shape and element type.  Returns (parts, whole_or_None,
+        results, stats)."""
+        import torch
+        spec = capi.CqtSpec.make(sample_rate=sample_rate, f_min=f_min, n_bins=n_bins, bins_per_octave=bins_per_octave, hop=hop,
+                                 filter_scale=filter_scale, gamma=gamma, window=window, scale=scale, pad=pad, output=output, bins_first=bins_first)
+        C_out = 1 if mono else int(channels)
+        if frames < 1 or hop < 1 or n_bins < 1 or C_out < 1:
+            raise ValueError("decode_ranges_cqt: frames, hop, n_bins and channels must be at least 1")
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        T, nb = spec.n_frames(frames), int(n_bins)
+        shape = (lambda rows: (rows, C_out, nb, T)) if bins_first else (lambda rows: (rows, C_out, T, nb))
+        out, whole, dst = self._group_tensors("decode_ranges_cqt", n, shape, torch.complex64 if output == "complex" else torch.float32, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = lib().vpzm_decode_ranges_cqt(self._h, n, ptrs, sizes, rng.ctypes.data, int(sample_rate), C_out, int(bool(mono)), C.byref(spec),
+                                          int(frames), dst, results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_decode_ranges_cqt failed (status %d): %s" % (rc, self.last_error()))
         return out, whole, results, stats
 
     def decode_ranges_fbank(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=80, low_freq=20.0, high_freq=0.0,

@@ -157,12 +157,12 @@ def sentinel_out(d, n, shape, dtype, value):
     return [torch.full(shape(hi - lo), value, dtype=dtype, device="cuda:%d" % i) for (lo, hi), i in zip(cuts, d.device_ids)]
 
 
-def check_failed_delivery(monkeypatch, d, run, empty_row):
+def check_failed_delivery(monkeypatch, d, run, empty_row, step=None):
     """VPZM_FAIL_DELIVERY (host/vorbis_multi.cpp): a sub-batch's delivery launch counts as failed without being made.  run() -> (tensor,
     results) of one call on dispatcher `d` into sentinel-filled tensors.  Every entry that a delivery launch serves -- OK in the plain
     call, with packets -- comes back E_SYNTH with no samples; an entry with a status of its own keeps it, and so does the empty window (OK,
     no packets: it is in no sub-batch, GroupRun::zero_rows alone defines its row); every row is `empty_row`; the next call without the
-    switch is the plain call bit for bit."""
+    switch is the plain call bit for bit.  step: the launch the switch fails -- the dispatcher's error text names it."""
     import torch
     from vorbispizza_amd import multi
     monkeypatch.delenv("VPZM_FAIL_DELIVERY", raising=False)
@@ -178,6 +178,8 @@ def check_failed_delivery(monkeypatch, d, run, empty_row):
     assert (as_bits(got) == empty_row).all()
     assert not (as_bits(plain) == empty_row).all()
     assert d.last_error() != ""
+    if step is not None:
+        assert step + ":" in d.last_error(), d.last_error()
     again, again_results = run()
     assert torch.equal(as_bits(again), as_bits(plain))
     for field in FIELDS:
@@ -200,7 +202,7 @@ def test_a_failed_pack_costs_its_members_e_synth_and_leaves_zero_rows(ctx, monke
         for planar, s16 in ((True, False), (False, True)):
             dtype, shape = (torch.int16 if s16 else torch.float32), (lambda rows: (rows, 2, n) if planar else (rows, n, 2))
             check_failed_delivery(monkeypatch, d, lambda: batch_call(entries, 2, n, planar, s16, dispatcher=d,
-                                                                     out=sentinel_out(d, len(entries), shape, dtype, 77))[:2], 0)
+                                                                     out=sentinel_out(d, len(entries), shape, dtype, 77))[:2], 0, step="vpz_pcm_pack")
     finally:
         d.close()
 

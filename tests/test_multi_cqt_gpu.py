@@ -173,7 +173,7 @@ def test_a_failed_cqt_launch_costs_its_members_e_synth_and_leaves_zero_rows(ctx,
         for spec in VARIANTS:
             entries, J, _, _ = refused_entries(spec)
             check_failed_delivery(monkeypatch, d, lambda: cqt_call(entries, J, spec, dispatcher=d, out=sentinel_out(
-                d, len(entries), lambda rows: shape_of(rows, J, spec), dtype_of(spec), 77.0))[:2], 0)
+                d, len(entries), lambda rows: shape_of(rows, J, spec), dtype_of(spec), 77.0))[:2], 0, step="vpz_pcm_cqt")
     finally:
         d.close()
 

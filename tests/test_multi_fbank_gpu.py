@@ -192,7 +192,7 @@ def test_a_failed_fbank_launch_costs_its_members_e_synth_and_leaves_pad_rows(ctx
     try:
         for spec in VARIANTS:
             check_failed_delivery(monkeypatch, d, lambda: fbank_call(entries, J, spec, dispatcher=d, out=sentinel_out(
-                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], pad_bits(spec))
+                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], pad_bits(spec), step="vpz_pcm_fbank")
     finally:
         d.close()
 

@@ -180,7 +180,7 @@ def test_a_failed_delivery_costs_its_members_e_synth_and_leaves_pad_rows(ctx, mo
     try:
         for kind, spec, post in CASES[:3]:
             check_failed_delivery(monkeypatch, d, lambda: post_call(kind, entries, J, spec, post, dispatcher=d, out=sentinel_out(
-                d, len(entries), lambda rows: shape_of(rows, J, kind, spec, post), torch.float32, 77.0))[:2], pad_bits(post))
+                d, len(entries), lambda rows: shape_of(rows, J, kind, spec, post), torch.float32, 77.0))[:2], pad_bits(post), step="vpz_pcm_" + kind)
     finally:
         d.close()
 

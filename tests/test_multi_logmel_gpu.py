@@ -173,7 +173,7 @@ def test_a_failed_logmel_launch_costs_its_members_e_synth_and_leaves_silence_row
         for spec in VARIANTS:
             silence = int(silence_value(spec["floor"]).view(np.int32)) if spec["log"] else 0
             check_failed_delivery(monkeypatch, d, lambda: logmel_call(entries, J, spec, dispatcher=d, out=sentinel_out(
-                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], silence)
+                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], silence, step="vpz_pcm_logmel")
     finally:
         d.close()
 

@@ -166,7 +166,7 @@ def test_a_failed_melspec_launch_costs_its_members_e_synth_and_leaves_silence_ro
             entries, J, _ = refused_entries(spec["sample_rate"])
             silence = int(silence_value(spec["floor"]).view(np.int32)) if spec["log"] else 0
             check_failed_delivery(monkeypatch, d, lambda: melspec_call(entries, J, spec, dispatcher=d, out=sentinel_out(
-                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], silence)
+                d, len(entries), lambda rows: shape_of(rows, J, spec), torch.float32, 77.0))[:2], silence, step="vpz_pcm_melspec")
     finally:
         d.close()
 

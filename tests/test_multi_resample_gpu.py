@@ -294,7 +294,8 @@ def test_failed_resample_launches_cost_their_members_e_synth_and_leave_zero_rows
         for planar, s16 in ((True, False), (False, True)):
             dtype, shape = (torch.int16 if s16 else torch.float32), (lambda rows: (rows, 2, J) if planar else (rows, J, 2))
             check_failed_delivery(monkeypatch, d, lambda: resampled_call(entries, RATE, 2, J, planar, s16, dispatcher=d,
-                                                                         out=sentinel_out(d, len(entries), shape, dtype, 77))[:2], 0)
+                                                                         out=sentinel_out(d, len(entries), shape, dtype, 77))[:2], 0,
+                                  step="vpz_pcm_resample")
     finally:
         d.close()
 

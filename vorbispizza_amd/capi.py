@@ -570,28 +570,38 @@ def resample_filter(up, down):
     return taps.value, first, coeffs
 
 
+def _pcm_feature(fn, ctx, src, rows, dst, spec, frames):
+    """a feature launch (vpz_pcm_logmel and its kin have one argument list): rows [(src, samples, row)] of `src` into rows of `dst`"""
+    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
+    _sync_producer(src, dst)
+    return fn(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst), int(dst.shape[0]))
+
+
+def _table_of(fn, name, head, shape, what):
+    """a float32 table of the library's: fn(*head, None, 0) says whether it exists (no: ValueError, "<name> refuses <what>"), then
+    fn(*head, table, size) fills one of shape() -- worked out behind the refusal"""
+    rc = fn(*head, None, 0)
+    if rc != OK:
+        raise ValueError("%s refuses %s (status %d)" % (name, what, rc))
+    table = np.zeros(shape(), dtype=np.float32)
+    rc = fn(*head, table.ctypes.data, table.size)
+    if rc != OK:
+        raise ValueError("%s failed (status %d)" % (name, rc))
+    return table
+
+
 def pcm_logmel(ctx, src, rows, dst, spec, frames):
     """vpz_pcm_logmel (vorbispizza_pcm_logmel.h): windows of the MONO float32 device array `src` (a torch tensor) as (log-)mel frames of
     rows padded to `frames` samples, into rows of `dst` -- a contiguous float32 torch tensor [rows, n_mels, T] (MEL_BANDS_FIRST) or
     [rows, T, n_mels], T = 1 + frames // hop; rows: [(src, samples, row)]; spec: a LogMelSpec.  Asynchronous on the context's stream;
     returns the status (a refusal is an answer, not an exception)."""
-    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
-    _sync_producer(src, dst)
-    return lib().vpz_pcm_logmel(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
-                                int(dst.shape[0]))
+    return _pcm_feature(lib().vpz_pcm_logmel, ctx, src, rows, dst, spec, frames)
 
 
 def logmel_dft_table(n_fft):
     """vpz_logmel_dft_table: float32 [n_fft, 2, n_fft // 2 + 1] -- [m, 0, k] = w[m] cos, [m, 1, k] = w[m] sin; needs no device.  A refused
     n_fft raises ValueError."""
-    rc = lib().vpz_logmel_dft_table(n_fft, None, 0)
-    if rc != OK:
-        raise ValueError("vpz_logmel_dft_table refuses n_fft %r (status %d)" % (n_fft, rc))
-    table = np.zeros((int(n_fft), 2, int(n_fft) // 2 + 1), dtype=np.float32)
-    rc = lib().vpz_logmel_dft_table(n_fft, table.ctypes.data, table.size)
-    if rc != OK:
-        raise ValueError("vpz_logmel_dft_table failed (status %d)" % rc)
-    return table
+    return _table_of(lib().vpz_logmel_dft_table, "vpz_logmel_dft_table", (n_fft,), lambda: (int(n_fft), 2, int(n_fft) // 2 + 1), "n_fft %r" % (n_fft,))
 
 
 def mel_filterbank(spec):
@@ -617,22 +627,13 @@ def pcm_melspec(ctx, src, rows, dst, spec, frames):
     """vpz_pcm_melspec (vorbispizza_pcm_melspec.h): pcm_logmel's arguments and shapes, for a LogMelSpec with n_fft 2048, 4096 or 8192 (a
     real FFT per frame, held to the header's bound).  Asynchronous on the context's stream; returns the status (a refusal is an answer,
     not an exception)."""
-    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
-    _sync_producer(src, dst)
-    return lib().vpz_pcm_melspec(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
-                                 int(dst.shape[0]))
+    return _pcm_feature(lib().vpz_pcm_melspec, ctx, src, rows, dst, spec, frames)
 
 
 def melspec_twiddles(n_fft):
     """vpz_melspec_twiddles: (w float32 [n_fft], t float32 [n_fft, 2]) -- the periodic Hann window and t[k] = (cos, -sin)(2 pi k / n_fft),
     two views of the one table of 3 * n_fft floats the kernel reads; needs no device.  A refused n_fft raises ValueError."""
-    rc = lib().vpz_melspec_twiddles(n_fft, None, 0)
-    if rc != OK:
-        raise ValueError("vpz_melspec_twiddles refuses n_fft %r (status %d)" % (n_fft, rc))
-    table = np.zeros(3 * int(n_fft), dtype=np.float32)
-    rc = lib().vpz_melspec_twiddles(n_fft, table.ctypes.data, table.size)
-    if rc != OK:
-        raise ValueError("vpz_melspec_twiddles failed (status %d)" % rc)
+    table = _table_of(lib().vpz_melspec_twiddles, "vpz_melspec_twiddles", (n_fft,), lambda: 3 * int(n_fft), "n_fft %r" % (n_fft,))
     return table[:int(n_fft)], table[int(n_fft):].reshape(int(n_fft), 2)
 
 
@@ -648,10 +649,7 @@ def pcm_stft(ctx, src, rows, dst, spec, frames):
     first dimension counts the rows: float32 [rows, n_freq, T] (bins first) or [rows, T, n_freq], with a last dimension of 2 for the
     complex output (or the complex64 tensor torch.view_as_complex gives of it).  rows: [(src element offset, samples, destination row)].
     Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
-    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
-    _sync_producer(src, dst)
-    return lib().vpz_pcm_stft(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
-                              int(dst.shape[0]))
+    return _pcm_feature(lib().vpz_pcm_stft, ctx, src, rows, dst, spec, frames)
 
 
 def stft_table(n_fft, win_length=None, window="hann"):
@@ -660,13 +658,8 @@ def stft_table(n_fft, win_length=None, window="hann"):
     VPZ_STFT_* value.  Refused arguments raise ValueError."""
     wl = int(n_fft if win_length is None else win_length)
     wd = {"hann": STFT_HANN, "hamming": STFT_HAMMING}.get(window, window)
-    rc = lib().vpz_stft_table(int(n_fft), wl, int(wd), None, 0)
-    if rc != OK:
-        raise ValueError("vpz_stft_table refuses n_fft %r, win_length %r, window %r (status %d)" % (n_fft, win_length, window, rc))
-    table = np.zeros(3 * int(n_fft), dtype=np.float32)
-    rc = lib().vpz_stft_table(int(n_fft), wl, int(wd), table.ctypes.data, table.size)
-    if rc != OK:
-        raise ValueError("vpz_stft_table failed (status %d)" % rc)
+    table = _table_of(lib().vpz_stft_table, "vpz_stft_table", (int(n_fft), wl, int(wd)), lambda: 3 * int(n_fft),
+                      "n_fft %r, win_length %r, window %r" % (n_fft, win_length, window))
     return table[:int(n_fft)], table[int(n_fft):].reshape(int(n_fft), 2)
 
 
@@ -676,10 +669,7 @@ def pcm_cqt(ctx, src, rows, dst, spec, frames):
     dimension counts the rows: float32 [rows, n_bins, T] (bins first) or [rows, T, n_bins], with a last dimension of 2 for the complex
     output.  rows: [(src element offset, samples, destination row)]; spec: a CqtSpec.  Asynchronous on the context's stream; returns the
     status (a refusal is an answer, not an exception)."""
-    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
-    _sync_producer(src, dst)
-    return lib().vpz_pcm_cqt(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
-                             int(dst.shape[0]))
+    return _pcm_feature(lib().vpz_pcm_cqt, ctx, src, rows, dst, spec, frames)
 
 
 def cqt_bins(spec):
@@ -712,39 +702,19 @@ def pcm_fbank(ctx, src, rows, dst, spec, frames):
     frames of rows padded to `frames` samples, into rows of `dst` -- a contiguous float32 torch tensor [rows, T, n_mels]
     (FBANK_FRAMES_FIRST) or [rows, n_mels, T], T = 1 + (frames - win) // hop; rows: [(src, samples, row)]; spec: an FbankSpec.
     Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
-    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
-    _sync_producer(src, dst)
-    return lib().vpz_pcm_fbank(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
-                               int(dst.shape[0]))
+    return _pcm_feature(lib().vpz_pcm_fbank, ctx, src, rows, dst, spec, frames)
 
 
 def fbank_table(spec):
     """vpz_fbank_table: float32 [win, 2, n_fft // 2] -- [m, 0, k] the coefficient of x[m] - mu in re[k], [m, 1, k] in im[k]; needs no
     device.  A refused spec raises ValueError."""
-    rc = lib().vpz_fbank_table(C.byref(spec), None, 0)
-    if rc != OK:
-        raise ValueError("vpz_fbank_table refuses the spec (status %d)" % rc)
-    table = np.zeros((int(spec.win), 2, int(spec.n_fft) // 2), dtype=np.float32)
-    rc = lib().vpz_fbank_table(C.byref(spec), table.ctypes.data, table.size)
-    if rc != OK:
-        raise ValueError("vpz_fbank_table failed (status %d)" % rc)
-    return table
+    return _table_of(lib().vpz_fbank_table, "vpz_fbank_table", (C.byref(spec),), lambda: (int(spec.win), 2, int(spec.n_fft) // 2), "the spec")
 
 
 def fbank_filterbank(spec):
     """vpz_fbank_filterbank: (first_bin[n_mels] int32, n_bins[n_mels] int32, weights float32 -- band after band, each band's live bins)
     of an FbankSpec; needs no device.  A refused spec raises ValueError."""
-    total = C.c_int64(0)
-    rc = lib().vpz_fbank_filterbank(C.byref(spec), None, None, None, 0, C.byref(total))
-    if rc != OK:
-        raise ValueError("vpz_fbank_filterbank refuses the spec (status %d)" % rc)
-    first, count = np.zeros(spec.n_mels, dtype=np.int32), np.zeros(spec.n_mels, dtype=np.int32)
-    weights = np.zeros(total.value, dtype=np.float32)
-    rc = lib().vpz_fbank_filterbank(C.byref(spec), first.ctypes.data, count.ctypes.data, weights.ctypes.data if total.value else None, weights.size,
-                                    C.byref(total))
-    if rc != OK:
-        raise ValueError("vpz_fbank_filterbank failed (status %d)" % rc)
-    return first, count, weights
+    return _mel_filterbank_of(lib().vpz_fbank_filterbank, "vpz_fbank_filterbank", spec)
 
 
 def pcm_mfcc(ctx, src, rows, dst, spec, frames):
@@ -752,23 +722,13 @@ def pcm_mfcc(ctx, src, rows, dst, spec, frames):
     rows padded to `frames` samples, into rows of `dst` -- a contiguous float32 torch tensor [rows, T, n_ceps] (FBANK_FRAMES_FIRST) or
     [rows, n_ceps, T], T = 1 + (frames - win) // hop; rows: [(src, samples, row)]; spec: an MfccSpec.
     Asynchronous on the context's stream; returns the status (a refusal is an answer, not an exception)."""
-    desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
-    _sync_producer(src, dst)
-    return lib().vpz_pcm_mfcc(ctx._h, _ptr(src), _numel(src), int(frames), C.byref(spec), desc.shape[0], desc.ctypes.data, _ptr(dst),
-                              int(dst.shape[0]))
+    return _pcm_feature(lib().vpz_pcm_mfcc, ctx, src, rows, dst, spec, frames)
 
 
 def mfcc_table(spec):
     """vpz_mfcc_table: float32 [n_ceps, n_mels], row j the weights of the log-mel values in a frame's j-th STORED value; needs no device.
     A refused spec raises ValueError."""
-    rc = lib().vpz_mfcc_table(C.byref(spec), None, 0)
-    if rc != OK:
-        raise ValueError("vpz_mfcc_table refuses the spec (status %d)" % rc)
-    table = np.zeros((int(spec.n_ceps), int(spec.fbank.n_mels)), dtype=np.float32)
-    rc = lib().vpz_mfcc_table(C.byref(spec), table.ctypes.data, table.size)
-    if rc != OK:
-        raise ValueError("vpz_mfcc_table failed (status %d)" % rc)
-    return table
+    return _table_of(lib().vpz_mfcc_table, "vpz_mfcc_table", (C.byref(spec),), lambda: (int(spec.n_ceps), int(spec.fbank.n_mels)), "the spec")
 
 
 def feat_delta_scales(spec, i):

@@ -401,66 +401,75 @@ struct Job {  // one stream of the library inside its group
     }
 };
 
+// One kind of feature call, stated once: a resampled call with a feature stage behind the resample launches, fed from the lane's
+// temporary.  The stage's step in a failure text, the entry point, the profile line's word, what GroupRun::zero_rows calls its rows of
+// no samples; whether a descriptor stands for its entry's `channels` rows or for one (mono); the launch, vpz_pcm_* of the kind
+struct Feature {
+    const char *step, *call, *name, *empty;
+    bool per_channel;
+    int (*launch)(vpz_context *ctx, const void *src, int64_t src_elems, int64_t frames, const void *spec, int32_t n, const vpz_pack_row *rows, void *to, int64_t to_rows);
+};
+template <class Spec, int (*Fn)(vpz_context *, const void *, int64_t, int64_t, const Spec *, int32_t, const vpz_pack_row *, void *, int64_t)>  // (the spec cast back to the type its entry point took)
+int launch_of(vpz_context *ctx, const void *src, int64_t src_elems, int64_t frames, const void *spec, int32_t n, const vpz_pack_row *rows, void *to, int64_t to_rows)
+{
+    return Fn(ctx, src, src_elems, frames, static_cast<const Spec *>(spec), n, rows, to, to_rows);
+}
+// `dst` is [rows][n_mels][T] (the mel spectrogram: with the transform sizes of vorbispizza_pcm_melspec.h), [rows][T][n_mels], [rows][T][n_ceps],
+// and entry k's channel c in row (k - lo) * channels + c of [rows][channels][n_freq or n_bins][T], complex pairs included -- or transposed
+const Feature kLogmel{"vpz_pcm_logmel", "vpzm_decode_ranges_logmel", "log-mel", "silence rows", false, launch_of<vpz_logmel_spec, vpz_pcm_logmel>};
+const Feature kMelspec{"vpz_pcm_melspec", "vpzm_decode_ranges_melspec", "mel-spectrogram", "silence rows", false, launch_of<vpz_logmel_spec, vpz_pcm_melspec>};
+const Feature kFbank{"vpz_pcm_fbank", "vpzm_decode_ranges_fbank", "fbank", "pad rows", false, launch_of<vpz_fbank_spec, vpz_pcm_fbank>};
+const Feature kMfcc{"vpz_pcm_mfcc", "vpzm_decode_ranges_mfcc", "mfcc", "pad rows", false, launch_of<vpz_mfcc_spec, vpz_pcm_mfcc>};
+const Feature kStft{"vpz_pcm_stft", "vpzm_decode_ranges_stft", "stft", "zero rows", true, launch_of<vpz_stft_spec, vpz_pcm_stft>};
+const Feature kCqt{"vpz_pcm_cqt", "vpzm_decode_ranges_cqt", "cqt", "zero rows", true, launch_of<vpz_cqt_spec, vpz_pcm_cqt>};
+
 // vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
 struct Batch {
-    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample; that, then vpz_pcm_logmel; or then vpz_pcm_fbank; or then
-    // vpz_pcm_mfcc; or then vpz_pcm_melspec; or then vpz_pcm_stft; or then vpz_pcm_cqt; or, into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
-    enum Kind { kPack, kResampled, kLogmel, kFbank, kLoudness, kR128, kMfcc, kMelspec, kStft, kCqt };
+    // what delivers a window into its row: vpz_pcm_pack; vpz_pcm_resample, and behind it the launch of `feature` where there is one; or,
+    // into its record, vpz_pcm_loudness and the gate; or those with vpz_pcm_true_peak, the range and the maxima
+    enum Kind { kPack, kResampled, kLoudness, kR128 };
     Kind kind = kPack;
     int32_t channels = 0, layout = 0;
     int64_t frames = 0;
-    int32_t rate = 0, downmix = 0;  // kResampled, kLogmel: every row at `rate`, mixed down to mono
-    // kLogmel, kMelspec: a resampled mono call whose rows are (log-)mel frames of this spec (`dst` is [rows][n_mels][T] or transposed);
-    // kMelspec with the transform sizes of vorbispizza_pcm_melspec.h
-    const vpz_logmel_spec *mel = nullptr;
-    // kFbank: the same with Kaldi filterbank frames of this spec (`dst` is [rows][T][n_mels] or transposed)
-    const vpz_fbank_spec *fbank = nullptr;
-    // kMfcc: the same with Kaldi MFCC frames of this spec (`dst` is [rows][T][n_ceps] or transposed)
-    const vpz_mfcc_spec *mfcc = nullptr;
-    // kFbank, kMfcc: vpz_feat_post of this spec behind the feature launch (`dst` is [rows][T][D_out] or transposed); null: none
+    int32_t rate = 0, downmix = 0;  // kResampled: every row at `rate`, mixed down to mono with `downmix`
+    // a feature call: its kind and its spec, of the type the kind's launch casts it back to; channels, layout and frames are then those
+    // of the resampled rows in the lane's temporary -- planar float32, mono where the kind is
+    const Feature *feature = nullptr;
+    const void *spec = nullptr;
+    // a posted call (fbank, MFCC): vpz_feat_post of this spec behind the feature launch (`dst` is [rows][T][D_out] or transposed), the
+    // feature spec's mel stage and the feature launch's columns D; null: none
     const vpz_feat_post_spec *post = nullptr;
-    // kStft: a resampled call of `channels` planar channels (one with `downmix`) whose every channel is a row of spectrum frames of this
-    // spec: entry k's channel c is row (k - lo) * channels + c of `dst` ([rows][channels][n_freq][T], complex pairs included, or transposed)
-    const vpz_stft_spec *stft = nullptr;
-    // kCqt: the same with constant-Q frames of this spec ([rows][channels][n_bins][T], complex pairs included, or transposed)
-    const vpz_cqt_spec *cqt = nullptr;
+    const vpz_fbank_spec *post_mel = nullptr;
+    int32_t post_D = 0;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
     // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
     int64_t rows = 0;     // of the group's piece: its entries
-    bool resampled() const { return kind == kResampled || features(); }
+    // (members are initialised by name: with a constructor of its own a Batch is no aggregate, and no initialiser can depend on their order)
+    Batch(Kind kind = kPack, int32_t channels = 0, int32_t layout = 0, int64_t frames = 0, int32_t rate = 0, int32_t downmix = 0, const Feature *feature = nullptr, const void *spec = nullptr)
+        : kind(kind), channels(channels), layout(layout), frames(frames), rate(rate), downmix(downmix), feature(feature), spec(spec) {}
+    static Batch featured(const Feature &feature, const void *spec, int32_t rate, int32_t downmix, int32_t channels, int64_t frames) { return Batch(kResampled, channels, VPZ_OUT_PLANAR, frames, rate, downmix, &feature, spec); }
+    bool resampled() const { return kind == kResampled; }
     bool measured() const { return kind == kLoudness || kind == kR128; }
     vpzm_loudness &record(int64_t row) const { return static_cast<vpzm_loudness *>(dst)[row]; }
     vpzm_r128 &record_r128(int64_t row) const { return static_cast<vpzm_r128 *>(dst)[row]; }
-    bool features() const { return kind == kLogmel || kind == kFbank || kind == kMfcc || kind == kMelspec || kind == kStft || kind == kCqt; }  // a feature stage behind the resample launches, fed from the lane's temporary
-    const char *feature_step() const { return kind == kMfcc ? "vpz_pcm_mfcc" : kind == kFbank ? "vpz_pcm_fbank" : kind == kMelspec ? "vpz_pcm_melspec" : kind == kStft ? "vpz_pcm_stft" : kind == kCqt ? "vpz_pcm_cqt" : "vpz_pcm_logmel"; }
-    const char *feature_call() const { return kind == kMfcc ? "vpzm_decode_ranges_mfcc" : kind == kFbank ? "vpzm_decode_ranges_fbank" : kind == kMelspec ? "vpzm_decode_ranges_melspec" : kind == kStft ? "vpzm_decode_ranges_stft" : kind == kCqt ? "vpzm_decode_ranges_cqt" : "vpzm_decode_ranges_logmel"; }
-    const char *feature_name() const { return kind == kMfcc ? "mfcc" : kind == kFbank ? "fbank" : kind == kMelspec ? "mel-spectrogram" : kind == kStft ? "stft" : kind == kCqt ? "cqt" : "log-mel"; }
     // the feature launch of the call's kind: these windows of a mono float32 array into their rows of `to` (the group's piece, or a
-    // posted call's temporary), which has `to_rows` rows.  An STFT or CQT call's array is planar -- a descriptor's `src` is the window in its
+    // posted call's temporary), which has `to_rows` rows.  A per-channel kind's array is planar -- a descriptor's `src` is the window in its
     // member's first channel, the next channel lies `frames` elements on (none is read where samples = 0) -- and a descriptor stands for
     // its entry's `channels` rows: one descriptor of the launch per channel
     int feature_rows(vpz_context *ctx, const void *src, int64_t src_elems, const std::vector<vpz_pack_row> &d, void *to, int64_t to_rows) const
     {
-        if (kind == kStft || kind == kCqt) {
-            std::vector<vpz_pack_row> each;
-            each.reserve(d.size() * (size_t)channels);
-            for (const vpz_pack_row &r : d)
-                for (int32_t c = 0; c < channels; ++c) each.push_back(vpz_pack_row{r.samples > 0 ? r.src + c * frames : 0, r.samples, r.row * channels + c});
-            if (kind == kCqt) return vpz_pcm_cqt(ctx, src, src_elems, frames, cqt, (int32_t)each.size(), each.data(), to, to_rows * channels);
-            return vpz_pcm_stft(ctx, src, src_elems, frames, stft, (int32_t)each.size(), each.data(), to, to_rows * channels);
-        }
-        if (kind == kMfcc) return vpz_pcm_mfcc(ctx, src, src_elems, frames, mfcc, (int32_t)d.size(), d.data(), to, to_rows);
-        if (kind == kFbank) return vpz_pcm_fbank(ctx, src, src_elems, frames, fbank, (int32_t)d.size(), d.data(), to, to_rows);
-        if (kind == kMelspec) return vpz_pcm_melspec(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), to, to_rows);
-        return vpz_pcm_logmel(ctx, src, src_elems, frames, mel, (int32_t)d.size(), d.data(), to, to_rows);
+        if (!feature->per_channel) return feature->launch(ctx, src, src_elems, frames, spec, (int32_t)d.size(), d.data(), to, to_rows);
+        std::vector<vpz_pack_row> each;
+        each.reserve(d.size() * (size_t)channels);
+        for (const vpz_pack_row &r : d)
+            for (int32_t c = 0; c < channels; ++c) each.push_back(vpz_pack_row{r.samples > 0 ? r.src + c * frames : 0, r.samples, r.row * channels + c});
+        return feature->launch(ctx, src, src_elems, frames, spec, (int32_t)each.size(), each.data(), to, to_rows * channels);
     }
-    // a posted call: the mel stage's spec, a row's frames T, its real frames T_L of J samples and the feature launch's columns D
-    const vpz_fbank_spec &mel_stage() const { return kind == kMfcc ? mfcc->fbank : *fbank; }
-    int64_t feat_T() const { return 1 + (frames - mel_stage().win) / mel_stage().hop; }
-    int64_t real_frames(int64_t J) const { return J < mel_stage().win ? 0 : 1 + (J - mel_stage().win) / mel_stage().hop; }
-    int32_t feat_D() const { return kind == kMfcc ? mfcc->n_ceps : fbank->n_mels; }
+    // a posted call: a row's frames T and its real frames T_L of J samples
+    int64_t feat_T() const { return 1 + (frames - post_mel->win) / post_mel->hop; }
+    int64_t real_frames(int64_t J) const { return J < post_mel->win ? 0 : 1 + (J - post_mel->win) / post_mel->hop; }
     // a posted call's vpz_feat_post launches on the lane's stream: rows of `src` ([src_rows][T][D], the lane's temporary) into their rows
     // of `dst`; the chunk sums live in the lane's scratch array, which grows here
     // `*own`: the text of a failure that is not the context's (its last error says nothing about it), else null.  Descriptors without
@@ -471,7 +480,7 @@ struct Batch {
         int64_t need = 0;
         bool any_real = false;
         for (const vpz_feat_row &r : d) any_real = any_real || r.real_frames > 0;
-        if (any_real && vpz_feat_post_scratch(post, (int32_t)d.size(), feat_T(), feat_D(), &need) != VPZ_OK) {
+        if (any_real && vpz_feat_post_scratch(post, (int32_t)d.size(), feat_T(), post_D, &need) != VPZ_OK) {
             *own = "the scratch memory's size overflows";
             return VPZ_E_INVALID_ARG;
         }
@@ -479,7 +488,7 @@ struct Batch {
             *own = "the chunk sums' device memory could not be allocated";
             return VPZ_E_NOMEM;
         }
-        return vpz_feat_post(L.ctx, src, src_rows, feat_T(), feat_D(), post, (int32_t)d.size(), d.data(), dst, rows, need > 0 ? L.buf[Lane::kPostScratch].p : nullptr,
+        return vpz_feat_post(L.ctx, src, src_rows, feat_T(), post_D, post, (int32_t)d.size(), d.data(), dst, rows, need > 0 ? L.buf[Lane::kPostScratch].p : nullptr,
                              need);
     }
 
@@ -494,10 +503,11 @@ struct Batch {
             const char *own;  // (no scratch memory is asked for: none can fail)
             return post_rows(L, dst, 0, none, &own);
         }
-        if (features()) return feature_rows(L.ctx, dst, 0, d, dst, rows);
+        if (feature) return feature_rows(L.ctx, dst, 0, d, dst, rows);
         return vpz_pcm_pack(L.ctx, dst, 0, channels, (int32_t)d.size(), d.data(), dst, rows, frames, layout);
     }
-    const char *empty_step() const { return post ? "vpz_feat_post" : features() ? feature_step() : "vpz_pcm_pack"; }
+    const char *empty_step() const { return post ? "vpz_feat_post" : feature ? feature->step : "vpz_pcm_pack"; }
+    const char *empty_words() const { return post ? "pad rows" : feature ? feature->empty : "zero rows"; }  // what that launch's rows are called
 };
 
 // ceil(samples * up / down): the output samples of a resampled window (the definition's J)
@@ -988,7 +998,7 @@ struct GroupRun {
                 if (!J.row_packed) rows.push_back(vpz_pack_row{0, 0, (int64_t)(&J - jobs.data())});
             if (batch.measured()) rows.clear();  // (a loudness call's records are the caller's and hold the empty record already)
             if (!rows.empty()) ok = batch.empty_rows(G.lanes[0], rows) == VPZ_OK;
-            if (!ok) m->fail(std::string(batch.post ? "vpz_feat_post (pad rows): " : batch.kind == Batch::kMfcc ? "vpz_pcm_mfcc (pad rows): " : batch.kind == Batch::kFbank ? "vpz_pcm_fbank (pad rows): " : batch.kind == Batch::kMelspec ? "vpz_pcm_melspec (silence rows): " : batch.kind == Batch::kStft ? "vpz_pcm_stft (zero rows): " : batch.kind == Batch::kCqt ? "vpz_pcm_cqt (zero rows): " : batch.mel ? "vpz_pcm_logmel (silence rows): " : "vpz_pcm_pack (zero rows): ") + vpz_context_last_error(G.lanes[0].ctx));
+            if (!ok) m->fail(std::string(batch.empty_step()) + " (" + batch.empty_words() + "): " + vpz_context_last_error(G.lanes[0].ctx));
         } catch (...) {
             ok = false;
         }
@@ -1393,11 +1403,11 @@ struct SubCall {
         } else {
             // (a log-mel, fbank or MFCC call: resampled into the lane's temporary, then ONE feature launch on the same stream -- stream-ordered:
             // no synchronise in between)
-            if (B.features()) rc = mono_temporary(rows.size());
+            if (B.feature) rc = mono_temporary(rows.size());
             if (rc == VPZ_OK) rc = resample_by_ratio(rows);
             for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
             if (rc != VPZ_OK) (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
-            else if (B.features()) rc = feature_rows(rows);
+            else if (B.feature) rc = feature_rows(rows);
         }
         if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
         for (size_t j = 0; j < sb.members.size(); ++j) {
@@ -1525,7 +1535,7 @@ struct SubCall {
     int mono_temporary(size_t members)
     {
         if (L.buf[Lane::kMono].grow(L.ctx, members * (size_t)B.channels * (size_t)B.frames, sizeof(float))) return VPZ_OK;
-        R.m->fail(std::string(B.feature_call()) + ": the resampled rows' device temporary could not be allocated");
+        R.m->fail(std::string(B.feature->call) + ": the resampled rows' device temporary could not be allocated");
         return VPZ_E_NOMEM;
     }
 
@@ -1548,12 +1558,12 @@ struct SubCall {
                 if (!taken[j] && (rows[j].samples == 0 || (job(j).up == up && job(j).down == down))) {
                     taken[j] = 1;
                     group.push_back(rows[j]);
-                    if (B.features()) group.back().row = (int64_t)j;
+                    if (B.feature) group.back().row = (int64_t)j;
                 }
             left -= group.size();
-            rc = R.sw.fail_delivery && !B.features() ? VPZ_E_HIP
+            rc = R.sw.fail_delivery && !B.feature ? VPZ_E_HIP
                                              : vpz_pcm_resample(L.ctx, L.pcm(), pcm_elems, C, up, down, B.downmix, (int32_t)group.size(), group.data(),
-                                                                B.features() ? (void *)L.mono() : B.dst, B.features() ? (int64_t)rows.size() : B.rows, B.channels, B.frames,
+                                                                B.feature ? (void *)L.mono() : B.dst, B.feature ? (int64_t)rows.size() : B.rows, B.channels, B.frames,
                                                                 B.layout);
             ++resample_launches;
         }
@@ -1570,8 +1580,8 @@ struct SubCall {
         // launches, stream-ordered behind it, deliver them into the group's piece with the row's real frames T_L(J))
         std::vector<vpz_feat_row> posted;
         if (B.post) {
-            if (!L.buf[Lane::kFeat].grow(L.ctx, rows.size() * (size_t)B.feat_T() * (size_t)B.feat_D(), sizeof(float))) {
-                R.m->fail(std::string(B.feature_call()) + ": the feature frames' device temporary could not be allocated");
+            if (!L.buf[Lane::kFeat].grow(L.ctx, rows.size() * (size_t)B.feat_T() * (size_t)B.post_D, sizeof(float))) {
+                R.m->fail(std::string(B.feature->call) + ": the feature frames' device temporary could not be allocated");
                 return VPZ_E_NOMEM;
             }
             for (size_t j = 0; j < rows.size(); ++j) {
@@ -1579,7 +1589,7 @@ struct SubCall {
                 rows[j].row = (int64_t)j;
             }
         }
-        int rc = launched(B.feature_step(), R.sw.fail_delivery ? VPZ_E_HIP
+        int rc = launched(B.feature->step, R.sw.fail_delivery ? VPZ_E_HIP
                                                                 : B.feature_rows(L.ctx, L.mono(), (int64_t)rows.size() * B.channels * B.frames, rows, B.post ? (void *)L.feat() : B.dst,
                                                                                  B.post ? (int64_t)rows.size() : B.rows));
         if (B.post && rc == VPZ_OK) {
@@ -1589,7 +1599,7 @@ struct SubCall {
             else rc = launched("vpz_feat_post", rc);
         }
         if (R.sw.profile && rc == VPZ_OK && vpz_context_synchronize(L.ctx) == VPZ_OK)
-            fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b, B.feature_name(),
+            fprintf(stderr, "[vpzm] group %d: sub-batch %zu %s kernel %.3f ms (%zu rows of %lld samples)\n", R.slot_index, b, B.feature->name,
                     seconds_since(t_mel) * 1e3, rows.size(), (long long)B.frames);
         return rc;
     }
@@ -1820,6 +1830,13 @@ static bool layout_of(int32_t layout, bool *s16, bool *planar)
     *planar = layout == VPZ_OUT_PLANAR || layout == VPZ_OUT_PLANAR_S16;
     return *s16 || *planar || layout == VPZ_OUT_INTERLEAVED;
 }
+// the rate of a batch is a whole number of Hz (that an int32_t holds)
+static bool whole_hz(double rate) { return rate >= 1.0 && rate <= 2147483647.0 && (double)(int32_t)rate == rate; }
+// what vpzm_decode_ranges_resampled refuses of a rate, a channel count and a downmix flag
+static bool resampled_args_fit(int32_t sample_rate, int32_t channels, int32_t downmix)
+{
+    return channels >= 1 && channels <= VPZ_MAX_CHANNELS && sample_rate >= 1 && (downmix == 0 || downmix == 1) && (!downmix || channels == 1);
+}
 
 // What the ranges family shares.  A call without ranges is refused; one without entries is a ranges call all the same.  A batch call
 // (`batch`: kind, channels, frames, layout and what its kind adds) has a piece per group, rows of at least one frame and one of the four
@@ -1858,7 +1875,7 @@ int vpzm_decode_ranges_batch(vpzm_dispatcher *m, int32_t n, const uint8_t *const
                              vpzm_stats *stats)
 {
     if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
-    const Batch batch{Batch::kPack, channels, out_layout, frames};
+    const Batch batch(Batch::kPack, channels, out_layout, frames);
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
@@ -1866,36 +1883,33 @@ int vpzm_decode_ranges_resampled(vpzm_dispatcher *m, int32_t n, const uint8_t *c
                                  int32_t sample_rate, int32_t channels, int32_t downmix, int64_t frames, int32_t out_layout, void *const *group_dst,
                                  vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
-    if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
-    const Batch batch{Batch::kResampled, channels, out_layout, frames, sample_rate, downmix};
+    if (!resampled_args_fit(sample_rate, channels, downmix)) return VPZM_E_ARG;
+    const Batch batch(Batch::kResampled, channels, out_layout, frames, sample_rate, downmix);
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+// the log-mel and the mel-spectrogram call: `filterbank` is the query of the kind's library, which states the kernel's limits
+static int mel_call(const Feature &feature, decltype(vpz_mel_filterbank) *filterbank, vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size,
+                    const vpzm_range *ranges, const vpz_logmel_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!spec) return VPZM_E_ARG;
+    if (filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
+    if (!whole_hz(spec->sample_rate)) return VPZM_E_ARG;
+    if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
+    const Batch batch = Batch::featured(feature, spec, (int32_t)spec->sample_rate, 1, 1, frames);
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_decode_ranges_logmel(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                               const vpz_logmel_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (!spec) return VPZM_E_ARG;
-    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
-    if (vpz_mel_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
-    if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
-    if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
-    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
-    const Batch batch{Batch::kLogmel, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
-    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+    return mel_call(kLogmel, vpz_mel_filterbank, m, n, data, size, ranges, spec, frames, group_dst, results, stats);
 }
 
 int vpzm_decode_ranges_melspec(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                                const vpz_logmel_spec *spec, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (!spec) return VPZM_E_ARG;
-    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
-    if (vpz_melspec_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
-    if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
-    if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
-    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
-    const Batch batch{Batch::kMelspec, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, spec};
-    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+    return mel_call(kMelspec, vpz_melspec_filterbank, m, n, data, size, ranges, spec, frames, group_dst, results, stats);
 }
 
 int vpzm_decode_ranges_stft(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
@@ -1910,12 +1924,8 @@ int vpzm_decode_ranges_stft(vpzm_dispatcher *m, int32_t n, const uint8_t *const 
     for (int32_t r : spec->reserved)
         if (r != 0) return VPZM_E_ARG;
     if (frames < spec->n_fft / 2 + 1) return VPZM_E_ARG;
-    // (what the resampled call refuses)
-    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
-    if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
-    // (channels and layout: of the resampled rows in the lane's temporary -- planar, float32)
-    Batch batch{Batch::kStft, channels, VPZ_OUT_PLANAR, frames, sample_rate, downmix};
-    batch.stft = spec;
+    if (!resampled_args_fit(sample_rate, channels, downmix)) return VPZM_E_ARG;
+    const Batch batch = Batch::featured(kStft, spec, sample_rate, downmix, channels, frames);
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
@@ -1929,21 +1939,26 @@ int vpzm_decode_ranges_cqt(vpzm_dispatcher *m, int32_t n, const uint8_t *const *
     int32_t n0 = 0;
     if (vpz_cqt_kernel(spec, 0, nullptr, 0, &n0) != VPZ_OK) return VPZM_E_ARG;
     if (frames < 1 || (spec->pad == VPZ_CQT_PAD_REFLECT && frames < n0 / 2 + 1)) return VPZM_E_ARG;
-    // (what the resampled call refuses)
-    if (channels < 1 || channels > VPZ_MAX_CHANNELS) return VPZM_E_ARG;
-    if (sample_rate < 1 || (downmix != 0 && downmix != 1) || (downmix && channels != 1)) return VPZM_E_ARG;
-    // (channels and layout: of the resampled rows in the lane's temporary -- planar, float32)
-    Batch batch{Batch::kCqt, channels, VPZ_OUT_PLANAR, frames, sample_rate, downmix};
-    batch.cqt = spec;
+    if (!resampled_args_fit(sample_rate, channels, downmix)) return VPZM_E_ARG;
+    const Batch batch = Batch::featured(kCqt, spec, sample_rate, downmix, channels, frames);
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
-// a post spec fits a feature call: inside vorbispizza_pcm_featpost.h's limits (asked of the library that states them) and in the
-// feature tensor's layout (the VPZ_FEAT_* values are the VPZ_FBANK_* ones)
-static bool post_fits(const vpz_feat_post_spec *post, const vpz_fbank_spec &mel, int64_t frames, int32_t D)
+// the fbank and the MFCC call, posted (`post`) or not, behind the refusals of the kind's own spec (its limits are the kernel's, asked of
+// the library that states them): `mel` is the spec's mel stage, D the feature launch's columns.  The lane's temporary is mono.  A post
+// spec fits in the feature tensor's layout (the VPZ_FEAT_* values are the VPZ_FBANK_* ones) and inside vorbispizza_pcm_featpost.h's limits
+static int kaldi_call(const Feature &feature, const void *spec, const vpz_fbank_spec &mel, int32_t D, const vpz_feat_post_spec *post, vpzm_dispatcher *m, int32_t n,
+                      const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges, int64_t frames, void *const *group_dst, vpzm_stream_result *results, vpzm_stats *stats)
 {
+    if (!whole_hz(mel.sample_rate)) return VPZM_E_ARG;
+    if (frames < mel.win) return VPZM_E_ARG;
     int64_t elems = 0;
-    return post->layout == mel.layout && vpz_feat_post_scratch(post, 0, 1 + (frames - mel.win) / mel.hop, D, &elems) == VPZ_OK;
+    if (post && (post->layout != mel.layout || vpz_feat_post_scratch(post, 0, 1 + (frames - mel.win) / mel.hop, D, &elems) != VPZ_OK)) return VPZM_E_ARG;
+    Batch batch = Batch::featured(feature, spec, (int32_t)mel.sample_rate, 1, 1, frames);
+    batch.post = post;
+    batch.post_mel = &mel;
+    batch.post_D = D;
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 
 int vpzm_decode_ranges_fbank(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
@@ -1957,14 +1972,8 @@ int vpzm_decode_ranges_fbank_post(vpzm_dispatcher *m, int32_t n, const uint8_t *
                                   vpzm_stream_result *results, vpzm_stats *stats)
 {
     if (!spec) return VPZM_E_ARG;
-    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
     if (vpz_fbank_filterbank(spec, nullptr, nullptr, nullptr, 0, nullptr) != VPZ_OK) return VPZM_E_ARG;
-    if (spec->sample_rate < 1.0 || spec->sample_rate > 2147483647.0 || (double)(int32_t)spec->sample_rate != spec->sample_rate) return VPZM_E_ARG;
-    if (frames < spec->win) return VPZM_E_ARG;
-    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
-    if (post && !post_fits(post, *spec, frames, spec->n_mels)) return VPZM_E_ARG;
-    const Batch batch{Batch::kFbank, 1, VPZ_OUT_PLANAR, frames, (int32_t)spec->sample_rate, 1, nullptr, spec, nullptr, post};
-    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+    return kaldi_call(kFbank, spec, *spec, spec->n_mels, post, m, n, data, size, ranges, frames, group_dst, results, stats);
 }
 
 int vpzm_decode_ranges_mfcc(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
@@ -1978,62 +1987,48 @@ int vpzm_decode_ranges_mfcc_post(vpzm_dispatcher *m, int32_t n, const uint8_t *c
                                  vpzm_stream_result *results, vpzm_stats *stats)
 {
     if (!spec) return VPZM_E_ARG;
-    // (the limits are the kernel's, asked of the library that states them; the rate of a batch is a whole number of Hz)
     if (vpz_mfcc_table(spec, nullptr, 0) != VPZ_OK) return VPZM_E_ARG;
-    const double rate = spec->fbank.sample_rate;
-    if (rate < 1.0 || rate > 2147483647.0 || (double)(int32_t)rate != rate) return VPZM_E_ARG;
-    if (frames < spec->fbank.win) return VPZM_E_ARG;
-    // (channels and layout: of the resampled rows in the lane's temporary -- mono, float32)
-    if (post && !post_fits(post, spec->fbank, frames, spec->n_ceps)) return VPZM_E_ARG;
-    const Batch batch{Batch::kMfcc, 1, VPZ_OUT_PLANAR, frames, (int32_t)rate, 1, nullptr, nullptr, spec, post};
-    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+    return kaldi_call(kMfcc, spec, spec->fbank, spec->n_ceps, post, m, n, data, size, ranges, frames, group_dst, results, stats);
+}
+
+// the loudness and the R 128 call: records of the kind's type, `empty` the record of an entry that delivered nothing
+extern "C++" {
+template <class Record>
+static int measure_call(Batch::Kind kind, const Record &empty, vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size,
+                        const vpzm_range *ranges, Record *out, vpzm_stream_result *results, vpzm_stats *stats)
+{
+    if (!m || n < 0 || (n > 0 && !out)) return VPZM_E_ARG;
+    // (no tensor and no row length: `frames` caps nothing; the synth calls write float32, interleaved; every group's piece is its part of
+    // the caller's records, which hold the empty record from here on -- a group without entries needs none)
+    static Record nobody{};
+    std::vector<vpzm_range> whole;
+    std::vector<void *> pieces;
+    try {
+        if (!ranges) whole.assign((size_t)n, vpzm_range{0, -1});
+        for (int g = 0; g < (int)m->groups.size(); ++g) {
+            int32_t lo, hi;
+            partition(n, g, (int)m->groups.size(), &lo, &hi);
+            pieces.push_back(hi > lo ? (void *)(out + lo) : (void *)&nobody);
+        }
+    } catch (const std::bad_alloc &) {
+        return VPZM_E_NOMEM;
+    }
+    for (int32_t k = 0; k < n; ++k) out[k] = empty;
+    const Batch batch(kind, 0, VPZ_OUT_INTERLEAVED, INT64_MAX);
+    return ranges_call(m, n, data, size, ranges ? ranges : whole.data(), 0, nullptr, nullptr, nullptr, results, stats, &batch, pieces.data());
+}
 }
 
 int vpzm_measure_loudness(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
                           vpzm_loudness *out, vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (!m || n < 0 || (n > 0 && !out)) return VPZM_E_ARG;
-    // (no tensor and no row length: `frames` caps nothing; the synth calls write float32, interleaved; every group's piece is its part of
-    // the caller's records, which hold the empty record from here on -- a group without entries needs none)
-    static vpzm_loudness nobody{};
-    std::vector<vpzm_range> whole;
-    std::vector<void *> pieces;
-    try {
-        if (!ranges) whole.assign((size_t)n, vpzm_range{0, -1});
-        for (int g = 0; g < (int)m->groups.size(); ++g) {
-            int32_t lo, hi;
-            partition(n, g, (int)m->groups.size(), &lo, &hi);
-            pieces.push_back(hi > lo ? (void *)(out + lo) : (void *)&nobody);
-        }
-    } catch (const std::bad_alloc &) {
-        return VPZM_E_NOMEM;
-    }
-    for (int32_t k = 0; k < n; ++k) out[k] = vpzm_loudness{-HUGE_VAL, 0.0, 0, 0};
-    const Batch batch{Batch::kLoudness, 0, VPZ_OUT_INTERLEAVED, INT64_MAX};
-    return ranges_call(m, n, data, size, ranges ? ranges : whole.data(), 0, nullptr, nullptr, nullptr, results, stats, &batch, pieces.data());
+    return measure_call(Batch::kLoudness, vpzm_loudness{-HUGE_VAL, 0.0, 0, 0}, m, n, data, size, ranges, out, results, stats);
 }
 
 int vpzm_measure_r128(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges, vpzm_r128 *out,
                       vpzm_stream_result *results, vpzm_stats *stats)
 {
-    if (!m || n < 0 || (n > 0 && !out)) return VPZM_E_ARG;
-    // (vpzm_measure_loudness with records of the other type)
-    static vpzm_r128 nobody{};
-    std::vector<vpzm_range> whole;
-    std::vector<void *> pieces;
-    try {
-        if (!ranges) whole.assign((size_t)n, vpzm_range{0, -1});
-        for (int g = 0; g < (int)m->groups.size(); ++g) {
-            int32_t lo, hi;
-            partition(n, g, (int)m->groups.size(), &lo, &hi);
-            pieces.push_back(hi > lo ? (void *)(out + lo) : (void *)&nobody);
-        }
-    } catch (const std::bad_alloc &) {
-        return VPZM_E_NOMEM;
-    }
-    for (int32_t k = 0; k < n; ++k) out[k] = vpzm_r128{-HUGE_VAL, 0.0, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, 0.0, 0.0, 0, 0, 0};
-    const Batch batch{Batch::kR128, 0, VPZ_OUT_INTERLEAVED, INT64_MAX};
-    return ranges_call(m, n, data, size, ranges ? ranges : whole.data(), 0, nullptr, nullptr, nullptr, results, stats, &batch, pieces.data());
+    return measure_call(Batch::kR128, vpzm_r128{-HUGE_VAL, 0.0, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL, 0.0, 0.0, 0, 0, 0}, m, n, data, size, ranges, out, results, stats);
 }
 
 int vpzm_set_mixed_setups(vpzm_dispatcher *m, int32_t on)

@@ -161,6 +161,7 @@ class Dispatcher:
             self.set_mixed_setups(True)
 
     def set_mixed_setups(self, on):
+        """vpzm_set_mixed_setups: from the next call on (see the class)"""
         rc = lib().vpzm_set_mixed_setups(self._h, 1 if on else 0)
         if rc != OK:
             raise MultiError("vpzm_set_mixed_setups failed (status %d)" % rc)
@@ -174,6 +175,7 @@ class Dispatcher:
         return counts
 
     def close(self):
+        """vpzm_destroy, once: contexts, decoders and page-locked memory go"""
         if getattr(self, "_h", None):
             lib().vpzm_destroy(self._h)
             self._h = None
@@ -185,6 +187,7 @@ class Dispatcher:
             pass
 
     def last_error(self):
+        """vpzm_last_error: the first failure text of the last call ('' when it had none)"""
         return lib().vpzm_last_error(self._h).decode()
 
     # ---- what the decode methods share
@@ -230,6 +233,30 @@ class Dispatcher:
         import torch
         for d in sorted(set(self.device_ids)):
             torch.cuda.current_stream(d).synchronize()
+
+    def _batch_call(self, name, fn, datas, ranges, shape, dtype, out, args, method=None):
+        """What the window-batch methods share behind their own argument checks: the inputs, the groups' tensors of shape(rows) and
+        `dtype` (checked under `method`: the library call's `name` unless given), torch's streams drained, and the call
+        fn(handle, n, containers, sizes, ranges, *args(the groups' pointers), results, stats).  -> (out, whole_or_None, results, stats)"""
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        out, whole, dst = self._group_tensors(method or name, n, shape, dtype, out)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        rc = fn(self._h, n, ptrs, sizes, rng.ctypes.data, *args(dst), results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_%s failed (status %d): %s" % (name, rc, self.last_error()))
+        return out, whole, results, stats
+
+    def _measure_call(self, name, fn, datas, ranges, dtype):
+        """a measuring call: no tensor, a record of `dtype` per entry.  -> (results, records, stats)"""
+        n, ptrs, sizes, rng = self._inputs(datas, ranges)
+        self._drain_torch()
+        results, stats = self._outputs(n)
+        out = np.zeros(n, dtype=dtype)
+        rc = fn(self._h, n, ptrs, sizes, None if rng is None else rng.ctypes.data, out.ctypes.data if n else None, results.ctypes.data, C.byref(stats))
+        if rc != OK:
+            raise MultiError("vpzm_%s failed (status %d): %s" % (name, rc, self.last_error()))
+        return results, out, stats
 
     def decode_library(self, datas, pcm_out, pcm_offset, pcm_capacity, s16=False):
         """datas: list of numpy uint8 arrays (containers); pcm_out: numpy float32 / int16 array (or a torch pinned tensor's
@@ -286,24 +313,15 @@ class Dispatcher:
             raise ValueError("decode_ranges_batch: channels and frames must be at least 1")
         if mono and (sample_rate is None or channels != 1):
             raise ValueError("decode_ranges_batch: mono needs a sample_rate (a resampled call has one rate) and channels == 1")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         shape = (lambda rows: (rows, channels, frames)) if planar else (lambda rows: (rows, frames, channels))
-        out, whole, dst = self._group_tensors("decode_ranges_batch", n, shape, torch.int16 if s16 else torch.float32, out)
+        dtype = torch.int16 if s16 else torch.float32
         layout = {(True, False): capi.OUT_PLANAR, (False, False): capi.OUT_INTERLEAVED, (True, True): capi.OUT_PLANAR_S16,
                   (False, True): capi.OUT_INTERLEAVED_S16}[(bool(planar), bool(s16))]
-        self._drain_torch()
-        results, stats = self._outputs(n)
         if sample_rate is None:
-            rc = lib().vpzm_decode_ranges_batch(self._h, n, ptrs, sizes, rng.ctypes.data, channels, frames, layout, dst, results.ctypes.data,
-                                                C.byref(stats))
-            name = "vpzm_decode_ranges_batch"
-        else:
-            rc = lib().vpzm_decode_ranges_resampled(self._h, n, ptrs, sizes, rng.ctypes.data, int(sample_rate), channels, int(bool(mono)), frames,
-                                                    layout, dst, results.ctypes.data, C.byref(stats))
-            name = "vpzm_decode_ranges_resampled"
-        if rc != OK:
-            raise MultiError("%s failed (status %d): %s" % (name, rc, self.last_error()))
-        return out, whole, results, stats
+            return self._batch_call("decode_ranges_batch", lib().vpzm_decode_ranges_batch, datas, ranges, shape, dtype, out,
+                                    lambda dst: (channels, frames, layout, dst))
+        return self._batch_call("decode_ranges_resampled", lib().vpzm_decode_ranges_resampled, datas, ranges, shape, dtype, out,
+                                lambda dst: (int(sample_rate), channels, int(bool(mono)), frames, layout, dst), method="decode_ranges_batch")
 
     def decode_ranges_logmel(self, datas, ranges, frames, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None,
                              mel_scale="slaney", mel_norm="slaney", log=True, floor=1e-10, bands_first=True, out=None):
@@ -318,17 +336,10 @@ class Dispatcher:
                                     mel_norm=mel_norm, log=log, floor=floor, bands_first=bands_first)
         if frames < 1 or hop < 1 or n_mels < 1:
             raise ValueError("decode_ranges_logmel: frames, hop and n_mels must be at least 1")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T = spec.n_frames(frames)
         shape = (lambda rows: (rows, n_mels, T)) if bands_first else (lambda rows: (rows, T, n_mels))
-        out, whole, dst = self._group_tensors("decode_ranges_logmel", n, shape, torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = lib().vpzm_decode_ranges_logmel(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
-                                             C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_decode_ranges_logmel failed (status %d): %s" % (rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call("decode_ranges_logmel", lib().vpzm_decode_ranges_logmel, datas, ranges, shape, torch.float32, out,
+                                lambda dst: (C.byref(spec), int(frames), dst))
 
     def decode_ranges_melspec(self, datas, ranges, frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=None,
                               mel_scale="slaney", mel_norm="slaney", log=True, floor=1e-10, bands_first=True, out=None):
@@ -340,17 +351,10 @@ class Dispatcher:
                                     mel_norm=mel_norm, log=log, floor=floor, bands_first=bands_first)
         if frames < 1 or hop < 1 or n_mels < 1:
             raise ValueError("decode_ranges_melspec: frames, hop and n_mels must be at least 1")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T = spec.n_frames(frames)
         shape = (lambda rows: (rows, n_mels, T)) if bands_first else (lambda rows: (rows, T, n_mels))
-        out, whole, dst = self._group_tensors("decode_ranges_melspec", n, shape, torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = lib().vpzm_decode_ranges_melspec(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
-                                              C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_decode_ranges_melspec failed (status %d): %s" % (rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call("decode_ranges_melspec", lib().vpzm_decode_ranges_melspec, datas, ranges, shape, torch.float32, out,
+                                lambda dst: (C.byref(spec), int(frames), dst))
 
     def decode_ranges_stft(self, datas, ranges, frames, sample_rate=44100, channels=2, mono=False, n_fft=4096, hop=1024, win_length=None,
                            window="hann", output="complex", bins_first=True, out=None):
@@ -367,17 +371,11 @@ class Dispatcher:
         C_out = 1 if mono else int(channels)
         if frames < 1 or hop < 1 or n_fft < 2 or C_out < 1:
             raise ValueError("decode_ranges_stft: frames, hop and channels must be at least 1")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T, n_freq = spec.n_frames(frames), spec.n_freq
         shape = (lambda rows: (rows, C_out, n_freq, T)) if bins_first else (lambda rows: (rows, C_out, T, n_freq))
-        out, whole, dst = self._group_tensors("decode_ranges_stft", n, shape, torch.complex64 if output == "complex" else torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = lib().vpzm_decode_ranges_stft(self._h, n, ptrs, sizes, rng.ctypes.data, int(sample_rate), C_out, int(bool(mono)), C.byref(spec),
-                                           int(frames), dst, results.ctypes.data, C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_decode_ranges_stft failed (status %d): %s" % (rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call("decode_ranges_stft", lib().vpzm_decode_ranges_stft, datas, ranges, shape,
+                                torch.complex64 if output == "complex" else torch.float32, out,
+                                lambda dst: (int(sample_rate), C_out, int(bool(mono)), C.byref(spec), int(frames), dst))
 
     def decode_ranges_cqt(self, datas, ranges, frames, sample_rate=22050, channels=1, mono=True, f_min=32.70319566257483, n_bins=84,
                           bins_per_octave=12, hop=512, filter_scale=1.0, gamma=0.0, window="hann", scale="sqrt_length", pad="reflect",
@@ -398,17 +396,11 @@ class Dispatcher:
         C_out = 1 if mono else int(channels)
         if frames < 1 or hop < 1 or n_bins < 1 or C_out < 1:
             raise ValueError("decode_ranges_cqt: frames, hop, n_bins and channels must be at least 1")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T, nb = spec.n_frames(frames), int(n_bins)
         shape = (lambda rows: (rows, C_out, nb, T)) if bins_first else (lambda rows: (rows, C_out, T, nb))
-        out, whole, dst = self._group_tensors("decode_ranges_cqt", n, shape, torch.complex64 if output == "complex" else torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = lib().vpzm_decode_ranges_cqt(self._h, n, ptrs, sizes, rng.ctypes.data, int(sample_rate), C_out, int(bool(mono)), C.byref(spec),
-                                          int(frames), dst, results.ctypes.data, C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_decode_ranges_cqt failed (status %d): %s" % (rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call("decode_ranges_cqt", lib().vpzm_decode_ranges_cqt, datas, ranges, shape,
+                                torch.complex64 if output == "complex" else torch.float32, out,
+                                lambda dst: (int(sample_rate), C_out, int(bool(mono)), C.byref(spec), int(frames), dst))
 
     def decode_ranges_fbank(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=80, low_freq=20.0, high_freq=0.0,
                             preemphasis=0.97, window="povey", remove_dc=True, scale=32768.0, log=True, floor=capi.FLT_EPSILON, pad_value=0.0,
@@ -426,17 +418,10 @@ class Dispatcher:
                                    pad_value=pad_value, frames_first=frames_first)
         if win < 1 or frames < win or hop < 1 or n_mels < 1:
             raise ValueError("decode_ranges_fbank: hop and n_mels must be at least 1, and frames at least win")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T = spec.n_frames(frames)
         shape = (lambda rows: (rows, T, n_mels)) if frames_first else (lambda rows: (rows, n_mels, T))
-        out, whole, dst = self._group_tensors("decode_ranges_fbank", n, shape, torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = lib().vpzm_decode_ranges_fbank(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
-                                            C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_decode_ranges_fbank failed (status %d): %s" % (rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call("decode_ranges_fbank", lib().vpzm_decode_ranges_fbank, datas, ranges, shape, torch.float32, out,
+                                lambda dst: (C.byref(spec), int(frames), dst))
 
     def decode_ranges_mfcc(self, datas, ranges, frames, sample_rate=16000, win=400, hop=160, n_fft=512, n_mels=23, low_freq=20.0, high_freq=0.0,
                            preemphasis=0.97, window="povey", remove_dc=True, scale=32768.0, floor=capi.FLT_EPSILON, pad_value=0.0,
@@ -456,17 +441,10 @@ class Dispatcher:
                                   htk_compat=htk_compat, subtract_mean=subtract_mean)
         if win < 1 or frames < win or hop < 1 or n_ceps < 1:
             raise ValueError("decode_ranges_mfcc: hop and n_ceps must be at least 1, and frames at least win")
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T = spec.n_frames(frames)
         shape = (lambda rows: (rows, T, n_ceps)) if frames_first else (lambda rows: (rows, n_ceps, T))
-        out, whole, dst = self._group_tensors("decode_ranges_mfcc", n, shape, torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = lib().vpzm_decode_ranges_mfcc(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), int(frames), dst, results.ctypes.data,
-                                           C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_decode_ranges_mfcc failed (status %d): %s" % (rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call("decode_ranges_mfcc", lib().vpzm_decode_ranges_mfcc, datas, ranges, shape, torch.float32, out,
+                                lambda dst: (C.byref(spec), int(frames), dst))
 
     def _decode_ranges_posted(self, name, fn, datas, ranges, frames, spec, mel, D, post, out):
         """the posted fbank / MFCC call: spec the feature spec, mel its FbankSpec, D its columns"""
@@ -479,16 +457,9 @@ class Dispatcher:
             raise ValueError("%s: the post spec's layout (frames_first) is the feature spec's" % name)
         if post.delta_order < 0 or post.delta_order > capi.FEAT_MAX_DELTA_ORDER:
             raise ValueError("%s: delta_order is 0 .. %d" % (name, capi.FEAT_MAX_DELTA_ORDER))
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
         T, D_out = mel.n_frames(frames), post.out_columns(D)
         shape = (lambda rows: (rows, T, D_out)) if mel.layout == capi.FBANK_FRAMES_FIRST else (lambda rows: (rows, D_out, T))
-        out, whole, dst = self._group_tensors(name, n, shape, torch.float32, out)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        rc = fn(self._h, n, ptrs, sizes, rng.ctypes.data, C.byref(spec), C.byref(post), int(frames), dst, results.ctypes.data, C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_%s failed (status %d): %s" % (name, rc, self.last_error()))
-        return out, whole, results, stats
+        return self._batch_call(name, fn, datas, ranges, shape, torch.float32, out, lambda dst: (C.byref(spec), C.byref(post), int(frames), dst))
 
     def decode_ranges_fbank_post(self, datas, ranges, frames, post=None, out=None, **fbank):
         """vpzm_decode_ranges_fbank_post: decode_ranges_fbank(datas, ranges, frames, **fbank) with Kaldi's feature post-processing behind
@@ -520,14 +491,7 @@ class Dispatcher:
         PCM comes down.  Returns (results, integrated, peak, steps, blocks_kept, stats): numpy arrays with an entry per stream --
         float64 LUFS (-inf with fewer than four steps or nothing kept), float64 sample peak, int64 whole 100 ms steps, int64 blocks
         behind the value; results["samples"] counts the samples measured.  An entry that delivered nothing has (-inf, 0, 0, 0)."""
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        out = np.zeros(n, dtype=LOUDNESS_DTYPE)
-        rc = lib().vpzm_measure_loudness(self._h, n, ptrs, sizes, None if rng is None else rng.ctypes.data, out.ctypes.data if n else None,
-                                         results.ctypes.data, C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_measure_loudness failed (status %d): %s" % (rc, self.last_error()))
+        results, out, stats = self._measure_call("measure_loudness", lib().vpzm_measure_loudness, datas, ranges, LOUDNESS_DTYPE)
         return (results, out["integrated"].copy(), out["peak"].copy(), out["steps"].copy(), out["blocks_kept"].copy(), stats)
 
     def measure_r128(self, datas, ranges=None):
@@ -538,12 +502,4 @@ class Dispatcher:
         peak and sample peak (float32 values), whole 100 ms steps, and the blocks behind the integrated value and the range;
         results["samples"] counts the samples measured.  integrated, sample_peak, steps and blocks_kept are measure_loudness's bits.  An
         entry that delivered nothing has (-inf, 0, -inf, -inf, -inf, -inf, 0, 0, 0, 0, 0)."""
-        n, ptrs, sizes, rng = self._inputs(datas, ranges)
-        self._drain_torch()
-        results, stats = self._outputs(n)
-        out = np.zeros(n, dtype=R128_DTYPE)
-        rc = lib().vpzm_measure_r128(self._h, n, ptrs, sizes, None if rng is None else rng.ctypes.data, out.ctypes.data if n else None,
-                                     results.ctypes.data, C.byref(stats))
-        if rc != OK:
-            raise MultiError("vpzm_measure_r128 failed (status %d): %s" % (rc, self.last_error()))
-        return results, out, stats
+        return self._measure_call("measure_r128", lib().vpzm_measure_r128, datas, ranges, R128_DTYPE)

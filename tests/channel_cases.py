@@ -289,7 +289,7 @@ class Built:
     """A case's batch as stream_major_batch makes it (pk, res, posts, counts) with the packets' mappings set."""
 
     def __init__(self, c, skew=None):
-        from test_host_paths_gpu import stream_major_batch
+        from synth_support import stream_major_batch
         self.case = c
         C = c["channels"]
         maps, floors = c["maps"], c["floors"]

@@ -7,6 +7,35 @@ blocks, pairs % kFbAhead k-steps behind them, win & 1 the odd sample), skew (an 
 waves, and for the cases at the LDS limit the tile and the floats fbank_truth.tile_plan gives (CROWD_CUS stands for a device's CU count
 where no device is; the device test takes the real one)."""
 import fbank_truth as ft
+import numpy as np
+from pcm_support import GUARD, SENTINEL, guarded
+
+
+WORST = {}
+
+
+def launch(ctx, d, src, rows, dst_rows, F, d_src=None):
+    """one vpz_pcm_fbank call of spec dict d -> [dst_rows][T][n_mels] float32 of the destination's body, the guards checked"""
+    import torch
+    from vorbispizza_amd import capi
+    spec = capi.FbankSpec.make(**d)
+    T, n_mels = spec.n_frames(F), d["n_mels"]
+    whole, dst = guarded(dst_rows, n_mels * T)
+    d_src = torch.from_numpy(src).to("cuda:0") if d_src is None else d_src
+    shape = (dst_rows, T, n_mels) if d["frames_first"] else (dst_rows, n_mels, T)
+    assert capi.pcm_fbank(ctx, d_src, rows, dst.view(shape), spec, F) == capi.OK, ctx.last_error()
+    ctx.synchronize()
+    bits = whole.cpu().numpy().view(np.uint32)
+    assert (bits[:GUARD] == SENTINEL).all() and (bits[-GUARD:] == SENTINEL).all()
+    body = bits[GUARD:-GUARD].view(np.float32)
+    return body.reshape(shape) if d["frames_first"] else body.reshape(shape).transpose(0, 2, 1)
+
+
+def note(key, ratio):
+    WORST[key] = max(WORST.get(key, 0.0), ratio)
+    print("error / bound %s: %.4f" % (key, ratio))
+    assert ratio < 1.0
+
 
 CROWD_CUS = 256
 

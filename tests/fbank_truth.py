@@ -18,6 +18,37 @@ ln(max(M + e_M, floor)), 4 u max(1, |ln|) allowed for logf; where M - e_M > floo
 import math
 
 import numpy as np
+from kernel_text import constants_of
+
+
+def make(capi, **kw):
+    d = spec_of(**kw)
+    return capi.FbankSpec.make(**d), d
+
+
+def refused_specs(capi):
+    """(what, spec) for every limit of the definition"""
+    cases = [("n_fft odd", dict(n_fft=513)), ("n_fft < 32", dict(n_fft=30, win=20, hop=10)), ("n_fft > 1024", dict(n_fft=1026)), ("win < 2", dict(win=1, hop=1)),
+             ("win > n_fft", dict(win=513)), ("hop < 1", dict(hop=0)), ("hop > win", dict(hop=401)), ("n_mels < 1", dict(n_mels=0)),
+             ("n_mels > 256", dict(n_mels=257)), ("low_freq < 0", dict(low_freq=-1.0)), ("low_freq == high", dict(low_freq=8000.0)),
+             ("low_freq > high", dict(low_freq=5000.0, high_freq=4000.0)), ("high > nyquist", dict(high_freq=8000.5)),
+             ("high offset below low_freq", dict(high_freq=-7990.0)), ("high_freq nan", dict(high_freq=float("nan"))),
+             ("low_freq nan", dict(low_freq=float("nan"))), ("sample_rate 0", dict(sample_rate=0)), ("sample_rate inf", dict(sample_rate=float("inf"))),
+             ("preemphasis < 0", dict(preemphasis=-0.01)), ("preemphasis > 1", dict(preemphasis=1.01)), ("preemphasis nan", dict(preemphasis=float("nan"))),
+             ("scale 0", dict(scale=0.0)), ("scale inf", dict(scale=float("inf"))), ("scale nan", dict(scale=float("nan"))),
+             ("scale underflows float32", dict(scale=1e-60)), ("pad_value inf", dict(pad_value=float("-inf"))), ("pad_value nan", dict(pad_value=float("nan"))),
+             ("floor 0", dict(floor=0.0)), ("floor < 0", dict(floor=-1.0)), ("floor underflows float32", dict(floor=1e-60)), ("floor nan", dict(floor=float("nan")))]
+    out = [(what, make(capi, **kw)[0]) for what, kw in cases]
+    for field, value in (("window", 3), ("window", -1), ("remove_dc", 2), ("output", 2), ("layout", 2)):
+        s = make(capi)[0]
+        setattr(s, field, value)
+        out.append((field, s))
+    for i in (0, 9):
+        s = make(capi)[0]
+        s.reserved[i] = 1
+        out.append(("a reserved word", s))
+    return out
+
 
 U = 2.0 ** -24
 FLT_EPSILON = 2.0 ** -23
@@ -155,17 +186,8 @@ def check_row(got, x, spec, W=None, B=None):
 
 
 # ---- the launch plan of vpz_pcm_fbank, restated
-def kernel_constants(root):
-    """kFbLdsFloats, kFbAhead, kFbCols, kFbMaxGridY, kFbMeans as csrc/pcm_fbank.hip states them"""
-    import os
-    import re
-    text = open(os.path.join(root, "vorbispizza_amd", "csrc", "pcm_fbank.hip")).read()
-    out = {}
-    for name in ("kFbLdsFloats", "kFbAhead", "kFbCols", "kFbMaxGridY", "kFbMeans"):
-        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert len(found) == 1, name
-        out[name] = int(found[0])
-    return out
+# kFbLdsFloats, kFbAhead, kFbCols, kFbMaxGridY, kFbMeans as csrc/pcm_fbank.hip states them
+kernel_constants = constants_of("pcm_fbank.hip", ("kFbLdsFloats", "kFbAhead", "kFbCols", "kFbMaxGridY", "kFbMeans"))
 
 
 def lds_plan(win, hop, n_fft, Tt):

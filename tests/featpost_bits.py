@@ -30,28 +30,23 @@ from fractions import Fraction
 import numpy as np
 
 import featpost_truth as pt
+from f32_model import fma32
+
+
+# (name, n, D, seed, far, the sliding spec): the spiked cases, mean only
+SPIKED = [
+    ("near W 100", 330, 4, 7, False, dict(norm="sliding", cmn_window=100, min_window=30)),
+    ("near W 200 centred", 330, 4, 7, False, dict(norm="sliding", cmn_window=200, min_window=1, center=True)),
+    ("near W 4", 330, 4, 7, False, dict(norm="sliding", cmn_window=4, min_window=2)),
+    ("far W 300 centred", 700, 3, 7, True, dict(norm="sliding", cmn_window=300, min_window=1, center=True)),
+    ("far W 600", 700, 3, 7, True, dict(norm="sliding", cmn_window=600, min_window=100)),
+]
+ROW_SPIKED = [("near row", 330, 4, 7, False, dict(norm="row")), ("far row", 700, 3, 7, True, dict(norm="row"))]
+
 
 F32, F64 = np.float32, np.float64
 CHUNK = pt.CHUNK
 ORDERS = ("running", "descending", "r_first", "chunks_first")
-
-
-def fma32(a, b, c):
-    """float32 arrays -> fl32(a * b + c), one rounding, element by element"""
-    a, b, c = (np.asarray(v, dtype=F32).astype(F64) for v in (a, b, c))
-    with np.errstate(invalid="ignore", over="ignore"):
-        p = a * b  # exact: 48 bits
-        s = p + c
-        z = s - p
-        err = (p - (s - z)) + (c - z)  # TwoSum: s + err is the exact p + c
-        r = s.astype(F32)
-        away = np.where(r.astype(F64) > s, F32(-np.inf), F32(np.inf))
-        other = np.nextafter(r, away)  # the float32 on the other side of s
-        rd, od = r.astype(F64), other.astype(F64)
-        tie = np.isfinite(s) & np.isfinite(od) & (rd != s) & (np.abs(rd - s) == np.abs(od - s)) & (err != 0)
-        up = np.where(rd > od, r, other)
-        down = np.where(rd > od, other, r)
-    return np.where(tie, np.where(err > 0, up, down), r).astype(F32)
 
 
 def fma64(a, b, c):

@@ -24,6 +24,41 @@ from fractions import Fraction
 
 import numpy as np
 
+
+def make(capi, **kw):
+    d = spec_of(**kw)
+    return capi.FeatPostSpec.make(**d), d
+
+
+# ---- the window
+NS = (1, 2, 99, 100, 101, 600, 601, 602, 1300)
+
+
+# ---- limits, refusals, the scratch size
+def refused_specs(capi):
+    """(what, spec) for every limit of the definition"""
+    out = []
+    base = dict(norm="sliding", delta_order=2)
+    for what, kw in (("cmn_window < 1", dict(cmn_window=0, min_window=0)), ("cmn_window > 2^20", dict(cmn_window=(1 << 20) + 1)),
+                     ("min_window < 1", dict(min_window=0)), ("min_window > cmn_window", dict(cmn_window=50, min_window=51)),
+                     ("delta_order < 0", dict(delta_order=-1)), ("delta_order > 3", dict(delta_order=4)),
+                     ("delta_window < 1", dict(delta_window=0)), ("delta_window > 8", dict(delta_window=9)),
+                     ("var_floor 0", dict(var_floor=0.0)), ("var_floor < 0", dict(var_floor=-1e-10)), ("var_floor nan", dict(var_floor=float("nan"))),
+                     ("var_floor inf", dict(var_floor=float("inf"))), ("pad_value nan", dict(pad_value=float("nan"))),
+                     ("pad_value inf", dict(pad_value=float("-inf"))), ("a spec that does nothing", dict(norm="none", delta_order=0))):
+        out.append((what, make(capi, **dict(base, **kw))[0]))
+    for field, values in (("norm", (-1, 3)), ("norm_vars", (-1, 2)), ("center", (-1, 2)), ("order", (-1, 2)), ("layout", (-1, 2))):
+        for value in values:
+            s = make(capi, **base)[0]
+            setattr(s, field, value)
+            out.append((field, s))
+    for i in (0, 10):
+        s = make(capi, **base)[0]
+        s.reserved[i] = 1
+        out.append(("a reserved word", s))
+    return out
+
+
 LD =np.longdouble
 U = LD(2.0) ** -24
 V = LD(2.0) ** -53

@@ -1,7 +1,7 @@
 """vpz_pcm_loudness at the limits of its launches: ONE case list, used by test_loudness_cpu.py (is every case the shape it is named for, and
 does the reference alone meet the conditions?) and by test_pcm_loudness_limits_gpu.py (does the device compute them?).
 
-A case is test_pcm_loudness_gpu.Case: rows of one launch, noise plus a tone, every channel's crest factor 4 or less (Case asserts it).
+A case is loudness_support.Case: rows of one launch, noise plus a tone, every channel's crest factor 4 or less (Case asserts it).
 EXPECT states, in numbers written down here and not computed, what each case is there for: G and the idle lanes of its channel count, and
 per row (units, steps, workgroups of (a), workgroups of (c), samples behind the last whole step); test_loudness_cpu.py holds the cases to
 them through loudness_truth.launch_plan and tiles_of.  The truth of all cases is one table, computed once per process in groups of similar
@@ -11,7 +11,7 @@ import types
 import numpy as np
 
 import loudness_truth as lt
-from test_pcm_loudness_gpu import Case, noise, tone
+from loudness_support import Case, noise, tone
 
 S = 800                      # the step at 8 000 Hz
 CHANNEL_COUNTS = (4, 5, 7, 9, 31, 32, 33, 64, 85, 86, 128, 129, 255)

@@ -9,6 +9,7 @@ Two forms of the same recurrence:
                         80-second sequences of EBU Tech 3341 affordable in numpy.  It is also the shape of the device kernels.
 The bound of the device tests is derived at `bound` below."""
 import numpy as np
+from kernel_text import constants_of
 
 SHELF = dict(f0=1681.974450955533, G=3.999843853973347, Q=0.7071752369554196, vb_exp=0.4996667741545416)
 HIGHPASS = dict(f0=38.13547087602444, Q=0.5003270373238773)
@@ -175,17 +176,8 @@ def relative_bound(fs):
 
 
 # ---- the launch plan of vpz_pcm_loudness, restated
-def kernel_constants(root):
-    """kLoudBlock, kChunk, kLoudMaxGridY as csrc/pcm_loudness.hip states them"""
-    import os
-    import re
-    text = open(os.path.join(root, "vorbispizza_amd", "csrc", "pcm_loudness.hip")).read()
-    out = {}
-    for name in ("kLoudBlock", "kChunk", "kLoudMaxGridY"):
-        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert len(found) == 1, name
-        out[name] = int(found[0])
-    return out
+# kLoudBlock, kChunk, kLoudMaxGridY as csrc/pcm_loudness.hip states them
+kernel_constants = constants_of("pcm_loudness.hip", ("kLoudBlock", "kChunk", "kLoudMaxGridY"))
 
 
 def launch_plan(channels, k):

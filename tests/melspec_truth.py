@@ -25,7 +25,36 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_logmel_cpu import U, extend, frames_of, mel_weights64  # noqa: E402,F401
+from f32_model import U  # noqa: E402,F401
+from logmel_truth import extend, frames_of, mel_weights64  # noqa: E402,F401
+from logmel_truth import refused_specs  # noqa: E402
+from kernel_text import constants_of  # noqa: E402
+import f32_model  # noqa: E402
+from f32_model import fma32 as _fma  # noqa: E402
+
+
+def melspec_refused_specs(capi):
+    """(what, spec) for every limit of the definition: logmel_truth's list carried to this stage's transform sizes, and the sizes it
+    does not take"""
+    good = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=128)
+    out = []
+    for what, s in refused_specs(capi):
+        if what.startswith("n_fft"):
+            continue
+        t = capi.LogMelSpec.make(**good)
+        scale = 22050.0 / 16000.0
+        t.f_min, t.f_max, t.floor = s.f_min * scale, s.f_max * scale, s.floor
+        t.sample_rate = s.sample_rate * scale
+        t.hop = {160: 512, 0: 0, 401: 2049}[s.hop]
+        t.n_mels = {80: 128, 0: 0, 257: 257}[s.n_mels]
+        t.mel_scale, t.mel_norm, t.output, t.layout = s.mel_scale, s.mel_norm, s.output, s.layout
+        for i in range(9):
+            t.reserved[i] = s.reserved[i]
+        out.append((what, t))
+    for n_fft in (1024, 2047, 2046, 3000, 6144, 16384, 0, -2048):
+        out.append(("n_fft %d" % n_fft, capi.LogMelSpec.make(**dict(good, n_fft=n_fft, hop=min(512, max(1, n_fft))))))
+    return out
+
 
 NFFTS = (2048, 4096, 8192)
 FLOOR = 1e-10
@@ -79,59 +108,15 @@ def tables64(n_fft):
     return hann64(n_fft), np.stack([c, s], axis=1)
 
 
-def _fma(a, b, c):
-    """float32 fused multiply-add: the float32 product is exact in float64"""
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(np.float32)
-
-
-def _cmul(tr, ti, vr, vi):
-    """t * v as the header writes it"""
-    return _fma(vr, tr, -(vi * ti)), _fma(vr, ti, vi * tr)
-
-
-def network32(X, n_fft, w=None, t=None):
-    """(re, im), float32 [T, n_fft / 2 + 1]: the header's network step for step on float32 frames X, with the float32 tables w [n_fft]
-    and t [n_fft, 2] (the library's own by default rounding of tables64)"""
+def _network32(X, n_fft, w=None, t=None):
+    """(re, im), float32 [T, n_fft / 2 + 1]: f32_model.network32 with the library's own tables by default (tables64 rounded once) and
+    this stage's sign, (re, -im)"""
     w64, t64 = tables64(n_fft)
-    w = w64.astype(np.float32) if w is None else w
-    t = t64.astype(np.float32) if t is None else t
-    N, H = n_fft, n_fft // 2
-    X = np.asarray(X, dtype=np.float32)
-    y = X * w[None, :]
-    zr, zi = y[:, 0::2].copy(), y[:, 1::2].copy()
-    n, s = H, 1
-    while n >= 4:
-        q4 = n // 4
-        # in[q + s (p + j n/4)] as [T, j, p, q]
-        ar, ai = zr.reshape(-1, 4, q4, s), zi.reshape(-1, 4, q4, s)
-        a_r, b_r, c_r, d_r = ar[:, 0], ar[:, 1], ar[:, 2], ar[:, 3]
-        a_i, b_i, c_i, d_i = ai[:, 0], ai[:, 1], ai[:, 2], ai[:, 3]
-        apc_r, apc_i, amc_r, amc_i = a_r + c_r, a_i + c_i, a_r - c_r, a_i - c_i
-        bpd_r, bpd_i, bmd_r, bmd_i = b_r + d_r, b_i + d_i, b_r - d_r, b_i - d_i
-        p = np.arange(q4)
-        t1, t2, t3 = t[2 * p * s][None, :, None, :], t[4 * p * s][None, :, None, :], t[6 * p * s][None, :, None, :]
-        o0r, o0i = apc_r + bpd_r, apc_i + bpd_i
-        o1r, o1i = _cmul(t1[..., 0], t1[..., 1], amc_r + bmd_i, amc_i - bmd_r)
-        o2r, o2i = _cmul(t2[..., 0], t2[..., 1], apc_r - bpd_r, apc_i - bpd_i)
-        o3r, o3i = _cmul(t3[..., 0], t3[..., 1], amc_r - bmd_i, amc_i + bmd_r)
-        # out[q + s (4p + j)] as [T, p, j, q]
-        zr = np.stack([o0r, o1r, o2r, o3r], axis=2).reshape(-1, H)
-        zi = np.stack([o0i, o1i, o2i, o3i], axis=2).reshape(-1, H)
-        n, s = n // 4, s * 4
-    if n == 2:
-        ar, ai = zr.reshape(-1, 2, s), zi.reshape(-1, 2, s)
-        zr = np.concatenate([ar[:, 0] + ar[:, 1], ar[:, 0] - ar[:, 1]], axis=1)
-        zi = np.concatenate([ai[:, 0] + ai[:, 1], ai[:, 0] - ai[:, 1]], axis=1)
-    k = np.arange(H // 2 + 1)
-    m = (H - k) % H
-    half = np.float32(0.5)
-    Er, Ei = (zr[:, k] + zr[:, m]) * half, (zi[:, k] - zi[:, m]) * half
-    Or, Oi = (zi[:, k] + zi[:, m]) * half, (zr[:, m] - zr[:, k]) * half
-    tr, ti = _cmul(t[k, 0][None, :], t[k, 1][None, :], Or, Oi)
-    re_, im_ = np.zeros((X.shape[0], H + 1), np.float32), np.zeros((X.shape[0], H + 1), np.float32)
-    re_[:, H - k], im_[:, H - k] = Er - tr, -(Ei - ti)  # conj(E - t O)
-    re_[:, k], im_[:, k] = Er + tr, Ei + ti
+    re_, im_ = f32_model.network32(X, n_fft, w64.astype(np.float32) if w is None else w, t64.astype(np.float32) if t is None else t)
     return re_, -im_
+
+
+network32 = _network32
 
 
 def proxy_mel(X, n_fft, W, w=None, t=None):
@@ -142,15 +127,9 @@ def proxy_mel(X, n_fft, W, w=None, t=None):
 
 
 # ---- the launch plan, restated
-def kernel_constants():
-    """the constants of csrc/pcm_melspec.hip's plan as the file states them"""
-    text = open(os.path.join(ROOT, "vorbispizza_amd", "csrc", "pcm_melspec.hip")).read()
-    out = {}
-    for name in ("kMsBlock", "kMsLdsFloats", "kMsMaxGridY", "kMsMelRoom", "kMsTileA", "kMsTileB", "kMsTileC"):
-        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert len(found) == 1, name
-        out[name] = int(found[0])
-    return out
+# the constants of csrc/pcm_melspec.hip's plan as the file states them
+kernel_constants = constants_of("pcm_melspec.hip", ("kMsBlock", "kMsLdsFloats", "kMsMaxGridY", "kMsMelRoom", "kMsTileA", "kMsTileB",
+                                "kMsTileC"))
 
 
 def lds_floats(n_fft, hop, Tt, k):

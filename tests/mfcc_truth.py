@@ -30,6 +30,40 @@ import numpy as np
 import fbank_truth as ft
 from fbank_truth import U
 
+
+def make(capi, **kw):
+    d = spec_of(**kw)
+    return capi.MfccSpec.make(**d), d
+
+
+def refused_specs(capi):
+    """(what, spec) for every limit of the definition: the mel stage's (fbank_truth's list, inside an MfccSpec) and its own"""
+    from fbank_truth import refused_specs as fbank_refused
+    out = []
+    for what, fb in fbank_refused(capi):
+        s = make(capi)[0]
+        s.fbank = fb
+        out.append(("fbank: " + what, s))
+    power = make(capi)[0]
+    power.fbank.output = capi.FBANK_POWER
+    out.append(("output is not the log", power))
+    for what, kw in (("n_ceps < 1", dict(n_ceps=0)), ("n_ceps > n_mels", dict(n_ceps=24)), ("n_ceps > n_mels at one band", dict(n_mels=1, n_ceps=2)),
+                     ("lifter < 0", dict(lifter=-1.0)), ("lifter nan", dict(lifter=float("nan"))), ("lifter inf", dict(lifter=float("inf"))),
+                     ("energy_floor < 0", dict(energy_floor=-1e-9)), ("energy_floor nan", dict(energy_floor=float("nan"))),
+                     ("energy_floor inf", dict(energy_floor=float("inf")))):
+        out.append((what, make(capi, **kw)[0]))
+    for field in ("use_energy", "htk_compat", "subtract_mean"):
+        for value in (2, -1):
+            s = make(capi)[0]
+            setattr(s, field, value)
+            out.append((field, s))
+    for i in (0, 11):
+        s = make(capi)[0]
+        s.reserved[i] = 1
+        out.append(("a reserved word", s))
+    return out
+
+
 ENERGY_EPS = 2.0 ** -23
 DEFAULTS = dict({k: v for k, v in ft.DEFAULTS.items() if k != "log"}, n_mels=23, n_ceps=13, lifter=22.0, use_energy=True, energy_floor=0.0,
                 htk_compat=False, subtract_mean=False)

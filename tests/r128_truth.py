@@ -9,6 +9,7 @@ import os
 import re
 
 import numpy as np
+from kernel_text import constants_of
 
 TAPS = 12
 
@@ -149,15 +150,8 @@ def loudness_maxima(sums, S):
 
 
 # ---- the launch plan of vpz_pcm_true_peak, restated
-def kernel_constants(root):
-    """kTpBlock, kTpTile, kTpTaps, kTpMaxGridY as csrc/pcm_truepeak.hip states them"""
-    text = open(os.path.join(root, "vorbispizza_amd", "csrc", "pcm_truepeak.hip")).read()
-    out = {}
-    for name in ("kTpBlock", "kTpTile", "kTpTaps", "kTpMaxGridY"):
-        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert len(found) == 1, name
-        out[name] = int(found[0])
-    return out
+# kTpBlock, kTpTile, kTpTaps, kTpMaxGridY as csrc/pcm_truepeak.hip states them
+kernel_constants = constants_of("pcm_truepeak.hip", ("kTpBlock", "kTpTile", "kTpTaps", "kTpMaxGridY"))
 
 
 def launch_plan(samples, channels, k):

@@ -27,7 +27,29 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from melspec_truth import K, passes, tables64  # noqa: E402,F401
-from test_logmel_cpu import U, extend, frames_of  # noqa: E402,F401
+from f32_model import cmul as _cmul, fma32 as _fma, network32, U  # noqa: E402,F401
+from logmel_truth import extend, frames_of  # noqa: E402,F401
+from kernel_text import constants_of  # noqa: E402
+
+
+def stft_refused_specs(capi):
+    """(what, spec) for every limit of the definition"""
+    good = dict(n_fft=2048, hop=512)
+    cases = [("n_fft 256", dict(n_fft=256, hop=64)), ("n_fft 400", dict(n_fft=400, hop=100)), ("n_fft 513", dict(n_fft=513)), ("n_fft 3000", dict(n_fft=3000)),
+             ("n_fft 16384", dict(n_fft=16384)), ("n_fft 0", dict(n_fft=0, hop=1, win_length=2)), ("n_fft < 0", dict(n_fft=-2048, hop=1, win_length=2)),
+             ("hop < 1", dict(hop=0)), ("hop > n_fft", dict(hop=2049)), ("win_length < 2", dict(win_length=1)), ("win_length 0", dict(win_length=0)),
+             ("win_length > n_fft", dict(win_length=2049))]
+    out = [(what, capi.StftSpec.make(**dict(good, **kw))) for what, kw in cases]
+    for field, value in (("window", 2), ("window", -1), ("output", 3), ("output", -1), ("layout", 2), ("layout", -1)):
+        s = capi.StftSpec.make(**good)
+        setattr(s, field, value)
+        out.append(("%s %d" % (field, value), s))
+    for i in (0, 9):
+        s = capi.StftSpec.make(**good)
+        s.reserved[i] = 1
+        out.append(("a reserved word", s))
+    return out
+
 
 NFFTS = (512, 1024, 2048, 4096, 8192)
 OUTPUTS = ("complex", "magnitude", "power")
@@ -81,66 +103,9 @@ def check_output(output, got, Z, d):
 
 # ---- the kernel's own network, in float32 numpy (frames along the first axis): tests/melspec_truth.py's network32 over a window table and
 # at every H from 256, with an exact fused multiply-add
-def _fma(a, b, c):
-    """float32 fused multiply-add, correctly rounded: the float32 product is exact in float64; the float64 sum is rounded to odd (TwoSum
-    gives what it lost), so that the second rounding, to float32, is the only one that counts"""
-    p, c = a.astype(np.float64) * b.astype(np.float64), np.asarray(c, dtype=np.float32).astype(np.float64)
-    s = p + c
-    bb = s - p
-    e = (p - (s - bb)) + (c - bb)
-    fix = (e != 0) & ((s.view(np.int64) & 1) == 0) & np.isfinite(s)
-    s = np.where(fix, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
-    return s.astype(np.float32)
-
-
-def _cmul(tr, ti, vr, vi):
-    """t * v as the header writes it"""
-    return _fma(vr, tr, -(vi * ti)), _fma(vr, ti, vi * tr)
-
-
 def tables32(n_fft, win_length=None, window="hann"):
     """(w, t) in float32: the restatement rounded once (tests/test_stft_cpu.py holds vpz_stft_table to these bits)"""
     return window64(n_fft, win_length, window).astype(np.float32), tables64(n_fft)[1].astype(np.float32)
-
-
-def network32(X, n_fft, w, t):
-    """(re, im) = (Re X, Im X), float32 [T, n_fft / 2 + 1]: the header's network step for step on float32 frames X, with the float32
-    tables w [n_fft] and t [n_fft, 2]"""
-    H = n_fft // 2
-    X = np.asarray(X, dtype=np.float32)
-    y = X * w[None, :]
-    zr, zi = y[:, 0::2].copy(), y[:, 1::2].copy()
-    n, s = H, 1
-    while n >= 4:
-        q4 = n // 4
-        ar, ai = zr.reshape(-1, 4, q4, s), zi.reshape(-1, 4, q4, s)  # in[q + s (p + j n/4)] as [T, j, p, q]
-        a_r, b_r, c_r, d_r = ar[:, 0], ar[:, 1], ar[:, 2], ar[:, 3]
-        a_i, b_i, c_i, d_i = ai[:, 0], ai[:, 1], ai[:, 2], ai[:, 3]
-        apc_r, apc_i, amc_r, amc_i = a_r + c_r, a_i + c_i, a_r - c_r, a_i - c_i
-        bpd_r, bpd_i, bmd_r, bmd_i = b_r + d_r, b_i + d_i, b_r - d_r, b_i - d_i
-        p = np.arange(q4)
-        t1, t2, t3 = t[2 * p * s][None, :, None, :], t[4 * p * s][None, :, None, :], t[6 * p * s][None, :, None, :]
-        o0r, o0i = apc_r + bpd_r, apc_i + bpd_i
-        o1r, o1i = _cmul(t1[..., 0], t1[..., 1], amc_r + bmd_i, amc_i - bmd_r)
-        o2r, o2i = _cmul(t2[..., 0], t2[..., 1], apc_r - bpd_r, apc_i - bpd_i)
-        o3r, o3i = _cmul(t3[..., 0], t3[..., 1], amc_r - bmd_i, amc_i + bmd_r)
-        zr = np.stack([o0r, o1r, o2r, o3r], axis=2).reshape(-1, H)  # out[q + s (4p + j)] as [T, p, j, q]
-        zi = np.stack([o0i, o1i, o2i, o3i], axis=2).reshape(-1, H)
-        n, s = n // 4, s * 4
-    if n == 2:
-        ar, ai = zr.reshape(-1, 2, s), zi.reshape(-1, 2, s)
-        zr = np.concatenate([ar[:, 0] + ar[:, 1], ar[:, 0] - ar[:, 1]], axis=1)
-        zi = np.concatenate([ai[:, 0] + ai[:, 1], ai[:, 0] - ai[:, 1]], axis=1)
-    k = np.arange(H // 2 + 1)
-    m = (H - k) % H
-    half = np.float32(0.5)
-    Er, Ei = (zr[:, k] + zr[:, m]) * half, (zi[:, k] - zi[:, m]) * half
-    Or, Oi = (zi[:, k] + zi[:, m]) * half, (zr[:, m] - zr[:, k]) * half
-    tr, ti = _cmul(t[k, 0][None, :], t[k, 1][None, :], Or, Oi)
-    re_, im_ = np.zeros((X.shape[0], H + 1), np.float32), np.zeros((X.shape[0], H + 1), np.float32)
-    re_[:, H - k], im_[:, H - k] = Er - tr, -(Ei - ti)  # conj(E - t O)
-    re_[:, k], im_[:, k] = Er + tr, Ei + ti            # (bin H / 2 is its own mirror: E + t O stands)
-    return re_, im_
 
 
 def outputs32(re_, im_):
@@ -152,15 +117,8 @@ def outputs32(re_, im_):
 
 
 # ---- the launch plan, restated
-def kernel_constants():
-    """the constants of csrc/pcm_stft.hip's plan as the file states them"""
-    text = open(os.path.join(ROOT, "vorbispizza_amd", "csrc", "pcm_stft.hip")).read()
-    out = {}
-    for name in ("kStBlock", "kStLdsFloats", "kStMaxGridY", "kStMaxTile"):
-        found = re.findall(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text)
-        assert len(found) == 1, name
-        out[name] = int(found[0])
-    return out
+# the constants of csrc/pcm_stft.hip's plan as the file states them
+kernel_constants = constants_of("pcm_stft.hip", ("kStBlock", "kStLdsFloats", "kStMaxGridY", "kStMaxTile"))
 
 
 def lanes_per_frame(n_fft, k):

@@ -9,7 +9,7 @@ import pytest
 
 import helpers
 from helpers import PKT_EOS
-from test_host_paths_gpu import env
+from synth_support import env
 
 pytestmark = pytest.mark.gpu
 

@@ -20,23 +20,12 @@ import numpy as np
 import pytest
 
 import channel_cases as cc
-from test_dual_gpu import same_bits
-from test_host_paths_gpu import env, run
-from test_s16_gpu import to_s16
+from synth_support import env, run, same_bits, to_s16
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 12345
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def decode(ctx, b, kv, layout, capfd, device_shift=None):

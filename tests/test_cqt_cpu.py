@@ -19,9 +19,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import cqt_truth as ct  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_logmel_cpu import KINDS  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from logmel_truth import KINDS  # noqa: E402
+from binding_support import imports_of  # noqa: E402
+from cqt_truth import cqt_refused_specs, make  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -30,37 +31,6 @@ def capi():
     ge.build()
     from vorbispizza_amd import capi
     return capi
-
-
-def make(capi, s, **kw):
-    return capi.CqtSpec.make(**dict(s, **kw))
-
-
-def cqt_refused_specs(capi, good=None):
-    """(what, spec) for every limit of the definition"""
-    good = dict(good or ct.spec_of())
-    limit = ct.CASES["limit_N0_65536"]["spec"]
-    cases = [("sample_rate 0", dict(sample_rate=0.0)), ("sample_rate < 0", dict(sample_rate=-8000.0)), ("sample_rate NaN", dict(sample_rate=float("nan"))),
-             ("f_min 0", dict(f_min=0.0)), ("f_min < 0", dict(f_min=-250.0)), ("the last bin over Nyquist", dict(n_bins=50)),
-             ("n_bins 0", dict(n_bins=0)), ("n_bins < 0", dict(n_bins=-1)), ("n_bins 513", dict(n_bins=513, bins_per_octave=96, f_min=50.0)),
-             ("bins_per_octave 0", dict(bins_per_octave=0)), ("bins_per_octave 97", dict(bins_per_octave=97)),
-             ("filter_scale 0", dict(filter_scale=0.0)), ("filter_scale < 0", dict(filter_scale=-1.0)), ("gamma < 0", dict(gamma=-1.0)),
-             ("gamma infinite", dict(gamma=float("inf"))),
-             ("N_k < 2", dict(f_min=975.0, n_bins=3, bins_per_octave=1, filter_scale=0.4)),
-             ("N_0 over 65536", dict(limit, f_min=ct._f_min_for(65537, limit["sample_rate"], limit["bins_per_octave"]))),
-             ("N_0 69365 (44.1 kHz, 36 to the octave)", dict(sample_rate=44100.0, f_min=32.70319566257483, n_bins=3, bins_per_octave=36)),
-             ("hop 0", dict(hop=0)), ("hop < 0", dict(hop=-64)), ("hop 2049", dict(hop=2049))]
-    out = [(what, make(capi, good, **kw)) for what, kw in cases]
-    for field, value in (("window", 2), ("window", -1), ("scale", 2), ("scale", -1), ("pad", 2), ("pad", -1), ("output", 3), ("output", -1), ("layout", 2),
-                         ("layout", -1)):
-        s = make(capi, good)
-        setattr(s, field, value)
-        out.append(("%s %d" % (field, value), s))
-    for i in (0, 7):
-        s = make(capi, good)
-        s.reserved[i] = 1
-        out.append(("a reserved word", s))
-    return out
 
 
 # ---- the exports

@@ -7,31 +7,11 @@ import pytest
 
 import helpers
 from helpers import PKT_EOS
-from test_host_paths_gpu import env, run, stream_major_batch
+from synth_support import env, run, stream_major_batch
+from synth_support import ROUTES, same_bits  # noqa: E402
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-ROUTES = (("dual", dict(VPZ_NO_DUAL=None, VPZ_NO_GROUP=None)), ("group", dict(VPZ_NO_DUAL=1, VPZ_NO_GROUP=None)),
-          ("separate", dict(VPZ_NO_DUAL=1, VPZ_NO_GROUP=1)))
-
-
-def same_bits(a, b, what=""):
-    assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2]) and a[3] == b[3], what
-    x, y = (a[0], b[0]) if a[0].dtype == np.int16 else (a[0].view(np.uint32), b[0].view(np.uint32))
-    bad = np.nonzero(x != y)[0]
-    assert len(bad) == 0, "%s: %d elements differ, first at %d (%r vs %r), last at %d; totals %r" % (
-        what, len(bad), bad[0], a[0][bad[0]], b[0][bad[0]], bad[-1], a[1][:6])
 
 
 @pytest.mark.parametrize("interleaved", [True, False])

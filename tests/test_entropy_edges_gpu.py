@@ -15,19 +15,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import edge_streams as es  # noqa: E402
-from test_entropy_gpu import check_stream, device_decode  # noqa: E402
+from synth_support import check_stream, device_decode  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 BIG = 65600
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def both_spaces():

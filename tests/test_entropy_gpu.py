@@ -11,82 +11,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_entropy_plan_cpu import FIXTURES, GOLDEN, streams  # noqa: E402
+from synth_support import FIXTURES, GOLDEN, check_stream, device_decode, streams  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
 def fixture(name):
     return open(os.path.join(GOLDEN, name), "rb").read()
-
-
-def cpu_decode(f, i16):
-    packets, residue, posts, counts = f.decode_packets(int16=i16)
-    return packets, residue, posts, counts
-
-
-def device_decode(ctx, setup, packets, spans, payload, n_values, channels, i16, mem_space):
-    import torch
-
-    from vorbispizza_amd import capi
-    n = len(packets)
-    dt = np.int16 if i16 else np.float32
-    if mem_space == capi.MEM_HOST:
-        residue = np.zeros(max(1, n_values), dtype=dt)
-        posts = np.full((n * channels, 64), 0x5A5A, dtype=np.int16)
-        counts = np.full(n * channels, 0xEE, dtype=np.uint8)
-        setup.decode(packets, spans, payload, residue, posts, counts, mem_space=mem_space)
-        return residue, posts, counts
-    dev = torch.device("cuda", ctx.device)
-    residue = torch.zeros(max(1, n_values), dtype=torch.int16 if i16 else torch.float32, device=dev)
-    posts = torch.full((n * channels, 64), 0x5A5A, dtype=torch.int16, device=dev)
-    counts = torch.full((n * channels,), 0xEE, dtype=torch.uint8, device=dev)
-    setup.decode(packets, spans, torch.from_numpy(payload).to(dev), residue, posts, counts, mem_space=mem_space)
-    ctx.synchronize()
-    return residue.cpu().numpy(), posts.cpu().numpy(), counts.cpu().numpy()
-
-
-def assert_same(name, f, packets, ref, got):
-    from vorbispizza_amd import capi
-    _, rres, rposts, rcounts = ref
-    res, posts, counts = got
-    assert np.array_equal(counts, rcounts), name
-    assert posts.tobytes() == rposts.tobytes(), name
-    for k in range(len(packets)):
-        if packets["flags"][k] & capi.PKT_NOT_DECODED:
-            continue
-        o = int(packets["residue_offset"][k])
-        n = f.channels * ((f.block_size1 if packets["flags"][k] & capi.PKT_BLOCK_FLAG else f.block_size0) // 2)
-        assert res[o:o + n].tobytes() == rres[o:o + n].tobytes(), (name, k)
-
-
-def check_stream(ctx, name, raw, mem_spaces):
-    from vorbispizza_amd import capi
-    from vorbispizza_amd.entropy import EntropySetup
-    from vorbispizza_amd.front import OggVorbisFile
-    f = OggVorbisFile(raw)
-    if not f.gpu_decode_supported:
-        f.close()
-        return False
-    setup = EntropySetup(ctx, f.entropy_setup())
-    packets, spans, payload, n_values = f.plan_packets()
-    for i16 in ([False, True] if f.residue_is_integral else [False]):
-        ref = cpu_decode(f, i16)
-        assert packets.tobytes() == ref[0].tobytes(), name
-        for ms in mem_spaces:
-            got = device_decode(ctx, setup, packets, spans, payload, n_values, f.channels, i16, ms)
-            assert_same((name, i16, ms), f, packets, ref, got)
-    setup.close()
-    f.close()
-    return True
 
 
 def test_every_eligible_stream_decodes_as_on_the_cpu(ctx):
@@ -99,7 +31,7 @@ def test_every_eligible_stream_decodes_as_on_the_cpu(ctx):
 
 def test_damaged_audio_decodes_as_on_the_cpu(ctx):
     """truncated packets, Huffman misses, early residue stops: 60 seeds over the two long fixtures and a writer stream"""
-    from test_hostile_input_gpu import damage_audio
+    from synth_support import damage_audio
 
     from vorbispizza_amd import capi
     import synthetic_streams as ss
@@ -113,7 +45,7 @@ def test_damaged_audio_decodes_as_on_the_cpu(ctx):
 
 def test_a_batch_of_several_streams_of_one_setup(ctx):
     """one call over three streams of 3test's setup (the file and two damaged copies), payloads and residues back to back"""
-    from test_hostile_input_gpu import damage_audio
+    from synth_support import damage_audio
 
     from vorbispizza_amd import capi
     from vorbispizza_amd.entropy import EntropySetup

@@ -11,6 +11,7 @@ import sys
 
 import numpy as np
 import pytest
+from gpu_context import ctx  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -19,14 +20,6 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 STEREO, THREE, MONO = (2, 12, 22, 32), (3, 13, 23), (1, 11, 21)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def both_spaces():
@@ -238,7 +231,7 @@ def test_int16_over_the_two_fixtures(ctx):
 
 
 def test_a_group_of_one_setup_writes_what_vpz_entropy_decode_writes(ctx):
-    from test_entropy_gpu import device_decode
+    from synth_support import device_decode
 
     from vorbispizza_amd.entropy import EntropySetup
     sets = tiles("tile_three_channels", (0,))

@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from synth_support import HEADER_EDGE, header_edge_stream, streams  # noqa: E402
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-FIXTURES = ("1test.ogg", "2test.ogg", "3test.ogg", "issue6test.ogg")
 
 
 def ogg_packets(raw):
@@ -37,52 +37,6 @@ def ogg_packets(raw):
                     out.append(pending)
                     pending = b""
         pos = body + size
-    return out
-
-
-# The smallest packets at which the parse of a packet's first bits can go wrong, in place of audio packets 3 ... 9 of ten long
-# blocks: nothing to read, each kind of record (type bit set, unused mode number), a header that ends inside the packet, and
-# EOS on a degenerate packet.  What the front end wrote for them before the parse became one function (flags per packet,
-# vpzh_decode_failures): BLOCK 1, PREV 2, NEXT 4, EOS 8, NOT_DECODED 16, INTERLEAVED 32.
-HEADER_EDGE = {
-    "stereo_coupled_res2": ([39, 39, 39, 32, 16, 16, 39, 39, 39, 40], (0, -1)),
-    "mono_floor1_res1": ([7, 7, 7, 0, 16, 16, 7, 7, 7, 8], (1, 5)),  # (three modes: mode number 3 is unused)
-    "three_channels_two_submaps": ([7, 7, 7, 0, 16, 16, 7, 7, 7, 8], (0, -1)),
-}
-
-
-def header_edge_stream(name):
-    import synthetic_streams as ss
-    import vorbis_writer as vw
-    stream, rng = getattr(ss, name)()
-    long_mode = next(i for i, (blockflag, _) in enumerate(stream.modes) if blockflag)
-    audio = [stream.audio_packet(rng, long_mode, 1, 1)[0] for _ in range(10)]
-    mode_bits = vw.ilog(len(stream.modes) - 1)
-    unused = (1 << mode_bits) - 1
-    audio[3] = b""
-    audio[4] = b"\x01"
-    audio[5] = bytes([unused << 1]) if unused >= len(stream.modes) else b"\x01\x02"
-    audio[6] = audio[6][:1]
-    audio[7] = audio[7][:3]
-    audio[9] = b""
-    granules = [0, 0, 0] + [stream.bs1 // 2 * i for i in range(10)]
-    return bytes(vw.ogg_mux(stream.headers() + audio, granules, packets_per_page=2))
-
-
-def streams():
-    """(name, container bytes) of every stream the tests below look at"""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import hostile_setups as hs
-    import synthetic_streams as ss
-    out = [(n, open(os.path.join(GOLDEN, n), "rb").read()) for n in FIXTURES]
-    out += [("header edges:" + name, header_edge_stream(name)) for name in sorted(HEADER_EDGE)]
-    for name, make in sorted(ss.ALL.items()):
-        st, rng = make()
-        ogg, _ = st.build(rng, 24)
-        out.append((name, bytes(ogg)))
-    for name, (raw, expect) in sorted(hs.crafted().items()):
-        if expect == "pcm":
-            out.append(("crafted:" + name, raw))
     return out
 
 
@@ -231,7 +185,7 @@ def test_entropy_header_compiles_as_c99(tmp_path):
 
 def test_the_csharp_binding_matches_the_entropy_header():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from test_csharp_binding_cpu import CS, c_functions, cs_imports
+    from binding_support import CS, c_functions, cs_imports
     c = c_functions("vorbispizza_entropy.h", "vpz_entropy_")
     front_syms = c_functions("vorbispizza_front.h", "vpzh_")
     host = {n: front_syms[n] for n in ("vpzh_gpu_decode_supported", "vpzh_get_entropy_setup", "vpzh_plan_range")}

@@ -19,9 +19,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from fbank_truth import U  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from fbank_truth import make, refused_specs, U  # noqa: E402
+from binding_support import imports_of  # noqa: E402
 
 KINDS = {C.c_void_p: "ptr", C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_int: "i32", None: "void"}
 # (sample_rate, n_fft, n_mels, low_freq, high_freq)
@@ -35,11 +35,6 @@ def capi():
     ge.build()
     from vorbispizza_amd import capi
     return capi
-
-
-def make(capi, **kw):
-    d = ft.spec_of(**kw)
-    return capi.FbankSpec.make(**d), d
 
 
 # ---- the tables
@@ -126,30 +121,6 @@ def test_sizing_calls_and_capacities(capi):
     w = np.full(total.value + 1, 7.0, dtype=np.float32)
     assert L.vpz_fbank_filterbank(C.byref(spec), None, None, w.ctypes.data, total.value - 1, None) == capi.E_CAPACITY and (w == 7.0).all()
     assert L.vpz_fbank_filterbank(C.byref(spec), None, None, w.ctypes.data, total.value, None) == capi.OK and w[-1] == 7.0 and (w[:-1] > 0).all()
-
-
-def refused_specs(capi):
-    """(what, spec) for every limit of the definition"""
-    cases = [("n_fft odd", dict(n_fft=513)), ("n_fft < 32", dict(n_fft=30, win=20, hop=10)), ("n_fft > 1024", dict(n_fft=1026)), ("win < 2", dict(win=1, hop=1)),
-             ("win > n_fft", dict(win=513)), ("hop < 1", dict(hop=0)), ("hop > win", dict(hop=401)), ("n_mels < 1", dict(n_mels=0)),
-             ("n_mels > 256", dict(n_mels=257)), ("low_freq < 0", dict(low_freq=-1.0)), ("low_freq == high", dict(low_freq=8000.0)),
-             ("low_freq > high", dict(low_freq=5000.0, high_freq=4000.0)), ("high > nyquist", dict(high_freq=8000.5)),
-             ("high offset below low_freq", dict(high_freq=-7990.0)), ("high_freq nan", dict(high_freq=float("nan"))),
-             ("low_freq nan", dict(low_freq=float("nan"))), ("sample_rate 0", dict(sample_rate=0)), ("sample_rate inf", dict(sample_rate=float("inf"))),
-             ("preemphasis < 0", dict(preemphasis=-0.01)), ("preemphasis > 1", dict(preemphasis=1.01)), ("preemphasis nan", dict(preemphasis=float("nan"))),
-             ("scale 0", dict(scale=0.0)), ("scale inf", dict(scale=float("inf"))), ("scale nan", dict(scale=float("nan"))),
-             ("scale underflows float32", dict(scale=1e-60)), ("pad_value inf", dict(pad_value=float("-inf"))), ("pad_value nan", dict(pad_value=float("nan"))),
-             ("floor 0", dict(floor=0.0)), ("floor < 0", dict(floor=-1.0)), ("floor underflows float32", dict(floor=1e-60)), ("floor nan", dict(floor=float("nan")))]
-    out = [(what, make(capi, **kw)[0]) for what, kw in cases]
-    for field, value in (("window", 3), ("window", -1), ("remove_dc", 2), ("output", 2), ("layout", 2)):
-        s = make(capi)[0]
-        setattr(s, field, value)
-        out.append((field, s))
-    for i in (0, 9):
-        s = make(capi)[0]
-        s.reserved[i] = 1
-        out.append(("a reserved word", s))
-    return out
 
 
 def test_every_limit_is_refused(capi):

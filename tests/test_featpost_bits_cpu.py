@@ -22,17 +22,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import featpost_bits as fb  # noqa: E402
 import featpost_truth as pt  # noqa: E402
-from test_pcm_mfcc_gpu import fma32 as fma32_rational  # noqa: E402
-
-# (name, n, D, seed, far, the sliding spec): the spiked cases, mean only
-SPIKED = [
-    ("near W 100", 330, 4, 7, False, dict(norm="sliding", cmn_window=100, min_window=30)),
-    ("near W 200 centred", 330, 4, 7, False, dict(norm="sliding", cmn_window=200, min_window=1, center=True)),
-    ("near W 4", 330, 4, 7, False, dict(norm="sliding", cmn_window=4, min_window=2)),
-    ("far W 300 centred", 700, 3, 7, True, dict(norm="sliding", cmn_window=300, min_window=1, center=True)),
-    ("far W 600", 700, 3, 7, True, dict(norm="sliding", cmn_window=600, min_window=100)),
-]
-ROW_SPIKED = [("near row", 330, 4, 7, False, dict(norm="row")), ("far row", 700, 3, 7, True, dict(norm="row"))]
+from f32_model import fma32_rational  # noqa: E402
+from featpost_bits import ROW_SPIKED, SPIKED  # noqa: E402
 
 
 def feats(n, D, seed, offset=0.0):

@@ -19,8 +19,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import featpost_truth as pt  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from binding_support import imports_of  # noqa: E402
+from featpost_truth import NS, make, refused_specs  # noqa: E402
 
 KINDS = {C.c_void_p: "ptr", C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_int: "i32", None: "void"}
 
@@ -31,11 +32,6 @@ def capi():
     ge.build()
     from vorbispizza_amd import capi
     return capi
-
-
-def make(capi, **kw):
-    d = pt.spec_of(**kw)
-    return capi.FeatPostSpec.make(**d), d
 
 
 # ---- the delta scales
@@ -83,10 +79,6 @@ def test_scales_capacities_and_orders(capi):
     assert L.vpz_feat_delta_scales(C.byref(s), 1, None, -1) == capi.E_INVALID_ARG and L.vpz_feat_delta_scales(None, 0, None, 0) == capi.E_INVALID_ARG
 
 
-# ---- the window
-NS = (1, 2, 99, 100, 101, 600, 601, 602, 1300)
-
-
 @pytest.mark.parametrize("center", [False, True])
 @pytest.mark.parametrize("W", [1, 2, 300, 600])
 def test_the_window_of_every_frame(capi, W, center):
@@ -124,31 +116,6 @@ def test_the_window_of_a_row_and_its_refusals(capi):
     assert L.vpz_feat_cmn_window(C.byref(row), 0, 5, None, C.byref(b)) == capi.E_INVALID_ARG
     assert L.vpz_feat_cmn_window(C.byref(row), 0, 5, C.byref(a), None) == capi.E_INVALID_ARG
     assert L.vpz_feat_cmn_window(None, 0, 5, C.byref(a), C.byref(b)) == capi.E_INVALID_ARG and (a.value, b.value) == (5, 5)
-
-
-# ---- limits, refusals, the scratch size
-def refused_specs(capi):
-    """(what, spec) for every limit of the definition"""
-    out = []
-    base = dict(norm="sliding", delta_order=2)
-    for what, kw in (("cmn_window < 1", dict(cmn_window=0, min_window=0)), ("cmn_window > 2^20", dict(cmn_window=(1 << 20) + 1)),
-                     ("min_window < 1", dict(min_window=0)), ("min_window > cmn_window", dict(cmn_window=50, min_window=51)),
-                     ("delta_order < 0", dict(delta_order=-1)), ("delta_order > 3", dict(delta_order=4)),
-                     ("delta_window < 1", dict(delta_window=0)), ("delta_window > 8", dict(delta_window=9)),
-                     ("var_floor 0", dict(var_floor=0.0)), ("var_floor < 0", dict(var_floor=-1e-10)), ("var_floor nan", dict(var_floor=float("nan"))),
-                     ("var_floor inf", dict(var_floor=float("inf"))), ("pad_value nan", dict(pad_value=float("nan"))),
-                     ("pad_value inf", dict(pad_value=float("-inf"))), ("a spec that does nothing", dict(norm="none", delta_order=0))):
-        out.append((what, make(capi, **dict(base, **kw))[0]))
-    for field, values in (("norm", (-1, 3)), ("norm_vars", (-1, 2)), ("center", (-1, 2)), ("order", (-1, 2)), ("layout", (-1, 2))):
-        for value in values:
-            s = make(capi, **base)[0]
-            setattr(s, field, value)
-            out.append((field, s))
-    for i in (0, 10):
-        s = make(capi, **base)[0]
-        s.reserved[i] = 1
-        out.append(("a reserved word", s))
-    return out
 
 
 def accepted_specs(capi):

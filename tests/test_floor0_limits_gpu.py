@@ -15,25 +15,16 @@ import numpy as np
 import pytest
 
 import floor0_cases as fc
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def decode(ctx, b, fused, capfd):
     """The case's calls on one decoder; fused False: VPZ_NO_F0_FUSED=1, planar temp + floor0_apply_kernel.  Returns the PCM and
     the routes the calls took, as VPZ_HOST_PROFILE=1 names them."""
     import re
-    from test_host_paths_gpu import env
+    from synth_support import env
     from vorbispizza_amd import Decoder, capi, make_packets
     c = b.case
     C_ = c["channels"]

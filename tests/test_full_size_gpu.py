@@ -123,7 +123,7 @@ def line(env):
 
 def _profiled(capfd, fn, **kv):
     """fn() with VPZ_HOST_PROFILE=1 (and kv) in the environment; the route its synth call printed (helpers.host_profile)"""
-    from test_host_paths_gpu import env as setenv
+    from synth_support import env as setenv
     capfd.readouterr()
     with setenv(VPZ_HOST_PROFILE=1, **kv):
         fn()
@@ -179,7 +179,7 @@ def test_north_star_line_full_size(env, line, oracle, capfd):
     the batch split into calls, the interleaved layouts."""
     ctx, torch = env
     import spec_synthesis as spec
-    from test_host_paths_gpu import env as setenv
+    from synth_support import env as setenv
     from vorbispizza_amd import Decoder, capi
     frames, S, cap = len(line.pk), line.samples, line.cap
     assert frames == 65536 and S == (frames - 1) * 1024
@@ -293,7 +293,7 @@ def test_a_decoder_held_to_one_host_thread_cuts_on_the_calling_thread(env, line,
     the parallel state machine takes: runs of 4 frames cut by length, enough of them for the pool's fill) -- and their PCM is the
     16-thread decoder's, bit for bit."""
     ctx, torch = env
-    from test_host_paths_gpu import env as setenv
+    from synth_support import env as setenv
     from vorbispizza_amd import Decoder
     frames, S, cap = len(line.pk), line.samples, line.cap
     with setenv(VPZ_HOST_THREADS=16):

@@ -13,127 +13,10 @@ import pytest
 
 import helpers
 from helpers import PKT_BLOCK_FLAG, PKT_EOS, PKT_INTERLEAVED, PKT_NEXT_FLAG, PKT_NO_FLOOR, PKT_NOT_DECODED, PKT_PREV_FLAG
+from synth_support import env, random_xlist, run, stream_major_batch  # noqa: E402
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-class env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        for k, v in self.kv.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def random_xlist(rng, half, count):
-    return [0, half] + [int(v) for v in rng.choice(np.arange(1, half), size=count - 2, replace=False)]
-
-
-def stream_major_batch(n_streams, frames, channels, seed, floor=False, interleaved=False, size0=256, size1=2048, xlists=None,
-                       p_ls=0.1, p_sl=0.3, silent_prob=0.1, channel_floors=None, skew=0):
-    """channel_floors: ([(x list, multiplier)] * channels of a short block, the same of a long block) -- every channel's posts are
-    drawn for ITS floor (tests/channel_cases.py); skew: the first packet's residue_offset (that many floats of 777.0 lie in front of
-    it in the residue array: every packet stays inside the buffer, off a multiple of four floats)."""
-    from vorbispizza_amd import make_packets
-    rng = np.random.default_rng(seed)
-    pk = make_packets(n_streams * frames)
-    res, posts, counts = ([np.full(skew, 777.0, dtype=np.float32)] if skew else []), [], []
-    off, i = skew, 0
-    for s in range(n_streams):
-        flags = helpers.markov_block_flags(frames, seed=seed * 1000 + s, p_ls=p_ls, p_sl=p_sl, start_long=bool(s & 1))
-        for f in range(frames):
-            half = (size1 if flags[f] & 1 else size0) // 2
-            r = (rng.standard_normal((channels, half)) * (4.0 if floor else 2.0 ** -8)).astype(np.float32)
-            if floor:
-                r = np.round(r)
-            pk[i]["stream"] = s
-            pk[i]["flags"] = flags[f] | (0 if floor else PKT_NO_FLOOR) | (PKT_INTERLEAVED if interleaved else 0)
-            pk[i]["granule"] = -1
-            pk[i]["residue_offset"] = off
-            res.append(r.T.reshape(-1) if interleaved else r.reshape(-1))
-            off += channels * half
-            if floor and channel_floors is not None:
-                for xl, mult in channel_floors[flags[f] & 1]:
-                    p, c = helpers.random_posts(rng, xl, mult, 1, silent_prob=silent_prob)
-                    posts.append(p)
-                    counts.append(c)
-            elif floor:
-                xl = (xlists[1] if flags[f] & 1 else xlists[0]) if xlists else \
-                    (helpers.LONG_XLIST if flags[f] & 1 else helpers.SHORT_XLIST)
-                p, c = helpers.random_posts(rng, xl, 2, channels, silent_prob=silent_prob)
-                posts.append(p)
-                counts.append(c)
-            i += 1
-    res = np.concatenate(res)
-    if floor:
-        return pk, res, np.concatenate(posts), np.concatenate(counts)
-    return pk, res, None, None
-
-
-def run(ctx, pk, res, posts, counts, n_streams, channels, floors=(), mappings=(), layout=None, splits=1, size0=256,
-        size1=2048, fill=0, device_shift=None):
-    """fill: what the PCM array holds before the first call (a sentinel shows what the calls wrote); device_shift: the calls are
-    device-memory ones (VPZ_MEM_DEVICE), the residue a torch tensor that starts that many floats behind its allocation's base."""
-    from vorbispizza_amd import Decoder, capi
-    layout = capi.OUT_PLANAR if layout is None else layout
-    dec = Decoder(ctx, channels, size0, size1, floors=floors, mappings=mappings, n_streams=n_streams)
-    per_stream = len(pk) // n_streams
-    cap = per_stream * 1024 + 64
-    s16 = layout in (capi.OUT_INTERLEAVED_S16, capi.OUT_PLANAR_S16)
-    out = np.full(n_streams * channels * cap, fill, dtype=np.int16 if s16 else np.float32)
-    offs = np.arange(n_streams, dtype=np.int64) * channels * cap
-    if device_shift is not None:
-        import torch
-        dev = torch.device("cuda", 0)
-        d_res = torch.cat([torch.zeros(device_shift, dtype=torch.float32), torch.from_numpy(res)]).to(dev)[device_shift:]
-        d_out = torch.from_numpy(out).to(dev)
-    total = np.zeros(n_streams, dtype=np.int64)
-    samples = []
-    # `splits` calls, each over a slice of every stream's packets (stream-major inside the call)
-    idx = np.arange(len(pk)).reshape(n_streams, per_stream)
-    cuts = np.linspace(0, per_stream, splits + 1).astype(int)
-    for a, b in zip(cuts[:-1], cuts[1:]):
-        sel = idx[:, a:b].reshape(-1)
-        sub = pk[sel].copy()
-        sub_posts = None if posts is None else np.ascontiguousarray(posts.reshape(len(pk), channels, 64)[sel].reshape(-1, 64))
-        sub_counts = None if counts is None else np.ascontiguousarray(counts.reshape(len(pk), channels)[sel].reshape(-1))
-        step_offs = offs + total * (channels if layout in (capi.OUT_INTERLEAVED, capi.OUT_INTERLEAVED_S16) else 1)
-        if device_shift is not None:
-            w = dec.synth_raw(sub, d_res, None if posts is None else torch.from_numpy(sub_posts).to(dev),
-                              None if counts is None else torch.from_numpy(sub_counts).to(dev), d_out, step_offs,
-                              cap - int(total.max()), layout, cap, capi.MEM_DEVICE, residue_floats=res.size)
-            ctx.synchronize()
-        else:
-            w = dec.synth_raw(sub, res, sub_posts, sub_counts, out, step_offs, cap - int(total.max()), layout, cap, capi.MEM_HOST)
-        samples.append(dec.last_packet_samples(len(sub)))
-        total += w
-    pos = [dec.position(s) for s in range(n_streams)]
-    dec.close()
-    if device_shift is not None:
-        out = d_out.cpu().numpy()
-    return out.copy(), total.copy(), np.concatenate(samples), pos
 
 
 @pytest.mark.parametrize("channels,n_streams,frames", [(2, 1, 700), (2, 37, 40), (1, 5, 333), (3, 16, 64)])

@@ -9,63 +9,12 @@ import struct
 
 import numpy as np
 import pytest
+from synth_support import damage_audio  # noqa: E402
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def _pages(raw):
-    """(start, header length, body length, packets completed) of every page"""
-    out, pos = [], 0
-    while pos + 27 <= len(raw) and raw[pos:pos + 4] == b"OggS":
-        nseg = raw[pos + 26]
-        lac = raw[pos + 27: pos + 27 + nseg]
-        out.append((pos, 27 + nseg, sum(lac), sum(1 for v in lac if v < 255)))
-        pos += 27 + nseg + sum(lac)
-    return out
-
-
-def damage_audio(raw, seed, hits):
-    import vorbis_writer as vw
-    rng = np.random.default_rng(seed)
-    pages, done, first_audio = _pages(raw), 0, None
-    for i, (_, _, _, completed) in enumerate(pages):
-        if done >= 3:
-            first_audio = i
-            break
-        done += completed
-    assert first_audio is not None
-    data = bytearray(raw)
-    touched = set()
-    for _ in range(hits):
-        i = int(rng.integers(first_audio, len(pages)))
-        start, hdr, body, _ = pages[i]
-        if body == 0:
-            continue
-        at = start + hdr + int(rng.integers(0, body))
-        kind = int(rng.integers(0, 3))
-        if kind == 0:
-            data[at] ^= 1 << int(rng.integers(0, 8))
-        elif kind == 1:
-            data[at] = int(rng.integers(0, 256))
-        else:
-            n = min(int(rng.integers(1, 24)), start + hdr + body - at)
-            data[at:at + n] = bytes(rng.integers(0, 256, n, dtype=np.uint8))
-        touched.add(i)
-    for i in touched:
-        start, hdr, body, _ = pages[i]
-        page = bytes(data[start:start + 22]) + b"\0\0\0\0" + bytes(data[start + 26:start + hdr + body])
-        data[start + 22:start + 26] = struct.pack("<I", vw._crc(page))
-    return bytes(data)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def hostile_library():
@@ -89,7 +38,7 @@ def hostile_library():
 
 
 def test_damaged_audio_pages_decode_the_same_way_however_the_job_is_cut(ctx):
-    from test_multi_gpu import run_dispatcher, single_stream_pcm
+    from multi_support import run_dispatcher, single_stream_pcm
     raws = hostile_library()
     runs = [run_dispatcher([0], raws, host_threads=3, streams_per_call=5, capacity_slack=int(os.environ.get("VPZ_HOSTILE_SLACK", "2048"))),
             run_dispatcher([0, 0, 0], raws, host_threads=6, streams_per_call=2),
@@ -150,7 +99,7 @@ def test_the_reader_gives_damaged_streams_the_samples_of_the_batch_decode(ctx):
     """VorbisReader.ReadSamples over the same damaged containers, in packet batches and buffers of odd sizes: a Read whose
     packet fails the window check throws (StreamDecoder.cs:777-778) and the stream goes on -- the samples delivered are those
     of the one-call decode, whatever the batching"""
-    from test_multi_gpu import single_stream_pcm
+    from multi_support import single_stream_pcm
     from vorbispizza_amd import capi
     from vorbispizza_amd.front import VorbisReader
     raws = [r for i, r in enumerate(hostile_library()) if i % 3 != 0][:14 * int(os.environ.get("VPZ_HOSTILE_ROUNDS", "1"))]
@@ -168,7 +117,7 @@ def test_a_stream_that_outgrows_its_announced_length_costs_only_itself(ctx):
     stream produces more samples than PacketProvider.GetGranuleCount announced (:35-49).  With areas of exactly the announced
     sizes the synth call that holds it fails -- and every other member gets a call of its own: four neighbours of the same
     setup decode to their usual bits, the one that does not fit is VPZM_E_CAPACITY, nothing of it is written"""
-    from test_multi_gpu import run_dispatcher, single_stream_pcm
+    from multi_support import run_dispatcher, single_stream_pcm
     from vorbispizza_amd import multi
     clean = open(os.path.join(GOLDEN, "1test.ogg"), "rb").read()
     grown = damage_audio(clean, 501, 2)

@@ -15,16 +15,9 @@ import os
 
 import numpy as np
 import pytest
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def parsed(raw):
@@ -65,7 +58,7 @@ def test_damaged_setup_headers_end_in_a_status_or_in_the_oracles_pcm(ctx):
     import helpers
     import hostile_setups as hs
     import oracle
-    from test_multi_gpu import single_stream_pcm
+    from multi_support import single_stream_pcm
     from vorbispizza_amd import capi
     cases = hs.committed_cases()
     assert len(cases) >= 500
@@ -117,7 +110,7 @@ def test_the_dispatcher_gives_every_damaged_setup_its_own_outcome(ctx):
     """the same containers, many per vpzm_decode_library call, undamaged files between them, two partitions: a stream's
     outcome is its own (a setup the back end refuses is VPZM_E_SETUP for its streams alone), PCM bit-equal to the plain ABI's"""
     import hostile_setups as hs
-    from test_multi_gpu import run_dispatcher, single_stream_pcm
+    from multi_support import run_dispatcher, single_stream_pcm
     from vorbispizza_amd import capi, multi
     cases = hs.committed_cases()
     src = hs.sources()
@@ -175,7 +168,7 @@ def test_setups_at_the_edges_of_what_the_headers_can_say(ctx):
     import helpers
     import hostile_setups as hs
     import oracle
-    from test_multi_gpu import run_dispatcher, single_stream_pcm
+    from multi_support import run_dispatcher, single_stream_pcm
     from vorbispizza_amd import multi
     from vorbispizza_amd.front import FrontError, OggVorbisFile
     made = hs.crafted()

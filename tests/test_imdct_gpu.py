@@ -3,20 +3,11 @@ the C ABI.  Tolerance for the FAST path is BASELINE.json's: <= 1e-5 max-abs per 
 |PCM| <~ 1 (sigma = 2^-8 spectra); the EXACT path must be bit-identical."""
 import numpy as np
 import pytest
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def spectra(count, half, seed):

@@ -26,7 +26,8 @@ import pytest
 import helpers
 import spec_synthesis
 from helpers import PKT_NO_FLOOR
-from test_host_paths_gpu import env, random_xlist
+from synth_support import env, random_xlist
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -40,16 +41,6 @@ BLOCKS_PER_GROUP = {256: 32, 512: 16, 1024: 8, 2048: 4, 4096: 4, 8192: 7}
 TAIL = {256: 43, 512: 23, 1024: 11, 2048: 5, 4096: 5, 8192: 10}
 EXACT_TAIL = 5
 SENTINEL = 0x7FA5C3E1  # a NaN with a payload: a guard row that was written, or an output element that was not, cannot pass for data
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def spectra(count, half, seed):

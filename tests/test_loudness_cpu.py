@@ -18,8 +18,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import loudness_truth as lt  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from binding_support import imports_of  # noqa: E402
 
 KINDS = {C.c_void_p: "ptr", C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_int: "i32", None: "void"}
 
@@ -324,7 +324,7 @@ def test_the_float64_restatement_meets_the_bound_with_room_on_the_limit_cases():
     """before any device run: step_sums_chunked -- float64, the shape of the kernels -- lies within 0.01 of the bound of the longdouble
     truth on a multi-workgroup case and on the 255-channel case, so a device result outside the bound is the device's doing"""
     import loudness_cases as lc
-    from test_pcm_loudness_gpu import LONGDOUBLE_BITS
+    from loudness_support import LONGDOUBLE_BITS
     assert LONGDOUBLE_BITS >= 63, "numpy.longdouble has %d mantissa bits here: float64 would be compared against itself" % LONGDOUBLE_BITS
     some = [lc.cases()[n] for n in ("edges_8", "channels_255_weights")]
     truth = lc.truth_of(some)

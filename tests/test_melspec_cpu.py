@@ -17,9 +17,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import melspec_truth as mt  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_logmel_cpu import KINDS, U, check_log, check_power, dft64, frames_of, mel_weights64, refused_specs  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from f32_model import U  # noqa: E402
+from logmel_truth import KINDS, check_log, check_power, dft64, frames_of, mel_weights64, refused_specs  # noqa: E402
+from binding_support import imports_of  # noqa: E402
 
 # (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
 BANKS = [(22050, 2048, 128, 0.0, 11025.0, "slaney", "slaney"), (44100, 4096, 128, 20.0, 20000.0, "htk", None), (48000, 8192, 256, 0.0, 24000.0, "htk", "slaney"),
@@ -93,7 +94,7 @@ def test_sizing_calls_and_capacities(capi):
 
 
 def test_every_limit_is_refused(capi):
-    from test_pcm_melspec_gpu import melspec_refused_specs
+    from melspec_truth import melspec_refused_specs
     L = capi.lib()
     for n_fft in (0, -2048, 1024, 2046, 2047, 2049, 3000, 6144, 8190, 16384):
         assert L.vpz_melspec_twiddles(n_fft, None, 0) == capi.E_INVALID_ARG, n_fft

@@ -20,9 +20,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
 import mfcc_truth as mt  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
+import binding_support as cs  # noqa: E402
 from fbank_truth import U  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+from binding_support import imports_of  # noqa: E402
+from mfcc_truth import make, refused_specs  # noqa: E402
 
 KINDS = {C.c_void_p: "ptr", C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_int: "i32", None: "void"}
 
@@ -33,11 +34,6 @@ def capi():
     ge.build()
     from vorbispizza_amd import capi
     return capi
-
-
-def make(capi, **kw):
-    d = mt.spec_of(**kw)
-    return capi.MfccSpec.make(**d), d
 
 
 # ---- the table
@@ -82,34 +78,6 @@ def test_sizing_calls_and_capacities(capi):
     buf = np.full(n + 1, 7.0, dtype=np.float32)
     assert L.vpz_mfcc_table(C.byref(spec), buf.ctypes.data, n - 1) == capi.E_CAPACITY and (buf == 7.0).all()
     assert L.vpz_mfcc_table(C.byref(spec), buf.ctypes.data, n) == capi.OK and buf[-1] == 7.0 and (buf[:-1] != 7.0).all()
-
-
-def refused_specs(capi):
-    """(what, spec) for every limit of the definition: the mel stage's (tests/test_fbank_cpu.py's list, inside an MfccSpec) and its own"""
-    from test_fbank_cpu import refused_specs as fbank_refused
-    out = []
-    for what, fb in fbank_refused(capi):
-        s = make(capi)[0]
-        s.fbank = fb
-        out.append(("fbank: " + what, s))
-    power = make(capi)[0]
-    power.fbank.output = capi.FBANK_POWER
-    out.append(("output is not the log", power))
-    for what, kw in (("n_ceps < 1", dict(n_ceps=0)), ("n_ceps > n_mels", dict(n_ceps=24)), ("n_ceps > n_mels at one band", dict(n_mels=1, n_ceps=2)),
-                     ("lifter < 0", dict(lifter=-1.0)), ("lifter nan", dict(lifter=float("nan"))), ("lifter inf", dict(lifter=float("inf"))),
-                     ("energy_floor < 0", dict(energy_floor=-1e-9)), ("energy_floor nan", dict(energy_floor=float("nan"))),
-                     ("energy_floor inf", dict(energy_floor=float("inf")))):
-        out.append((what, make(capi, **kw)[0]))
-    for field in ("use_energy", "htk_compat", "subtract_mean"):
-        for value in (2, -1):
-            s = make(capi)[0]
-            setattr(s, field, value)
-            out.append((field, s))
-    for i in (0, 11):
-        s = make(capi)[0]
-        s.reserved[i] = 1
-        out.append(("a reserved word", s))
-    return out
 
 
 def test_every_limit_is_refused(capi):

@@ -11,7 +11,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import test_csharp_binding_cpu as cs  # noqa: E402  (its parsers)
+import binding_support as cs  # noqa: E402
+from binding_support import imports_of  # noqa: E402
 
 
 def test_the_new_headers_are_plain_c(tmp_path):
@@ -27,14 +28,6 @@ def test_the_new_headers_are_plain_c(tmp_path):
     assert subprocess.run([str(exe)]).returncode == 0
     from vorbispizza_amd import multi
     assert C.sizeof(multi.CallCounts) == 64
-
-
-def imports_of(tmp_path, name):
-    """cs.cs_imports of a binding file, the dispatcher's SafeHandle read as the pointer it marshals as"""
-    text = open(os.path.join(cs.CS, name)).read().replace("VorbisPizzaMulti.DispatcherHandle", "IntPtr")
-    path = tmp_path / name
-    path.write_text(text)
-    return cs.cs_imports(str(path))
 
 
 def test_the_group_binding_matches_its_header(tmp_path):

@@ -11,8 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from binding_support import imports_of, vpzm_statuses  # noqa: E402
 
 KINDS = {C.c_void_p: "ptr", C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_int: "i32", None: "void"}
 
@@ -58,16 +58,6 @@ def test_the_batch_binding_matches_its_header(tmp_path):
     assert callable(multi.Dispatcher.decode_ranges_batch) and callable(multi.Dispatcher.batch_partition)
     assert cs.c_structs("vorbispizza_multi_batch.h")[0] == {}  # (no struct of its own: the ranges', the results' and the stats' serve)
     assert len(cs.c_functions("vorbispizza_multi.h", "vpzm_")) == 5 and sorted(cs.c_functions("vorbispizza_multi_ranges.h", "vpzm_")) == ["vpzm_decode_ranges"]
-
-
-def vpzm_statuses():
-    """{name: value} of every VPZM_E_* of every header"""
-    out = {}
-    for header in sorted(os.listdir(cs.INC)):
-        text = cs.strip_c_comments(open(os.path.join(cs.INC, header)).read())
-        for name, value in re.findall(r"#define\s+(VPZM_E_\w+)\s+\(?(-?\d+)\)?", text):
-            assert out.setdefault(name, int(value)) == int(value), name
-    return out
 
 
 def test_the_channels_status_collides_with_no_other():

@@ -14,92 +14,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, golden, streams  # noqa: E402
+from multi_support import FIELDS, OPTIONS, Stream, golden, streams  # noqa: E402
+from multi_support import (as_bits, batch_call, check_failed_delivery, entries_of, most_samples, same_on_device,  # noqa: E402
+    sentinel_out, truth_on_device, truth_rows)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 LAYOUTS = {"planar": (True, False), "interleaved": (False, False), "planar_s16": (True, True), "interleaved_s16": (False, True)}
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def entries_of(channels):
-    """[(stream, start, count)]: every window of every stream of `channels` channels, the streams interleaved so that sub-batches mix them"""
-    per = [[(s, a, n) for a, n in s.windows()] for s in streams().values() if s.channels == channels]
-    assert per
-    out = []
-    for i in range(max(len(p) for p in per)):
-        out += [p[i] for p in per if i < len(p)]
-    return out
-
-
-def most_samples(entries):
-    return max(s.f.window(a, n)["samples"] for s, a, n in entries)
-
-
-def truth_rows(ctx, entries, frames, s16, delivered=None):
-    """numpy [n, channels, frames]: every entry's slice of its stream's whole decode, zeros behind it (delivered[k] samples; None: the
-    window rule's; an entry of None is a zero row)"""
-    C = next(s.channels for s, _, _ in entries if s is not None)
-    rows = np.zeros((len(entries), C, frames), dtype=np.int16 if s16 else np.float32)
-    for k, (s, a, n) in enumerate(entries):
-        if s is None:
-            continue
-        m = s.f.window(a, n)["samples"] if delivered is None else int(delivered[k])
-        rows[k, :, :m] = s.truth(ctx, s16)[a: a + m].T
-    return rows
-
-
-_truth = {}
-
-
-def truth_on_device(ctx, channels, s16):
-    """the planar truth of entries_of(channels) at frames = its largest window, on the device as integers (computed once, never changed)"""
-    import torch
-    if (channels, s16) not in _truth:
-        entries = entries_of(channels)
-        rows = truth_rows(ctx, entries, most_samples(entries), s16)
-        _truth[(channels, s16)] = torch.from_numpy(rows.view(np.int16 if s16 else np.int32)).to("cuda:0")
-    return _truth[(channels, s16)]
-
-
-def as_bits(t):
-    import torch
-    return t.view(torch.int16 if t.dtype == torch.int16 else torch.int32)
-
-
-def same_on_device(got, planar_truth, planar):
-    import torch
-    return torch.equal(as_bits(got), planar_truth if planar else planar_truth.permute(0, 2, 1))
-
-
-def batch_call(entries, channels, frames, planar=True, s16=False, device_ids=(0,), dispatcher=None, out=None, **opt):
-    """-> (the batch as one tensor, results, stats); groups on one device share one tensor"""
-    import torch
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        parts, whole, results, stats = d.decode_ranges_batch([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], channels, frames,
-                                                             planar=planar, s16=s16, out=out)
-    finally:
-        if dispatcher is None:
-            d.close()
-    assert len(parts) == d.n_devices and all(p.is_cuda for p in parts)
-    if whole is None:
-        whole = torch.cat(list(parts))
-    assert tuple(whole.shape) == ((len(entries), channels, frames) if planar else (len(entries), frames, channels))
-    assert whole.dtype == (torch.int16 if s16 else torch.float32)
-    return whole, results, stats
 
 
 @pytest.mark.parametrize("layout", list(LAYOUTS))
@@ -148,43 +70,6 @@ def test_a_bad_entry_costs_only_itself_and_leaves_a_zero_row(ctx, gpu_entropy):
         want = torch.from_numpy(truth_rows(ctx, clean, frames, s16).view(np.int16 if s16 else np.int32)).to("cuda:0")
         assert same_on_device(got, want, planar), (planar, s16)
         assert not as_bits(got)[[1, 3, 4, 5, 6, 7]].any()
-
-
-def sentinel_out(d, n, shape, dtype, value):
-    """one tensor per group of `d` for an n-entry call, filled with `value`: shape(rows) is a group's"""
-    import torch
-    cuts = [d.batch_partition(n, g) for g in range(d.n_devices)]
-    return [torch.full(shape(hi - lo), value, dtype=dtype, device="cuda:%d" % i) for (lo, hi), i in zip(cuts, d.device_ids)]
-
-
-def check_failed_delivery(monkeypatch, d, run, empty_row, step=None):
-    """VPZM_FAIL_DELIVERY (host/vorbis_multi.cpp): a sub-batch's delivery launch counts as failed without being made.  run() -> (tensor,
-    results) of one call on dispatcher `d` into sentinel-filled tensors.  Every entry that a delivery launch serves -- OK in the plain
-    call, with packets -- comes back E_SYNTH with no samples; an entry with a status of its own keeps it, and so does the empty window (OK,
-    no packets: it is in no sub-batch, GroupRun::zero_rows alone defines its row); every row is `empty_row`; the next call without the
-    switch is the plain call bit for bit.  step: the launch the switch fails -- the dispatcher's error text names it."""
-    import torch
-    from vorbispizza_amd import multi
-    monkeypatch.delenv("VPZM_FAIL_DELIVERY", raising=False)
-    plain, plain_results = run()
-    monkeypatch.setenv("VPZM_FAIL_DELIVERY", "1")
-    got, results = run()
-    monkeypatch.delenv("VPZM_FAIL_DELIVERY")
-    delivered = (plain_results["status"] == 0) & (plain_results["packets"] > 0)
-    assert delivered.sum() >= 3 and (plain_results["status"] != 0).sum() >= 4 and ((plain_results["status"] == 0) & ~delivered).sum() == 1
-    assert (results["status"][delivered] == multi.E_SYNTH).all(), results["status"]
-    assert np.array_equal(results["status"][~delivered], plain_results["status"][~delivered])
-    assert (results["samples"] == 0).all()
-    assert (as_bits(got) == empty_row).all()
-    assert not (as_bits(plain) == empty_row).all()
-    assert d.last_error() != ""
-    if step is not None:
-        assert step + ":" in d.last_error(), d.last_error()
-    again, again_results = run()
-    assert torch.equal(as_bits(again), as_bits(plain))
-    for field in FIELDS:
-        if field != "device_slot":
-            assert np.array_equal(again_results[field], plain_results[field]), field
 
 
 @pytest.mark.parametrize("gpu_entropy", [False, True])
@@ -269,8 +154,8 @@ def test_the_switches_change_no_byte(ctx, monkeypatch, switch, value):
 def test_a_damaged_stream_delivers_what_decode_ranges_delivers_then_zeros(ctx, gpu_entropy):
     """a damaged stream has no truth but the host-destination call: the row is its samples, then zeros"""
     import torch
-    from test_hostile_input_gpu import damage_audio
-    from test_multi_ranges_gpu import call
+    from synth_support import damage_audio
+    from multi_support import call
     damaged = [Stream(damage_audio(raw, seed, hits), False) for raw, (seed, hits) in
                ((golden("3test.ogg"), (1, 8)), (golden("2test.ogg"), (2, 16)), (streams()["stereo_coupled_res2_30"].raw, (3, 6)),
                 (streams()["six_channels_51_12"].raw, (4, 4)))]
@@ -296,7 +181,7 @@ def test_a_damaged_stream_delivers_what_decode_ranges_delivers_then_zeros(ctx, g
 
 def test_library_ranges_and_batch_on_one_dispatcher(ctx):
     """the three calls on one dispatcher, in that order and reversed, give what each gives alone"""
-    from test_multi_ranges_gpu import SENTINEL, call, expected, same_bits
+    from multi_support import SENTINEL, call, expected, same_bits
     from vorbispizza_amd import multi
     raws = [golden("3test.ogg"), golden("1test.ogg"), streams()["stereo_floor0_12"].raw, streams()["stereo_coupled_res2_30"].raw] * 2
     ss = {r: Stream(r, False) for r in set(raws)}

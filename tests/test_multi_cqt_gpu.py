@@ -16,11 +16,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_cqt_cpu import cqt_refused_specs  # noqa: E402
-from test_multi_logmel_gpu import mixed_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, streams  # noqa: E402
-from test_multi_resample_gpu import most_outputs, resampled_call  # noqa: E402
-from test_multi_stft_gpu import bits, channels_of, refused_entries  # noqa: E402
+from cqt_truth import cqt_refused_specs  # noqa: E402
+from multi_support import (bits_of_any as bits, channels_of, FIELDS, mixed_entries, most_outputs, OPTIONS,  # noqa: E402
+    refused_entries_by_channel as refused_entries, resampled_call, streams)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -33,16 +32,6 @@ VARIANTS = [dict(sample_rate=OWN, channels=2, mono=False, f_min=220.0, n_bins=30
             dict(sample_rate=22050, channels=1, mono=True, f_min=32.70319566257483, n_bins=84, bins_per_octave=12, hop=512, window="hamming", scale="none",
                  pad="zero", output="magnitude", bins_first=False)]
 IDS = ["stereo_44100_30_bins_complex_bins_first", "mono_22050_music_magnitude_frames_first"]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def shape_of(n, frames, spec):
@@ -164,9 +153,9 @@ def test_a_refused_entry_costs_only_itself_and_leaves_zero_rows_in_all_its_chann
 
 @pytest.mark.parametrize("gpu_entropy", [False, True])
 def test_a_failed_cqt_launch_costs_its_members_e_synth_and_leaves_zero_rows(ctx, monkeypatch, gpu_entropy):
-    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of test_multi_batch_gpu.py): the resample launches into
+    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of multi_support.py): the resample launches into
     the lane's temporary are made, the CQT launch is not"""
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
     try:

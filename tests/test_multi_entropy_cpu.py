@@ -80,7 +80,7 @@ def test_the_plan_counts_the_packets_it_gives_up():
     import numpy as np
     sys.path.insert(0, os.path.dirname(__file__))
     import synthetic_streams as ss
-    from test_hostile_input_gpu import damage_audio
+    from synth_support import damage_audio
     from vorbispizza_amd.front import OggVorbisFile
     stream, rng = ss.ALL["mono_floor1_res1"]()  # (three modes in a two-bit field: mode number 3 is unused)
     ogg, _ = stream.build(rng, 24)

@@ -47,7 +47,7 @@ def supported(raw):
 
 
 def run(raws, gpu_entropy, device_ids=(0,), **opt):
-    from test_multi_gpu import run_dispatcher
+    from multi_support import run_dispatcher
     opt.setdefault("host_threads", 4)
     return run_dispatcher(list(device_ids), raws, gpu_entropy=gpu_entropy, **opt)
 
@@ -139,7 +139,7 @@ def test_float_residue_on_the_device():
 
 
 def test_damaged_audio():
-    from test_hostile_input_gpu import damage_audio
+    from synth_support import damage_audio
     from vorbispizza_amd.front import OggVorbisFile
     clean = fixtures()
     mono = synthetic("mono_floor1_res1")  # (three modes in a two-bit field: damage can name the unused one)

@@ -17,53 +17,17 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, all_entries, streams  # noqa: E402
-from test_multi_resample_gpu import RATE, most_outputs, out_len, ratio, rerated, resampled_call  # noqa: E402
+from multi_support import (all_entries, FIELDS, most_outputs, OPTIONS, out_len, RATE, ratio, rerated, resampled_call, Stream,  # noqa: E402
+    streams)
+from multi_support import (FBANK_VARIANTS as VARIANTS, bits, fbank_call, mixed_entries, refused_entries, fbank_shape_of as  # noqa: E402
+    shape_of)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-# Kaldi's own defaults, and a second spec so that every window, both output modes, both layouts, remove_dc off, another scale and a
-# pad_value pass through the dispatcher
-VARIANTS = [ft.spec_of(sample_rate=RATE),
-            ft.spec_of(sample_rate=RATE, win=96, hop=17, n_fft=128, n_mels=13, low_freq=100.0, high_freq=-1000.0, preemphasis=0.5, window="hamming",
-                       remove_dc=False, scale=1.0, log=False, pad_value=-3.5, frames_first=False)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def shape_of(n, frames, spec):
-    T = ft.n_frames(frames, spec["win"], spec["hop"])
-    return (n, T, spec["n_mels"]) if spec["frames_first"] else (n, spec["n_mels"], T)
 
 
 def pad_bits(spec):
     return int(np.float32(spec["pad_value"]).view(np.int32))
-
-
-def fbank_call(entries, frames, spec, device_ids=(0,), dispatcher=None, out=None, **opt):
-    """-> (the features as one tensor, results, stats)"""
-    import torch
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        parts, whole, results, stats = d.decode_ranges_fbank([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], frames, out=out, **spec)
-    finally:
-        if dispatcher is None:
-            d.close()
-    if whole is None:
-        whole = torch.cat(list(parts))
-    assert tuple(whole.shape) == shape_of(len(entries), frames, spec) and whole.dtype == torch.float32
-    return whole, results, stats
 
 
 def by_hand(ctx, entries, frames, spec, truth=False, **opt):
@@ -83,22 +47,6 @@ def by_hand(ctx, entries, frames, spec, truth=False, **opt):
     W, B = ft.mel_weights64(spec), ft.operator64(spec)
     worst = max(ft.check_row(img[k], mono[k, : int(results["samples"][k])], spec, W, B) for k in range(len(entries)))
     return dst, results, worst
-
-
-def bits(t):
-    import torch
-    return t.view(torch.int32)
-
-
-def mixed_entries():
-    """every window of every stream -- 1, 2 and 6 channels; 44 100, 48 000, 8 000 and 16 000 Hz -- and the stereo setup at two more rates"""
-    entries = all_entries()
-    for rate in (48000, 22050):
-        s = rerated(rate)
-        for i, (a, n) in enumerate(s.windows()[:12]):
-            entries.insert(5 + 17 * i + (rate == 48000), (s, a, n))
-    assert {s.channels for s, _, _ in entries} == {1, 2, 6} and len({ratio(s, RATE) for s, _, _ in entries}) >= 5
-    return entries
 
 
 @pytest.mark.parametrize("variant", [0, 1], ids=["kaldi_log_frames_first", "hamming_power_bands_first"])
@@ -148,19 +96,6 @@ def test_the_partition_the_cut_and_the_failure_paths_change_no_bit(ctx, monkeypa
             assert np.array_equal(results[field], one_results[field]), (switch, field)
 
 
-def refused_entries():
-    """-> (entries, J): entry 2 has one output sample more than a row holds; entry 3 is no Ogg; entry 4 is 200 output samples, fewer than
-    the Kaldi window; entry 5 has a ratio the resampler refuses; entry 6 is an empty window"""
-    s, mono, odd = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"], rerated(44101)
-    garbage = Stream.__new__(Stream)
-    garbage.data = np.frombuffer(b"not an ogg file at all" * 10, dtype=np.uint8)
-    up, down = ratio(s, RATE)
-    a, n = s.bounds[3] + 7, 7 * down
-    J = out_len(n, up, down)
-    assert J >= 400 and out_len(n + 1, up, down) == J + 1
-    return [(s, a, n), (s, -1, n), (s, a, n + 1), (garbage, a, n), (mono, 5, 100), (odd, 3, 500), (s, s.total, 10), (s, a + 1, n)], J
-
-
 @pytest.mark.parametrize("gpu_entropy", [False, True])
 def test_a_refused_entry_costs_only_itself_and_leaves_the_pad_row(ctx, gpu_entropy):
     import torch
@@ -185,7 +120,7 @@ def test_a_failed_fbank_launch_costs_its_members_e_synth_and_leaves_pad_rows(ctx
     """the entries of test_a_refused_entry_costs_only_itself_and_leaves_the_pad_row under VPZM_FAIL_DELIVERY (check_failed_delivery of
     test_multi_batch_gpu.py): the resample launches into the lane's temporary are made, the fbank launch is not"""
     import torch
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     entries, J = refused_entries()
     d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
@@ -199,7 +134,7 @@ def test_a_failed_fbank_launch_costs_its_members_e_synth_and_leaves_pad_rows(ctx
 
 def test_a_wrong_out_tensor_raises_and_a_wrong_spec_is_refused(ctx):
     import torch
-    from test_fbank_cpu import refused_specs
+    from fbank_truth import refused_specs
     from vorbispizza_amd import capi, multi
     s = streams()["stereo_coupled_res2_12"]
     entries = [(s, a, n) for a, n in s.windows()[:6]]

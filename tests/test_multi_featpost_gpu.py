@@ -19,11 +19,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
 import featpost_truth as pt  # noqa: E402
-import test_multi_fbank_gpu as fb  # noqa: E402
-import test_multi_mfcc_gpu as mf  # noqa: E402
-from test_multi_fbank_gpu import bits, mixed_entries, refused_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, streams  # noqa: E402
-from test_multi_resample_gpu import RATE, most_outputs  # noqa: E402
+import multi_support as ms  # noqa: E402
+from multi_support import bits, FIELDS, mixed_entries, most_outputs, OPTIONS, RATE, refused_entries, streams  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -31,22 +29,12 @@ pytestmark = pytest.mark.gpu
 # deltas, over the HTK-order, columns-first MFCC spec with its own subtract_mean; deltas alone over 80 filterbank bands; a short
 # uncentred window with variance over the columns-first mel power
 CASES = [
-    ("mfcc", mf.VARIANTS[0], pt.spec_of(norm="sliding", cmn_window=30, min_window=10, center=True, delta_order=2, deltas_first=True, pad_value=-1.5)),
-    ("mfcc", mf.VARIANTS[1], pt.spec_of(norm="row", norm_vars=True, delta_order=1, delta_window=3, frames_first=False, pad_value=9.0)),
-    ("fbank", fb.VARIANTS[0], pt.spec_of(delta_order=3, delta_window=1)),
-    ("fbank", fb.VARIANTS[1], pt.spec_of(norm="sliding", cmn_window=20, min_window=5, norm_vars=True, frames_first=False, pad_value=2.0 ** -130)),
+    ("mfcc", ms.MFCC_VARIANTS[0], pt.spec_of(norm="sliding", cmn_window=30, min_window=10, center=True, delta_order=2, deltas_first=True, pad_value=-1.5)),
+    ("mfcc", ms.MFCC_VARIANTS[1], pt.spec_of(norm="row", norm_vars=True, delta_order=1, delta_window=3, frames_first=False, pad_value=9.0)),
+    ("fbank", ms.FBANK_VARIANTS[0], pt.spec_of(delta_order=3, delta_window=1)),
+    ("fbank", ms.FBANK_VARIANTS[1], pt.spec_of(norm="sliding", cmn_window=20, min_window=5, norm_vars=True, frames_first=False, pad_value=2.0 ** -130)),
 ]
 IDS = ["mfcc_deltas_sliding", "mfcc_cmvn_deltas_columns_first", "fbank_deltas", "fbank_sliding_vars_columns_first"]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def columns(kind, spec):
@@ -63,7 +51,7 @@ def pad_bits(post):
 
 
 def plain_call(kind, *a, **kw):
-    return (mf.mfcc_call if kind == "mfcc" else fb.fbank_call)(*a, **kw)
+    return (ms.mfcc_call if kind == "mfcc" else ms.fbank_call)(*a, **kw)
 
 
 def post_call(kind, entries, frames, spec, post, device_ids=(0,), dispatcher=None, out=None, **opt):
@@ -170,10 +158,10 @@ def test_a_refused_entry_costs_only_itself_and_leaves_the_pad_row(ctx, gpu_entro
 
 @pytest.mark.parametrize("gpu_entropy", [False, True])
 def test_a_failed_delivery_costs_its_members_e_synth_and_leaves_pad_rows(ctx, monkeypatch, gpu_entropy):
-    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of test_multi_batch_gpu.py): the resample launches
+    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of multi_support.py): the resample launches
     into the lane's temporary are made, the feature launch and the post launches behind it are not"""
     import torch
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     entries, J = refused_entries()
     d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
@@ -218,7 +206,7 @@ def test_without_a_post_spec_the_new_entry_points_are_the_old_ones(ctx):
 
 def test_a_wrong_out_tensor_raises_and_a_wrong_post_spec_is_refused(ctx):
     import torch
-    from test_featpost_cpu import refused_specs
+    from featpost_truth import refused_specs
     from vorbispizza_amd import capi, multi
     s = streams()["stereo_coupled_res2_12"]
     entries = [(s, a, n) for a, n in s.windows()[:6]]
@@ -289,7 +277,7 @@ def test_the_calls_in_turn_on_one_dispatcher(ctx):
         for _ in range(2):
             for (kind, spec, post), want in zip(CASES, wants):
                 assert torch.equal(bits(post_call(kind, entries, frames, spec, post, dispatcher=d)[0]), bits(want))
-                now = plain_call("mfcc", entries, frames, mf.VARIANTS[0], dispatcher=d)[0]
+                now = plain_call("mfcc", entries, frames, ms.MFCC_VARIANTS[0], dispatcher=d)[0]
                 assert plain is None or torch.equal(bits(now), bits(plain))
                 plain = now
     finally:

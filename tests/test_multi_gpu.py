@@ -6,60 +6,12 @@ import os
 
 import numpy as np
 import pytest
+from multi_support import library, run_dispatcher, single_stream_pcm  # noqa: E402
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def single_stream_pcm(ctx, raw, s16=False):
-    """interleaved PCM of one container through the plain ABI: front end + one decoder + one synth call"""
-    from vorbispizza_amd import Decoder, capi
-    from vorbispizza_amd.front import OggVorbisFile
-    f = OggVorbisFile(raw)
-    pk, res, posts, counts = f.decode_packets()
-    dec = Decoder(ctx, f.channels, f.block_size0, f.block_size1, floors=f.floors, mappings=f.mappings)
-    if f.floor0_data is not None:
-        dec.set_floor0_data(*f.floor0_data)
-    out = dec.synth(pk, res, posts, counts, out_layout=capi.OUT_INTERLEAVED_S16 if s16 else capi.OUT_INTERLEAVED,
-                    on_mismatch="ignore")[0]
-    dec.close()
-    return out
-
-
-def library(kinds, n):
-    raws = [open(os.path.join(GOLDEN, k), "rb").read() for k in kinds]
-    return [raws[i % len(raws)] for i in range(n)]
-
-
-def run_dispatcher(device_ids, raws, s16=False, capacity_slack=2048, **opt):
-    from vorbispizza_amd import multi
-    from vorbispizza_amd.front import OggVorbisFile
-    infos = {}
-    for r in set(raws):
-        f = OggVorbisFile(r)
-        infos[r] = (f.channels, int(f.total_samples))
-    caps = np.array([infos[r][1] + capacity_slack for r in raws], dtype=np.int64)
-    sizes = np.array([c * infos[r][0] for c, r in zip(caps, raws)], dtype=np.int64)
-    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
-    pcm = np.full(int(sizes.sum()), 7, dtype=np.int16) if s16 else np.full(int(sizes.sum()), np.float32(7.0), dtype=np.float32)
-    datas = [np.frombuffer(r, dtype=np.uint8) for r in raws]
-    d = multi.Dispatcher(device_ids, **opt)
-    try:
-        results, stats = d.decode_library(datas, pcm, offs, caps, s16=s16)
-    finally:
-        d.close()
-    return pcm, offs, results, stats, infos
 
 
 @pytest.mark.parametrize("groups", [1, 2, 4, 8])

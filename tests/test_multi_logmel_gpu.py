@@ -15,78 +15,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_logmel_cpu import U, dft64, frames_of, mel_weights64, silence_value  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, all_entries, golden, streams  # noqa: E402
-from test_multi_resample_gpu import RATE, most_outputs, out_len, ratio, rerated, resampled_call  # noqa: E402
-from test_resample_cpu import bound, resample_truth  # noqa: E402
+from f32_model import U  # noqa: E402
+from logmel_truth import dft64, frames_of, mel_weights64, silence_value  # noqa: E402
+from multi_support import (all_entries, FIELDS, golden, most_outputs, OPTIONS, out_len, RATE, ratio, rerated, resampled_call,  # noqa: E402
+    Stream, streams)
+from resample_truth import bound, resample_truth  # noqa: E402
+from multi_support import (LOGMEL_VARIANTS as VARIANTS, WHISPER, bits, logmel_by_hand as by_hand, logmel_call,  # noqa: E402
+    mixed_entries, logmel_shape_of as shape_of)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-WHISPER = dict(sample_rate=RATE, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None, mel_scale="slaney", mel_norm="slaney", floor=1e-10)
-# (log, bands_first) and a second spec, so that both output modes, both layouts and both scales pass through the dispatcher
-VARIANTS = [dict(WHISPER, log=True, bands_first=True),
-            dict(sample_rate=RATE, n_fft=96, hop=17, n_mels=13, f_min=100.0, f_max=7000.0, mel_scale="htk", mel_norm=None, floor=1e-6, log=False, bands_first=False)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def shape_of(n, frames, spec):
-    T = 1 + frames // spec["hop"]
-    return (n, spec["n_mels"], T) if spec["bands_first"] else (n, T, spec["n_mels"])
-
-
-def logmel_call(entries, frames, spec, device_ids=(0,), dispatcher=None, out=None, **opt):
-    """-> (the features as one tensor, results, stats)"""
-    import torch
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        parts, whole, results, stats = d.decode_ranges_logmel([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], frames, out=out, **spec)
-    finally:
-        if dispatcher is None:
-            d.close()
-    if whole is None:
-        whole = torch.cat(list(parts))
-    assert tuple(whole.shape) == shape_of(len(entries), frames, spec) and whole.dtype == torch.float32
-    return whole, results, stats
-
-
-def by_hand(ctx, entries, frames, spec, **opt):
-    """capi.pcm_logmel over the mono resampled batch of the same entries, results["samples"] as L: what the call must equal"""
-    import torch
-    from vorbispizza_amd import capi
-    batch, results, _ = resampled_call(entries, spec["sample_rate"], 1, frames, True, False, True, **opt)
-    dst = torch.full(shape_of(len(entries), frames, spec), 7.0, dtype=torch.float32, device="cuda:0")
-    rows = [(k * frames, int(results["samples"][k]), k) for k in range(len(entries))]
-    assert capi.pcm_logmel(ctx, batch.reshape(-1), rows, dst, capi.LogMelSpec.make(**spec), frames) == capi.OK, ctx.last_error()
-    ctx.synchronize()
-    return dst, results
-
-
-def bits(t):
-    import torch
-    return t.view(torch.int32)
-
-
-def mixed_entries():
-    """every window of every stream -- 1, 2 and 6 channels; 44 100, 48 000, 8 000 and 16 000 Hz -- and the stereo setup at two more rates"""
-    entries = all_entries()
-    for rate in (48000, 22050):
-        s = rerated(rate)
-        for i, (a, n) in enumerate(s.windows()[:12]):
-            entries.insert(5 + 17 * i + (rate == 48000), (s, a, n))
-    assert {s.channels for s, _, _ in entries} == {1, 2, 6} and len({ratio(s, RATE) for s, _, _ in entries}) >= 5
-    return entries
 
 
 @pytest.mark.parametrize("variant", [0, 1], ids=["whisper_log_bands_first", "htk_power_frames_first"])
@@ -159,7 +97,7 @@ def test_a_failed_logmel_launch_costs_its_members_e_synth_and_leaves_silence_row
     """the entries of test_a_refused_entry_costs_only_itself_and_leaves_the_silence_row under VPZM_FAIL_DELIVERY (check_failed_delivery
     of test_multi_batch_gpu.py): the resample launches into the lane's temporary are made, the log-mel launch is not"""
     import torch
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     s, mono, odd = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"], rerated(44101)
     garbage = Stream.__new__(Stream)
@@ -211,7 +149,7 @@ def test_a_wrong_out_tensor_raises_and_a_wrong_spec_is_refused(ctx):
                                                        ("spec", C.byref(ok)), ("frames", frames), ("dst", dst), ("results", res.ctypes.data), ("stats", None))]
         L = multi.lib()
         assert L.vpzm_decode_ranges_logmel(*args()) == multi.OK
-        from test_logmel_cpu import refused_specs
+        from logmel_truth import refused_specs
         changes = [dict(spec=None), dict(frames=0), dict(frames=200), dict(dst=None), dict(m=None), dict(results=None), dict(ranges=None), dict(n=-1)]
         changes += [dict(spec=C.byref(sp)) for _, sp in refused_specs(capi)]
         changes.append(dict(spec=C.byref(capi.LogMelSpec.make(**dict(spec, sample_rate=16000.5)))))  # (no whole number of Hz)

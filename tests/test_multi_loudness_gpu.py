@@ -17,41 +17,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import loudness_truth as lt  # noqa: E402
-from test_multi_batch_gpu import batch_call, most_samples  # noqa: E402
-from test_multi_fbank_gpu import mixed_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, streams  # noqa: E402
-from test_multi_resample_gpu import rerated  # noqa: E402
+from multi_support import (batch_call, FIELDS, loudness_entries, loudness_refused_entries as refused_entries, measure_call,  # noqa: E402
+    mixed_entries, most_samples, OPTIONS, rerated, Stream, streams)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 EMPTY = (-np.inf, 0.0, 0, 0)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def measure_call(entries, device_ids=(0,), dispatcher=None, ranges=True, **opt):
-    """-> (records [n] as a LOUDNESS_DTYPE array, results, stats)"""
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        results, integrated, peak, steps, kept, stats = d.measure_loudness([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries] if ranges else None)
-    finally:
-        if dispatcher is None:
-            d.close()
-    rec = np.zeros(len(entries), dtype=multi.LOUDNESS_DTYPE)
-    rec["integrated"], rec["peak"], rec["steps"], rec["blocks_kept"] = integrated, peak, steps, kept
-    assert integrated.dtype == peak.dtype == np.float64 and steps.dtype == kept.dtype == np.int64
-    return rec, results, stats
 
 
 def by_hand(ctx, entries, **opt):
@@ -84,22 +56,6 @@ def by_hand(ctx, entries, **opt):
 
 def same_records(a, b):
     return a.tobytes() == b.tobytes()
-
-
-_entries = []
-
-
-def loudness_entries():
-    """the fbank tests' entries -- every window of every stream, three more rates of the stereo setup among them -- and windows of the
-    stereo setup at 8 000 Hz with thirty packets, whole and in parts"""
-    if not _entries:
-        entries = mixed_entries()
-        s = rerated(8000, 30)
-        assert s.total >= 6 * 800
-        for i, (a, n) in enumerate([(0, -1), (0, s.total), (s.bounds[2], 5 * 800 + 3), (s.bounds[1] + 1, 4 * 800), (s.bounds[3], 4 * 800 - 1)]):
-            entries.insert(3 + 11 * i, (s, a, n))
-        _entries.extend(entries)
-    return list(_entries)
 
 
 @pytest.mark.parametrize("route", list(OPTIONS))
@@ -154,16 +110,6 @@ def test_no_ranges_are_whole_streams(ctx):
             assert np.array_equal(res_a[field], res_b[field]), field
         assert list(res_b["samples"]) == [s.total for s, _, _ in whole] and (res_b["status"] == 0).all()
         assert np.isfinite(without["integrated"][5])
-
-
-def refused_entries():
-    """entry 1 lies outside its stream; entry 2 is no Ogg; entries 3 and 4 have rates just outside the limits; entry 5 is an empty window;
-    entry 6 is shorter than a step"""
-    s, mono = rerated(8000, 30), streams()["mono_floor1_res1_12"]
-    garbage = Stream.__new__(Stream)
-    garbage.data = np.frombuffer(b"not an ogg file at all" * 10, dtype=np.uint8)
-    a, n = s.bounds[2] + 7, 5 * 800 + 1
-    return [(s, a, n), (s, -1, n), (garbage, a, n), (rerated(7999), 0, -1), (rerated(384001), 3, 500), (s, s.total, 10), (mono, 5, 100), (s, a + 1, n)]
 
 
 @pytest.mark.parametrize("gpu_entropy", [False, True])
@@ -241,10 +187,10 @@ def test_the_calls_in_turn_on_one_dispatcher(ctx):
     """the lane's temporary and the context's scratch serve call after call, between calls of the other five kinds of the ranges family,
     whose results the loudness call does not disturb"""
     import torch
-    from test_multi_fbank_gpu import VARIANTS, bits, fbank_call
-    from test_multi_ranges_gpu import call as ranges_call
-    from test_multi_ranges_gpu import same_bits
-    from test_multi_resample_gpu import RATE, most_outputs, resampled_call
+    from multi_support import FBANK_VARIANTS as VARIANTS, bits, fbank_call
+    from multi_support import call as ranges_call
+    from multi_support import same_bits
+    from multi_support import RATE, most_outputs, resampled_call
     from vorbispizza_amd import multi
     entries = loudness_entries()[::3]
     stereo = [e for e in entries if e[0].channels == 2]

@@ -18,64 +18,16 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import melspec_truth as mt  # noqa: E402
-from test_logmel_cpu import U, frames_of, mel_weights64, silence_value  # noqa: E402
-from test_multi_logmel_gpu import VARIANTS as LOGMEL_VARIANTS, bits, by_hand as logmel_by_hand, logmel_call, mixed_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, golden, streams  # noqa: E402
-from test_multi_resample_gpu import RATE, most_outputs, out_len, ratio, rerated, resampled_call  # noqa: E402
-from test_resample_cpu import bound, resample_truth  # noqa: E402
+from f32_model import U  # noqa: E402
+from logmel_truth import frames_of, mel_weights64, silence_value  # noqa: E402
+from multi_support import (bits, FIELDS, golden, logmel_by_hand, logmel_call, LOGMEL_VARIANTS, mixed_entries, most_outputs,  # noqa: E402
+    OPTIONS, out_len, RATE, ratio, rerated, resampled_call, Stream, streams)
+from resample_truth import bound, resample_truth  # noqa: E402
+from multi_support import (LIBROSA, MELSPEC_VARIANTS as VARIANTS, melspec_by_hand as by_hand, melspec_call, melspec_shape_of  # noqa: E402
+    as shape_of)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-OWN = 44100  # the rate of the stereo and six-channel fixture streams
-LIBROSA = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=None, mel_scale="slaney", mel_norm="slaney", floor=1e-10)
-# (log, bands_first), a second transform size and the other scale, so that both output modes and both layouts pass through the dispatcher
-VARIANTS = [dict(LIBROSA, log=True, bands_first=True),
-            dict(sample_rate=OWN, n_fft=4096, hop=441, n_mels=40, f_min=30.0, f_max=16000.0, mel_scale="htk", mel_norm=None, floor=1e-6, log=False, bands_first=False)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def shape_of(n, frames, spec):
-    T = 1 + frames // spec["hop"]
-    return (n, spec["n_mels"], T) if spec["bands_first"] else (n, T, spec["n_mels"])
-
-
-def melspec_call(entries, frames, spec, device_ids=(0,), dispatcher=None, out=None, **opt):
-    """-> (the features as one tensor, results, stats)"""
-    import torch
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        parts, whole, results, stats = d.decode_ranges_melspec([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], frames, out=out, **spec)
-    finally:
-        if dispatcher is None:
-            d.close()
-    if whole is None:
-        whole = torch.cat(list(parts))
-    assert tuple(whole.shape) == shape_of(len(entries), frames, spec) and whole.dtype == torch.float32
-    return whole, results, stats
-
-
-def by_hand(ctx, entries, frames, spec, **opt):
-    """capi.pcm_melspec over the mono resampled batch of the same entries, results["samples"] as L: what the call must equal"""
-    import torch
-    from vorbispizza_amd import capi
-    batch, results, _ = resampled_call(entries, spec["sample_rate"], 1, frames, True, False, True, **opt)
-    dst = torch.full(shape_of(len(entries), frames, spec), 7.0, dtype=torch.float32, device="cuda:0")
-    rows = [(k * frames, int(results["samples"][k]), k) for k in range(len(entries))]
-    assert capi.pcm_melspec(ctx, batch.reshape(-1), rows, dst, capi.LogMelSpec.make(**spec), frames) == capi.OK, ctx.last_error()
-    ctx.synchronize()
-    return dst, results
 
 
 def frames_for(entries, spec, more=5):
@@ -158,7 +110,7 @@ def test_a_failed_melspec_launch_costs_its_members_e_synth_and_leaves_silence_ro
     """the entries of test_a_refused_entry_costs_only_itself_and_leaves_the_silence_row under VPZM_FAIL_DELIVERY (check_failed_delivery
     of test_multi_batch_gpu.py): the resample launches into the lane's temporary are made, the mel-spectrogram launch is not"""
     import torch
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
     try:
@@ -173,7 +125,7 @@ def test_a_failed_melspec_launch_costs_its_members_e_synth_and_leaves_silence_ro
 
 def test_a_wrong_out_tensor_raises_and_a_wrong_spec_is_refused(ctx):
     import torch
-    from test_pcm_melspec_gpu import melspec_refused_specs
+    from melspec_truth import melspec_refused_specs
     from vorbispizza_amd import capi, multi
     s = streams()["stereo_coupled_res2_12"]
     entries = [(s, a, n) for a, n in s.windows()[:6]]

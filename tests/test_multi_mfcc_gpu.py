@@ -18,55 +18,15 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
 import mfcc_truth as mt  # noqa: E402
-from test_multi_fbank_gpu import bits, mixed_entries, refused_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, streams  # noqa: E402
-from test_multi_resample_gpu import RATE, most_outputs, resampled_call  # noqa: E402
+from multi_support import (bits, FIELDS, mfcc_call, mfcc_shape_of as shape_of, MFCC_VARIANTS as VARIANTS, mixed_entries,  # noqa: E402
+    most_outputs, OPTIONS, RATE, refused_entries, resampled_call, streams)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-# Kaldi's own defaults, and a second spec so that the mean over frames, HTK's order without the energy, the other layout, remove_dc off,
-# another window and a pad_value pass through the dispatcher
-VARIANTS = [mt.spec_of(sample_rate=RATE),
-            mt.spec_of(sample_rate=RATE, win=96, hop=17, n_fft=128, n_mels=13, n_ceps=9, low_freq=100.0, high_freq=-1000.0, preemphasis=0.5,
-                       window="hamming", remove_dc=False, pad_value=-3.5, frames_first=False, lifter=0.0, use_energy=False, htk_compat=True,
-                       subtract_mean=True)]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def shape_of(n, frames, spec):
-    T = ft.n_frames(frames, spec["win"], spec["hop"])
-    return (n, T, spec["n_ceps"]) if spec["frames_first"] else (n, spec["n_ceps"], T)
 
 
 def pad_bits(spec):
     return int(np.float32(spec["pad_value"]).view(np.int32))
-
-
-def mfcc_call(entries, frames, spec, device_ids=(0,), dispatcher=None, out=None, **opt):
-    """-> (the features as one tensor, results, stats)"""
-    import torch
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        parts, whole, results, stats = d.decode_ranges_mfcc([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], frames, out=out, **spec)
-    finally:
-        if dispatcher is None:
-            d.close()
-    if whole is None:
-        whole = torch.cat(list(parts))
-    assert tuple(whole.shape) == shape_of(len(entries), frames, spec) and whole.dtype == torch.float32
-    return whole, results, stats
 
 
 def by_hand(ctx, entries, frames, spec, truth=False, **opt):
@@ -155,10 +115,10 @@ def test_a_refused_entry_costs_only_itself_and_leaves_the_pad_row(ctx, gpu_entro
 
 @pytest.mark.parametrize("gpu_entropy", [False, True])
 def test_a_failed_mfcc_launch_costs_its_members_e_synth_and_leaves_pad_rows(ctx, monkeypatch, gpu_entropy):
-    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of test_multi_batch_gpu.py): the resample launches
+    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of multi_support.py): the resample launches
     into the lane's temporary are made, the MFCC launch is not"""
     import torch
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     entries, J = refused_entries()
     d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
@@ -172,7 +132,7 @@ def test_a_failed_mfcc_launch_costs_its_members_e_synth_and_leaves_pad_rows(ctx,
 
 def test_a_wrong_out_tensor_raises_and_a_wrong_spec_is_refused(ctx):
     import torch
-    from test_mfcc_cpu import refused_specs
+    from mfcc_truth import refused_specs
     from vorbispizza_amd import capi, multi
     s = streams()["stereo_coupled_res2_12"]
     entries = [(s, a, n) for a, n in s.windows()[:6]]

@@ -207,7 +207,7 @@ def test_damaged_members_inside_mixed_sub_batches():
     """tests/test_multi_entropy_gpu.py's damage (damage_audio).  Eight writer streams of 24 packets from six setups, three of them
     damaged, are one mixed sub-batch; the two stereo fixtures and a damaged copy of each are another (issue6test.ogg's trailing
     packet fails the window check, so skipped_packets is not all zero)."""
-    from test_hostile_input_gpu import damage_audio
+    from synth_support import damage_audio
 
     clean = [writer("stereo_coupled_res2", seed, 24) for seed in SEEDS]
     fixtures = [open(os.path.join(GOLDEN, n), "rb").read() for n in FIXTURES[2:]]

@@ -17,24 +17,13 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import loudness_truth as lt  # noqa: E402
-from test_multi_batch_gpu import batch_call, most_samples  # noqa: E402
-from test_multi_loudness_gpu import loudness_entries, measure_call as loudness_call, refused_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, streams  # noqa: E402
-from test_multi_resample_gpu import rerated  # noqa: E402
+from multi_support import (batch_call, FIELDS, loudness_entries, loudness_refused_entries as refused_entries, measure_call as  # noqa: E402
+    loudness_call, most_samples, OPTIONS, rerated, streams)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 EMPTY = (-np.inf, 0.0, -np.inf, -np.inf, -np.inf, -np.inf, 0.0, 0.0, 0, 0, 0)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def r128_call(entries, device_ids=(0,), dispatcher=None, ranges=True, **opt):

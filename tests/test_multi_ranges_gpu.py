@@ -1,5 +1,5 @@
 """vpzm_decode_ranges (include/vorbispizza_multi_ranges.h, host/vorbis_multi.cpp): a window of samples out of every stream in one
-batched call.  The truth is the slice of the stream-by-stream whole decode (single_stream_pcm of tests/test_multi_gpu.py), compared as
+batched call.  The truth is the slice of the stream-by-stream whole decode (single_stream_pcm of tests/multi_support.py), compared as
 raw bits: a window decoded from its pre-roll packet is the same samples, on both routes, for both PCM types, whatever the caller's
 layout, the partition, the sub-batch cut and the failure path.
 
@@ -17,139 +17,12 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from multi_support import FIELDS, OPTIONS, SENTINEL, Stream, all_entries, call, expected, golden, place, same_bits, streams  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-FIELDS = ("status", "device_slot", "channels", "sample_rate", "samples", "packets", "skipped_packets")
-SENTINEL = 7
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def golden(name):
-    return open(os.path.join(GOLDEN, name), "rb").read()
-
-
-class Stream:
-    """a container, what the front end says about it and its whole decode (computed once per PCM type, never changed)"""
-
-    def __init__(self, raw, synthetic):
-        from vorbispizza_amd.front import FrontError, OggVorbisFile
-        self.raw = raw
-        self.data = np.frombuffer(raw, dtype=np.uint8)
-        self.f = OggVorbisFile(raw)
-        self.channels, self.total, self.packets = self.f.channels, int(self.f.total_samples), int(self.f.audio_packets)
-        self.bounds = [p for p in range(self.total + 1) if self.f.seek(p)[1] == 0]
-        assert self.bounds[0] == 0 and len(self.bounds) >= 3
-        if synthetic:  # (nothing trimmed at the end: the counted length is the total)
-            with pytest.raises(FrontError):
-                self.f.seek(self.total + 1)
-        self.whole = {}
-
-    def truth(self, ctx, s16):
-        from test_multi_gpu import single_stream_pcm
-        if s16 not in self.whole:
-            self.whole[s16] = single_stream_pcm(ctx, self.raw, s16=s16)
-        return self.whole[s16]
-
-    def windows(self):
-        b, total = self.bounds, self.total
-        out = [(0, 1), (0, b[1]), (total, 10), (0, total), (b[2], total + 1000)]
-        for i in range(1, len(b)):
-            out += [(b[i] - 1, 2), (b[i] + 1, 5), (b[i], -1)]
-            if i + 1 < len(b):
-                out.append((b[i], b[i + 1] - b[i]))
-        # three packets' samples where the packets' lengths change (a short / long transition): the last sample of one, the next one
-        # whole, the first sample of the one after
-        spans = [b[i + 1] - b[i] for i in range(len(b) - 1)]
-        out += [(b[i] - 1, spans[i] + 2) for i in range(1, len(spans)) if spans[i - 1] != spans[i]]
-        return out
-
-
-_streams = {}
-
-
-def streams():
-    import synthetic_streams as ss
-    if not _streams:
-        for name, packets in (("stereo_coupled_res2", 12), ("stereo_coupled_res2", 30), ("mono_floor1_res1", 12), ("six_channels_51", 12),
-                              ("stereo_floor0", 12)):
-            st, rng = getattr(ss, name)()
-            _streams["%s_%d" % (name, packets)] = Stream(bytes(st.build(rng, packets)[0]), True)
-        _streams["1test.ogg"] = Stream(golden("1test.ogg"), False)
-        assert _streams["1test.ogg"].packets == 25 and _streams["1test.ogg"].total == 17318
-        assert not _streams["stereo_floor0_12"].f.gpu_decode_supported and _streams["stereo_coupled_res2_30"].f.gpu_decode_supported
-        # a change of packet length inside every stream of two block sizes
-        for name, s in _streams.items():
-            spans = {s.bounds[i + 1] - s.bounds[i] for i in range(len(s.bounds) - 1)}
-            assert len(spans) > 1 or name == "stereo_floor0_12", name
-    return _streams
-
-
-def all_entries():
-    """[(stream, start, count)], every window of every stream, the streams interleaved so that sub-batches mix them"""
-    per = [[(s, a, n) for a, n in s.windows()] for s in streams().values()]
-    out = []
-    for i in range(max(len(p) for p in per)):
-        out += [p[i] for p in per if i < len(p)]
-    return out
-
-
-def place(entries, dense, s16, seed=5):
-    """the caller's array: areas of exactly the samples asked for -- back to back in entry order (dense), or shuffled with gaps"""
-    sizes = [s.f.window(a, n)["samples"] * s.channels for s, a, n in entries]
-    caps = np.array([s.f.window(a, n)["samples"] for s, a, n in entries], dtype=np.int64)
-    offs = np.zeros(len(entries), dtype=np.int64)
-    rng = np.random.default_rng(seed)
-    order = np.arange(len(entries)) if dense else rng.permutation(len(entries))
-    at = 0
-    for k in order:
-        at += 0 if dense else int(rng.integers(1, 9))
-        offs[k] = at
-        at += sizes[k]
-    pcm = np.full(at + (0 if dense else 3), SENTINEL, dtype=np.int16 if s16 else np.float32)
-    return pcm, offs, caps
-
-
-def call(entries, s16=False, dense=True, device_ids=(0,), dispatcher=None, **opt):
-    from vorbispizza_amd import multi
-    pcm, offs, caps = place(entries, dense, s16)
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        results, stats = d.decode_ranges([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], pcm, offs, caps, s16=s16)
-    finally:
-        if dispatcher is None:
-            d.close()
-    return pcm, offs, results, stats
-
-
-def expected(ctx, entries, s16, dense):
-    """the array a correct call leaves: the sentinel, and every window's slice of the whole decode in its area"""
-    pcm, offs, _ = place(entries, dense, s16)
-    for k, (s, a, n) in enumerate(entries):
-        w = s.f.window(a, n)
-        ref = s.truth(ctx, s16)
-        assert ref.shape[0] == s.total  # (a clean stream: the whole decode delivers the total)
-        pcm[offs[k]: offs[k] + w["samples"] * s.channels] = ref[a: a + w["samples"]].reshape(-1)
-    return pcm
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-OPTIONS = {"host": dict(gpu_entropy=False), "device": dict(gpu_entropy=True), "mixed": dict(gpu_entropy=True, mixed_setups=True)}
 
 
 @pytest.mark.parametrize("dense", [True, False], ids=["dense", "gaps"])
@@ -221,7 +94,7 @@ def test_the_switches_change_no_byte(ctx, monkeypatch, capfd, switch, value):
 def test_a_window_over_a_skipped_last_packet(ctx, gpu_entropy):
     """issue6test.ogg's trailing packet fails the window check: the whole decode ends 63 samples short of the total, and so does a window
     over the last 5 000 samples"""
-    from test_multi_gpu import single_stream_pcm
+    from multi_support import single_stream_pcm
     s = Stream(golden("issue6test.ogg"), False)
     ref = single_stream_pcm(ctx, s.raw)
     assert ref.shape[0] == s.total - 63
@@ -258,8 +131,8 @@ def test_a_bad_entry_costs_only_itself(ctx, gpu_entropy):
 
 
 def test_damaged_audio_is_the_same_on_both_routes(ctx):
-    from test_hostile_input_gpu import damage_audio
-    from test_multi_gpu import single_stream_pcm
+    from synth_support import damage_audio
+    from multi_support import single_stream_pcm
     clean = [golden("3test.ogg"), golden("2test.ogg"), streams()["stereo_coupled_res2_30"].raw, streams()["six_channels_51_12"].raw]
     damaged = [Stream(damage_audio(raw, seed, hits), False) for raw, (seed, hits) in zip(clean, ((1, 8), (2, 16), (3, 6), (4, 4)))]
     entries = []

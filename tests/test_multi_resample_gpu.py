@@ -18,46 +18,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_multi_batch_gpu import as_bits, batch_call, entries_of  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, all_entries, golden, streams  # noqa: E402
-from test_resample_cpu import bound, launch_plan, ratio_of, ratio_ok, resample_truth, to_s16  # noqa: E402
+from multi_support import (all_entries, as_bits, batch_call, entries_of, FIELDS, golden, most_outputs, OPTIONS, out_len,  # noqa: E402
+    RATE, ratio, rerated, resampled_call, Stream, streams)
+from resample_truth import bound, launch_plan, ratio_of, ratio_ok, resample_truth, to_s16  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-RATE = 16000
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def out_len(m, up, down):
-    return -(-m * up // down)
-
-
-def ratio(s, rate):
-    return ratio_of(int(s.f.sample_rate), rate)
-
-
-_rerated = {}
-
-
-def rerated(rate, packets=12):
-    """stereo_coupled_res2 at 12 packets with another rate in its identification header: the same setup header, so it shares sub-batches
-    with its 44 100 Hz twin, at another ratio"""
-    import synthetic_streams as ss
-    if (rate, packets) not in _rerated:
-        st, rng = ss.stereo_coupled_res2()
-        st.rate = rate
-        _rerated[(rate, packets)] = Stream(bytes(st.build(rng, packets)[0]), True)
-        assert _rerated[(rate, packets)].f.sample_rate == rate and _rerated[(rate, packets)].channels == 2
-    return _rerated[(rate, packets)]
 
 
 _many = {}
@@ -83,30 +49,6 @@ def truth_row(ctx, s, a, m, rate, mono):
         up, down = ratio(s, rate)
         _rows[key] = resample_truth(s.truth(ctx, False)[a: a + m], up, down, mono)
     return _rows[key]
-
-
-def resampled_call(entries, rate, channels, frames, planar=True, s16=False, mono=False, device_ids=(0,), dispatcher=None, out=None, **opt):
-    """-> (the batch as one tensor, results, stats)"""
-    import torch
-    from vorbispizza_amd import multi
-    opt.setdefault("host_threads", 4)
-    opt.setdefault("streams_per_call", 16)
-    d = dispatcher or multi.Dispatcher(list(device_ids), **opt)
-    try:
-        parts, whole, results, stats = d.decode_ranges_batch([s.data for s, _, _ in entries], [(a, n) for _, a, n in entries], channels, frames,
-                                                             planar=planar, s16=s16, sample_rate=rate, mono=mono, out=out)
-    finally:
-        if dispatcher is None:
-            d.close()
-    if whole is None:
-        whole = torch.cat(list(parts))
-    assert tuple(whole.shape) == ((len(entries), channels, frames) if planar else (len(entries), frames, channels))
-    assert whole.dtype == (torch.int16 if s16 else torch.float32)
-    return whole, results, stats
-
-
-def most_outputs(entries, rate):
-    return max(out_len(s.f.window(a, n)["samples"], *ratio(s, rate)) for s, a, n in entries)
 
 
 def check_against_truth(ctx, got_planar, results, entries, rate, mono, delivered=None):
@@ -279,7 +221,7 @@ def test_failed_resample_launches_cost_their_members_e_synth_and_leave_zero_rows
     """the entries of test_a_bad_entry_costs_only_itself_and_leaves_a_zero_row under VPZM_FAIL_DELIVERY (check_failed_delivery of
     test_multi_batch_gpu.py)"""
     import torch
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     s, mono, odd = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"], rerated(44101)
     garbage = Stream.__new__(Stream)
@@ -303,8 +245,8 @@ def test_failed_resample_launches_cost_their_members_e_synth_and_leave_zero_rows
 def test_damaged_audio_is_the_same_on_both_routes(ctx):
     """a damaged stream has no truth but the host-destination call: the row is the restatement of the samples decode_ranges delivers"""
     import torch
-    from test_hostile_input_gpu import damage_audio
-    from test_multi_ranges_gpu import call
+    from synth_support import damage_audio
+    from multi_support import call
     damaged = [Stream(damage_audio(raw, seed, hits), False) for raw, (seed, hits) in
                ((golden("3test.ogg"), (1, 8)), (golden("2test.ogg"), (2, 16)), (streams()["stereo_coupled_res2_30"].raw, (3, 6)))]
     entries = []
@@ -333,8 +275,8 @@ def test_damaged_audio_is_the_same_on_both_routes(ctx):
 
 def test_the_four_calls_in_turn_on_one_dispatcher(ctx):
     import torch
-    from test_multi_batch_gpu import most_samples, same_on_device, truth_on_device
-    from test_multi_ranges_gpu import call, expected, same_bits
+    from multi_support import most_samples, same_on_device, truth_on_device
+    from multi_support import call, expected, same_bits
     from vorbispizza_amd import multi
     entries = entries_of(2)[::3]
     frames = most_samples(entries)

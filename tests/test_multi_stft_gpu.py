@@ -17,12 +17,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import stft_truth as st  # noqa: E402
-from test_logmel_cpu import U, frames_of  # noqa: E402
-from test_multi_logmel_gpu import VARIANTS as LOGMEL_VARIANTS, by_hand as logmel_by_hand, logmel_call, mixed_entries  # noqa: E402
-from test_multi_ranges_gpu import FIELDS, OPTIONS, Stream, golden, streams  # noqa: E402
-from test_multi_resample_gpu import RATE, most_outputs, out_len, ratio, rerated, resampled_call  # noqa: E402
-from test_resample_cpu import bound, resample_truth  # noqa: E402
-from test_stft_cpu import stft_refused_specs  # noqa: E402
+from f32_model import U  # noqa: E402
+from logmel_truth import frames_of  # noqa: E402
+from multi_support import (bits_of_any as bits, channels_of, FIELDS, golden, logmel_by_hand, logmel_call, LOGMEL_VARIANTS,  # noqa: E402
+    mixed_entries, most_outputs, OPTIONS, out_len, RATE, ratio, refused_entries_by_channel as refused_entries, rerated,
+    resampled_call, Stream, streams)
+from resample_truth import bound, resample_truth  # noqa: E402
+from stft_truth import stft_refused_specs  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -34,20 +36,6 @@ VARIANTS = [dict(sample_rate=OWN, channels=2, mono=False, n_fft=4096, hop=1024, 
 IDS = ["stereo_44100_4096_complex_bins_first", "mono_22050_1024_magnitude_frames_first"]
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def channels_of(spec):
-    return 1 if spec["mono"] else spec["channels"]
-
-
 def shape_of(n, frames, spec):
     T, NF = 1 + frames // spec["hop"], spec["n_fft"] // 2 + 1
     return (n, channels_of(spec)) + ((NF, T) if spec["bins_first"] else (T, NF))
@@ -56,11 +44,6 @@ def shape_of(n, frames, spec):
 def dtype_of(spec):
     import torch
     return torch.complex64 if spec["output"] == "complex" else torch.float32
-
-
-def bits(t):
-    import torch
-    return torch.view_as_real(t).view(torch.int32) if t.is_complex() else t.view(torch.int32)
 
 
 def stft_call(entries, frames, spec, device_ids=(0,), dispatcher=None, out=None, **opt):
@@ -154,26 +137,6 @@ def test_the_partition_the_cut_and_the_failure_paths_change_no_bit(ctx, monkeypa
             assert np.array_equal(results[field], one_results[field]), field
 
 
-def refused_entries(spec):
-    from vorbispizza_amd import multi
-    rate = spec["sample_rate"]
-    s, mono, odd = streams()["stereo_coupled_res2_30"], streams()["mono_floor1_res1_12"], rerated(44101)
-    garbage = Stream.__new__(Stream)
-    garbage.data = np.frombuffer(b"not an ogg file at all" * 10, dtype=np.uint8)
-    up, down = ratio(s, rate)
-    a, n = s.bounds[3] + 7, 2100 * down
-    J = out_len(n, up, down)
-    assert J >= 2049 and out_len(n + 1, up, down) == J + 1  # (a row of J samples holds a transform of 4096)
-    m_up, m_down = ratio(mono, rate)
-    J_mono = out_len(100, m_up, m_down)
-    # entry 2: one output sample more than a row holds (too few frames); entry 3: no Ogg; entry 4: a mono stream -- refused in a stereo
-    # batch, mixed down to itself in a mono one; entry 5: a ratio the resampler refuses; entry 6: an empty window
-    entries = [(s, a, n), (s, -1, n), (s, a, n + 1), (garbage, a, n), (mono, 5, 100), (odd, 3, 500), (s, s.total, 10), (s, a + 1, n), (s, a + 2, n)]
-    status = [0, multi.E_RANGE, multi.E_CAPACITY, multi.E_OPEN, 0 if spec["mono"] else multi.E_CHANNELS, multi.E_RATE, 0, 0, 0]
-    samples = [J, 0, 0, 0, J_mono if spec["mono"] else 0, 0, 0, J, J]
-    return entries, J, status, samples
-
-
 @pytest.mark.parametrize("gpu_entropy", [False, True])
 def test_a_refused_entry_costs_only_itself_and_leaves_zero_rows_in_all_its_channels(ctx, gpu_entropy):
     import torch
@@ -192,9 +155,9 @@ def test_a_refused_entry_costs_only_itself_and_leaves_zero_rows_in_all_its_chann
 
 @pytest.mark.parametrize("gpu_entropy", [False, True])
 def test_a_failed_stft_launch_costs_its_members_e_synth_and_leaves_zero_rows(ctx, monkeypatch, gpu_entropy):
-    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of test_multi_batch_gpu.py): the resample launches into
+    """the entries of the test above under VPZM_FAIL_DELIVERY (check_failed_delivery of multi_support.py): the resample launches into
     the lane's temporary are made, the STFT launch is not"""
-    from test_multi_batch_gpu import check_failed_delivery, sentinel_out
+    from multi_support import check_failed_delivery, sentinel_out
     from vorbispizza_amd import multi
     d = multi.Dispatcher([0, 0], host_threads=3, streams_per_call=2, gpu_entropy=gpu_entropy)
     try:
@@ -258,7 +221,7 @@ def test_the_calls_in_turn_on_one_dispatcher(ctx):
     """the lane's temporary -- mono rows for the older feature calls, planar channels for this one -- and the context's table caches serve
     call after call: the log-mel call and the plain batch still deliver their old bits beside the new one"""
     import torch
-    from test_multi_melspec_gpu import VARIANTS as MELSPEC_VARIANTS, by_hand as melspec_by_hand, melspec_call
+    from multi_support import MELSPEC_VARIANTS, melspec_by_hand, melspec_call
     entries = mixed_entries()[::3]
     frames = max(frames_for(entries, spec, 0) for spec in VARIANTS)
     wants = [by_hand(ctx, entries, frames, spec)[0] for spec in VARIANTS]

@@ -6,20 +6,10 @@ import numpy as np
 import pytest
 
 import helpers
-from test_dual_gpu import same_bits
-from test_host_paths_gpu import env, run, stream_major_batch
+from synth_support import env, run, same_bits, stream_major_batch
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 # (VPZ_PAIRS=1: the pairs wherever they can run -- left to itself the decoder keeps group mode where that is as fast or faster: the

@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
 import mfcc_truth as mt  # noqa: E402
+from f32_model import fma32  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -272,21 +273,8 @@ def test_staging_memory_grows_and_is_reused(capi):
         dec.close()
 
 
-def fma32(a, b, c):
-    """float32 fused multiply-adds, elementwise: the product is exact in float64; the sum is rounded to odd there (its error from the
-    two-sum), so that the one rounding to float32 behind it is the rounding of the exact value"""
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = np.broadcast_to(c.astype(np.float64), p.shape)
-    s = p + c
-    bb = s - p
-    e = (p - (s - bb)) + (c - bb)
-    even = (s.view(np.int64) & 1) == 0
-    s = np.where((e != 0) & even, np.nextafter(s, np.where(e > 0, np.inf, -np.inf)), s)
-    return s.astype(np.float32)
-
-
 def test_fma32_is_the_exact_one():
-    from test_pcm_mfcc_gpu import fma32 as one
+    from f32_model import fma32_rational as one
     rng = np.random.default_rng(11)
     a, b = rng.standard_normal(300).astype(np.float32), rng.standard_normal(300).astype(np.float32)
     c = (rng.standard_normal(300) * 2.0 ** rng.integers(-30, 30, 300)).astype(np.float32)

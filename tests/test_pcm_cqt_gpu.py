@@ -24,23 +24,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import cqt_truth as ct  # noqa: E402
-from test_cqt_cpu import cqt_refused_specs  # noqa: E402
+from cqt_truth import cqt_refused_specs  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0x5A5A5A5A
 GUARD = 64
 DST_ROWS = ct.DST_ROWS
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def guarded(n_floats):

@@ -21,76 +21,12 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_truth as ft  # noqa: E402
-from test_fbank_cpu import refused_specs  # noqa: E402
+from fbank_truth import refused_specs  # noqa: E402
+from fbank_cases import WORST, launch, note  # noqa: E402
+from pcm_support import GUARD, SENTINEL, guarded, place, signal  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x5A5A5A5A
-GUARD = 64
-WORST = {}
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def signal(n, seed, sample_rate=16000, amplitude=0.3):
-    """seeded noise plus a tone, float32"""
-    rng = np.random.default_rng(seed)
-    t = np.arange(n, dtype=np.float64)
-    return (amplitude * rng.standard_normal(n) + 0.2 * np.sin(2 * np.pi * 440.0 * t / sample_rate + 0.3)).astype(np.float32)
-
-
-def place(windows, gap=3):
-    """one source array for these windows (float32 arrays): window i at an offset that is odd for odd i and a multiple of 4 for even i,
-    NaN between and behind them (what lies at or behind src + L must not be read).  -> (src, offsets)"""
-    offs, at = [], 0
-    for i, w in enumerate(windows):
-        at += gap
-        at += (-at) % 4 if i % 2 == 0 else (at + 1) % 2
-        offs.append(at)
-        at += len(w)
-    src = np.full(at + gap, np.nan, dtype=np.float32)
-    for o, w in zip(offs, windows):
-        src[o: o + len(w)] = w
-    return src, offs
-
-
-def guarded(dst_rows, row_elems):
-    """a destination of dst_rows * row_elems float32 with GUARD sentinels on either side, every element the sentinel"""
-    import torch
-    flat = np.full(GUARD + dst_rows * row_elems + GUARD, SENTINEL, dtype=np.uint32)
-    whole = torch.from_numpy(flat.view(np.float32).copy()).to("cuda:0")
-    return whole, whole[GUARD: GUARD + dst_rows * row_elems]
-
-
-def launch(ctx, d, src, rows, dst_rows, F, d_src=None):
-    """one vpz_pcm_fbank call of spec dict d -> [dst_rows][T][n_mels] float32 of the destination's body, the guards checked"""
-    import torch
-    from vorbispizza_amd import capi
-    spec = capi.FbankSpec.make(**d)
-    T, n_mels = spec.n_frames(F), d["n_mels"]
-    whole, dst = guarded(dst_rows, n_mels * T)
-    d_src = torch.from_numpy(src).to("cuda:0") if d_src is None else d_src
-    shape = (dst_rows, T, n_mels) if d["frames_first"] else (dst_rows, n_mels, T)
-    assert capi.pcm_fbank(ctx, d_src, rows, dst.view(shape), spec, F) == capi.OK, ctx.last_error()
-    ctx.synchronize()
-    bits = whole.cpu().numpy().view(np.uint32)
-    assert (bits[:GUARD] == SENTINEL).all() and (bits[-GUARD:] == SENTINEL).all()
-    body = bits[GUARD:-GUARD].view(np.float32)
-    return body.reshape(shape) if d["frames_first"] else body.reshape(shape).transpose(0, 2, 1)
-
-
-def note(key, ratio):
-    WORST[key] = max(WORST.get(key, 0.0), ratio)
-    print("error / bound %s: %.4f" % (key, ratio))
-    assert ratio < 1.0
 
 
 @pytest.mark.parametrize("pad_value", [0.0, -15.9424])

@@ -34,8 +34,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import fbank_cases as fc  # noqa: E402
 import fbank_truth as ft  # noqa: E402
-import test_pcm_fbank_gpu as first  # noqa: E402
-from test_pcm_fbank_gpu import SENTINEL, launch, place, signal  # noqa: E402
+import fbank_cases as first  # noqa: E402
+from fbank_cases import launch  # noqa: E402
+from pcm_support import SENTINEL, place, signal  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -46,16 +48,6 @@ def note(key, ratio):
     """test_pcm_fbank_gpu.note, and this file's own record beside it"""
     first.note(key, ratio)
     WORST[key] = max(WORST.get(key, 0.0), ratio)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 @pytest.fixture(scope="module")

@@ -31,24 +31,15 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import featpost_bits as fb  # noqa: E402
 import featpost_truth as pt  # noqa: E402
-from test_featpost_bits_cpu import ROW_SPIKED, SPIKED  # noqa: E402
-from test_pcm_fbank_gpu import SENTINEL  # noqa: E402
-from test_pcm_featpost_gpu import LAYOUTS, WORST, batch, by_column_slices, check_rows, feats, launch  # noqa: E402
+from featpost_bits import ROW_SPIKED, SPIKED  # noqa: E402
+from pcm_support import SENTINEL  # noqa: E402
+from featpost_cases import LAYOUTS, WORST, batch, by_column_slices, check_rows, feats, launch  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 MODEL = {}  # computed once per (input, spec), shared by the layouts
 NOTED = set()  # this file's keys of test_pcm_featpost_gpu's table of ratios, which check_rows fills
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def spec_key(d):
@@ -189,7 +180,7 @@ def test_kaldis_default_window(ctx, norm, norm_vars, frames_first):
     """cmn_window 600 with min_window 100 -- the spec's defaults --, centred too, and the row, over n = 99, 100, 101 (around
     min_window), 600, 601, 602 (around the window) and 1300 = T, in one launch permuted into nine rows: a window holds up to nine whole
     chunks between its partial ones, a row's sum 21 chunk sums"""
-    from test_featpost_cpu import NS
+    from featpost_truth import NS
     assert set(KALDI_NS) <= set(NS) and pt.DEFAULTS["cmn_window"] == 600 and pt.DEFAULTS["min_window"] == 100
     xs = [feats(n, 3, 3000 + n, offset=2.0) for n in KALDI_NS]
     d = pt.spec_of(norm_vars=norm_vars, frames_first=frames_first, pad_value=-1.0, **KALDI[norm])

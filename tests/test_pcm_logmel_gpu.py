@@ -19,14 +19,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_logmel_cpu import check_log, check_power, logmel_truth, mel_weights64, refused_specs, silence_value  # noqa: E402
+from logmel_truth import check_log, check_power, logmel_truth, mel_weights64, refused_specs, silence_value  # noqa: E402
+from pcm_support import LOGMEL_DST_ROWS as DST_ROWS, FLOOR, SENTINEL, guarded, rows_back  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
-FLOOR = 1e-10
-SENTINEL = 0x5A5A5A5A
-GUARD = 64
-DST_ROWS = 9
+
 # name: (sample_rate, n_fft, hop, n_mels, f_min, f_max, mel_scale, mel_norm, F) -- F so that T = 1 + F // hop is no multiple of the frame
 # tile and the last tile is a partial one.  These launches are small, so their tiles are 32 frames (16 at n_fft = hop = 1024, where the LDS
 # holds no more); test_a_window_alone_and_among_hundreds_gives_the_same_bits has a launch of 64-frame tiles
@@ -39,16 +38,6 @@ SPECS = {
 }
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
 def make_spec(name, log, bands_first):
     from vorbispizza_amd import capi
     sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F = SPECS[name]
@@ -59,22 +48,6 @@ def make_spec(name, log, bands_first):
 def weights_of(name):
     sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F = SPECS[name]
     return mel_weights64(sr, n_fft, n_mels, f_min, f_max, scale, norm)
-
-
-def guarded(dst_rows, row_elems):
-    """a destination of dst_rows * row_elems float32 with GUARD sentinels on either side, every element the sentinel"""
-    import torch
-    flat = np.full(GUARD + dst_rows * row_elems + GUARD, SENTINEL, dtype=np.uint32)
-    whole = torch.from_numpy(flat.view(np.float32).copy()).to("cuda:0")
-    return whole, whole[GUARD: GUARD + dst_rows * row_elems]
-
-
-def rows_back(whole, dst_rows, n_mels, T, bands_first):
-    """[row][T][n_mels] float32 of the destination's body, after checking the guards"""
-    bits = whole.cpu().numpy().view(np.uint32)
-    assert (bits[:GUARD] == SENTINEL).all() and (bits[-GUARD:] == SENTINEL).all()
-    body = bits[GUARD:-GUARD].view(np.float32)
-    return body.reshape(dst_rows, n_mels, T).transpose(0, 2, 1) if bands_first else body.reshape(dst_rows, T, n_mels)
 
 
 _CASES = {}

@@ -36,25 +36,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_logmel_cpu import (CROWD_T, LIMIT_CROWDS, LIMIT_GROUPS, LIMIT_HOPS, LIMIT_LDS, LIMIT_TAIL, check_log, check_power, crowd_rows,  # noqa: E402
-                             frames_of, limit_F, limit_frames, logmel_truth, mel_weights64, silence_value, tile_plan)
-from test_pcm_logmel_gpu import DST_ROWS, FLOOR, SENTINEL, guarded, rows_back  # noqa: E402
+from logmel_truth import (CROWD_T, LIMIT_CROWDS, LIMIT_GROUPS, LIMIT_HOPS, LIMIT_LDS, LIMIT_TAIL, check_log, check_power, crowd_rows,
+    frames_of, limit_F, limit_frames, logmel_truth, mel_weights64, silence_value, tile_plan)
+from pcm_support import LOGMEL_DST_ROWS as DST_ROWS, FLOOR, SENTINEL, guarded, rows_back  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 MODES = [(False, True), (False, False), (True, True), (True, False)]  # (log, bands_first)
 MODE_IDS = ["power-bands_first", "power-frames_first", "log10-bands_first", "log10-frames_first"]
 TWO_MODES, TWO_MODE_IDS = [MODES[0], MODES[3]], [MODE_IDS[0], MODE_IDS[3]]
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def case_id(case):

@@ -41,8 +41,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import loudness_cases as lc  # noqa: E402
 import loudness_truth as lt  # noqa: E402
-import test_pcm_loudness_gpu as first  # noqa: E402
-from test_pcm_loudness_gpu import PEAK_SENTINEL, SENTINEL, check_case, launch, needs_longdouble  # noqa: E402
+import loudness_support as first  # noqa: E402
+from loudness_support import PEAK_SENTINEL, SENTINEL, check_case, launch, needs_longdouble  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -51,18 +52,8 @@ WORST = {}
 
 
 @pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-@pytest.fixture(scope="module")
 def truth():
-    """check_case reads test_pcm_loudness_gpu.truth(): that table, with this file's cases added to it once"""
+    """check_case reads loudness_support.truth(): that table, with this file's cases added to it once"""
     table = first.truth()
     if ("edges_8", 0) not in table:
         table.update(lc.truth())

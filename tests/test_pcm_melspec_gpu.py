@@ -20,7 +20,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import melspec_truth as mt  # noqa: E402
-from test_logmel_cpu import check_log, check_power, mel_weights64, refused_specs, silence_value  # noqa: E402
+from logmel_truth import check_log, check_power, mel_weights64, refused_specs, silence_value  # noqa: E402
+from melspec_truth import melspec_refused_specs  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,16 +30,6 @@ FLOOR = mt.FLOOR
 SENTINEL = 0x5A5A5A5A
 GUARD = 64
 DST_ROWS = mt.DST_ROWS
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def make_spec(name, log, bands_first):
@@ -253,29 +245,6 @@ def raw_call(ctx, src_ptr, src_elems, frames, spec, rows, dst_ptr, dst_rows, n_r
     desc = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 3))
     return capi.lib().vpz_pcm_melspec(ctx._h if handle else None, src_ptr, src_elems, frames, None if null_spec else C.byref(spec),
                                       desc.shape[0] if n_rows is None else n_rows, None if null_rows else desc.ctypes.data, dst_ptr, dst_rows)
-
-
-def melspec_refused_specs(capi):
-    """(what, spec) for every limit of the definition: test_logmel_cpu's list carried to this stage's transform sizes, and the sizes it
-    does not take"""
-    good = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=128)
-    out = []
-    for what, s in refused_specs(capi):
-        if what.startswith("n_fft"):
-            continue
-        t = capi.LogMelSpec.make(**good)
-        scale = 22050.0 / 16000.0
-        t.f_min, t.f_max, t.floor = s.f_min * scale, s.f_max * scale, s.floor
-        t.sample_rate = s.sample_rate * scale
-        t.hop = {160: 512, 0: 0, 401: 2049}[s.hop]
-        t.n_mels = {80: 128, 0: 0, 257: 257}[s.n_mels]
-        t.mel_scale, t.mel_norm, t.output, t.layout = s.mel_scale, s.mel_norm, s.output, s.layout
-        for i in range(9):
-            t.reserved[i] = s.reserved[i]
-        out.append((what, t))
-    for n_fft in (1024, 2047, 2046, 3000, 6144, 16384, 0, -2048):
-        out.append(("n_fft %d" % n_fft, capi.LogMelSpec.make(**dict(good, n_fft=n_fft, hop=min(512, max(1, n_fft))))))
-    return out
 
 
 def test_every_refusal_is_invalid_arg_and_writes_nothing(ctx):

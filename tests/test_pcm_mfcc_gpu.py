@@ -25,23 +25,15 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import fbank_cases as fc  # noqa: E402
 import fbank_truth as ft  # noqa: E402
 import mfcc_truth as mt  # noqa: E402
-from test_mfcc_cpu import refused_specs  # noqa: E402
-from test_pcm_fbank_gpu import GUARD, SENTINEL, guarded, place, signal  # noqa: E402
+from mfcc_truth import refused_specs  # noqa: E402
+from pcm_support import GUARD, SENTINEL, guarded, place, signal  # noqa: E402
+from f32_model import fma32_rational as fma32  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 WORST = {}
 LOG_EPS = np.float32(np.log(2.0 ** -23))  # logf(2^-23): the float32 nearest to the logarithm
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def launch(ctx, d, src, rows, dst_rows, F, d_src=None):
@@ -350,22 +342,12 @@ def test_a_sample_that_is_not_finite(ctx, subtract_mean):
         assert (got[1, TL:] == 1.5).all()
 
 
-def fma32(a, b, c):
-    """one float32 fused multiply-add: the exact a * b + c (rationals), rounded once"""
-    from fractions import Fraction
-    exact = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
-    near = np.float32(float(exact))  # (rounded twice: at most one float32 off; the neighbours decide)
-    best = min((near, np.nextafter(near, np.float32(np.inf)), np.nextafter(near, np.float32(-np.inf))),
-               key=lambda v: (abs(Fraction(float(v)) - exact), int(np.float32(v).view(np.uint32)) & 1))
-    return np.float32(best)
-
-
 def test_the_cepstra_are_the_stated_chain_over_vpz_pcm_fbank_bit_for_bit(ctx):
     """items 1 and 2 of the definition as bits: the log-mel values are vpz_pcm_fbank's, and a coefficient is the fused chain of
     vpz_mfcc_table's row over them, b ascending -- in the HTK order too; with one band and no lifter C is 1 and the cepstrum is the
     log-mel value itself"""
     import torch
-    from test_pcm_fbank_gpu import launch as fbank_launch
+    from fbank_cases import launch as fbank_launch
     from vorbispizza_amd import capi
     F = 400 + 160 * 8 + 11  # T = 9
     Ls = [F, 1000]

@@ -8,6 +8,7 @@ import sys
 
 import numpy as np
 import pytest
+from gpu_context import ctx  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,16 +17,6 @@ pytestmark = pytest.mark.gpu
 
 LAYOUTS = {"interleaved": 0, "planar": 1, "interleaved_s16": 2, "planar_s16": 3}
 FRAMES = (1, 7, 64, 1023, 1024, 1025)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def is_s16(layout):

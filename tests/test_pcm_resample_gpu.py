@@ -15,116 +15,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_resample_cpu import bound, resample_truth, to_s16  # noqa: E402
+from resample_truth import bound, resample_truth, to_s16  # noqa: E402
+from pcm_support import (INTERLEAVED, INTERLEAVED_S16, PLANAR, PLANAR_S16, guarded_layout as guarded, layout_windows,  # noqa: E402
+    out_len, random_source, rows_of, run_layouts)
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
-INTERLEAVED, PLANAR, INTERLEAVED_S16, PLANAR_S16 = 0, 1, 2, 3
+
 # up / down; 1/1 is the copy (and, with a downmix, the mean alone)
 RATIOS = [(160, 441), (1, 3), (3, 1), (160, 147), (147, 160), (441, 80), (1, 6), (2, 1), (1, 2), (1, 1)]
 MIXES = [(1, False), (2, False), (6, False), (2, True), (6, True)]  # (source channels, downmix)
-DST_ROWS = 13
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def lengths(down):
     """shorter than the filter, around one period of the phases, several tiles"""
     return [0, 1, 2, 5, 13, max(down - 1, 0), down, down + 1, 1000, 3001]
-
-
-def out_len(L, up, down):
-    return -(-L * up // down)
-
-
-def random_source(n, seed):
-    """n float32 in +-1.25 (so that the int16 conversion clamps now and then), none of them zero"""
-    rng = np.random.default_rng(seed)
-    a = rng.uniform(-1.25, 1.25, n).astype(np.float32)
-    a[a == 0] = np.float32(0.5)
-    assert (a != 0).all()
-    return a
-
-
-def layout_windows(Ls, channels, rng):
-    """every window from an ODD element offset, at least 9 elements of other data in front of it and behind it"""
-    rows, at = [], 0
-    order = rng.permutation(DST_ROWS)[: len(Ls)]
-    for L, row in zip(Ls, order):
-        at += 9 + int(rng.integers(0, 5))
-        at += 1 - at % 2
-        rows.append((at, L, int(row)))
-        at += L * channels
-    return rows, at + 11
-
-
-def guarded(dst_rows, channels, frames, layout, guard):
-    import torch
-    s16 = layout in (INTERLEAVED_S16, PLANAR_S16)
-    body = dst_rows * channels * frames
-    flat = np.full(guard + body + guard, 0x5A5A if s16 else 0x5A5A5A5A, dtype=np.uint16 if s16 else np.uint32)
-    whole = torch.from_numpy(flat.view(np.int16 if s16 else np.float32).copy()).to("cuda:0")
-    shape = (dst_rows, channels, frames) if layout in (PLANAR, PLANAR_S16) else (dst_rows, frames, channels)
-    return whole, whole[guard: guard + body].view(shape), flat
-
-
-def rows_of(whole, guard, dst_rows, channels, frames, layout):
-    """the destination as [row][frame][channel] numpy (float32 or int16), and the two guards' bits"""
-    a = whole.cpu().numpy()
-    body = a[guard: a.size - guard]
-    img = body.reshape(dst_rows, channels, frames).transpose(0, 2, 1) if layout in (PLANAR, PLANAR_S16) else body.reshape(dst_rows, frames, channels)
-    bits = a.view(np.uint16 if a.dtype == np.int16 else np.uint32)
-    return img, bits[:guard], bits[a.size - guard:]
-
-
-def run_layouts(ctx, src_np, rows, channels, downmix, up, down, frames, guards, layouts, truths):
-    """one call per layout over the same descriptors; the float32 outputs against the truth, the int16 ones against the float32 ones"""
-    import torch
-    from vorbispizza_amd import capi
-    src = torch.from_numpy(src_np).to("cuda:0").view(-1, channels) if src_np.size % channels == 0 else None
-    assert src is not None
-    co = 1 if downmix else channels
-    named = {row for _, _, row in rows}
-    f32 = {}
-    worst = 0.0
-    for layout, guard in zip(layouts, guards):
-        whole, dst, flat = guarded(DST_ROWS, co, frames, layout, guard)
-        assert capi.pcm_resample(ctx, src, rows, dst, layout, up, down, downmix) == capi.OK, ctx.last_error()
-        ctx.synchronize()
-        img, g0, g1 = rows_of(whole, guard, DST_ROWS, co, frames, layout)
-        sent = flat[0]
-        assert (g0 == sent).all() and (g1 == sent).all(), "a guard was written"
-        bits = img.view(np.uint16 if img.dtype == np.int16 else np.uint32)
-        for r in range(DST_ROWS):
-            if r not in named:
-                assert (bits[r] == sent).all(), ("an unnamed row was written", r)
-        for (at, L, row), (y, B) in zip(rows, truths):
-            J = out_len(L, up, down)
-            assert (bits[row, J:] == 0).all(), ("not zero bits behind the samples", layout, L, row)
-            if layout in (INTERLEAVED, PLANAR):
-                err = np.abs(img[row, :J].astype(np.float64) - y)
-                tol = bound(B, up, down, channels if downmix else 1)
-                if J:
-                    worst = max(worst, float((err / np.maximum(tol, 1e-300)).max()))
-                assert (err <= tol).all(), (layout, channels, downmix, up, down, L, int(np.argmax(err - tol)), float(err.max()))
-                f32.setdefault((row, L), img[row, :J].copy())
-            else:
-                assert (row, L) in f32, "the int16 layouts come after a float32 one"
-                assert img[row, :J].tobytes() == to_s16(f32[(row, L)]).tobytes(), ("int16 is not the conversion of the float32 output", layout, L)
-        # the float32 layouts agree bit for bit with each other (the same arithmetic, another store)
-        for (at, L, row) in rows:
-            if layout in (INTERLEAVED, PLANAR):
-                assert img[row, :out_len(L, up, down)].tobytes() == f32[(row, L)].tobytes()
-    assert (torch.from_numpy(src_np).to("cuda:0") == src.view(-1)).all()
-    return worst
 
 
 @pytest.mark.parametrize("channels,downmix", MIXES)

@@ -24,21 +24,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from test_pcm_resample_gpu import (DST_ROWS, INTERLEAVED, INTERLEAVED_S16, PLANAR, PLANAR_S16, guarded, layout_windows, out_len,  # noqa: E402
-                                   random_source, rows_of, run_layouts)
-from test_resample_cpu import LIMIT_CASES, filter_table, launch_plan, live_taps, passes_text, resample_truth  # noqa: E402
+from pcm_support import (RESAMPLE_DST_ROWS as DST_ROWS, INTERLEAVED, INTERLEAVED_S16, PLANAR, PLANAR_S16, guarded_layout as guarded,
+    layout_windows, out_len, random_source, rows_of, run_layouts)
+from resample_truth import LIMIT_CASES, filter_table, launch_plan, live_taps, passes_text, resample_truth  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def length_for(J, up, down):

@@ -23,24 +23,15 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import stft_truth as st  # noqa: E402
-from test_logmel_cpu import frames_of  # noqa: E402
-from test_stft_cpu import stft_refused_specs  # noqa: E402
+from logmel_truth import frames_of  # noqa: E402
+from stft_truth import stft_refused_specs  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL = 0x5A5A5A5A
 GUARD = 64
 DST_ROWS = st.DST_ROWS
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def guarded(n_floats):

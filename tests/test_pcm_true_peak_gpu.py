@@ -20,21 +20,12 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import r128_cases as rc  # noqa: E402
 import r128_truth as rt  # noqa: E402
+from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 SENTINEL, SAMPLE_SENTINEL = -7.25, -3.5
 T = rc.T
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def launch(ctx, case, order=None, gap=3, extra_rows=1, first=0, fill=9.0, rows=None, sample_peak=True):

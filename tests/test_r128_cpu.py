@@ -18,8 +18,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import loudness_truth as lt  # noqa: E402
 import r128_truth as rt  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from binding_support import imports_of  # noqa: E402
 
 KINDS = {C.c_void_p: "ptr", C.c_int32: "i32", C.c_int64: "i64", C.c_uint64: "u64", C.c_int: "i32", None: "void"}
 

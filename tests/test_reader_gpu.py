@@ -9,19 +9,10 @@ import numpy as np
 import pytest
 
 import helpers
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def oracle_truth(oracle, path, interleave, clip=True):

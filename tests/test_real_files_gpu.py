@@ -6,20 +6,11 @@ import numpy as np
 import pytest
 
 import helpers
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SAMPLES = {"1test.ogg": 17318, "2test.ogg": 315790, "3test.ogg": 288094, "issue6test.ogg": 548160}
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 @pytest.mark.parametrize("name", sorted(SAMPLES))

@@ -8,21 +8,11 @@ import numpy as np
 import pytest
 
 import helpers
-from test_dual_gpu import ROUTES, same_bits
-from test_host_paths_gpu import env, run, stream_major_batch
+from synth_support import env, ROUTES, run, same_bits, stream_major_batch
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 @pytest.mark.parametrize("name", ["2test.ogg", "3test.ogg", "issue6test.ogg"])
@@ -98,7 +88,7 @@ def test_int16_residue_in_device_memory_and_bad_formats(ctx):
 
 
 def test_the_dispatcher_ships_integral_residues_as_int16_and_floats_on_request(ctx):
-    from test_multi_gpu import library, run_dispatcher
+    from multi_support import library, run_dispatcher
     raws = library(("3test.ogg", "issue6test.ogg", "2test.ogg"), 9)
     a = run_dispatcher([0, 0], raws, host_threads=4, streams_per_call=2)
     b = run_dispatcher([0, 0], raws, host_threads=4, streams_per_call=2, float_residue=True)
@@ -112,7 +102,7 @@ def test_residues_that_accumulate_beyond_int16_are_shipped_as_floats(ctx):
     reference's never-cleared decode buffer builds up in row 0 reaches 72000.  The dispatcher and the reader, both with their
     defaults, must give the bits of the float32 hand-over -- the front end has to say that this stream is not integral."""
     import edge_streams as es
-    from test_multi_gpu import run_dispatcher
+    from multi_support import run_dispatcher
     from vorbispizza_amd.front import OggVorbisFile, VorbisReader
     raw, exps, _ = es.accumulating_stream(list(range(16)), 8000)
     assert float(np.abs(es.expected_residue(exps)).max()) >= 32768

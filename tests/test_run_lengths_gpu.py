@@ -36,7 +36,8 @@ import pytest
 
 import helpers
 from helpers import PKT_BLOCK_FLAG, PKT_EOS, PKT_INTERLEAVED, PKT_NEXT_FLAG, PKT_NO_FLOOR, PKT_PREV_FLAG
-from test_host_paths_gpu import env, random_xlist
+from synth_support import env, random_xlist
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -54,16 +55,6 @@ SWITCHES = ("VPZ_NO_BIG", "VPZ_NO_DUAL", "VPZ_NO_GROUP", "VPZ_NO_PAIRS", "VPZ_PA
 # what the cases' cut lines reported: (group of cases, R) and (group, R, staged frames of a run); the last test reads it (it
 # needs the whole file to have run in its process: not under -k, --lf or a split over workers)
 REACHED = set()
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def case(ident, kernel, R, channels, size0, size1, kind, **kw):

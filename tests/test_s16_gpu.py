@@ -9,23 +9,11 @@ import pytest
 
 import helpers
 from helpers import PKT_NO_FLOOR
+from synth_support import to_s16  # noqa: E402
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
-
-
-def to_s16(x):  # AssetTest.cs:131-132
-    return np.clip((x.astype(np.float32) * np.float32(32768.0)).astype(np.int64), -32768, 32767).astype(np.int16)
 
 
 @pytest.mark.parametrize("channels", [1, 2, 3, 6])

@@ -14,6 +14,7 @@ import pytest
 
 import helpers
 import spec_synthesis as spec
+from synth_support import spec_packets, to_s16_wide as to_s16  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -24,26 +25,6 @@ def front():
     ge.build()
     from vorbispizza_amd import front as f
     return f
-
-
-def to_s16(x):  # AssetTest.cs:131-132
-    return np.clip((x.astype(np.float32) * np.float32(32768.0)).astype(np.int64), -32768, 32767)
-
-
-def spec_packets(f, pk, res, posts, counts):
-    out = []
-    C_ = f.channels
-    for i in range(len(pk)):
-        flags = int(pk["flags"][i])
-        if flags & helpers.PKT_NOT_DECODED:
-            continue
-        half = (f.block_size1 if flags & 1 else f.block_size0) // 2
-        off = int(pk["residue_offset"][i])
-        r = res[off: off + C_ * half]
-        r = r.reshape(half, C_).T if flags & helpers.PKT_INTERLEAVED else r.reshape(C_, half)
-        out.append({"flags": flags, "mapping": int(pk["mapping"][i]), "residue": r,
-                    "posts": posts[i * C_:(i + 1) * C_], "post_count": counts[i * C_:(i + 1) * C_]})
-    return out
 
 
 def test_inverse_db_table_is_the_geometric_progression_of_the_spec(oracle):

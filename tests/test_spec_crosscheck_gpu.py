@@ -10,20 +10,11 @@ import numpy as np
 import pytest
 
 import spec_synthesis as spec
-from test_spec_crosscheck_cpu import spec_packets, to_s16
+from synth_support import spec_packets, to_s16_wide as to_s16
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 @pytest.mark.parametrize("name", ["1test.ogg", "2test.ogg", "3test.ogg", "issue6test.ogg"])

@@ -19,7 +19,7 @@ import pytest
 
 import helpers
 from helpers import PKT_BLOCK_FLAG, PKT_EOS, PKT_NEXT_FLAG, PKT_NO_FLOOR, PKT_PREV_FLAG
-from test_host_paths_gpu import env
+from synth_support import env
 
 pytestmark = pytest.mark.gpu
 

@@ -17,9 +17,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import stft_truth as st  # noqa: E402
-import test_csharp_binding_cpu as cs  # noqa: E402
-from test_logmel_cpu import KINDS, U, frames_of  # noqa: E402
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from f32_model import U  # noqa: E402
+from logmel_truth import KINDS, frames_of  # noqa: E402
+from binding_support import imports_of  # noqa: E402
+from stft_truth import stft_refused_specs  # noqa: E402
 
 # (n_fft, win_length, window): centring with an even and an odd remainder, both windows, the limits of win_length
 TABLES = [(512, 512, "hann"), (512, 400, "hamming"), (512, 511, "hann"), (512, 2, "hann"), (1024, 1024, "hamming"), (1024, 1001, "hann"), (2048, 2048, "hann"),
@@ -32,25 +34,6 @@ def capi():
     ge.build()
     from vorbispizza_amd import capi
     return capi
-
-
-def stft_refused_specs(capi):
-    """(what, spec) for every limit of the definition"""
-    good = dict(n_fft=2048, hop=512)
-    cases = [("n_fft 256", dict(n_fft=256, hop=64)), ("n_fft 400", dict(n_fft=400, hop=100)), ("n_fft 513", dict(n_fft=513)), ("n_fft 3000", dict(n_fft=3000)),
-             ("n_fft 16384", dict(n_fft=16384)), ("n_fft 0", dict(n_fft=0, hop=1, win_length=2)), ("n_fft < 0", dict(n_fft=-2048, hop=1, win_length=2)),
-             ("hop < 1", dict(hop=0)), ("hop > n_fft", dict(hop=2049)), ("win_length < 2", dict(win_length=1)), ("win_length 0", dict(win_length=0)),
-             ("win_length > n_fft", dict(win_length=2049))]
-    out = [(what, capi.StftSpec.make(**dict(good, **kw))) for what, kw in cases]
-    for field, value in (("window", 2), ("window", -1), ("output", 3), ("output", -1), ("layout", 2), ("layout", -1)):
-        s = capi.StftSpec.make(**good)
-        setattr(s, field, value)
-        out.append(("%s %d" % (field, value), s))
-    for i in (0, 9):
-        s = capi.StftSpec.make(**good)
-        s.reserved[i] = 1
-        out.append(("a reserved word", s))
-    return out
 
 
 # ---- the table

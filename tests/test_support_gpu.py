@@ -6,20 +6,10 @@ import numpy as np
 import pytest
 
 import helpers
-from test_dual_gpu import ROUTES, same_bits
-from test_host_paths_gpu import env, run, stream_major_batch
+from synth_support import env, ROUTES, run, same_bits, stream_major_batch
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def zero_beyond(pk, res, channels, end_short, end_long, interleaved, fill=0.0):

@@ -7,19 +7,10 @@ import pytest
 import helpers
 from helpers import (PKT_BLOCK_FLAG, PKT_EOS, PKT_INTERLEAVED, PKT_NEXT_FLAG, PKT_NO_FLOOR, PKT_NOT_DECODED,
                      PKT_PREV_FLAG)
+from gpu_context import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import __graft_entry__ as ge
-    ge.build()
-    from vorbispizza_amd import Context
-    c = Context(0)
-    yield c
-    c.close()
 
 
 def build_batch(flags_list, spectra_list, channels, size0=256, size1=2048, extra_flags=0, stream_ids=None,
@@ -539,7 +530,7 @@ def test_floor0_inside_the_stereo_fast_path_equals_the_separate_floor0_pass(ctx,
     the bark indices from floor0_curve_kernel, looked up per bin -- Floor0.cs:188-222 multiplies a run of bins of one bark
     index by one q), instead of planar temp + floor0_apply_kernel + the one-channel kernel (VPZ_NO_F0_FUSED=1).  Same bits;
     and against the oracle.  Coupled, a silent channel, window switching, two calls (the overlap state crosses them)."""
-    from test_host_paths_gpu import env
+    from synth_support import env
     from vorbispizza_amd import Decoder, capi, make_packets
     rng = np.random.default_rng(order * 7 + bark)
     frames = 36

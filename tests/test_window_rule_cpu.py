@@ -13,8 +13,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-import test_csharp_binding_cpu as cs  # noqa: E402  (its parsers)
-from test_mixed_setups_cpu import imports_of  # noqa: E402
+import binding_support as cs  # noqa: E402
+from binding_support import imports_of  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 

@@ -162,6 +162,24 @@ def truth(x, L, F, s):
     return Z, dr, di
 
 
+def truth_of_a_row_within(y, r, L, F, s):
+    """(Z, d_re, d_im) where the row the kernel reads is not y itself but lies within r[j] >= 0 of it (y, r float64 [L]): the transform is
+    linear, so the truth over y moves by at most sum_j r |h_k[j]|, and the kernel's own roundings act on magnitudes of at most |y| + r:
+    d = (N_k + 2) u sum_j (|y| + r) |h_k[j]| + sum_j r |h_k[j]| of either component.  r = 0 is truth()"""
+    f, n = bins(s)
+    margin = n[0] // 2 + 2
+    y, r = np.asarray(y[:L], dtype=np.float64), np.asarray(r[:L], dtype=np.float64)
+    assert (r >= 0).all()
+    ye, me, re_ = extend(y, L, F, s, margin), extend(np.abs(y) + r, L, F, s, margin), extend(r, L, F, s, margin)
+    T = 1 + F // s["hop"]
+    Z, dr, di = np.zeros((T, len(n)), dtype=np.complex128), np.zeros((T, len(n))), np.zeros((T, len(n)))
+    for k, (hr, hi) in enumerate(kernels64(s)):
+        X, M, R = (frames_of(e, margin, T, s["hop"], -(n[k] // 2), n[k]) for e in (ye, me, re_))
+        Z[:, k] = X @ hr + 1j * (X @ hi)
+        dr[:, k], di[:, k] = (n[k] + 2) * U * (M @ np.abs(hr)) + R @ np.abs(hr), (n[k] + 2) * U * (M @ np.abs(hi)) + R @ np.abs(hi)
+    return Z, dr, di
+
+
 def check_output(output, got, Z, dr, di):
     """`got` -- complex64 or float32 [T, n_bins] -- within the bound of the truth, every element; exactly zero where the bound is.  Re is
     held to d of hr, Im to d of hi; power and magnitude take the larger of the two as the header's d.  Returns the largest error / bound"""

@@ -486,6 +486,19 @@ def bits_of_any(t):
     return torch.view_as_real(t).view(torch.int32) if t.is_complex() else t.view(torch.int32)
 
 
+# the CQT call's end-to-end truth test (tests/test_multi_cqt_gpu.py) and the CPU case that holds its bound to the reference arithmetic
+# (tests/test_cqt_cpu.py): N_0 = 3372, so the reflection reaches 1686 samples
+CQT_END_TO_END = dict(sample_rate=22050, f_min=110.0, n_bins=48, bins_per_octave=12, hop=256, filter_scale=1.0, gamma=0.0, window="hann",
+                      scale="sqrt_length", pad="reflect")
+
+
+def end_to_end_entries():
+    """a 9000-sample window of a recorded stream (golden/3test.ogg, stereo) and a 5000-sample one of the synthetic stereo stream: the
+    STFT call's end-to-end entries"""
+    fixture, synthetic = Stream(golden("3test.ogg"), False), streams()["stereo_coupled_res2_30"]
+    return [(fixture, fixture.bounds[len(fixture.bounds) // 2] + 11, 9000), (synthetic, synthetic.bounds[3] + 7, 5000)]
+
+
 def refused_entries_by_channel(spec):
     from vorbispizza_amd import multi
     rate = spec["sample_rate"]

@@ -239,6 +239,37 @@ def test_the_restatement_stays_inside_the_bound_on_every_case(name):
     assert max(worst.values()) < 1.0
 
 
+def test_the_end_to_end_bound_admits_the_reference_arithmetic(oracle):
+    """tests/test_multi_cqt_gpu.py's end-to-end spec over its synthetic entry, without a device: the window of the stream's whole decode
+    (the CPU oracle's: no decoder on the device), resampled in float64 to y; the float32 restatement of the chains over y rounded to
+    float32 stays within d = (N_k + 2) u sum |y| |h_k| of the direct sum over y -- the multi test's bound with r = 0"""
+    from multi_support import CQT_END_TO_END, end_to_end_entries, out_len, ratio
+    from resample_truth import resample_truth
+    rate = CQT_END_TO_END["sample_rate"]
+    s = dict(ct.DEFAULT, **dict(CQT_END_TO_END, sample_rate=float(rate)))
+    assert ct.bins(s)[1][0] == 3372 and ct.bins(s)[1][0] // 2 == 1686
+    stream, a, n = end_to_end_entries()[1]
+    f = stream.f
+    pk, res, posts, counts = f.decode_packets()
+    fs = oracle.FlooredStream(f.channels, f.block_size0, f.block_size1, pk, res, posts, counts, floors=f.floors, mappings=f.mappings)
+    assert fs.run() == stream.total and stream.channels == 2 and a + n <= stream.total
+    up, down = ratio(stream, rate)
+    y, _ = resample_truth(fs.pcm[:, a: a + n].T, up, down, False)
+    J = out_len(n, up, down)
+    assert y.shape == (J, 2) and 2400 <= J <= 2600
+    F = J + 3 * s["hop"]
+    worst = 0.0
+    for c in range(2):
+        Z, dr, di = ct.truth_of_a_row_within(y[:, c], np.zeros(J), J, F, s)
+        plain = ct.truth(y[:, c], J, F, s)
+        assert all(np.array_equal(p, q) for p, q in zip((Z, dr, di), plain))  # (r = 0 is the stage's own truth and bound)
+        (re_, im_), = ct.chains32([(y[:, c].astype(np.float32), J)], F, s)
+        worst = max(worst, ct.check_output("complex", ct.outputs32(re_, im_)["complex"], Z, dr, di))
+        assert (dr == 0).any() and (np.abs(Z) > 1e-3).any()
+    print("restatement error / bound, end to end: %.4f" % worst)
+    assert worst < 1.0
+
+
 def test_a_wrong_coefficient_or_order_fails_the_value_check():
     """what the bound cannot see the restatement does: one coefficient off by one ulp, or the chain run in descending j, changes values"""
     s = ct.spec_of(n_bins=3)

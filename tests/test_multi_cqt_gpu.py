@@ -3,8 +3,9 @@
 The call is vpzm_decode_ranges_resampled into the lane's temporary followed by vpz_pcm_cqt, so on the fixture streams it must equal
 decode_ranges_resampled followed by capi.pcm_cqt bit for bit -- on the host route and with gpu_entropy, with one and two groups, mono
 and stereo (two rows per entry); the statuses are the STFT call's, the rows of an entry that delivered nothing are zeros in all its
-channels, VPZM_FAIL_DELIVERY ends members as VPZM_E_SYNTH with zero rows, and a spec outside the limits is VPZM_E_ARG.  (The stage's
-own values are tests/test_pcm_cqt_gpu.py's business.)"""
+channels, VPZM_FAIL_DELIVERY ends members as VPZM_E_SYNTH with zero rows, and a spec outside the limits is VPZM_E_ARG.  The stage's
+own values are tests/test_pcm_cqt_gpu.py's business; one test here holds the whole chain to the float64 truth end to end (its docstring
+states the bound)."""
 import ctypes as C
 import os
 import sys
@@ -16,9 +17,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import cqt_truth as ct  # noqa: E402
 from cqt_truth import cqt_refused_specs  # noqa: E402
-from multi_support import (bits_of_any as bits, channels_of, FIELDS, mixed_entries, most_outputs, OPTIONS,  # noqa: E402
+from multi_support import (bits_of_any as bits, channels_of, CQT_END_TO_END, end_to_end_entries, FIELDS, logmel_by_hand, logmel_call,  # noqa: E402
+    LOGMEL_VARIANTS, MELSPEC_VARIANTS, melspec_by_hand, melspec_call, mixed_entries, most_outputs, OPTIONS, out_len, RATE, ratio,
     refused_entries_by_channel as refused_entries, resampled_call, streams)
+from resample_truth import bound, resample_truth  # noqa: E402
 from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
@@ -210,3 +214,69 @@ def test_a_spec_outside_the_limits_is_refused(ctx):
         assert L.vpzm_decode_ranges_cqt(*args(spec=C.byref(zero), frames=reach(spec) - 1)) == multi.OK  # (the zero mode takes the shorter row)
     finally:
         d.close()
+
+
+def test_the_calls_in_turn_on_one_dispatcher(ctx):
+    """the lane's temporary -- mono rows for the older feature calls, planar channels of another row layout for this one -- and the
+    context's table caches serve call after call: the log-mel call, the melspec call and the plain batch still deliver their old bits
+    beside both CQT variants, twice round"""
+    import torch
+    from vorbispizza_amd import multi
+    entries = mixed_entries()[::3]
+    frames = max(frames_for(entries, spec, 0) for spec in VARIANTS)
+    wants = [by_hand(ctx, entries, frames, spec)[0] for spec in VARIANTS]
+    old_want = logmel_by_hand(ctx, entries, frames, LOGMEL_VARIANTS[0])[0]
+    mel_want = melspec_by_hand(ctx, entries, frames, MELSPEC_VARIANTS[0])[0]
+    stereo = resampled_call(entries, RATE, 2, frames, True, False, False)[0]
+    d = multi.Dispatcher([0, 0], host_threads=4, streams_per_call=4, gpu_entropy=True)
+    try:
+        for _ in range(2):
+            for spec, want in zip(VARIANTS, wants):
+                assert torch.equal(bits(cqt_call(entries, frames, spec, dispatcher=d)[0]), bits(want))
+                assert torch.equal(bits(logmel_call(entries, frames, LOGMEL_VARIANTS[0], dispatcher=d)[0]), bits(old_want))
+                assert torch.equal(bits(melspec_call(entries, frames, MELSPEC_VARIANTS[0], dispatcher=d)[0]), bits(mel_want))
+                assert torch.equal(bits(resampled_call(entries, RATE, 2, frames, True, False, False, dispatcher=d)[0]), bits(stereo))
+    finally:
+        d.close()
+
+
+def test_a_fixture_window_against_the_float64_truth_end_to_end(ctx):
+    """One window of a recorded stream (golden/3test.ogg, stereo) and one of the synthetic stereo stream, through decode, resample to
+    22 050 Hz and the complex CQT of both channels (48 bins from 110 Hz, hop 256, reflected: N_0 = 3372), against the float64
+    restatements of both definitions over the host's stream-by-stream whole decode of the same window.  The row holds the longest window's
+    output samples and three hops of padding, so the last frames of the high bins lie wholly in zeros.
+
+    THE BOUND, derived and not measured.  The resampled row the kernel reads differs from its float64 truth y by at most
+    r[j] = bound(B, up, down, 1) (tests/test_resample_cpu.py, the resample's documented bound).  The CQT is linear in the row, so Re moves
+    by at most sum_j r |hr_k[j]|; on top come the kernel's own roundings on the row it read, whose magnitudes are at most |y| + r.  So Re
+    lies within d_re = (N_k + 2) u sum_j (|y| + r) |hr_k[j]| + sum_j r |hr_k[j]| of cqt_truth's direct sum over y, and Im the same with
+    hi_k (cqt_truth.truth_of_a_row_within); tests/test_cqt_cpu.py holds the float32 restatement of the chains to the same d with r = 0.
+
+    Largest error / bound observed on an MI355X: 0.0143 (the restatement's on the synthetic entry alone, without a device: 0.0143)."""
+    rate, hop = CQT_END_TO_END["sample_rate"], CQT_END_TO_END["hop"]
+    s = dict(ct.DEFAULT, **dict(CQT_END_TO_END, sample_rate=float(rate)))
+    spec = dict(CQT_END_TO_END, channels=2, mono=False, output="complex", bins_first=True)
+    assert ct.bins(s)[1][0] == 3372
+    entries = end_to_end_entries()
+    frames = most_outputs(entries, rate) + 3 * hop
+    assert frames >= reach(spec)
+    got, results, _ = cqt_call(entries, frames, spec, gpu_entropy=False)
+    img = got.cpu().numpy().transpose(0, 1, 3, 2)  # [row][channel][T][n_bins]
+    worst = 0.0
+    for k, (stream, a, n) in enumerate(entries):
+        up, down = ratio(stream, rate)
+        m = stream.f.window(a, n)["samples"]
+        J = out_len(m, up, down)
+        assert results["status"][k] == 0 and results["samples"][k] == J and m == n and stream.channels == 2
+        y, B = resample_truth(stream.truth(ctx, False)[a: a + m], up, down, False)
+        r = bound(B, up, down, 1)
+        for c in range(2):
+            Z, dr, di = ct.truth_of_a_row_within(y[:, c], r[:, c], J, frames, s)
+            er, ei = np.abs(img[k, c].real.astype(np.float64) - Z.real), np.abs(img[k, c].imag.astype(np.float64) - Z.imag)
+            assert np.isfinite(img[k, c].real).all() and np.isfinite(img[k, c].imag).all()
+            assert (er <= dr).all() and (ei <= di).all(), (k, c, float((er / np.maximum(dr, 1e-300)).max()), float((ei / np.maximum(di, 1e-300)).max()))
+            assert (img[k, c].real[dr == 0] == 0).all() and (img[k, c].imag[di == 0] == 0).all()
+            assert (dr == 0).any() and (di == 0).any() and (np.abs(Z) > 1e-3).any()
+            worst = max(worst, float((er[dr > 0] / dr[dr > 0]).max()), float((ei[di > 0] / di[di > 0]).max()))
+        assert not np.array_equal(img[k, 0], img[k, 1])  # (two channels, not one twice)
+    print("end to end: largest error / bound %.4f" % worst)

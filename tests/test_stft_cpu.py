@@ -60,6 +60,15 @@ def test_the_table_is_the_restatement_rounded_once(capi, n_fft, win_length, wind
             assert np.array_equal(w, capi.melspec_twiddles(n_fft)[0])
 
 
+@pytest.mark.parametrize("n_fft", [2048, 4096, 8192])
+def test_the_mel_stage_reads_the_same_table(capi, n_fft):
+    """vpz_melspec_twiddles is vpz_stft_table with hann over the whole transform, bit for bit, window and twiddles: the two kernels'
+    networks read one table (csrc/melspec_tables.hpp's twiddle_fill fills both)"""
+    (w_mel, t_mel), (w_stft, t_stft) = capi.melspec_twiddles(n_fft), capi.stft_table(n_fft, n_fft, "hann")
+    assert w_mel.dtype == w_stft.dtype == t_mel.dtype == t_stft.dtype == np.float32 and w_mel.shape == (n_fft,) and t_mel.shape == (n_fft, 2)
+    assert np.array_equal(w_mel.view(np.uint32), w_stft.view(np.uint32)) and np.array_equal(t_mel.view(np.uint32), t_stft.view(np.uint32))
+
+
 def test_the_windows_are_torchs():
     import torch
     for n_fft, win_length, window in TABLES:

@@ -18,6 +18,7 @@
 //   dimension.
 //   LDS floats: 2 n_fft (the two complex arrays) + (Tt - 1) hop + n_fft (the span) + Tt * 256 (the mel tile, sized for the most bands).
 //   A tile whose span lies wholly in a row's zeros stores the silence value without computing.
+// The complex arithmetic and the span staging are real_fft.hpp's, shared with pcm_stft.hip, whose passes are this network once more.
 // All element indices are 64-bit.  No scratch memory.  Built with -ffp-contract=off: every fused step is written as one.
 #include <algorithm>
 #include <cstring>
@@ -27,6 +28,7 @@
 #include "vpz_internal.hpp"
 #include "device_table.hpp"
 #include "melspec_tables.hpp"
+#include "real_fft.hpp"
 #include "../../include/vorbispizza_pcm_melspec.h"
 
 namespace vpz {
@@ -55,14 +57,6 @@ struct MelspecArgs {
     float floor, silence;
 };
 
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-// t * v as the header writes it: one rounded product and one fused multiply-add per component
-__device__ __forceinline__ float2 cmul(float2 t, float2 v)
-{
-    return make_float2(__builtin_fmaf(v.x, t.x, -(v.y * t.y)), __builtin_fmaf(v.x, t.y, v.y * t.x));
-}
-
 template <int N>
 __global__ __launch_bounds__(kMsBlock) void pcm_melspec_kernel(const MelspecArgs a)
 {
@@ -77,7 +71,6 @@ __global__ __launch_bounds__(kMsBlock) void pcm_melspec_kernel(const MelspecArgs
     const int nt = (int)(T - t0 < Tt ? T - t0 : Tt);  // the tile's frames (the grid covers T)
     const int64_t lo = t0 * hop - H;                  // the span's first extended sample
     const int count = (nt - 1) * hop + N;             // its samples
-    const int64_t hi = lo + count - 1;
     const int items = nt * n_mels;
     const float2 *const win = reinterpret_cast<const float2 *>(a.table);
     const float2 *const tw = reinterpret_cast<const float2 *>(a.table + N);
@@ -101,15 +94,9 @@ __global__ __launch_bounds__(kMsBlock) void pcm_melspec_kernel(const MelspecArgs
     for (int r = blockIdx.y; r < a.n_rows; r += gridDim.y) {
         const vpz_pack_row d = a.rows[r];
         const int64_t L = d.samples;
-        // every sample of the span is one of the row's zeros (behind F - 1 the span reflects: its last sample reaches back furthest)
-        const bool silent = L == 0 || (lo >= L && (hi <= F - 1 || 2 * (F - 1) - hi >= L));  // (the same for the whole workgroup)
+        const bool silent = span_silent(lo, count, F, L);
         if (!silent) {
-            const float *in_row = a.src + d.src;
-            for (int i = t; i < count; i += kMsBlock) {
-                const int64_t e = lo + i;
-                const int64_t x = e < 0 ? -e : e > F - 1 ? 2 * (F - 1) - e : e;
-                span[i] = x < L ? in_row[x] : 0.0f;
-            }
+            span_stage<kMsBlock>(span, a.src + d.src, lo, count, F, L, t);
             __syncthreads();
             for (int f = 0; f < nt; ++f) {
                 const float *x = span + f * hop;
@@ -238,18 +225,6 @@ int melspec_bank_for(Context *ctx, const vpz_logmel_spec &s, const Context::Logm
 // floats of a tile's LDS at `Tt` frames: the two complex arrays, the span, the mel tile
 int lds_floats(int n_fft, int hop, int Tt) { return 2 * n_fft + (Tt - 1) * hop + n_fft + Tt * kMsMelRoom; }
 
-template <int N>
-int launch(Context *ctx, const MelspecArgs &a, dim3 grid, size_t lds)
-{
-    // (the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never lower it under each other)
-    VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&pcm_melspec_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(sizeof(float) * kMsLdsFloats)));
-    pcm_melspec_kernel<N><<<grid, kMsBlock, lds, ctx->stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, VPZ_E_HIP, "pcm_melspec kernel launch", e);
-    return VPZ_OK;
-}
-
 }  // namespace
 
 }  // namespace vpz
@@ -327,7 +302,8 @@ extern "C" int vpz_pcm_melspec(vpz_context *c, const void *src_dev, int64_t src_
     a.silence = a.log ? (float)log10((double)a.floor) : 0.0f;
     const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kMsMaxGridY));
     const size_t lds = sizeof(float) * (size_t)vpz::lds_floats(s.n_fft, s.hop, a.Tt);
-    if (s.n_fft == 2048) return vpz::launch<2048>(ctx, a, grid, lds);
-    if (s.n_fft == 4096) return vpz::launch<4096>(ctx, a, grid, lds);
-    return vpz::launch<8192>(ctx, a, grid, lds);
+    void (*const kernel)(vpz::MelspecArgs) = s.n_fft == 2048   ? &vpz::pcm_melspec_kernel<2048>
+                                             : s.n_fft == 4096 ? &vpz::pcm_melspec_kernel<4096>
+                                                               : &vpz::pcm_melspec_kernel<8192>;
+    return vpz::launch_in_lds(ctx, kernel, "pcm_melspec kernel launch", a, grid, vpz::kMsBlock, lds, sizeof(float) * vpz::kMsLdsFloats);
 }

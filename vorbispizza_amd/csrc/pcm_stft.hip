@@ -1,7 +1,7 @@
 // vpz_pcm_stft and vpz_stft_table (include/vorbispizza_pcm_stft.h, which states the definition; the network is
 // include/vorbispizza_pcm_melspec.h's): windows of a float32 device PCM array as short-time Fourier spectrograms -- complex, magnitude
-// or power -- with transforms of 512 to 8192 samples, one launch.  The butterfly code is pcm_melspec.hip's, copied: that file, its
-// header and its tests stand as they are.
+// or power -- with transforms of 512 to 8192 samples, one launch.  The complex arithmetic and the span staging are real_fft.hpp's; the
+// passes are the network of pcm_melspec.hip, and tests/test_rfft_one_network_gpu.py holds the two kernels to each other bit for bit.
 //
 // The mapping:
 //   a TILE is Tt consecutive frames [t0, t0 + Tt) of one destination row (Tt = 32, 16, 8, 4, 2 or 1: the largest whose LDS fits, chosen
@@ -31,6 +31,7 @@
 #include "vpz_internal.hpp"
 #include "device_table.hpp"
 #include "stft_tables.hpp"
+#include "real_fft.hpp"
 #include "../../include/vorbispizza_pcm_stft.h"
 
 namespace vpz {
@@ -51,14 +52,6 @@ struct StftArgs {
     int32_t n_rows, hop, output, frames_first;
     int32_t Tt, span_cap;  // frames of a tile; floats of the span (even)
 };
-
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-// t * v as the header writes it: one rounded product and one fused multiply-add per component
-__device__ __forceinline__ float2 cmul(float2 t, float2 v)
-{
-    return make_float2(__builtin_fmaf(v.x, t.x, -(v.y * t.y)), __builtin_fmaf(v.x, t.y, v.y * t.x));
-}
 
 // one bin of one frame on its way out: `at` is the value's index in the destination row or in the stage
 __device__ __forceinline__ void emit(float *to, int64_t at, float2 X, int output)
@@ -90,7 +83,6 @@ __global__ __launch_bounds__(kStBlock) void pcm_stft_kernel(const StftArgs a)
     const int nt = (int)(T - t0 < Tt ? T - t0 : Tt);  // the tile's frames (the grid covers T)
     const int64_t lo = t0 * hop - H;                  // the span's first extended sample
     const int count = (nt - 1) * hop + N;             // its samples
-    const int64_t hi = lo + count - 1;
     const float2 *const win = reinterpret_cast<const float2 *>(a.table);
     const float2 *const tw = reinterpret_cast<const float2 *>(a.table + N);
     // what a lane reads from the table does not depend on the frame: its window values, the twiddles of its butterflies in every pass
@@ -112,15 +104,9 @@ __global__ __launch_bounds__(kStBlock) void pcm_stft_kernel(const StftArgs a)
     for (int r = blockIdx.y; r < a.n_rows; r += gridDim.y) {
         const vpz_pack_row d = a.rows[r];
         const int64_t L = d.samples;
-        // every sample of the span is one of the row's zeros (behind F - 1 the span reflects: its last sample reaches back furthest)
-        const bool silent = L == 0 || (lo >= L && (hi <= F - 1 || 2 * (F - 1) - hi >= L));  // (the same for the whole workgroup)
+        const bool silent = span_silent(lo, count, F, L);
         if (!silent) {
-            const float *in_row = a.src + d.src;
-            for (int i = t; i < count; i += kStBlock) {
-                const int64_t e = lo + i;
-                const int64_t x = e < 0 ? -e : e > F - 1 ? 2 * (F - 1) - e : e;
-                span[i] = x < L ? in_row[x] : 0.0f;
-            }
+            span_stage<kStBlock>(span, a.src + d.src, lo, count, F, L, t);
             __syncthreads();
             for (int f0 = 0; f0 < nt; f0 += G) {
                 const int f = f0 + g;
@@ -239,18 +225,6 @@ int lds_floats(const vpz_stft_spec &s, int Tt)
     return side_by_side(s.n_fft) * 2 * s.n_fft + span_floats(s.n_fft, s.hop, Tt) + stage;
 }
 
-template <int N>
-int launch(Context *ctx, const StftArgs &a, dim3 grid, size_t lds)
-{
-    // (the attribute is the kernel's, not the launch's: always the whole budget, so that two contexts never lower it under each other)
-    VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&pcm_stft_kernel<N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)(sizeof(float) * kStLdsFloats)));
-    pcm_stft_kernel<N><<<grid, kStBlock, lds, ctx->stream>>>(a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(ctx, VPZ_E_HIP, "pcm_stft kernel launch", e);
-    return VPZ_OK;
-}
-
 }  // namespace
 
 }  // namespace vpz
@@ -316,11 +290,13 @@ extern "C" int vpz_pcm_stft(vpz_context *c, const void *src_dev, int64_t src_ele
     a.span_cap = vpz::span_floats(s.n_fft, s.hop, a.Tt);
     const dim3 grid((unsigned)blocks, (unsigned)std::min<int64_t>(n_rows, vpz::kStMaxGridY));
     const size_t lds = sizeof(float) * (size_t)vpz::lds_floats(s, a.Tt);
+    void (*kernel)(vpz::StftArgs) = nullptr;
     switch (s.n_fft) {
-    case 512: return vpz::launch<512>(ctx, a, grid, lds);
-    case 1024: return vpz::launch<1024>(ctx, a, grid, lds);
-    case 2048: return vpz::launch<2048>(ctx, a, grid, lds);
-    case 4096: return vpz::launch<4096>(ctx, a, grid, lds);
-    default: return vpz::launch<8192>(ctx, a, grid, lds);
+    case 512: kernel = &vpz::pcm_stft_kernel<512>; break;
+    case 1024: kernel = &vpz::pcm_stft_kernel<1024>; break;
+    case 2048: kernel = &vpz::pcm_stft_kernel<2048>; break;
+    case 4096: kernel = &vpz::pcm_stft_kernel<4096>; break;
+    default: kernel = &vpz::pcm_stft_kernel<8192>; break;
     }
+    return vpz::launch_in_lds(ctx, kernel, "pcm_stft kernel launch", a, grid, vpz::kStBlock, lds, sizeof(float) * vpz::kStLdsFloats);
 }

@@ -1,10 +1,11 @@
 // The table of vpz_pcm_stft (include/vorbispizza_pcm_stft.h states the definition): host code only, no device, so that
 // tests/test_stft_cpu.py can hold vpz_stft_table to a float64 restatement.  Every value is evaluated in double and rounded once to
-// float32.  The twiddles are melspec_tables.hpp's, value for value.
+// float32.  The twiddles are melspec_tables.hpp's twiddle_fill.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
+#include "melspec_tables.hpp"
 #include "../../include/vorbispizza_pcm_stft.h"
 
 namespace vpz {
@@ -27,7 +28,7 @@ inline bool stft_spec_ok(const vpz_stft_spec &s)
     return true;
 }
 
-// table[0 .. n) = w[m]: g over win_length, centred in n; table[n + 2k], table[n + 2k + 1] = cos, -sin of 2 pi k / n, k = 0 .. n-1: 3 n floats
+// table[0 .. n) = w[m]: g over win_length, centred in n; table[n ..) = the twiddles: 3 n floats
 inline void stft_table_fill(int n, int win_length, int window, float *table)
 {
     const double two_pi = 6.283185307179586476925286766559;
@@ -37,13 +38,7 @@ inline void stft_table_fill(int n, int win_length, int window, float *table)
         const int j = m - left;
         table[m] = j < 0 || j >= win_length ? 0.0f : (float)(a0 - a1 * cos(two_pi * (double)j / (double)win_length));
     }
-    for (int k = 0; k < n; ++k) {
-        const double a = two_pi * (double)k / (double)n;
-        // (on the axes the values are exact, not the 1e-16 that cos and sin give at a rounded multiple of pi / 2; no -0.0 either)
-        const double c = 4 * k == n || 4 * k == 3 * n ? 0.0 : cos(a), s = k == 0 || 2 * k == n ? 0.0 : -sin(a);
-        table[n + 2 * k] = (float)c;
-        table[n + 2 * k + 1] = (float)s;
-    }
+    twiddle_fill(n, table + n);
 }
 
 }  // namespace vpz

@@ -152,6 +152,19 @@ bool layout_of(int32_t layout, bool *s16, bool *planar);
         if (_e != hipSuccess) return vpz::set_error((ctx), VPZ_E_HIP, #expr, _e); \
     } while (0)
 
+// a kernel that takes its arguments as one struct and may use `lds_budget` bytes of dynamic LDS: set the attribute, launch with `lds`
+// bytes on the context's stream, report as `what`.  (The attribute is the kernel's, not the launch's: always the whole budget, so that
+// two contexts never lower it under each other.)
+template <class Args>
+int launch_in_lds(Context *ctx, void (*kernel)(Args), const char *what, const Args &a, dim3 grid, int block, size_t lds, size_t lds_budget)
+{
+    VPZ_HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
+    kernel<<<grid, block, lds, ctx->stream>>>(a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(ctx, VPZ_E_HIP, what, e);
+    return VPZ_OK;
+}
+
 // ---- kernel launchers (imdct_fast.hip / imdct_exact.hip / synth_kernels.hip) ----
 // spectra [count][n/2] -> out [count][n], device pointers, asynchronous on `stream`.
 // optional gather lists (float offsets of each block's spectrum / output) serve the three-pass decoder path

@@ -13,11 +13,16 @@ The bound (u = 2^-24).  For a frame with extended samples x[m] and window w[m], 
 order).  Then
     e_P = 2 |re| d + 2 |im| d + 2 d^2 + 3 u P
     e_M = e_P W^T + (B + 2) u M        B: the largest live-bin count of a band
-and the values go through test_logmel_cpu's check_log / check_power as they stand."""
+and the values go through test_logmel_cpu's check_log / check_power as they stand.
+
+The whole stage restated in float32 (restated_power32): network32 on the float32 frames, P = fma32(re, re, im * im), one fma32 chain per
+band over its live bins, k ascending from 0.0, with the bank the library's host code returns.  tests/test_pcm_melspec_limits_gpu.py holds
+the kernel to it bit for bit, over CASES and over LIMIT_CASES: the hops on either side of every change of tile at n_fft 4096 and 8192."""
 import math
 import os
 import re
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -27,7 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from f32_model import U  # noqa: E402,F401
 from logmel_truth import extend, frames_of, mel_weights64  # noqa: E402,F401
-from logmel_truth import refused_specs  # noqa: E402
+from logmel_truth import refused_specs, silence_value  # noqa: E402
 from kernel_text import constants_of  # noqa: E402
 import f32_model  # noqa: E402
 from f32_model import fma32 as _fma  # noqa: E402
@@ -126,10 +131,70 @@ def proxy_mel(X, n_fft, W, w=None, t=None):
     return P.astype(np.float64) @ W.astype(np.float32).astype(np.float64).T
 
 
+# ---- the whole stage in float32
+def band_sums32(P, first, count, weights):
+    """[T, n_mels] float32 of the power P [T, n_fft / 2 + 1]: acc = fma32(w[i], P[first + i], acc) over a band's live bins, i ascending"""
+    start = np.concatenate([[0], np.cumsum(count)[:-1]])
+    bins = np.ascontiguousarray(P.T)  # (a step gathers whole bins: rows of this)
+    acc = np.zeros((count.size, P.shape[0]), dtype=np.float32)
+    for i in range(int(count.max())):
+        live = np.nonzero(i < count)[0]
+        acc[live] = _fma(weights[start[live] + i][:, None], bins[first[live] + i], acc[live])
+    return np.ascontiguousarray(acc.T)
+
+
+_POOL = []
+
+
+def power32(X, n_fft):
+    """P = fma32(re, re, im * im), float32 [T, n_fft / 2 + 1], of the float32 frames X.  Frames that are equal bit for bit to the first
+    all-zero one are restated once; the others in blocks of 64 frames, side by side (numpy leaves the interpreter's lock in its loops)"""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    assert X.ndim == 2 and X.shape[1] == n_fft
+
+    def block(Y):
+        re_, im_ = network32(Y, n_fft)
+        return _fma(re_, re_, im_ * im_)
+
+    P = np.empty((X.shape[0], n_fft // 2 + 1), dtype=np.float32)
+    zero = (X.view(np.uint32) == 0).all(axis=1)
+    if zero.any():
+        P[zero] = block(X[zero][:1])
+    rest = np.nonzero(~zero)[0]
+    parts = [rest[i: i + 64] for i in range(0, rest.size, 64)]
+    if len(parts) > 1 and not _POOL:
+        _POOL.append(ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))))
+    for at, out in zip(parts, _POOL[0].map(lambda at: block(X[at]), parts) if len(parts) > 1 else [block(X[at]) for at in parts]):
+        P[at] = out
+    return P
+
+
+def restated_power32(X, n_fft, first, count, weights):
+    """the stage's power output, float32 [T, n_mels], of the float32 frames X [T, n_fft]: network32 with the library's tables, the fused
+    power, and the band sums of the library's bank (first, count, weights as vpz_melspec_filterbank returns them)"""
+    assert weights.dtype == np.float32
+    return band_sums32(power32(X, n_fft), np.asarray(first, dtype=np.int64), np.asarray(count, dtype=np.int64), weights)
+
+
+def check_log_exact(got, acc32, floor):
+    """the log10 mode against the restated power acc32, no element exempt: the silence value's bits where acc32 <= float32(floor), else
+    within 4 u max(1, |got|) of log10(acc32) -- what check_log allows log10f, and nothing for the power: that is known by its bits.
+    Returns the largest error / bound ratio."""
+    got, acc32 = np.asarray(got, dtype=np.float32), np.asarray(acc32, dtype=np.float32)
+    assert got.shape == acc32.shape
+    below = acc32 <= np.float32(floor)
+    assert (got[below].view(np.uint32) == silence_value(floor).view(np.uint32)).all()
+    g = got[~below].astype(np.float64)
+    err = np.abs(g - np.log10(acc32[~below].astype(np.float64)))
+    tol = 4 * U * np.maximum(1.0, np.abs(g))
+    assert (err <= tol).all(), float((err / tol).max())  # (a NaN fails here)
+    return float((err / tol).max()) if g.size else 0.0
+
+
 # ---- the launch plan, restated
 # the constants of csrc/pcm_melspec.hip's plan as the file states them
-kernel_constants = constants_of("pcm_melspec.hip", ("kMsBlock", "kMsLdsFloats", "kMsMaxGridY", "kMsMelRoom", "kMsTileA", "kMsTileB",
-                                "kMsTileC"))
+kernel_constants = constants_of("pcm_melspec.hip", ("kMsBlock", "kMsLdsFloats", "kMsMaxGridY", "kMsMelRoom", "kMsAhead", "kMsTileA",
+                                "kMsTileB", "kMsTileC"))
 
 
 def lds_floats(n_fft, hop, Tt, k):
@@ -147,9 +212,10 @@ def tile_plan(n_fft, hop, k=None):
 
 
 # ---- the cases of tests/test_pcm_melspec_gpu.py
-# name: (sample_rate, n_fft, hop, n_mels, f_min, f_max, mel_scale, mel_norm, F, the tile the plan takes).  f_max None: Nyquist, so that bin
-# n_fft / 2 is live.  Every case carries rows of L = F, F - 1 (the right-hand reflection starts at the one zero), F - n_fft / 4 (it reads
-# the zero tail), about a third (silent tiles behind it), 1 and 0.
+# name: (sample_rate, n_fft, hop, n_mels, f_min, f_max, mel_scale, mel_norm, F, the tile the plan takes).  f_max None: Nyquist, so that the
+# bands reach bin n_fft / 2 (live where the rounding of the mel points leaves it a weight: tests/test_melspec_cpu.py).  Every case
+# carries rows of L = F, F - 1 (the right-hand reflection starts at the one zero), F - n_fft / 4 (it reads the zero tail), about a third
+# (silent tiles behind it), 1 and 0.
 def _smallest(n_fft, hop, tile):
     return (44100, n_fft, hop, 16, 0.0, None, "slaney", "slaney", n_fft // 2 + 1, tile)
 
@@ -173,9 +239,45 @@ CASES = {
 }
 DST_ROWS = 9
 
+# ---- the cases of tests/test_pcm_melspec_limits_gpu.py, besides CASES: the last hop of a tile size and the first of the next at n_fft 4096
+# and 8192 (the 2048 kernel takes 16 frames at every hop), and the 75 % overlap of 8192 that fills the LDS to the float.  F = hop (T - 1) + 5.
+# The banks: 256 htk bands up to Nyquist where an 8192 launch asks for the most LDS, both scales and both norms, f_max None in most, and
+# one bank with bands narrower than a bin.
+_WIDE = (48000, 8192, 2048, 256, 0.0, None, "htk", "slaney")
+LIMIT_CASES = {
+    "tile16_last_4096_1638": (44100, 4096, 1638, 128, 0.0, None, "slaney", "slaney", 1638 * 16 + 5, 16),   # T = 17: a whole tile and one of 1
+    "tile8_first_4096_1639": (48000, 4096, 1639, 64, 20.0, 20000.0, "htk", None, 1639 * 8 + 5, 8),         # T = 9
+    "tile8_last_4096_3803": (44100, 4096, 3803, 128, 0.0, None, "slaney", "slaney", 3803 * 8 + 5, 8),      # T = 9; the 4096 kernel's most LDS
+    "tile2_first_4096_3804": (44100, 4096, 3804, 128, 0.0, 500.0, "slaney", None, 3804 * 2 + 5, 2),        # T = 3; bands narrower than a bin
+    "tile16_last_8192_819": (48000, 8192, 819, 256, 0.0, None, "htk", None, 819 * 16 + 5, 16),             # T = 17
+    "tile8_first_8192_820": (22050, 8192, 820, 64, 0.0, None, "slaney", "slaney", 820 * 8 + 5, 8),         # T = 9
+    "full_lds_8192_2048_T7": _WIDE + (2048 * 6 + 5, 8),                                                    # the whole 160 KiB
+    "full_lds_8192_2048_T8": _WIDE + (2048 * 7 + 5, 8),
+    "full_lds_8192_2048_T9": _WIDE + (2048 * 8 + 5, 8),
+    "tile2_first_8192_2049": (16000, 8192, 2049, 128, 50.0, 7600.0, "htk", "slaney", 2049 * 2 + 5, 2),     # T = 3
+}
+assert not set(CASES) & set(LIMIT_CASES)
+
+
+def case_of(name):
+    return CASES[name] if name in CASES else LIMIT_CASES[name]
+
+
+def bank_of(case):
+    """(sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm) of a case, f_max resolved: mel_weights64's arguments"""
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case
+    return (sr, n_fft, n_mels, f_min, sr / 2.0 if f_max is None else f_max, scale, norm)
+
+
+def case_spec(name, log=False, bands_first=True, floor=FLOOR):
+    from vorbispizza_amd import capi
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case_of(name)
+    return capi.LogMelSpec.make(sample_rate=sr, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max, mel_scale=scale, mel_norm=norm, log=log,
+                                floor=floor, bands_first=bands_first)
+
 
 def case_weights(name):
-    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = CASES[name]
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case_of(name)
     return mel_weights64(sr, n_fft, n_mels, f_min, sr / 2.0 if f_max is None else f_max, scale, norm)
 
 
@@ -187,7 +289,7 @@ def case_input(name):
     magnitude, so that with the floor at 1e-10 the check's cap is a property of the input (test_melspec_cpu confirms it)"""
     if name in _INPUTS:
         return _INPUTS[name]
-    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = CASES[name]
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case_of(name)
     rng = np.random.default_rng(sum(name.encode()) * 1000 + hop)
     Ls = [F, F - 1, F - n_fft // 4, F // 3, 1, 0]
     gap = F // 5
@@ -207,8 +309,23 @@ _TRUTHS = {}
 def case_truth(name):
     """[(M, e_M)] of a case's rows, computed once"""
     if name not in _TRUTHS:
-        sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = CASES[name]
+        sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case_of(name)
         src, rows = case_input(name)
         W = case_weights(name)
         _TRUTHS[name] = [melspec_truth(src[a: a + L], L, F, n_fft, hop, W) for a, L, _ in rows]
     return _TRUTHS[name]
+
+
+_RESTATED = {}
+
+
+def case_restated(name):
+    """[acc32] of a case's rows, float32 [T, n_mels] each: restated_power32 with the library's bank for the case's spec, computed once"""
+    if name not in _RESTATED:
+        from vorbispizza_amd import capi
+        sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case_of(name)
+        src, rows = case_input(name)
+        first, count, weights = capi.melspec_filterbank(case_spec(name))
+        _RESTATED[name] = [restated_power32(frames_of(src[a: a + L], L, F, n_fft, hop).astype(np.float32), n_fft, first, count, weights)
+                           for a, L, _ in rows]
+    return _RESTATED[name]

@@ -18,13 +18,16 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import melspec_truth as mt  # noqa: E402
 import binding_support as cs  # noqa: E402
-from f32_model import U  # noqa: E402
+from f32_model import U, fma32  # noqa: E402
 from logmel_truth import KINDS, check_log, check_power, dft64, frames_of, mel_weights64, refused_specs  # noqa: E402
 from binding_support import imports_of  # noqa: E402
 
 # (sample_rate, n_fft, n_mels, f_min, f_max, mel_scale, mel_norm)
 BANKS = [(22050, 2048, 128, 0.0, 11025.0, "slaney", "slaney"), (44100, 4096, 128, 20.0, 20000.0, "htk", None), (48000, 8192, 256, 0.0, 24000.0, "htk", "slaney"),
          (44100, 2048, 1, 0.0, 22050.0, "slaney", "slaney"), (44100, 2048, 256, 0.0, 2000.0, "slaney", None)]
+# and the bank of every case the GPU tests restate with the library's table
+BANKS += sorted({mt.bank_of(c) for c in list(mt.CASES.values()) + list(mt.LIMIT_CASES.values())} - set(BANKS), key=repr)
+ALL_CASES = list(mt.CASES) + list(mt.LIMIT_CASES)
 
 
 def spec_of(bank, **kw):
@@ -74,7 +77,7 @@ def test_the_filterbank_is_the_restatement_rounded_once(capi, bank):
         got = weights[at: at + count[b]].astype(np.float64)
         assert (np.abs(got - want) <= U * want + 8 * 2.0 ** -52 * np.abs(W[b]).max() + 2.0 ** -149).all(), b
         at += count[b]
-    if bank[2] == 256 and bank[1] == 2048:
+    if (bank[2] == 256 and bank[1] == 2048) or bank == mt.bank_of(mt.LIMIT_CASES["tile2_first_4096_3804"]):
         assert (count == 0).any() and (count > 0).any()  # (bands narrower than a bin: allowed)
 
 
@@ -187,7 +190,7 @@ def test_the_network_restated_is_the_dft(n_fft):
 def test_every_case_stays_under_the_checks_cap():
     """check_log lets at most 1 % of values lie within e_M of the floor: a condition on the inputs, confirmed here with the truth alone
     (the truth handed to the check as the value: only the cap can fail)"""
-    for name in mt.CASES:
+    for name in ALL_CASES:
         for (M, e_M) in mt.case_truth(name):
             between = ~((M - e_M > mt.FLOOR) | (M + e_M < mt.FLOOR))
             assert between.sum() <= 0.01 * M.size, (name, int(between.sum()), M.size)
@@ -198,7 +201,7 @@ def test_every_case_stays_under_the_checks_cap():
 # ---- the bound discriminates
 def proxy_rows(name, W, w=None, t=None, extend_repeats=False, hop_off=0):
     """the float32 network's M for every row of a case, with the named mistake"""
-    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = mt.CASES[name]
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = mt.case_of(name)
     src, rows = mt.case_input(name)
     out = []
     for a, L, _ in rows:
@@ -229,7 +232,7 @@ def passes_the_check(name, Ms):
     return True
 
 
-@pytest.mark.parametrize("name", list(mt.CASES))
+@pytest.mark.parametrize("name", ALL_CASES)
 def test_the_restated_network_passes_on_every_case(name):
     assert passes_the_check(name, proxy_rows(name, mt.case_weights(name)))
 
@@ -291,6 +294,111 @@ def test_the_launch_plan_fits_and_the_cases_take_their_tiles():
     assert all({tile - 1, tile, tile + 1} <= Ts[tile] for tile in tiles), Ts
     # the smallest padded length at every n_fft, with one frame and with hop 1
     assert {(c[1], c[2]) for c in mt.CASES.values() if c[8] == c[1] // 2 + 1} == {(n, h) for n in mt.NFFTS for h in (1, n)}
+
+
+# what tests/test_pcm_melspec_limits_gpu.py launches: name -> (frames of the tile, LDS floats, T)
+LIMIT_PLAN = {"tile16_last_4096_1638": (16, 40954, 17), "tile8_first_4096_1639": (8, 25809, 9), "tile8_last_4096_3803": (8, 40957, 9),
+              "tile2_first_4096_3804": (2, 16604, 3), "tile16_last_8192_819": (16, 40957, 17), "tile8_first_8192_820": (8, 32364, 9),
+              "full_lds_8192_2048_T7": (8, 40960, 7), "full_lds_8192_2048_T8": (8, 40960, 8), "full_lds_8192_2048_T9": (8, 40960, 9),
+              "tile2_first_8192_2049": (2, 27137, 3)}
+
+
+def test_the_limit_cases_take_their_tiles_and_the_banks_every_trip_of_the_band_loop(capi):
+    """LIMIT_CASES against the plan: every case takes the tile it is named for with the LDS floats of the table above -- the last hop of
+    a tile size, and the first of the next, at n_fft 4096 and 8192; the whole 160 KiB at 8192 and three floats less at 4096 -- and the
+    library's banks of CASES and LIMIT_CASES together give the band loop (kMsAhead = 16 steps issued together, a step beyond the band
+    reading its last bin again) every count around its trips"""
+    k = mt.kernel_constants()
+    assert sorted(mt.LIMIT_CASES) == sorted(LIMIT_PLAN)
+    for name, case in mt.LIMIT_CASES.items():
+        sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = case
+        assert mt.tile_plan(n_fft, hop, k) == LIMIT_PLAN[name][:2] and tile == LIMIT_PLAN[name][0] and 1 + F // hop == LIMIT_PLAN[name][2], name
+        assert F >= n_fft // 2 + 1 and F % hop == 5 and n_mels <= k["kMsMelRoom"], name
+        assert name.split("_")[0] in ("tile%d" % tile, "full") and "_%d_%d" % (n_fft, hop) in name
+    # either side of every change of tile
+    for n_fft, last16, last8 in ((4096, 1638, 3803), (8192, 819, 2048)):
+        hops = {c[2]: c[9] for c in mt.LIMIT_CASES.values() if c[1] == n_fft}
+        assert (hops[last16], hops[last16 + 1], hops[last8], hops[last8 + 1]) == (16, 8, 8, 2)
+        assert mt.tile_plan(n_fft, last16 + 1, k)[0] == 8 and mt.tile_plan(n_fft, last8 + 1, k)[0] == 2
+    floats = {(c[1], mt.tile_plan(c[1], c[2], k)[1]) for c in mt.LIMIT_CASES.values()}
+    assert (8192, 40960) in floats and (4096, 40957) in floats and k["kMsLdsFloats"] == 40960
+    # a T one less than, equal to and one more than the tile at the full LDS
+    assert {1 + c[8] // c[2] for n, c in mt.LIMIT_CASES.items() if n.startswith("full_lds")} == {7, 8, 9}
+    # the banks: both scales, both norms, bin n_fft / 2 live, empty bands, 256 bands where an 8192 launch asks for the most
+    cases = mt.LIMIT_CASES.values()
+    assert {c[6] for c in cases} == {"htk", "slaney"} and {c[7] for c in cases} == {None, "slaney"} and any(c[5] is None for c in cases)
+    most = sorted((mt.tile_plan(c[1], c[2], k)[1], n) for n, c in mt.LIMIT_CASES.items() if c[1] == 8192)[-2:]
+    assert all(mt.LIMIT_CASES[n][3] == 256 and mt.LIMIT_CASES[n][5] is None and mt.LIMIT_CASES[n][6] == "htk" and mt.LIMIT_CASES[n][0] == 48000 for _, n in most)
+    counts, top_live = set(), set()
+    for name in ALL_CASES:
+        first, count, weights = capi.melspec_filterbank(mt.case_spec(name))
+        counts |= set(count.tolist())
+        if mt.case_of(name)[5] is None:
+            # f_max at Nyquist: the last band's triangle ends on bin n_fft / 2, where its weight is 0 or what the rounding of the mel
+            # points leaves of it -- the bin is live in some banks only
+            half = mt.case_of(name)[1] // 2
+            assert (first + count).max() in (half, half + 1), name
+            if (first + count).max() == half + 1 and name in mt.LIMIT_CASES:
+                top_live.add(name)
+    assert {"tile16_last_4096_1638", "tile8_last_4096_3803"} <= top_live  # (the kernel reads P[n_fft / 2], which the split pass writes twice)
+    assert k["kMsAhead"] == 16
+    assert {0, 1, 15, 16, 17, 31, 32, 33} <= counts and max(counts) > 256, sorted(counts)
+    first, count, weights = capi.melspec_filterbank(mt.case_spec("tile2_first_4096_3804"))
+    assert (count == 0).any() and (count > 0).any()
+
+
+def test_the_bit_check_tells_what_the_bound_does_not(capi):
+    """On a row of LIMIT_CASES: one band's chain summed k descending, and P = re * re + im * im with two roundings, both pass check_power
+    against the float64 truth -- at a fraction of the bound -- and both differ from restated_power32 in bits"""
+    name = "full_lds_8192_2048_T9"
+    sr, n_fft, hop, n_mels, f_min, f_max, scale, norm, F, tile = mt.LIMIT_CASES[name]
+    src, rows = mt.case_input(name)
+    (a, L, _), (M, e_M) = rows[0], mt.case_truth(name)[0]
+    assert L == F
+    first, count, weights = capi.melspec_filterbank(mt.case_spec(name))
+    first, count = first.astype(np.int64), count.astype(np.int64)
+    X = frames_of(src[a: a + L], L, F, n_fft, hop).astype(np.float32)
+    want = mt.restated_power32(X, n_fft, first, count, weights)
+    assert check_power(want, M, e_M) < 1.0
+    # one band, k descending
+    P = mt.power32(X, n_fft)
+    b = int(np.argmax(count))
+    start = int(count[:b].sum())
+    assert count[b] > 2 * 16
+    acc = np.zeros(X.shape[0], dtype=np.float32)
+    for i in range(int(count[b]) - 1, -1, -1):
+        acc = fma32(weights[start + i], P[:, first[b] + i], acc)
+    other = want.copy()
+    other[:, b] = acc
+    ratio = check_power(other, M, e_M)
+    differ = int((other.view(np.uint32) != want.view(np.uint32)).sum())
+    print("one chain descending: error / bound %.4f, %d of %d values of the band differ in bits" % (ratio, differ, X.shape[0]))
+    assert ratio < 1.0 and differ > 0
+    # the power unfused
+    re_, im_ = mt.network32(X, n_fft)
+    other = mt.band_sums32(re_ * re_ + im_ * im_, first, count, weights)
+    ratio = check_power(other, M, e_M)
+    differ = int((other.view(np.uint32) != want.view(np.uint32)).sum())
+    print("the power unfused: error / bound %.4f, %d of %d values differ in bits" % (ratio, differ, other.size))
+    assert ratio < 1.0 and differ > 0
+
+
+def test_check_log_exact_has_no_exempt_share():
+    """the silence value's bits at and under float32(floor), 4 u max(1, |got|) above it, and nothing else"""
+    floor = 0.25 * (1 + 2.0 ** -30)  # (float32 rounds it to 0.25)
+    acc = np.array([0.0, 0.25, np.nextafter(np.float32(0.25), np.float32(1)), 3.0, 1e-30], dtype=np.float32)
+    silence = mt.silence_value(floor)
+    good = np.where(acc <= np.float32(0.25), silence, np.log10(np.maximum(acc.astype(np.float64), 1e-300))).astype(np.float32)
+    assert silence == np.float32(np.log10(0.25)) and (good[[0, 1, 4]] == silence).all() and good[2] != silence
+    assert mt.check_log_exact(good, acc, floor) <= 0.125  # (a correctly rounded log10: half a unit of 4)
+    up = np.float32(np.inf)
+    # one float32 off the silence value at, and under, the floor; the logarithm of a value under it; five units off a logarithm; a NaN
+    for at, value in ((0, np.nextafter(silence, up)), (1, np.nextafter(silence, -up)), (4, np.float32(-30.0)),
+                      (3, good[3] + np.float32(5 * 2.0 ** -24)), (3, np.float32("nan"))):
+        bad = good.copy()
+        bad[at] = value
+        with pytest.raises(AssertionError):
+            mt.check_log_exact(bad, acc, floor)
 
 
 # ---- the surface

@@ -16,24 +16,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from f32_model import fma32  # noqa: E402
+from melspec_truth import band_sums32  # noqa: E402
 from gpu_context import ctx  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
 
 N_FFT, F, N_MELS, SAMPLE_RATE = 2048, 1025, 128, 22050
-
-
-def band_sums32(P, first, count, weights):
-    """[T, n_mels] float32 of the power P [T, n_fft / 2 + 1]: acc = fma32(w[i], P[first + i], acc) over a band's live bins, i ascending"""
-    start = np.concatenate([[0], np.cumsum(count)[:-1]])
-    acc = np.zeros((P.shape[0], count.size), dtype=np.float32)
-    for i in range(int(count.max())):
-        live = i < count
-        at = np.where(live, i, 0)
-        step = fma32(weights[start + at][None, :], P[:, first + at], acc)
-        acc = np.where(live[None, :], step, acc)
-    return acc
 
 
 @pytest.mark.parametrize("hop,T", [(2048, 1), (64, 17)])

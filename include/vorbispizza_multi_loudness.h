@@ -9,7 +9,8 @@
  * sample rate among a sub-batch's members measures it there, the step sums and peaks come down in one small copy, and
  * vpz_loudness_gate runs per member on the issuing thread.
  *
- * Out of scope: the true peak, loudness range and short-term values, a gain applied on delivery, the vpzr_* reader.
+ * Out of scope: the true peak, loudness range and short-term values, the vpzr_* reader.  A gain applied on delivery is
+ * vpzm_decode_ranges_normalized's (vorbispizza_multi_normalize.h): its loudness mode measures as this call does and delivers in one call.
  *
  * A header of its own: the older headers, their structs and their bindings do not change with it.
  */

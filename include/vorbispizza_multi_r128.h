@@ -9,7 +9,8 @@
  * (vorbispizza_pcm_r128.h, which states the definitions); the step sums, sample peaks and true peaks come down in the one small copy, and
  * vpz_loudness_gate, vpz_loudness_range and vpz_loudness_maxima run per member on the issuing thread.  No PCM crosses the host link.
  *
- * Out of scope: a gain applied on delivery, int16 sources, per-channel peaks, the vpzr_* reader.
+ * Out of scope: int16 sources, per-channel peaks, the vpzr_* reader.  A gain applied on delivery is vpzm_decode_ranges_normalized's
+ * (vorbispizza_multi_normalize.h), whose loudness mode measures the integrated loudness and applies the gain in one call.
  *
  * A header of its own: the older headers, their structs and their bindings do not change with it.
  */

@@ -27,8 +27,9 @@
  * l_k = -0.691 + 10 log10 p_k.  The blocks with l_k > -70 pass the absolute gate; of those, the ones with l_k above
  * -0.691 + 10 log10(mean p of those) - 10 are kept; the integrated loudness is -0.691 + 10 log10(mean p of the kept), in LUFS.
  *
- * Out of scope: the true peak (oversampled); loudness range and the short-term and momentary values; int16 sources; a gain applied on
- * delivery; the vpzr_* reader (vorbispizza_reader.h).
+ * Out of scope: the true peak (oversampled); loudness range and the short-term and momentary values; int16 sources; the vpzr_* reader
+ * (vorbispizza_reader.h).  A gain applied on delivery is vpz_pcm_normalize's (vorbispizza_pcm_normalize.h), and
+ * vpzm_decode_ranges_normalized (vorbispizza_multi_normalize.h) measures and applies it in one call.
  *
  * A header of its own: vorbispizza_synth.h, the older vorbispizza_pcm_*.h, VPZ_ABI_VERSION and their bindings do not change with it.
  * Conventions are those of vorbispizza_synth.h: cdecl, int status (VPZ_OK / VPZ_E_*), caller-owned buffers.

@@ -35,7 +35,7 @@
  * Maxima (vpz_loudness_maxima).  The largest l over the gate's 400 ms blocks (steps k .. k+3, p = the sum of the four / (4 S)): the
  * maximum momentary loudness; the largest l over the 3 s blocks above: the maximum short-term loudness.  A NaN level is passed over.
  *
- * Out of scope: a gain applied on delivery; int16 sources; per-channel peaks; an oversampling other than the factor rule above; the
+ * Out of scope (a gain applied on delivery is vpz_pcm_normalize's, vorbispizza_pcm_normalize.h): int16 sources; per-channel peaks; an oversampling other than the factor rule above; the
  * vpzr_* reader (vorbispizza_reader.h).
  *
  * A header of its own: vorbispizza_synth.h, the older vorbispizza_pcm_*.h, VPZ_ABI_VERSION and their bindings do not change with it.

@@ -111,7 +111,15 @@ maxima, the true peak).  Three dispatchers taking turns: decode_library into flo
 measure_r128 -- the cost of the added numbers, and what a host scanner must do first.  The records of the first two streams are
 printed.  With VPZM_PROFILE=1 the library prints the loudness and the true-peak launches' own time per sub-batch.
 --r128-kernel: vpz_pcm_true_peak alone and vpz_pcm_loudness beside it, the same rows as --loudness-kernel, the context's event timer:
-the median of 5 with its extremes, GB/s against 8 TB/s and multiply-adds per second against the float32 vector peak (157.3 TFLOP/s)."""
+the median of 5 with its extremes, GB/s against 8 TB/s and multiply-adds per second against the float32 vector peak (157.3 TFLOP/s).
+--ranges SAMPLES --batch --resample RATE [--mono] --normalize MODE (meanvar, peak, rms or loudness): the window batch delivered normalised
+(vorbispizza_amd.normalize.decode_ranges_normalized) against what a loader does without the call: decode_ranges_batch at the same rate,
+then the torch chain -- a mask from results["samples"], the masked mean and variance (or peak, or RMS) and the scale --, with a
+measure_loudness call in front of it for the loudness mode (the second decode that the call saves).  Both legs' first rows are held to
+the longdouble truth of tests/normalize_truth.py with the header's bound; two dispatchers taking turns as above.
+--normalize-kernel: vpz_pcm_normalize alone, 64 mono rows of one second and of thirty at 16 000 Hz from odd offsets, the context's event
+timer: the median of 10 with its extremes, and the bytes moved (a float32 row is read twice and written once: 12 B per sample) per
+second against 8 TB/s."""
 import argparse, os, statistics, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -153,6 +161,8 @@ ap.add_argument("--loudness", action="store_true")
 ap.add_argument("--loudness-kernel", action="store_true")
 ap.add_argument("--r128", action="store_true")
 ap.add_argument("--r128-kernel", action="store_true")
+ap.add_argument("--normalize", default="")
+ap.add_argument("--normalize-kernel", action="store_true")
 ap.add_argument("settings", nargs="*")
 args = ap.parse_args()
 streams = int(os.environ.get("STREAMS", "1024"))
@@ -1140,6 +1150,119 @@ def loudness_kernel_job():
     ctx.close()
 
 
+def normalize_job(samples, rate, mode):
+    """--normalize MODE: normalize.decode_ranges_normalized against what a loader does without it"""
+    import time
+    import normalize_truth as nt
+    from vorbispizza_amd import normalize
+    totals = [smp for _, smp in bench.REAL_FIXTURES]
+    rng = np.random.default_rng(7)
+    windows = [(int(rng.integers(0, totals[i] - samples - 64)), samples) for i in pick]
+    n, C_, out, kept = len(datas), 1 if args.mono else 2, [None, None], {}
+    target = normalize.DEFAULT_TARGETS[mode]
+    J = -(-samples * rate // 44100)  # (the set's streams are at 44 100 Hz)
+
+    def by_batch_and_torch(d):
+        t0 = time.perf_counter()
+        gain = None
+        if mode == "loudness":  # measure first: the second decode that the call saves
+            _, integrated, _, _, _, _ = d.measure_loudness(datas, windows)
+            g = np.where(np.isfinite(integrated), 10.0 ** ((target - np.where(np.isfinite(integrated), integrated, target)) / 20.0), 1.0)
+            gain = torch.from_numpy(g.astype(np.float32)).to("cuda:0")
+            kept["loudness"] = integrated
+        _, x, res, st = d.decode_ranges_batch(datas, windows, C_, J, planar=True, s16=False, sample_rate=rate, mono=args.mono)
+        count = torch.from_numpy(res["samples"].astype(np.int64)).to("cuda:0")
+        mask = (torch.arange(J, device="cuda:0")[None, :] < count[:, None])[:, None, :].to(torch.float32)
+        N = (count * C_).clamp(min=1).to(torch.float32)[:, None, None]
+        if mode == "meanvar":
+            mean = (x * mask).sum(dim=(1, 2), keepdim=True) / N
+            var = (((x - mean) * mask) ** 2).sum(dim=(1, 2), keepdim=True) / N
+            y = (x - mean) / torch.sqrt(var + 1e-7) * mask
+        elif mode == "peak":
+            y = x * (target / (x * mask).abs().amax(dim=(1, 2), keepdim=True).clamp(min=1e-30)) * mask
+        elif mode == "rms":
+            y = x * (target / torch.sqrt(((x * mask) ** 2).sum(dim=(1, 2), keepdim=True) / N).clamp(min=1e-30)) * mask
+        else:
+            y = x * gain[:, None, None] * mask
+        out[0] = y
+        kept["x"], kept["count"] = x, res["samples"]
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, res, st
+
+    def by_normalized(d):
+        t0 = time.perf_counter()
+        _, out[1], res, st = normalize.decode_ranges_normalized(d, datas, windows, C_, J, rate, mono=args.mono, mode=mode)
+        kept["results"] = res
+        return time.perf_counter() - t0, res, st
+
+    for groups, thr, spc, ctxs, slots in [tuple(int(x) for x in a.split(",")) for a in args.settings]:
+        what = "f32 groups %d threads %3d streams/call %2d contexts %d slots %d gpu_entropy %s, %d streams, windows of %d samples to %d Hz%s, %s" % (
+            groups, thr, spc, ctxs, slots, "on" if args.gpu_entropy else "off", n, samples, rate, ", mono" if args.mono else "", mode)
+        ds = [multi.Dispatcher([0] * groups, host_threads=thr, streams_per_call=spc, contexts_per_device=ctxs, slots_per_device=slots,
+                               gpu_entropy=args.gpu_entropy) for _ in range(2)]
+        legs = [lambda: by_batch_and_torch(ds[0]), lambda: by_normalized(ds[1])]
+        for leg in legs:  # (one pass each that does not count: slots, decoders, device arrays and tables are allocated in it)
+            _, res, st = leg()
+            assert (res["status"] == 0).all()
+        # both legs against the same truth (tests/normalize_truth.py: longdouble, two passes, the header's bound), on the first rows
+        rows = slice(0, 16)
+        x = kept["x"][rows].cpu().numpy()
+        res = kept["results"]
+        assert (kept["count"] == J).all() and np.array_equal(res["samples"], kept["count"])
+        if mode == "loudness":
+            assert np.array_equal(res["loudness"].view(np.uint64), kept["loudness"].view(np.uint64)), "the loudness is not measure_loudness's"
+            kw = dict(mode=nt.GAIN, gains=res["gain"][rows])
+        else:
+            kw = dict(mode=nt.MODES[mode], target=target)
+        ystar, bound, _ = nt.truth(x, **kw)
+        ratios = [nt.worst_ratio(out[i][rows].cpu().numpy(), ystar, bound) for i in (0, 1)]
+        print("%s:\n    a tensor of %.1f MB; error / derived bound on the first 16 rows: torch chain %.3g, the call %.3g; largest difference of the two tensors "
+              "%.3g (largest value %.3g), %d streams on the device" % (
+                  what, out[1].numel() * 4 / 1e6, ratios[0], ratios[1], float((out[0] - out[1]).abs().max()), float(out[1].abs().max()),
+                  int(sum(st.device_gpu_entropy_streams))), flush=True)
+        for run in (1, 2):
+            walls = [[], []]
+            for _ in range(args.reps or 5):
+                for i, leg in enumerate(legs):
+                    walls[i].append(leg()[0])
+            print("    A/B run %d: %sdecode_ranges_batch + torch chain %s; decode_ranges_normalized %s" % (
+                run, "measure_loudness + " if mode == "loudness" else "", describe(walls[0]), describe(walls[1])), flush=True)
+        for d in ds:
+            d.close()
+
+
+def normalize_kernel_job():
+    """--normalize-kernel: vpz_pcm_normalize alone, 64 mono rows of one second and of thirty at 16 000 Hz, the context's event timer"""
+    import ctypes as C
+    from vorbispizza_amd import Context, capi
+    ctx = Context(0)
+    n = 64
+    for samples in (16000, 30 * 16000):
+        src = (torch.rand(n * samples + 8, device="cuda:0") * 2 - 1)
+        desc = (capi.NormRow * n)()
+        for k in range(n):
+            desc[k].src, desc[k].samples, desc[k].row, desc[k].gain = k * samples + 1, samples, k, 0.5  # (odd offsets: unaligned sources)
+        scratch = torch.empty(capi.pcm_normalize_scratch(n, 1, samples), dtype=torch.float64, device="cuda:0")
+        for name, mode, lay, dtype in (("meanvar f32", "meanvar", capi.OUT_PLANAR, torch.float32), ("meanvar s16", "meanvar", capi.OUT_PLANAR_S16, torch.int16),
+                                       ("peak f32", "peak", capi.OUT_PLANAR, torch.float32), ("plain gain f32", "gain", capi.OUT_PLANAR, torch.float32)):
+            dst = torch.empty((n, 1, samples), dtype=dtype, device="cuda:0")
+            spec = capi.NormSpec.make(mode, channels=1)
+            times = []
+            for _ in range(11):
+                ctx.timer_start()
+                rc = capi.lib().vpz_pcm_normalize(ctx._h, C.c_void_p(src.data_ptr()), src.numel(), samples, C.byref(spec), n, C.cast(desc, C.c_void_p),
+                                                  C.c_void_p(dst.data_ptr()), n, lay, C.c_void_p(scratch.data_ptr()), scratch.numel(), None)
+                assert rc == capi.OK, ctx.last_error()
+                times.append(ctx.timer_stop())
+            passes = 1 if mode == "gain" else 2  # (a plain gain reads its rows once)
+            moved = n * samples * (4 * passes + dst.element_size())
+            ms = statistics.median(times[1:])
+            print("vpz_pcm_normalize %-14s 64 mono rows of %6d samples: median %.1f us (min %.1f, max %.1f) for %.2f MB moved (read %s, written once) = %.0f GB/s, "
+                  "%.1f %% of 8 TB/s" % (name, samples, ms * 1e3, min(times[1:]) * 1e3, max(times[1:]) * 1e3, moved / 1e6, "twice" if passes == 2 else "once",
+                                        moved / ms / 1e6, 100.0 * moved / ms / 1e6 / 8000.0), flush=True)
+    ctx.close()
+
+
 def r128_job():
     import time
     n = len(datas)
@@ -1226,6 +1349,12 @@ def r128_kernel_job():
     ctx.close()
 
 
+if args.normalize_kernel:
+    normalize_kernel_job()
+    sys.exit(0)
+if args.ranges and args.batch and args.resample and args.normalize:
+    normalize_job(args.ranges, args.resample, args.normalize)
+    sys.exit(0)
 if args.r128_kernel:
     r128_kernel_job()
     sys.exit(0)

@@ -38,6 +38,7 @@ SOURCES = {
     "pcm_loudness.hip": [],  # vpz_pcm_loudness: windows of an interleaved device array as K-weighted step sums and a peak (float64; the recurrence cut into steps, carried exactly)
     "pcm_truepeak.hip": [],  # vpz_pcm_true_peak: the same windows' true peak (a 4x / 2x polyphase interpolator in float32, fused, one order) and sample peak; range and maxima of step sums, host only
     "pcm_featpost.hip": ["-ffp-contract=off"],  # vpz_feat_post: deltas and mean / variance normalisation of a padded batch of feature frames (every fused step is written as one)
+    "pcm_normalize.hip": ["-ffp-contract=off"],  # vpz_pcm_normalize: windows of a planar float32 array delivered normalised -- unit variance, peak, RMS or a gain --: ordered float64 chunk sums, then the values as two float32 operations, never fused
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-Wno-constant-logical-operand", "-fno-strict-aliasing"]
@@ -72,6 +73,7 @@ def _deps(src):
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_loudness.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_r128.h"))
     deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_featpost.h"))
+    deps.append(os.path.join(_HERE, "..", "include", "vorbispizza_pcm_normalize.h"))
     return deps
 
 
@@ -101,7 +103,8 @@ def build_host(force=False, verbose=False):
                    os.path.join(inc, "vorbispizza_multi_featpost.h"), os.path.join(inc, "vorbispizza_pcm_melspec.h"),
                    os.path.join(inc, "vorbispizza_multi_melspec.h"), os.path.join(inc, "vorbispizza_pcm_stft.h"),
                    os.path.join(inc, "vorbispizza_multi_stft.h"), os.path.join(inc, "vorbispizza_pcm_cqt.h"),
-                   os.path.join(inc, "vorbispizza_multi_cqt.h"), LIB_PATH]
+                   os.path.join(inc, "vorbispizza_multi_cqt.h"), os.path.join(inc, "vorbispizza_pcm_normalize.h"),
+                   os.path.join(inc, "vorbispizza_multi_normalize.h"), LIB_PATH]
     stale = force or not os.path.exists(HOST_LIB_PATH) or any(
         os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(HOST_LIB_PATH) for d in deps)
     if stale:

@@ -367,6 +367,44 @@ _PCM_FEATPOST_SIGNATURES = [
                                 C.c_int64]),
 ]
 PCM_FEATPOST_EXPORTED_SYMBOLS = [s[0] for s in _PCM_FEATPOST_SIGNATURES]
+
+
+NORM_MEANVAR, NORM_PEAK, NORM_RMS, NORM_GAIN = 1, 2, 3, 4
+NORM_CHUNK = 1024
+NORM_MODES = {"meanvar": NORM_MEANVAR, "peak": NORM_PEAK, "rms": NORM_RMS, "gain": NORM_GAIN}
+NORM_DEFAULT_TARGETS = {"meanvar": 0.0, "peak": 1.0, "rms": 0.1, "gain": 1.0, "loudness": -23.0}
+
+
+class NormSpec(C.Structure):
+    """vpz_norm_spec (include/vorbispizza_pcm_normalize.h).  NormSpec.make(...) takes the names a Python caller uses; eps is
+    Wav2Vec2FeatureExtractor's 1e-7, target=None the mode's usual level (1.0 for a peak, 0.1 for an RMS level; a gain's is per row)."""
+    _fields_ = [("target", C.c_double), ("eps", C.c_double), ("ceiling", C.c_double), ("mode", C.c_int32), ("channels", C.c_int32),
+                ("reserved", C.c_int32 * 8)]
+
+    @classmethod
+    def make(cls, mode="meanvar", channels=1, target=None, eps=1e-7, ceiling=0.0):
+        if mode not in NORM_MODES:
+            raise ValueError("NormSpec: mode is 'meanvar', 'peak', 'rms' or 'gain'")
+        s = cls()
+        s.mode, s.channels = NORM_MODES[mode], int(channels)
+        s.target = float(NORM_DEFAULT_TARGETS[mode] if target is None else target)
+        s.eps, s.ceiling = float(eps), float(ceiling)
+        return s
+
+
+class NormRow(C.Structure):
+    """vpz_norm_row"""
+    _fields_ = [("src", C.c_int64), ("samples", C.c_int64), ("row", C.c_int64), ("gain", C.c_double)]
+
+
+NORM_RESULT_FIELDS = ("sum", "sum_sq", "peak", "mean", "gain")  # vpz_norm_result: five doubles
+# include/vorbispizza_pcm_normalize.h (a header of its own again)
+_PCM_NORMALIZE_SIGNATURES = [
+    ("vpz_pcm_normalize_scratch", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    ("vpz_pcm_normalize", C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.POINTER(NormSpec), C.c_int32, _vp, _vp, C.c_int64, C.c_int32, _vp,
+                                    C.c_int64, _vp]),
+]
+PCM_NORMALIZE_EXPORTED_SYMBOLS = [s[0] for s in _PCM_NORMALIZE_SIGNATURES]
 LOUDNESS_MIN_RATE, LOUDNESS_MAX_RATE = 8000, 384000
 # include/vorbispizza_pcm_loudness.h (a header of its own again)
 _PCM_LOUDNESS_SIGNATURES = [
@@ -419,7 +457,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         later = (_PCM_SIGNATURES + _PCM_PACK_SIGNATURES + _PCM_RESAMPLE_SIGNATURES + _PCM_LOGMEL_SIGNATURES + _PCM_FBANK_SIGNATURES
                  + _PCM_LOUDNESS_SIGNATURES + _PCM_R128_SIGNATURES + _PCM_MFCC_SIGNATURES + _PCM_FEATPOST_SIGNATURES + _PCM_MELSPEC_SIGNATURES
-                 + _PCM_STFT_SIGNATURES + _PCM_CQT_SIGNATURES)
+                 + _PCM_STFT_SIGNATURES + _PCM_CQT_SIGNATURES + _PCM_NORMALIZE_SIGNATURES)
         for name, restype, argtypes in _SIGNATURES + _DEBUG_SIGNATURES + later:
             if (name, restype, argtypes) in later and not hasattr(L, name):
                 continue  # (an older build taken through VPZ_LIB_DIR for an A/B run has none: using one raises)
@@ -794,6 +832,53 @@ def feat_post(ctx, src, rows, dst, spec, scratch=None):
     if own is not None:
         ctx.synchronize()
     return rc
+
+
+def pcm_normalize_scratch(n_rows, channels, frames):
+    """vpz_pcm_normalize_scratch: the float64 elements of scratch memory a call needs; needs no device.  A refusal raises ValueError."""
+    doubles = C.c_int64(0)
+    rc = lib().vpz_pcm_normalize_scratch(n_rows, channels, frames, C.byref(doubles))
+    if rc != OK:
+        raise ValueError("vpz_pcm_normalize_scratch refuses the sizes (status %d)" % rc)
+    return doubles.value
+
+
+def pcm_normalize(ctx, src, rows, dst, spec, frames, gains=None, results=False):
+    """vpz_pcm_normalize (vorbispizza_pcm_normalize.h): windows of the PLANAR float32 device array `src` (a torch tensor; a window's
+    channel c lies c * frames elements behind its channel 0) normalised into rows of `dst` -- a contiguous torch tensor
+    [rows, channels, frames] or [rows, frames, channels], float32 or int16: the layout is read off dst's dtype and shape against
+    spec.channels and `frames` (planar where both fit).  rows: [(src, samples, row)]; gains: one linear gain per row (NORM_GAIN;
+    None: 1.0); spec: a NormSpec.  The scratch memory is made here, so the call waits for the context's stream before it returns.
+    Returns the status (a refusal is an answer, not an exception); with `results`, (status, float64 array [n_rows, 5] of
+    NORM_RESULT_FIELDS), the array None after a refusal."""
+    import torch
+    channels, frames = int(spec.channels), int(frames)
+    if dst.dim() != 3 or not dst.is_contiguous():
+        raise ValueError("pcm_normalize: dst is a contiguous tensor of three dimensions")
+    planar = tuple(dst.shape[1:]) == (channels, frames)
+    if not planar and tuple(dst.shape[1:]) != (frames, channels):
+        raise ValueError("pcm_normalize: dst is [rows, %d, %d] or [rows, %d, %d], not %r" % (channels, frames, frames, channels, tuple(dst.shape)))
+    s16 = dst.dtype == torch.int16
+    if not s16 and dst.dtype != torch.float32:
+        raise ValueError("pcm_normalize: dst is float32 or int16")
+    layout = (OUT_PLANAR_S16 if s16 else OUT_PLANAR) if planar else (OUT_INTERLEAVED_S16 if s16 else OUT_INTERLEAVED)
+    desc3 = np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+    n = desc3.shape[0]
+    desc = np.zeros(n, dtype=[("src", "<i8"), ("samples", "<i8"), ("row", "<i8"), ("gain", "<f8")])
+    desc["src"], desc["samples"], desc["row"] = desc3[:, 0], desc3[:, 1], desc3[:, 2]
+    desc["gain"] = 1.0 if gains is None else np.asarray(gains, dtype=np.float64).reshape(n)
+    scratch = None
+    need = C.c_int64(0)
+    if lib().vpz_pcm_normalize_scratch(n, channels, frames, C.byref(need)) == OK and need.value:
+        scratch = torch.empty(need.value, dtype=torch.float64, device=src.device)
+    res = torch.zeros((n, len(NORM_RESULT_FIELDS)), dtype=torch.float64, device=src.device) if results else None
+    _sync_producer(src, dst)
+    rc = lib().vpz_pcm_normalize(ctx._h, _ptr(src), _numel(src), frames, C.byref(spec), n, desc.ctypes.data, _ptr(dst), int(dst.shape[0]),
+                                 layout, _ptr(scratch), _numel(scratch), _ptr(res))
+    ctx.synchronize()
+    if not results:
+        return rc
+    return rc, (res.cpu().numpy() if rc == OK else None)
 
 
 def loudness_filter(sample_rate):

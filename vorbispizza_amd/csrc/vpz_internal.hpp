@@ -72,7 +72,7 @@ struct Context {
     // persistent grids of the IMDCT kernels on THIS context's device (workgroups the chip keeps resident), filled by the first
     // launch of each; per context, not per process: a host with several GPUs holds one context per device
     int resident[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // the row launches -- vpz_pcm_pack, vpz_pcm_resample, vpz_pcm_logmel, vpz_pcm_fbank and vpz_pcm_mfcc -- share it (upload_rows, pcm_pack.hip): a launch's row
+    // the row launches -- vpz_pcm_pack, vpz_pcm_resample, vpz_pcm_logmel, vpz_pcm_fbank, vpz_pcm_mfcc and vpz_pcm_normalize (whose 32-byte descriptors travel as so many 24-byte ones) -- share it (upload_rows, pcm_pack.hip): a launch's row
     // descriptors go up through a page-locked buffer of the context's into its device copy; `pack_done` says that the last launch's copy
     // has left the buffer
     void *pack_host = nullptr, *pack_dev = nullptr;

@@ -53,6 +53,10 @@
 // vpzm_measure_r128 (include/vorbispizza_multi_r128.h) is that call with one vpz_pcm_true_peak launch per rate beside the loudness one --
 // the true peaks ride in the same copy -- and vpz_loudness_range and vpz_loudness_maxima beside the gate.
 //
+// vpzm_decode_ranges_normalized (include/vorbispizza_multi_normalize.h) is the resampled call with vpz_pcm_normalize as its last stage: the
+// resample launches write planar rows into the lane's temporary, as for an STFT call, and one launch set per sub-batch delivers them
+// normalised into the group's piece in the caller's layout; its loudness mode measures a sub-batch's members first, as the loudness call does.
+//
 // In the file's order: Setup, Buffer (the one owner of a page-locked or device array; Slot and Lane hold lists of them), SetupCache,
 // Switches (the VPZM_* environment of one call), GroupRun (a group's pipeline) and SubCall (a sub-batch's synth step, stage by stage).
 #include <algorithm>
@@ -99,6 +103,8 @@
 #include "../../include/vorbispizza_multi_loudness.h"
 #include "../../include/vorbispizza_pcm_r128.h"
 #include "../../include/vorbispizza_multi_r128.h"
+#include "../../include/vorbispizza_pcm_normalize.h"
+#include "../../include/vorbispizza_multi_normalize.h"
 #include "../../include/vorbispizza_entropy_group.h"
 
 namespace {
@@ -301,9 +307,11 @@ struct Lane {  // one context (HIP stream) of a device group and the decoders th
     // vpz_pcm_loudness launches and the one copy that brings them down; an R 128 call's true peaks [members] float32 lie behind the peaks;
     // owned like kMono)
     // (kFeat: a posted fbank or MFCC call's feature frames [members][T][D] float32, between the feature launch and the vpz_feat_post
-    // launches that read them; kPostScratch: those launches' chunk sums, float64; owned like kMono)
-    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kLoud, kFeat, kPostScratch, kBuffers };
-    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
+    // launches that read them; kPostScratch: those launches' chunk sums, float64 -- and a normalised call's, sized by its own stage's
+    // rule: one array, whichever call grew it last; kNormResult: a normalised call's vpz_norm_result [members], between the launches and
+    // the copy that brings them down; owned like kMono)
+    enum { kPayload, kResidue, kPosts, kCounts, kPcm, kF0Amp, kF0Coeff, kMono, kLoud, kFeat, kPostScratch, kNormResult, kBuffers };
+    Buffer buf[kBuffers] = {{true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}, {true}};  // (device memory, every one)
     uint8_t *payload() const { return static_cast<uint8_t *>(buf[kPayload].p); }
     float *residue() const { return static_cast<float *>(buf[kResidue].p); }  // (float32 or int16 values; the ABI's parameter is float-typed)
     int16_t *posts() const { return static_cast<int16_t *>(buf[kPosts].p); }
@@ -352,7 +360,7 @@ struct Switches {
     int64_t max_merged_mappings = number("VPZM_MAX_MERGED_MAPPINGS") > 0 ? number("VPZM_MAX_MERGED_MAPPINGS") : (int64_t)Setup::kMergedMost;  // (tests: small merged setups)
     bool fail_gpu_entropy = number("VPZM_FAIL_GPU_ENTROPY") != 0;  // (tests: every device-decoded sub-batch is refused, so that the host path after all runs)
     bool fail_batch_calls = number("VPZM_FAIL_BATCH_CALLS") != 0;  // (tests: every sub-batch's call counts as failed, so that the member-by-member path runs)
-    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, STFT, CQT, fbank or MFCC call, or a loudness call's -- is not made and counts as failed)
+    bool fail_delivery = number("VPZM_FAIL_DELIVERY") != 0;        // (tests: a batch call's delivery launch -- pack, resample, the feature launch of a log-mel, mel-spectrogram, STFT, CQT, fbank or MFCC call, a loudness call's or a normalised call's vpz_pcm_normalize -- is not made and counts as failed)
     bool profile = getenv("VPZM_PROFILE") != nullptr;              // a line per sub-batch on stderr
     bool no_synth = getenv("VPZM_NO_SYNTH") != nullptr;            // (diagnosis: the decode side of the pipeline alone)
 };
@@ -422,6 +430,8 @@ const Feature kFbank{"vpz_pcm_fbank", "vpzm_decode_ranges_fbank", "fbank", "pad 
 const Feature kMfcc{"vpz_pcm_mfcc", "vpzm_decode_ranges_mfcc", "mfcc", "pad rows", false, launch_of<vpz_mfcc_spec, vpz_pcm_mfcc>};
 const Feature kStft{"vpz_pcm_stft", "vpzm_decode_ranges_stft", "stft", "zero rows", true, launch_of<vpz_stft_spec, vpz_pcm_stft>};
 const Feature kCqt{"vpz_pcm_cqt", "vpzm_decode_ranges_cqt", "cqt", "zero rows", true, launch_of<vpz_cqt_spec, vpz_pcm_cqt>};
+// (a normalised call: the delivery stage has gains, scratch memory and a result array beside the rows -- Batch::norm_rows launches it)
+const Feature kNormalized{"vpz_pcm_normalize", "vpzm_decode_ranges_normalized", "normalize", "zero rows", false, nullptr};
 
 // vpzm_decode_ranges_batch: what the call delivers into instead of the caller's host array -- one group's piece of the batch (rows of
 // `channels * frames` elements in `layout`, entry k of the group in row k - lo); dst == nullptr: not a batch call
@@ -442,6 +452,11 @@ struct Batch {
     const vpz_feat_post_spec *post = nullptr;
     const vpz_fbank_spec *post_mel = nullptr;
     int32_t post_D = 0;
+    // a normalised call (feature == &kNormalized): vpz_pcm_normalize of this spec delivers the lane's temporary into the group's piece in
+    // `norm_layout`, one of the four; `norm_out`: the caller's records, entry k's at [k] (null: none wanted)
+    const vpzm_norm_spec *norm = nullptr;
+    int32_t norm_layout = 0;
+    vpzm_norm_out *norm_out = nullptr;
     // kLoudness: no tensor and no row length (`frames` caps nothing, `channels` is every stream's own); `dst` is the group's part of the
     // caller's records, HOST memory -- vpzm_loudness[rows], filled with the empty record before the run.  kR128: the same with vpzm_r128
     void *dst = nullptr;  // (decode_call fills these two in)
@@ -492,6 +507,45 @@ struct Batch {
                              need);
     }
 
+    bool by_loudness() const { return norm && norm->mode == VPZM_NORM_LOUDNESS; }
+    // a normalised call's vpz_pcm_normalize launches on the lane's stream: windows of the planar array `src` into their rows of `dst`.
+    // The loudness mode delivers through the descriptors' gains, the gain mode through the spec's one; the chunk sums live in the lane's
+    // scratch array and the result records (`want_result`) in its result array, which grow here.  `*own` as in post_rows.  Descriptors
+    // without samples (zero rows) need neither
+    int norm_rows(Lane &L, const void *src, int64_t src_elems, std::vector<vpz_norm_row> &d, bool want_result, const char **own) const
+    {
+        *own = nullptr;
+        vpz_norm_spec stage{};
+        stage.mode = by_loudness() ? VPZ_NORM_GAIN : norm->mode;
+        stage.channels = channels;
+        stage.target = norm->target;
+        stage.eps = norm->eps;
+        stage.ceiling = norm->ceiling;
+        bool any_real = false;
+        for (vpz_norm_row &r : d) {
+            any_real = any_real || r.samples > 0;
+            if (!by_loudness()) r.gain = stage.mode == VPZ_NORM_GAIN ? norm->target : 1.0;
+        }
+        want_result = want_result && any_real;
+        int64_t need = 0;
+        if (any_real && (stage.mode != VPZ_NORM_GAIN || stage.ceiling > 0.0 || want_result) &&
+            vpz_pcm_normalize_scratch((int32_t)d.size(), channels, frames, &need) != VPZ_OK) {
+            *own = "the scratch memory's size overflows";
+            return VPZ_E_INVALID_ARG;
+        }
+        if (need > 0 && !L.buf[Lane::kPostScratch].grow(L.ctx, (size_t)need, sizeof(double))) {
+            *own = "the chunk sums' device memory could not be allocated";
+            return VPZ_E_NOMEM;
+        }
+        if (want_result && !L.buf[Lane::kNormResult].grow(L.ctx, d.size(), sizeof(vpz_norm_result))) {
+            *own = "the result records' device memory could not be allocated";
+            return VPZ_E_NOMEM;
+        }
+        return vpz_pcm_normalize(L.ctx, src, src_elems, frames, &stage, (int32_t)d.size(), d.data(), dst, rows, norm_layout,
+                                 need > 0 ? L.buf[Lane::kPostScratch].p : nullptr, need,
+                                 want_result ? static_cast<vpz_norm_result *>(L.buf[Lane::kNormResult].p) : nullptr);
+    }
+
     // These descriptors (samples = 0 each) get rows of no samples -- zeros, or the silence row of a log-mel call or the pad_value row of
     // an fbank or MFCC call (a posted one: the post spec's), which their own kernels write -- from a launch that reads nothing: the
     // destination stands in for a source of no elements
@@ -502,6 +556,12 @@ struct Batch {
             for (const vpz_pack_row &r : d) none.push_back(vpz_feat_row{0, 0, r.row});
             const char *own;  // (no scratch memory is asked for: none can fail)
             return post_rows(L, dst, 0, none, &own);
+        }
+        if (norm) {
+            std::vector<vpz_norm_row> none;
+            for (const vpz_pack_row &r : d) none.push_back(vpz_norm_row{0, 0, r.row, 1.0});
+            const char *own;  // (no memory is asked for: none can fail)
+            return norm_rows(L, dst, 0, none, false, &own);
         }
         if (feature) return feature_rows(L.ctx, dst, 0, d, dst, rows);
         return vpz_pcm_pack(L.ctx, dst, 0, channels, (int32_t)d.size(), d.data(), dst, rows, frames, layout);
@@ -626,6 +686,7 @@ struct GroupRun {
                 if (up < 1 || down < 1 || up > VPZ_RESAMPLE_MAX_UP || down > VPZ_RESAMPLE_MAX_DOWN_PER_UP * up) { J.status = VPZM_E_RATE; return; }
                 J.up = (int32_t)up;
                 J.down = (int32_t)down;
+                if (batch.by_loudness() && (info.sample_rate < VPZ_LOUDNESS_MIN_RATE || info.sample_rate > VPZ_LOUDNESS_MAX_RATE)) { J.status = VPZM_E_RATE; return; }
                 if (J.wanted > INT64_MAX / 2048 || resampled_length(J.wanted, J.up, J.down) > batch.frames) { J.status = VPZM_E_CAPACITY; return; }
             } else {
                 if (J.wanted > capacity_of(J.k)) { J.status = VPZM_E_CAPACITY; return; }
@@ -1111,6 +1172,9 @@ struct SubCall {
     double t_upload = 0, t_entropy = 0, t_call = 0, t_download = 0;
     int member_calls = 0;  // synth calls made for single members after the batch call failed (the profile line says how many)
     int resample_launches = 0;  // a resampled call: vpz_pcm_resample launches of this sub-batch, one per ratio among its members
+    // a normalised call, per member: the loudness mode's measurement and the gain it gives; the stage's result records on their way down
+    std::vector<double> norm_loud, norm_gain;
+    std::vector<vpz_norm_result> norm_down;
 
     Job &job(size_t j) const { return R.jobs[(size_t)sb.members[j]]; }
     bool live(size_t j) const { return job(j).status == VPZM_OK; }
@@ -1404,12 +1468,19 @@ struct SubCall {
             // (a log-mel, fbank or MFCC call: resampled into the lane's temporary, then ONE feature launch on the same stream -- stream-ordered:
             // no synchronise in between)
             if (B.feature) rc = mono_temporary(rows.size());
+            if (rc == VPZ_OK && B.by_loudness()) rc = measure_gains(rows);  // (at the streams' own rates, before the resample)
             if (rc == VPZ_OK) rc = resample_by_ratio(rows);
             for (size_t j = 0; j < sb.members.size(); ++j) written[j] = resampled_length(written[j], job(j).up, job(j).down);
             if (rc != VPZ_OK) (void)vpz_context_synchronize(L.ctx);  // (the launches before the failed one have left the lane's array)
             else if (B.feature) rc = feature_rows(rows);
         }
         if (rc == VPZ_OK) rc = vpz_context_synchronize(L.ctx);  // (the lane's arrays are the next sub-batch's once the stream has drained)
+        // (a normalised call: the result records came down with that synchronise; a member without samples has the empty record's values)
+        // (the gain is reported in double where the row's float32 gain is its rounding: the loudness mode's, unless the ceiling bound)
+        for (size_t j = 0; rc == VPZ_OK && j < norm_down.size(); ++j) {
+            const bool own = !norm_gain.empty() && (double)(float)norm_gain[j] == norm_down[j].gain;
+            B.norm_out[job(j).k] = vpzm_norm_out{own ? norm_gain[j] : norm_down[j].gain, norm_down[j].mean, norm_down[j].peak, norm_loud[j]};
+        }
         for (size_t j = 0; j < sb.members.size(); ++j) {
             if (rc == VPZ_OK) job(j).row_packed = true;
             else if (member_rc[j] == VPZ_OK) member_rc[j] = VPZ_E_HIP;
@@ -1430,7 +1501,8 @@ struct SubCall {
     // record and needs no launch.  A record is written once everything has succeeded: a failed sub-batch's stay empty.
     // An R 128 call makes one vpz_pcm_true_peak launch per rate behind the loudness launches, over the same descriptors; the true peaks
     // [members] float32 lie behind the peaks in the temporary and come down in the same copy; range and maxima run beside the gate
-    int measure_rows(std::vector<vpz_pack_row> &rows, bool staged)
+    // `into` (a normalised call's loudness mode): member j's record goes to (*into)[j], not to the group's piece
+    int measure_rows(std::vector<vpz_pack_row> &rows, bool staged, std::vector<vpzm_loudness> *into = nullptr)
     {
         const size_t M = rows.size();
         std::vector<int32_t> rate(M, 0), step(M, 1);
@@ -1524,10 +1596,54 @@ struct SubCall {
                 full_records.emplace_back((int64_t)(job(j).k - R.lo), full);
                 continue;
             }
-            B.record((int64_t)(job(j).k - R.lo)) = rec;
+            (into ? (*into)[j] : B.record((int64_t)(job(j).k - R.lo))) = rec;
         }
         for (const auto &fr : full_records) B.record_r128(fr.first) = fr.second;
         return VPZ_OK;
+    }
+
+    // A normalised call's loudness mode: the members' windows measured where the loudness call measures them -- the lane's interleaved
+    // PCM at the streams' own rates --, by the same launches, copy and gate; member j's gain is 10^((target - L) / 20), 1 where nothing
+    // was measured.  (With VPZM_FAIL_DELIVERY the measurement is not made either: the failed step is the delivery's)
+    int measure_gains(const std::vector<vpz_pack_row> &rows)
+    {
+        norm_loud.assign(rows.size(), -HUGE_VAL);
+        norm_gain.assign(rows.size(), 1.0);
+        if (R.sw.fail_delivery) return VPZ_OK;
+        std::vector<vpz_pack_row> mine(rows);  // (measure_rows renumbers its descriptors' rows)
+        std::vector<vpzm_loudness> recs(rows.size(), vpzm_loudness{-HUGE_VAL, 0.0, 0, 0});
+        const int rc = measure_rows(mine, true, &recs);
+        for (size_t j = 0; rc == VPZ_OK && j < rows.size(); ++j) {
+            norm_loud[j] = recs[j].integrated;
+            if (norm_loud[j] != -HUGE_VAL) norm_gain[j] = pow(10.0, (B.norm->target - norm_loud[j]) / 20.0);
+        }
+        return rc;
+    }
+
+    // a normalised call: row j's first `written[j]` samples per channel of the temporary become row k - lo of the group's piece; the
+    // result records start their way down, and deliver_batch's synchronise lands them
+    int normalize_rows(const std::vector<vpz_pack_row> &rows)
+    {
+        std::vector<vpz_norm_row> d;
+        for (size_t j = 0; j < rows.size(); ++j) d.push_back(vpz_norm_row{rows[j].src, rows[j].samples, rows[j].row, norm_gain.empty() ? 1.0 : norm_gain[j]});
+        if (R.sw.fail_delivery) return launched(B.feature->step, VPZ_E_HIP);
+        bool any_real = false;
+        for (const vpz_norm_row &r : d) any_real = any_real || r.samples > 0;
+        const bool want = B.norm_out != nullptr && any_real;
+        const char *own = nullptr;
+        int rc = B.norm_rows(L, L.mono(), (int64_t)rows.size() * B.channels * B.frames, d, want, &own);
+        if (own) {
+            R.m->fail(std::string(B.feature->step) + ": " + own);  // (a failure in front of the call: the context's last error is an older one)
+            return rc;
+        }
+        rc = launched(B.feature->step, rc);
+        if (rc == VPZ_OK && want) {
+            if (norm_loud.empty()) norm_loud.assign(rows.size(), -HUGE_VAL);
+            norm_down.assign(rows.size(), vpz_norm_result{0.0, 0.0, 0.0, 0.0, 1.0});
+            rc = launched("vpz_pcm_download", vpz_pcm_download(L.ctx, norm_down.data(), L.buf[Lane::kNormResult].p, (uint64_t)(rows.size() * sizeof(vpz_norm_result))));
+            if (rc != VPZ_OK) norm_down.clear();
+        }
+        return rc;
     }
 
     // a log-mel, fbank or MFCC call's resampled rows go to the lane's temporary: mono planar float32 [members][frames], member j in row j;
@@ -1574,6 +1690,7 @@ struct SubCall {
     int feature_rows(std::vector<vpz_pack_row> &rows)
     {
         for (size_t j = 0; j < rows.size(); ++j) rows[j] = vpz_pack_row{(int64_t)j * B.channels * B.frames, written[j], rows[j].row};
+        if (B.norm) return normalize_rows(rows);
         if (R.sw.profile) (void)vpz_context_synchronize(L.ctx);  // (the timeline wants the launch's own time)
         const auto t_mel = Clock::now();
         // (a posted call: the feature launch writes member j's frames into row j of the lane's second temporary, and vpz_feat_post's
@@ -1885,6 +2002,31 @@ int vpzm_decode_ranges_resampled(vpzm_dispatcher *m, int32_t n, const uint8_t *c
 {
     if (!resampled_args_fit(sample_rate, channels, downmix)) return VPZM_E_ARG;
     const Batch batch(Batch::kResampled, channels, out_layout, frames, sample_rate, downmix);
+    return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
+}
+
+// the normalised call: the resampled call's arguments and refusals, the spec's own, and the caller's records hold the empty one from here on
+int vpzm_decode_ranges_normalized(vpzm_dispatcher *m, int32_t n, const uint8_t *const *data, const uint64_t *size, const vpzm_range *ranges,
+                                  int32_t sample_rate, int32_t channels, int32_t downmix, int64_t frames, int32_t out_layout, void *const *group_dst,
+                                  vpzm_stream_result *results, vpzm_stats *stats, const vpzm_norm_spec *spec, vpzm_norm_out *out)
+{
+    if (!m || n < 0 || !spec) return VPZM_E_ARG;
+    const vpzm_norm_spec &s = *spec;
+    if (s.mode < VPZM_NORM_MEANVAR || s.mode > VPZM_NORM_LOUDNESS) return VPZM_E_ARG;
+    const bool linear = s.mode == VPZM_NORM_PEAK || s.mode == VPZM_NORM_RMS || s.mode == VPZM_NORM_GAIN;
+    if ((linear || s.mode == VPZM_NORM_LOUDNESS) && !std::isfinite(s.target)) return VPZM_E_ARG;
+    if (linear && !(s.target > 0.0)) return VPZM_E_ARG;
+    if (!std::isfinite(s.eps) || s.eps < 0.0 || !std::isfinite(s.ceiling) || s.ceiling < 0.0) return VPZM_E_ARG;
+    if (s.mode == VPZM_NORM_MEANVAR && s.ceiling != 0.0) return VPZM_E_ARG;
+    for (int32_t r : s.reserved)
+        if (r != 0) return VPZM_E_ARG;
+    bool s16, planar;
+    if (!resampled_args_fit(sample_rate, channels, downmix) || !layout_of(out_layout, &s16, &planar)) return VPZM_E_ARG;
+    for (int32_t k = 0; out && k < n; ++k) out[k] = vpzm_norm_out{1.0, 0.0, 0.0, -HUGE_VAL};
+    Batch batch = Batch::featured(kNormalized, spec, sample_rate, downmix, channels, frames);
+    batch.norm = spec;
+    batch.norm_layout = out_layout;
+    batch.norm_out = out;
     return ranges_call(m, n, data, size, ranges, 0, nullptr, nullptr, nullptr, results, stats, &batch, group_dst);
 }
 

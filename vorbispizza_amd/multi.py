@@ -130,6 +130,9 @@ def lib():
         if hasattr(L, "vpzm_measure_r128"):
             L.vpzm_measure_r128.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
             L.vpzm_measure_r128.restype = C.c_int
+        if hasattr(L, "vpzm_decode_ranges_normalized"):  # (vorbispizza_multi_normalize.h; vorbispizza_amd/normalize.py is its Python surface)
+            L.vpzm_decode_ranges_normalized.argtypes = L.vpzm_decode_ranges_resampled.argtypes + [vp, vp]
+            L.vpzm_decode_ranges_normalized.restype = C.c_int
         _bound = True
     return L
 
@@ -322,6 +325,19 @@ class Dispatcher:
                                     lambda dst: (channels, frames, layout, dst))
         return self._batch_call("decode_ranges_resampled", lib().vpzm_decode_ranges_resampled, datas, ranges, shape, dtype, out,
                                 lambda dst: (int(sample_rate), channels, int(bool(mono)), frames, layout, dst), method="decode_ranges_batch")
+
+    def _decode_ranges_normalized(self, datas, ranges, sample_rate, channels, mono, frames, planar, s16, out, spec, records):
+        """vpzm_decode_ranges_normalized behind vorbispizza_amd.normalize.decode_ranges_normalized, which checks the arguments and makes
+        `spec` (a ctypes vpzm_norm_spec) and `records` (a contiguous array of n vpzm_norm_out): decode_ranges_batch's resampled call with
+        the two behind its arguments.  -> (parts, whole_or_None, results, stats)"""
+        import torch
+        shape = (lambda rows: (rows, channels, frames)) if planar else (lambda rows: (rows, frames, channels))
+        layout = {(True, False): capi.OUT_PLANAR, (False, False): capi.OUT_INTERLEAVED, (True, True): capi.OUT_PLANAR_S16,
+                  (False, True): capi.OUT_INTERLEAVED_S16}[(bool(planar), bool(s16))]
+        fn = lib().vpzm_decode_ranges_normalized
+        return self._batch_call("decode_ranges_normalized", lambda *head: fn(*head, C.byref(spec), records.ctypes.data if records.size else None),
+                                datas, ranges, shape, torch.int16 if s16 else torch.float32, out,
+                                lambda dst: (int(sample_rate), channels, int(bool(mono)), frames, layout, dst))
 
     def decode_ranges_logmel(self, datas, ranges, frames, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=None,
                              mel_scale="slaney", mel_norm="slaney", log=True, floor=1e-10, bands_first=True, out=None):
